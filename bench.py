@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — the headline measurement of BASELINE.json on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+Everything else below - roofline, cpu_baseline, the side sections, the GPU clocks, the N > 1 per-iteration split - runs only
+with --full.  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (see dump_outputs()).
 
 N > 1: one rank per GPU over RCCL.  Either the caller starts the ranks (`python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...`: RANK / LOCAL_RANK / WORLD_SIZE in the environment) or, when WORLD_SIZE is unset, this process
@@ -471,9 +475,10 @@ def composite_training_section(device):
                         f'max_iteration = {it}; gnn_train_step with per-type networks (csrc/train_composite.hpp), predict() batch by batch'}
 
 
-def measure_loop(gnn, inputs, s0, steps, warmup):
-    """(elapsed seconds of `steps` forwards, k, seconds per iteration kernel launch) on one GPU; the per-launch time comes from
-    HIP events the library records on the launch stream around the iteration launches (gnn.loop_events)."""
+def measure_loop(gnn, inputs, s0, steps, warmup, launch_time=True):
+    """(elapsed seconds of `steps` forwards, k, seconds per iteration kernel launch, the last timed forward's (k, state, out)) on one
+    GPU; the per-launch time comes from HIP events the library records on the launch stream around the iteration launches
+    (gnn.loop_events), over 5 more forwards after the timed ones - None without `launch_time`."""
     ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
     for e in ev: e.record()
     gnn.loop_events = ev
@@ -481,16 +486,43 @@ def measure_loop(gnn, inputs, s0, steps, warmup):
     for _ in range(warmup): step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps): k, state, out = step()
+    for _ in range(steps): last = step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     k_val = gnn.check_last_k()
-    t_loop_ms = []
-    for _ in range(5):
-        step(); torch.cuda.synchronize()
-        t_loop_ms.append(ev[0].elapsed_time(ev[1]))
+    t_iter = None
+    if launch_time:
+        t_loop_ms = []
+        for _ in range(5):
+            step(); torch.cuda.synchronize()
+            t_loop_ms.append(ev[0].elapsed_time(ev[1]))
+        t_iter = 1e-3 * float(np.median(t_loop_ms)) / max(k_val, 1)
     gnn.loop_events = None
-    return elapsed, k_val, 1e-3 * float(np.median(t_loop_ms)) / max(k_val, 1)
+    return elapsed, k_val, t_iter, last
+
+
+DUMP_BYTES = 60 * 2**20          # the data of all files of --dump-outputs together (npy headers come on top: < 64 MB in all)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: `arrays` (name -> tensor, what a caller of the timed path receives from its last step) as DIR/<name>.npy in
+    float32 (float64 stays float64).  Smallest first, every array gets an equal share of what is left of DUMP_BYTES; one larger
+    than its share keeps a fixed sample of its rows - default_rng(0), in row order - so that runs with the same arguments write
+    the same rows."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = sorted(((n, a.detach()) for n, a in arrays.items()), key=lambda na: na[1].numel() * na[1].element_size())
+    left = DUMP_BYTES
+    for i, (name, a) in enumerate(arrays):
+        share = left // (len(arrays) - i)
+        nbytes = a.numel() * a.element_size()
+        if nbytes > share and a.dim() > 0:
+            row_bytes = nbytes // max(a.shape[0], 1)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=share // row_bytes, replace=False))
+            a = a[torch.as_tensor(rows, device=a.device)]
+        a = a.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        np.save(os.path.join(dirname, name + '.npy'), a)
+        left -= a.nbytes
 
 
 def roofline_record(b_iter, t_iter, kernel_name, n_nodes=None, h1=None):
@@ -564,7 +596,7 @@ def beyond_cache_section(device, d, K_it, aggregation):
     gnn = GNNnodeBased(ns, no, d, K_it, 0.0)
     gen = torch.Generator(device=device); gen.manual_seed(1)
     s0 = torch.randn((N, d), generator=gen, device=device) * 0.1
-    elapsed, k_val, t_iter = measure_loop(gnn, gnn.process_inputs(x), s0, steps=SIDE_STEPS, warmup=1)
+    elapsed, k_val, t_iter, _ = measure_loop(gnn, gnn.process_inputs(x), s0, steps=SIDE_STEPS, warmup=1)
     b_iter = algorithmic_bytes_per_iteration(N, E, d, ns.units[0], False)
     kernel_name = nat.lib().gnn_last_kernel_name().decode()
     rec = roofline_record(b_iter, t_iter, kernel_name, N, ns.units[0])
@@ -587,7 +619,7 @@ def wide_state_section(device, aggregation):
     gen = torch.Generator(device=device); gen.manual_seed(2)
     s0 = torch.randn((N, d), generator=gen, device=device) * 0.1
     gnn = GNNnodeBased(ns, no, d, 20, 0.0)
-    elapsed, k_val, t_iter = measure_loop(gnn, gnn.process_inputs(x), s0, steps=SIDE_STEPS, warmup=1)      # t_iter: HIP events around the iteration launches
+    elapsed, k_val, t_iter, _ = measure_loop(gnn, gnn.process_inputs(x), s0, steps=SIDE_STEPS, warmup=1)      # t_iter: HIP events around the iteration launches
     b_iter = algorithmic_bytes_per_iteration(N, E, d, ns.units[0], False)
     kernel_name = nat.lib().gnn_last_kernel_name().decode()
     rec = {'workload': f'Erdos-Renyi {N} nodes / {E} arcs, state_dim={d}, {aggregation} aggregation', 'k': k_val, 'us_per_iteration': 1e6 * t_iter,
@@ -703,9 +735,16 @@ def main():
     ap.add_argument('--state-dim', type=int, default=64)
     ap.add_argument('--max-iteration', type=int, default=50)
     ap.add_argument('--aggregation', default='average')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline line: roofline (5 more event-timed forwards), GPU clocks, cpu_baseline and the side '
+                         'sections (MUTAG, training, beyond_infinity_cache, wide_state_d200; the --no-* options below drop single ones), '
+                         'N > 1: the per-iteration kernel / exchange split')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned (k, state, out of rank 0) as DIR/<name>.npy, float32, '
+                         'under 64 MB in all: an array too large keeps a fixed seeded sample of its rows')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-mutag', action='store_true')
-    ap.add_argument('--mutag-dp', action='store_true', help='N>1: also run the MUTAG data-parallel side section (collective; a rank that fails in it ends the job)')
+    ap.add_argument('--mutag-dp', action='store_true', help='N>1 with --full: also run the MUTAG data-parallel side section (collective; a rank that fails in it ends the job)')
     ap.add_argument('--no-beyond-cache', action='store_true')
     ap.add_argument('--no-training', action='store_true', help='skip the train_step / fit() section')
     ap.add_argument('--unfused', action='store_true')
@@ -812,7 +851,7 @@ def main():
             Sequencer([graph], 'n', args.aggregation, 1, shuffle=False, device=device)[0][0]
         inputs = gnn.process_inputs(x)
         per_arc_w = inputs[7 if composite else 5].device_csr(device)['w'] is not None
-        elapsed, k_val, t_iter = measure_loop(gnn, inputs, s0, args.steps, args.warmup)
+        elapsed, k_val, t_iter, last = measure_loop(gnn, inputs, s0, args.steps, args.warmup, launch_time=args.full)
         kernel_name = nat.lib().gnn_last_kernel_name().decode()
     else:
         import torch.distributed as dist
@@ -839,23 +878,24 @@ def main():
         sync_all()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            k, state, out = step()
+            last = step()
         sync_all()
         elapsed = time.perf_counter() - t0
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
-        k_val = float(k)
-        prof = sl.profile_iteration(s0)            # per-iteration device time: kernel(s) alone, exchange alone, both overlapped
-        t_iter = prof['kernel_s']
-        kernel_name = nat.lib().gnn_last_kernel_name().decode()
-        tt = torch.tensor([prof['kernel_s'], prof['exchange_s'], prof['iteration_s']], dtype=torch.float64, device=device)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        extra['per_iteration_ms'] = {'kernel': 1e3 * float(tt[0]), 'exchange': 1e3 * float(tt[1]),
-                                     'iteration_overlapped': 1e3 * float(tt[2]),
-                                     'note': 'max over ranks; kernel = own-range + halo launches without the collective, exchange = '
-                                             'the collective alone, iteration = what one iteration costs with both in flight'}
-        if 'host_issue_s' in prof: extra['host_issue_us_per_iteration'] = 1e6 * prof['host_issue_s']
+        k_val = float(last[0])
+        if args.full:
+            prof = sl.profile_iteration(s0)            # per-iteration device time: kernel(s) alone, exchange alone, both overlapped
+            t_iter = prof['kernel_s']
+            kernel_name = nat.lib().gnn_last_kernel_name().decode()
+            tt = torch.tensor([prof['kernel_s'], prof['exchange_s'], prof['iteration_s']], dtype=torch.float64, device=device)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            extra['per_iteration_ms'] = {'kernel': 1e3 * float(tt[0]), 'exchange': 1e3 * float(tt[1]),
+                                         'iteration_overlapped': 1e3 * float(tt[2]),
+                                         'note': 'max over ranks; kernel = own-range + halo launches without the collective, exchange = '
+                                                 'the collective alone, iteration = what one iteration costs with both in flight'}
+            if 'host_issue_s' in prof: extra['host_issue_us_per_iteration'] = 1e6 * prof['host_issue_s']
         extra['exchange_bytes_per_rank_per_iteration'] = sl.exchange_bytes()
         extra['exchange_transport'] = getattr(sl, 'transport', 'all_to_all')
         if getattr(sl, 'transport_times', None): extra['exchange_transport_ms_measured'] = {k_: 1e3 * v for k_, v in sl.transport_times.items()}
@@ -863,14 +903,18 @@ def main():
         if getattr(sl, 'pipeline_times', None): extra['exchange_pipeline_ms_per_iteration_measured'] = {str(k_): 1e3 * v for k_, v in sl.pipeline_times.items()}
     ms_per_step = 1e3 * elapsed / args.steps
     value = E * k_val * args.steps / elapsed
-    if rank == 0: extra['gpu_state_after_timed_region'] = gpu_state()
-
     h1 = ns.units[0]
-    n_local = N if not sharded else sl.n_local
-    e_local = E if not sharded else sl.e_local
-    b_iter = algorithmic_bytes_per_iteration(n_local, e_local, d, h1, per_arc_w)
-    roofline = roofline_record(b_iter, t_iter, kernel_name, n_local, h1)
-    if not sharded: traffic_lookup(roofline, kernel_name, N, E, d)
+    if args.full:
+        if rank == 0: extra['gpu_state_after_timed_region'] = gpu_state()
+        n_local = N if not sharded else sl.n_local
+        e_local = E if not sharded else sl.e_local
+        b_iter = algorithmic_bytes_per_iteration(n_local, e_local, d, h1, per_arc_w)
+        extra['roofline'] = roofline_record(b_iter, t_iter, kernel_name, n_local, h1)
+        if not sharded: traffic_lookup(extra['roofline'], kernel_name, N, E, d)
+        extra['loop_only_updates_per_s'] = E / t_iter if not sharded else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(zip(('k', 'state', 'out'), last)))
+    del last
 
     result = {
         'metric': 'node-state updates/s (arcs x iterations / s), forward Loop',
@@ -884,13 +928,11 @@ def main():
                    'sharding': 'single GPU' if not sharded else f'node-range shards over {world} GPUs, '
                                                                f'RCCL {"all-to-all of compacted halos" if type(sl).__name__ == "HaloShardedLoop" else ("all-gather of state slices" if sl.transport == "ring" else "pair-wise send/recv of state slices (one-hop all-gather)")} per iteration'
                                                                + (', own-range arcs overlapped with the exchange' if sharded and sl.overlap else '')},
-        'roofline': roofline,
-        'loop_only_updates_per_s': E / t_iter if not sharded else None,
         'fwd_ms_per_graph': ms_per_step,
     }
     result.update(extra)
 
-    if rank == 0 and not sharded and not args.no_cpu_baseline and not composite and not on_device:
+    if args.full and rank == 0 and not sharded and not args.no_cpu_baseline and not composite and not on_device:
         from oracle import cpu_baseline as cb
         from oracle.harness import _np, _triple
         ops = (_np(x[0]), _np(x[1]), _triple(x[5]), _triple(x[6]), ns.spec(), d, 0.0, s0_host)
@@ -909,14 +951,14 @@ def main():
                                             f'{os.cpu_count()} host cpus',
                                   'variants': variants}
         result['speedup_vs_cpu_loop'] = (E / t_iter) / result['cpu_baseline']['value']
-    if rank == 0 and not sharded and not args.no_mutag and args.workload == 'c4':
+    if args.full and rank == 0 and not sharded and not args.no_mutag and args.workload == 'c4':
         result['mutag'] = mutag_section(device, cpu=not args.no_cpu_baseline)
-    if rank == 0 and not sharded and not args.no_training and args.workload == 'c4' and not args.unfused and args.state_dim in (16, 32, 64):
+    if args.full and rank == 0 and not sharded and not args.no_training and args.workload == 'c4' and not args.unfused and args.state_dim in (16, 32, 64):
         try:
             result['training'] = training_section(device, (x,), d)
         except Exception as e:                        # never lose the headline line to the extras
             result['training'] = {'error': str(e)[:300]}
-    if rank == 0 and not sharded and not args.no_beyond_cache and args.workload == 'c4' and not args.unfused:
+    if args.full and rank == 0 and not sharded and not args.no_beyond_cache and args.workload == 'c4' and not args.unfused:
         del gnn, inputs, x, s0
         torch.cuda.empty_cache()
         result['beyond_infinity_cache'] = beyond_cache_section(device, d, K_it, args.aggregation)
@@ -937,7 +979,7 @@ def main():
     # the others are in).  So at world size > 1 it runs only when asked for (--mutag-dp), after everything the headline line needs has been
     # measured, and a failing rank exits non-zero - the launcher then tears the job down instead of letting it hang.  At world size 1
     # (--force-sharded on a 1-GPU box) a failure is local and simply recorded.
-    if sharded and ((world == 1 and args.force_sharded) or (world > 1 and args.mutag_dp)) and not args.no_mutag and args.workload == 'c4':
+    if args.full and sharded and ((world == 1 and args.force_sharded) or (world > 1 and args.mutag_dp)) and not args.no_mutag and args.workload == 'c4':
         del sl
         torch.cuda.empty_cache()
         try:

@@ -36,5 +36,5 @@ for (N, E, d) in [(300_000, 3_000_000, 200), (1_000_000, 10_000_000, 160), (200_
     b_iter = bench.algorithmic_bytes_per_iteration(N, E, d, ns.units[0], False)
     for env in ({},):
         os.environ.update(env)
-        el, k, t_iter = bench.measure_loop(gnn, inputs, s0, steps=3, warmup=1)
+        el, k, t_iter, _ = bench.measure_loop(gnn, inputs, s0, steps=3, warmup=1)
         print(f"N={N} d={d} {env}: {1e6 * t_iter:.1f} us per iteration, {b_iter / t_iter / 8e12:.3f} of 8 TB/s  [{nat.lib().gnn_last_kernel_name().decode()}]", flush=True)

@@ -6,7 +6,7 @@ TAG=${1:-r02}
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/$TAG; mkdir -p $OUT
 run() {  # name, bench args...
   name=$1; shift
-  ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -o $name -- python3 $ROOT/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-mutag --no-beyond-cache "$@" > $OUT/bench_prof_$name.json 2> $OUT/bench_prof_$name.err )
+  ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -o $name -- python3 $ROOT/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-mutag --no-beyond-cache "$@" > $OUT/bench_prof_$name.json 2> $OUT/bench_prof_$name.err )
   f=$(find $OUT/prof_$name -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && head -12 $f > $OUT/${TAG}_${name}_kernel_stats.csv && head -3 $OUT/${TAG}_${name}_kernel_stats.csv | cut -c1-160
   rm -rf $OUT/prof_$name

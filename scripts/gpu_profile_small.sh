@@ -13,5 +13,5 @@ prof() {  # name, program args...
   rm -rf $OUT/prof_$name
 }
 prof mutag_groups $ROOT/scripts/mutag_groups.py
-prof n30k_mid $ROOT/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-mutag --no-beyond-cache --workload c3 --nodes 3e4 --arcs 3e5
+prof n30k_mid $ROOT/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-mutag --no-beyond-cache --workload c3 --nodes 3e4 --arcs 3e5
 tail -4 $OUT/prof_mutag_groups.out

@@ -11,11 +11,11 @@ echo '{"records": []}' > $OUT/hbm_traffic.json          # (records of other libr
 COMMON="--warmup 1 --no-cpu-baseline --no-mutag --no-beyond-cache --no-training"
 run() {   # name, bench args...
   local name=$1; shift
-  ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -o $name -- python3 $ROOT/bench.py "$@" --steps 5 $COMMON > $OUT/bench_prof_$name.json 2> $OUT/bench_prof_$name.err )
+  ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -o $name -- python3 $ROOT/bench.py --full "$@" --steps 5 $COMMON > $OUT/bench_prof_$name.json 2> $OUT/bench_prof_$name.err )
   f=$(find $OUT/prof_$name -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $OUT/${TAG}_${name}_kernel_stats.csv && head -3 $OUT/${TAG}_${name}_kernel_stats.csv | cut -c1-160
   for c in FETCH_SIZE WRITE_SIZE; do
-    ( cd /tmp && rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_${name}_$c -o $name -- python3 $ROOT/bench.py "$@" --steps 3 $COMMON > /dev/null 2> $OUT/pmc_${name}_$c.err )
+    ( cd /tmp && rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_${name}_$c -o $name -- python3 $ROOT/bench.py --full "$@" --steps 3 $COMMON > /dev/null 2> $OUT/pmc_${name}_$c.err )
     f=$(find $OUT/pmc_${name}_$c -name "*counter_collection.csv" | head -1)
     [ -n "$f" ] && grep -E "Counter_Name|k_state_" $f > $OUT/${TAG}_${name}_pmc_$c.csv
   done
@@ -36,6 +36,6 @@ cp $OUT/hbm_traffic.json profiles/hbm_traffic.json        # (so that the bench l
 bash scripts/gpu_profile_train.sh $TAG > $OUT/train_profile.log 2>&1 || true
 bash scripts/gpu_pmc_train.sh $TAG > $OUT/train_pmc.log 2>&1 || true      # (FETCH / WRITE passes of the large-graph training kernels: ${TAG}_train_pmc.txt)
 bash scripts/gpu_sq_train.sh $TAG > $OUT/train_sq.log 2>&1 || true         # (SQ / GRBM counters of the same kernels: ${TAG}_train_sq_counters.txt)
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -c 4000 $OUT/bench_default.json
 python3 -c "from gnnkeras_amd._native import source_hash; print('library sources', source_hash())"

@@ -20,7 +20,7 @@ bash scripts/gpu_pmc_train_c5.sh ${TAG}_c5 > $OUT/train_c5_pmc.log 2>&1 || true
 COMMON="--warmup 1 --no-cpu-baseline --no-mutag --no-beyond-cache --no-training --steps 5"
 trace() {   # name, bench args...: kernel-trace summary only
   local name=$1; shift
-  ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -o $name -- python3 $ROOT/bench.py "$@" $COMMON > $OUT/bench_prof_$name.json 2> $OUT/bench_prof_$name.err )
+  ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -o $name -- python3 $ROOT/bench.py --full "$@" $COMMON > $OUT/bench_prof_$name.json 2> $OUT/bench_prof_$name.err )
   f=$(find $OUT/prof_$name -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $OUT/${TAG}_${name}_kernel_stats.csv && head -2 $OUT/${TAG}_${name}_kernel_stats.csv | cut -c1-160
   rm -rf $OUT/prof_$name

@@ -103,7 +103,7 @@ def test_bench_self_launches_two_ranks():
     """`python bench.py --gpus 2` with WORLD_SIZE unset (the driver's command form) starts its own ranks and prints ONE
     JSON line with n_gpus = 2, a roofline record and the exchange / kernel split."""
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
-    res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--workload', 'c3'],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--workload', 'c3', '--full'],
                          capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith('{')]
@@ -117,7 +117,7 @@ def test_bench_forced_sharded_path_on_one_gpu():
     """The N > 1 code path of bench.py (ShardedLoop + RCCL collectives + overlap) with the one rank a 1-GPU box allows."""
     env = dict(os.environ, RANK='0', LOCAL_RANK='0', WORLD_SIZE='1', MASTER_ADDR='127.0.0.1', MASTER_PORT='29617')
     res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--workload', 'c3',
-                          '--force-sharded'], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                          '--force-sharded', '--full'], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     r = json.loads([l for l in res.stdout.splitlines() if l.startswith('{')][0])
     assert r['n_gpus'] == 1 and 'per_iteration_ms' in r and r['roofline']['kernel'].startswith('k_state_fused4')

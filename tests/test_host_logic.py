@@ -364,6 +364,29 @@ def test_bench_reports_pmc_traffic_only_for_the_library_sources_it_runs_on(tmp_p
     assert rec['traffic'] is None and 'missing' in rec['traffic_null_reason']
 
 
+def test_bench_dump_outputs_keeps_a_fixed_sample_under_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: arrays that fit their share are written whole (float32, float64 stays float64); a larger one keeps the
+    same seeded rows, in row order, on every run; the data of all files stays within the budget."""
+    import importlib.util, os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_for_test', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 4096)
+    arrays = {'k': torch.tensor(50.0), 'out': torch.arange(100, dtype=torch.float64).reshape(50, 2),
+              'state': torch.arange(16000, dtype=torch.float32).reshape(1000, 16)}
+    bench.dump_outputs(str(tmp_path / 'a'), arrays)
+    bench.dump_outputs(str(tmp_path / 'b'), arrays)
+    assert sorted(os.listdir(tmp_path / 'a')) == ['k.npy', 'out.npy', 'state.npy']
+    k, out, state = (np.load(tmp_path / 'a' / f) for f in ('k.npy', 'out.npy', 'state.npy'))
+    assert k.dtype == np.float32 and float(k) == 50.0
+    assert out.dtype == np.float64 and np.array_equal(out, arrays['out'].numpy())
+    assert state.dtype == np.float32 and state.shape == ((4096 - 4 - 800) // 64, 16)
+    rows = state[:, 0].astype(np.int64) // 16
+    assert np.array_equal(state, arrays['state'].numpy()[rows]) and (np.diff(rows) > 0).all()
+    assert np.array_equal(state, np.load(tmp_path / 'b' / 'state.npy'))
+    assert k.nbytes + out.nbytes + state.nbytes <= 4096
+
+
 def test_graphobject_copy_field_by_field_equals_the_constructor_path(mutag_graphs):
     """`GraphObject.copy()` (reference graph_class.py:141-146 copies through the constructor) takes a field-by-field path when the constructor
     would change nothing; both must give the same object - every array, every operator, the DIM_* fields - and a graph whose ArcNode or arc
