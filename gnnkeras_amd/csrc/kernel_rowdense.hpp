@@ -2,8 +2,10 @@
 // MLP.py:12-78, every Dense behind the first): Y = act(X . W + b), optionally with the convergence predicate of the loop in the epilogue
 // (GNN.py:196-214) when Y is the new state.  k_segdense (kernels_general.hpp) stages 64 x 32 chunks of a VIRTUAL concatenation through
 // LDS with 4-byte loads - the right tool for the first layer's narrow label segments, 350 us per million rows for a 64 -> 64 layer.
-// Here the rows go straight into the matrix cores as in k_train_fwd (kernels_train_big.hpp): operands swapped (weights = A from LDS in
-// fragment order, the lane's 16-byte row pieces = B), so the result comes out row-major: 16-byte loads and stores only, no staging.
+// Here the rows go straight into the matrix cores: operands swapped (weights = A from LDS in fragment order, the lane's 16-byte row
+// pieces = B - for v_mfma_f32_16x16x4_f32 both operands have the same register layout, lane l supplies element (l % 16, l / 16)), so
+// the result D[i][j] = Y[row j][16 ct + i] leaves lane (c, g) holding four consecutive columns of its own row: 16-byte loads and
+// stores only, no staging.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels_train_big.hpp"        // BFrag, TB_MFMA_DRAIN, TB_WAVES

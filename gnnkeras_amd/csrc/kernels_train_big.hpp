@@ -4,25 +4,24 @@
 // Round 2 ran a training iteration on the general kernels: aggregate (401 us at C4 size) + four column-statistics passes
 // (4 x 115 us) + the staged dense kernel k_segdense<1> (378 us, 1.5-2.4 TB/s: its waves are parked 67 % of the time at the
 // workgroup barriers of its LDS staging) forward; activation gradient + weight gradient + two more k_segdense calls + the
-// BatchNorm input gradient + the transposed aggregate backward.  Here:
+// BatchNorm input gradient + the transposed aggregate backward.  Here, per iteration:
 //
 //   * k_aggregate_stats   - the neighbour sum of an iteration (kept on the tape) that also leaves the per-column sum and sum of
 //                           squares of what it wrote: the training-mode BatchNormalization statistics of the aggregated-state
 //                           columns (reference MLP.py:67-70) cost no extra pass;
-//   * k_train_fwd<SQ,NCT> - the first Dense of the state network over [state | agg | constant inputs] with the batch statistics
-//                           folded into its weights: rows go from global memory STRAIGHT into MFMA A-fragment registers (16-byte
-//                           loads, permuted k order, as kernel_state_wide.hpp / kernel_state_lds.hpp do), the folded weights sit
-//                           in LDS in the matching order - no staging tile, no barrier inside the row loop; activation, the
-//                           convergence predicate (GNN.py:196-212) and the column statistics of the NEW state (next iteration's
-//                           BatchNorm input) in the epilogue;
-//   * k_train_bwd_dx<HQ,NCT> - d loss / d [state | agg] = BN-input-gradient(dZ . W1^T): the same row-streaming MFMA loop, the
-//                           BatchNormalization input gradient (three coefficients per column) and the row scale of 'average'
-//                           aggregation in the epilogue - replaces two dense launches and the BN-gradient pass.
-// Round 4: the forward Dense and dZ . W^T run on the bf16 matrix cores with every f32 operand split into three bf16 terms
-// (k_train_fwd_b6, k_train_bwd_dx_b6: f32-chain accuracy, not its bits; GNN_TRAIN_BF16X6=0 selects the f32 kernels), the weight
-// gradient on v_mfma_f32_32x32x2_f32 (k_train_wgrad32).  The f32-input MFMA kernels below stay as the exact path and for S = 16.
-// Exact float32 on v_mfma_f32_16x16x4_f32 like every other dense kernel here (k_train_fwd, k_train_bwd_dx, k_train_wgrad); deterministic (fixed tile -> wave assignment,
-// per-workgroup partial statistics summed in workgroup order by k_stats_finish).
+//   * k_train_fwd_b6      - the first Dense of the state network over [state | agg | constant inputs] with the batch statistics
+//                           folded into its weights: rows go from global memory STRAIGHT into matrix-core fragments (16-byte loads),
+//                           the folded weights sit in LDS in the matching order - no staging tile, no barrier inside the row loop;
+//                           activation, the convergence predicate (GNN.py:196-212) and the column statistics of the NEW state (next
+//                           iteration's BatchNorm input) in the epilogue;
+//   * k_train_wgrad_b6    - the first layer's weight gradient P = X^T dZ, the rows brought into LDS by an LDS-DMA ring
+//                           (k_train_wgrad<1> at S = 16);
+//   * k_train_bwd_dx_b6   - d loss / d [state | agg] = BN-input-gradient(dZ . W1^T): the same row-streaming loop, the BatchNorm input
+//                           gradient (per-column coefficients) and the row scale of 'average' aggregation in the epilogue;
+//   * k_train_wgrad_dx_b6 - both backward products from one pass over the rows (S = 32 / 64, no BatchNormalization);
+//   * k_aggregate_dz      - the transposed aggregate that leaves the previous iteration's dZ, so the dense kernels read dZ alone.
+// The _b6 kernels run on the bf16 matrix cores with every f32 operand split into three bf16 terms (f32-chain accuracy, not its bits).
+// Deterministic: fixed tile -> wave assignment, per-workgroup partials summed in workgroup order (k_stats_finish, k_reduce_partials).
 #pragma once
 #include "bf16_split.hpp"
 #include <hip/hip_runtime.h>
@@ -35,20 +34,14 @@
 
 namespace gnn {
 
-#ifndef TB_STREAM_AUX
-#define TB_STREAM_AUX 0                  // cache-policy bits of the row loads of k_train_fwd_b6 / k_train_bwd_dx_b6 (experiment: scripts/micro/rowgemm_bench.hip)
-#endif
-#ifndef TB_RING_AUX
-#define TB_RING_AUX 2                    // cache-policy bits of the ring's LDS-DMA loads: 2 = nt.  k_train_wgrad_b6 at 1 M rows: 181.5 us default policy, 172.4 nt (183.5 / 177.6
-                                         // with sc0 / sc0 + nt); inside the step 188 -> 171 us.  (nt on the register loads of k_train_fwd_b6 / k_train_bwd_dx_b6: 199 -> 202, 196 -> 207.)
-#endif
-#ifndef TB_ABL
-#define TB_ABL 0                         // ablation switches of scripts/micro/rowgemm_bench.hip (1 no MFMAs, 2 no predicate, 4 no stores, 8 no statistics); 0 in the library
-#endif
+constexpr int TB_STREAM_AUX = 0;         // cache-policy bits of the row loads of k_train_fwd_b6 / k_train_bwd_dx_b6: the default policy (nt: 199 -> 202 us,
+                                         // 196 -> 207 us per 1 M rows)
+constexpr int TB_RING_AUX = 2;           // cache-policy bits of the ring's LDS-DMA loads: 2 = nt.  k_train_wgrad_b6 at 1 M rows: 181.5 us default policy, 172.4 nt
+                                         // (183.5 / 177.6 with sc0 / sc0 + nt); inside the step 188 -> 171 us.
 // Results of the last MFMAs of a tile are consumed behind a branch (the activation switch, `if (gamma)`): hipcc 7.2's hazard
 // recognizer does not carry the "XDL write -> VALU / VMEM read" wait states (up to 18 for this shape) across the block boundary -
-// k_train_bwd_dx<1, 2> without BatchNormalization read its accumulators two instructions after the MFMA that wrote them and
-// returned stale registers (scripts/micro/rowgemm_check.hip reproduces it).  Explicit wait states after the MFMA loop.
+// an f32 form of the input-gradient kernel without BatchNormalization read its accumulators two instructions after the MFMA that
+// wrote them and returned stale registers.  Explicit wait states after the MFMA loop.
 #define TB_MFMA_DRAIN() asm volatile("s_nop 15\n\ts_nop 3" ::: "memory")
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int TB_WAVES = 8;              // waves per workgroup (512 threads; launch bound 4 waves per SIMD = 2 workgroups per CU at <= 128 VGPRs)
@@ -222,191 +215,6 @@ template <> struct BFrag<8> { float v[8]; __device__ __forceinline__ void load(c
     const f32x4 t = *reinterpret_cast<const f32x4 *>(p), u = *reinterpret_cast<const f32x4 *>(p + 4);
     v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3]; v[4] = u[0]; v[5] = u[1]; v[6] = u[2]; v[7] = u[3]; } };
 
-// The matrix core is fed TRANSPOSED: the weights are the A operand (A[i][k] = W[k][16 ct + i]), the input rows the B operand
-// (B[k][j] = X[row j][k]) - for v_mfma_f32_16x16x4_f32 both operands have the same register layout (lane l supplies element
-// (l % 16, l / 16)), so the 16-byte row chunks a lane loaded serve as they are - and the result D[i][j] = Y[row j][16 ct + i] leaves
-// lane (c, g) holding Y[row c][16 ct + 4 g .. + 3]: four CONSECUTIVE columns of its own row.  Output, old state (the A chunks of the
-// state segment) and stores all share the row-major 16-byte layout: no transposition, no 4-byte accesses, no loads in the epilogue.
-#ifndef TB_PREFETCH
-#define TB_PREFETCH 0                  // 1 (experiment): the next tile's rows are requested before this tile's MFMAs.  162 VGPRs = 3 waves per SIMD
-                                       // instead of 4: SLOWER, 227 -> 247 us per 1 M rows (scripts/micro/rowgemm_bench.hip): the waves hide more than the prefetch
-#endif
-#ifndef TB_FWD_MIN_WAVES
-#define TB_FWD_MIN_WAVES 4             // waves per SIMD the register allocation is held to (experiment knob of scripts/micro/rowgemm_bench.hip)
-#endif
-template <int SQ, int NCT>
-__global__ void __launch_bounds__(64 * TB_WAVES, TB_PREFETCH ? 2 : TB_FWD_MIN_WAVES) k_train_fwd(TrainFwdArgs a) {
-    if (gate_closed(a.gate)) return;
-    constexpr int NQ = 2 * SQ + 2;                    // 16-column chunks of an input row: state, agg, constant inputs (32 columns)
-    constexpr int HP = 16 * NCT;
-    extern __shared__ __attribute__((aligned(16))) float tb_smem[];
-    float *Wl = tb_smem;                               // [4 NQ k-steps][4 g][16 c][NCT]
-    float *bias_l = tb_smem + 16 * NQ * HP;            // [HP]
-    float *red = bias_l + HP;                          // [TB_WAVES][2 HP] statistics hand-over
-    float *shift_l = red + TB_WAVES * 2 * HP;          // [HP] what the statistics are taken around
-    float *mean_l = shift_l + HP;                      // [16 NQ] the input columns' means (a.in_mean), 0 where there is none
-    __shared__ int any_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int c = lane & 15, g = lane >> 4;
-    if (tid == 0) any_s = 0;
-    for (int h = tid; h < HP; h += 64 * TB_WAVES) shift_l[h] = (a.stat_shift && h < a.H) ? a.stat_shift[h] : 0.0f;
-    for (int k = tid; k < 16 * NQ; k += 64 * TB_WAVES) mean_l[k] = fwd_in_mean(a, SQ, k);
-    // ---- folded weights into LDS in fragment order: k-step (q, e) of lane group g multiplies virtual column 16 q + 4 g + e ------
-    for (int i = tid; i < 16 * NQ * HP; i += 64 * TB_WAVES) {
-        const int k = i / HP, h = i % HP;
-        int row = -1;
-        if (k < 16 * SQ) row = a.wrow_state + k;
-        else if (k < 32 * SQ) row = a.wrow_agg + (k - 16 * SQ);
-        else if (a.xc) {
-            int j = k - 32 * SQ, beg = 0;
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                if (s < a.cs.n && j >= beg && j < beg + a.cs.width[s]) row = a.cs.wrow[s] + (j - beg);
-                if (s < a.cs.n) beg += a.cs.width[s];
-            }
-        }
-        const float v = (row >= 0 && h < a.H) ? a.Wf[(size_t)row * a.H + h] : 0.0f;
-        const int q = k >> 4, rem = k & 15, gg = rem >> 2, e = rem & 3;
-        Wl[(((4 * q + e) * 4 + gg) * 16 + (h & 15)) * NCT + (h >> 4)] = v;
-    }
-    for (int h = tid; h < HP; h += 64 * TB_WAVES) bias_l[h] = h < a.H ? a.bf[h] : 0.0f;
-    __syncthreads();
-
-    const __amdgpu_buffer_rsrc_t r_s = buf_rsrc(a.state), r_a = buf_rsrc(a.agg), r_x = buf_rsrc(a.xc), r_y = buf_rsrc(a.Y);
-    const int n_tiles = (a.M + 15) >> 4;
-    f32x4 cs1[NCT], cs2[NCT];                           // column sums / squares of this lane's four columns per tile
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) { cs1[ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; cs2[ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-    int any = 0;
-    auto fetch = [&](int t, f32x4 (&A_)[NQ]) {          // this lane's 16-byte pieces of row 16 t + c: state, agg, constants line
-        const int row_ = 16 * t + c;
-        const bool in_ = t < n_tiles && row_ < a.M;
-#pragma unroll
-        for (int q = 0; q < SQ; ++q) {
-            A_[q] = buf_ld_f32x4(r_s, in_ ? ((unsigned)row_ * (unsigned)a.ld_state + 16u * q + 4u * g) * 4u : BUF_OFF);
-            A_[SQ + q] = buf_ld_f32x4(r_a, in_ ? ((unsigned)row_ * (unsigned)a.ld_agg + 16u * q + 4u * g) * 4u : BUF_OFF);
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) A_[2 * SQ + q] = buf_ld_f32x4(r_x, in_ ? ((unsigned)row_ * 32u + 16u * q + 4u * g) * 4u : BUF_OFF);
-    };
-    const int t_step = gridDim.x * TB_WAVES;
-    f32x4 A[NQ];
-#if TB_PREFETCH
-    fetch(blockIdx.x * TB_WAVES + wave, A);
-#endif
-#pragma unroll 1
-    for (int t = blockIdx.x * TB_WAVES + wave; t < n_tiles; t += t_step) {
-        const int row = 16 * t + c;                     // this lane's row: input chunks, output chunks, old state
-        const bool in = row < a.M;
-#if TB_PREFETCH
-        f32x4 An[NQ];
-        fetch(t + t_step, An);                          // (in flight while this tile multiplies)
-#else
-        fetch(t, A);
-#endif
-        f32x4 acc[NCT];
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) acc[ct] = *reinterpret_cast<const f32x4 *>(bias_l + 16 * ct + 4 * g);
-#if (TB_ABL & 1)
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) acc[q % NCT] += A[q];
-#else
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const f32x4 xq = A[q] - *reinterpret_cast<const f32x4 *>(mean_l + 16 * q + 4 * g);      // (centred: see TrainFwdArgs::in_mean)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                BFrag<NCT> w;
-                w.load(Wl + (((4 * q + e) * 4 + g) * 16 + c) * NCT);
-#pragma unroll
-                for (int ct = 0; ct < NCT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.v[ct], xq[e], acc[ct], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);         // keep the fragment reads of later chunks from being hoisted (register budget)
-        }
-        TB_MFMA_DRAIN();
-#endif
-        // ---- epilogue: acc[ct] = Y[row][16 ct + 4 g .. + 3] ----------------------------------------------------------------------------
-        float d2 = 0.0f, n2 = 0.0f;
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) {
-            f32x4 v = acc[ct];
-            activate4(a.act, v);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = (in && 16 * ct + 4 * g + e < a.H) ? v[e] : 0.0f;
-            const u32x4 bits = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
-#if (TB_ABL & 4)
-            __builtin_amdgcn_raw_buffer_store_b128(bits, r_y, (in && v[0] == 1.2345e30f) ? (int)(((unsigned)row * (unsigned)a.ldy + 16u * ct + 4u * g) * 4u) : (int)BUF_OFF, 0, 0);
-#else
-            __builtin_amdgcn_raw_buffer_store_b128(bits, r_y, (in && 16 * ct + 4 * g < a.H) ? (int)(((unsigned)row * (unsigned)a.ldy + 16u * ct + 4u * g) * 4u) : (int)BUF_OFF, 0, 0);
-#endif
-#if !(TB_ABL & 8)
-            {
-                const f32x4 sh = *reinterpret_cast<const f32x4 *>(shift_l + 16 * ct + 4 * g);
-                f32x4 dv;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) dv[e] = in ? v[e] - sh[e] : 0.0f;
-                cs1[ct] += dv; cs2[ct] += dv * dv;
-            }
-#endif
-            if (a.pred_flag && !(TB_ABL & 2) && ct < SQ) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { const float o = A[ct][e], d = v[e] - o; d2 = fmaf(d, d, d2); n2 = fmaf(o, o, n2); }
-            }
-        }
-        if (a.pred_flag && !(TB_ABL & 2)) {             // the row's four lane groups
-            d2 += __shfl_xor(d2, 16, 64); d2 += __shfl_xor(d2, 32, 64);
-            n2 += __shfl_xor(n2, 16, 64); n2 += __shfl_xor(n2, 32, 64);
-            if (in && sqrtf(d2) > a.thr * sqrtf(n2)) any = 1;
-        }
-#if TB_PREFETCH
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) A[q] = An[q];
-#endif
-    }
-    // ---- predicate flag, k, statistics partial of this workgroup ---------------------------------------------------------------------
-    if (a.pred_flag && __any(any) && lane == 0) any_s = 1;             // benign race: every writer stores 1
-    if (a.stat_part) {
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {                                 // fold the 16 rows of the tile layout (lanes c = 0 .. 15 of a group)
-                const float s1 = row16_sum_to_lane15(cs1[ct][e]), s2 = row16_sum_to_lane15(cs2[ct][e]);
-                if (c == 15) { red[wave * 2 * HP + 16 * ct + 4 * g + e] = s1; red[wave * 2 * HP + HP + 16 * ct + 4 * g + e] = s2; }
-            }
-    }
-    __syncthreads();
-    if (a.stat_part && tid < 2 * HP) {
-        float t = 0.0f;
-        for (int w = 0; w < TB_WAVES; ++w) t += red[w * 2 * HP + tid];    // waves in order
-        a.stat_part[(size_t)blockIdx.x * 2 * HP + tid] = t;
-    }
-    if (a.pred_flag && tid == 0) {
-        if (any_s) atomicOr(a.pred_flag, 1);
-        if (blockIdx.x == 0 && a.pred_k) *a.pred_k = a.pred_kval;
-    }
-}
-
-#ifndef TB_STAMP_BLOCK
-#define TB_STAMP_BLOCK 0
-#endif
-#ifdef TB_STAMPS                        // debug build of scripts/micro: clock stamps of one wave (block 0, wave 0), 4 per trip
-__device__ unsigned long long g_tb_stamps[4 * 64];
-__device__ unsigned long long g_tb_blocks[2 * 4096];      // s_memrealtime (100 MHz, one base for the whole device) at the start / end of every workgroup
-__device__ unsigned g_tb_hwid[2 * 4096];                  // HW_ID and XCC_ID of wave 0 of every workgroup
-#define TB_BLOCK_TIME(i_) do { if (threadIdx.x == 0 && blockIdx.x < 4096) { g_tb_blocks[2 * blockIdx.x + (i_)] = __builtin_amdgcn_s_memrealtime(); \
-    g_tb_hwid[2 * blockIdx.x] = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)); g_tb_hwid[2 * blockIdx.x + 1] = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11)); } } while (0)
-#define TB_STAMP(i_) do { if (blockIdx.x == TB_STAMP_BLOCK && wave == 0 && trip_ < 60) { const unsigned long long c_ = __builtin_amdgcn_s_memtime(); if (lane == 0) g_tb_stamps[4 * trip_ + (i_)] = c_; } } while (0)
-#define TB_STAMP_DEP(i_, r_) do { asm volatile("" : "+v"(r_)); TB_STAMP(i_); } while (0)
-#define TB_MARK(i_) do { if (blockIdx.x == TB_STAMP_BLOCK && threadIdx.x == 0) g_tb_stamps[240 + (i_)] = __builtin_amdgcn_s_memtime(); } while (0)      // kernel phases
-#define TB_TRIP_END() (++trip_)
-#else
-#define TB_MARK(i_) do {} while (0)
-#define TB_BLOCK_TIME(i_) do {} while (0)
-#define TB_STAMP(i_) do {} while (0)
-#define TB_STAMP_DEP(i_, r_) do {} while (0)
-#define TB_TRIP_END() do {} while (0)
-#endif
-
 // the activation as a template parameter: no branch inside an instruction stream that is to be interleaved (a basic-block boundary is
 // a scheduling boundary for hipcc)
 template <int ACT> __device__ __forceinline__ float activate1(float v) {
@@ -420,15 +228,15 @@ template <int ACT> __device__ __forceinline__ float activate1(float v) {
     return v;
 }
 
-// ---- ... and on the bf16 matrix cores, every f32 operand split into three bf16 terms -------------------------------------------------
+// ---- the dense products on the bf16 matrix cores, every f32 operand split into three bf16 terms -------------------------------------
 // scripts/micro/mfma_valu_overlap.hip: the f32-input MFMAs run on the SIMD's f32 FMA lanes - a wave's VALU instructions do not issue in
-// their shadow (2 MFMAs + 16 v_fma per loop trip: 208 cycles against 128 / 76 alone), so the three dense training kernels cost MFMA time
-// PLUS epilogue time whichever way they are scheduled (tried this round, profiles/r04_notes.txt: 32-row tiles on the 32x32x2 form 237 us
-// per 1 M rows, the same with the epilogue of tile t - 1 interleaved into tile t's MFMA stream 229, against 225 for k_train_fwd).
+// their shadow (2 MFMAs + 16 v_fma per loop trip: 208 cycles against 128 / 76 alone), so dense training kernels on them cost MFMA time
+// PLUS epilogue time whichever way they are scheduled (profiles/r04_notes.txt: the forward Dense on the 16x16x4 f32 form 225 us per 1 M
+// rows, 32-row tiles on the 32x32x2 form 237, the same with the epilogue of tile t - 1 interleaved into tile t's MFMA stream 229).
 // The bf16 matrix cores are a separate pipe at 16x the rate.  x = hi + mid + lo with hi = bf16(x), mid = bf16(x - hi),
 // lo = bf16(x - hi - mid): exact (8 + 8 + 8 significand bits, signed), and  x w = hi wh + (hi wm + mid wh) + (mid wm + hi wl + lo wh) + O(2^-24 |x w|):
 // six v_mfma_f32_32x32x16_bf16 per 16 columns of k, each product exact in f32, f32 accumulation - the accuracy of an f32 product chain
-// (not its bits; scripts/micro/rowgemm_check.hip: max error against a float64 loop 0.5-1.4e-6 for both forms).
+// (not its bits; scripts/micro/rowgemm_check.hip: max error against a float64 loop 0.5-1.4e-6).
 // Round to NEAREST at both levels (v_cvt_pk_bf16_f32): with truncation every dropped term has the sign of its product, a relative bias of
 // ~3e-8 that the column statistics and the BatchNormalization gradients add up coherently over 10^4 .. 10^6 rows (state-network
 // gradients of the 40 000-node test against float64: 3e-4 .. 7e-3 with truncation; the f32 chain 1e-5 .. 4e-4).
@@ -473,33 +281,22 @@ __device__ __forceinline__ void split3_store(unsigned short *base, int plane_str
     base[2 * plane_stride + idx] = __builtin_bit_cast(unsigned short, vl);
 }
 
-__device__ __forceinline__ f32x4 mfma_b6_16(const u32x4 &wh, const u32x4 &wm, const u32x4 &wl, const u32x4 &xh, const u32x4 &xm, const u32x4 &xl, f32x4 acc) {
-#define B8(v_) __builtin_bit_cast(bf16x8, v_)
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B8(wl), B8(xh), acc, 0, 0, 0);      // small terms first
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B8(wh), B8(xl), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B8(wm), B8(xm), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B8(wm), B8(xh), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B8(wh), B8(xm), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B8(wh), B8(xh), acc, 0, 0, 0);
-#undef B8
-    return acc;
-}
 
-// k_train_fwd's tile (16 rows a wave, lane (c, g) = row c, 16-byte pieces at columns 16 q + 4 g) on v_mfma_f32_16x16x32_bf16: a k block is
-// two chunks (the lane's 8 values = its pieces of chunks 2 kb and 2 kb + 1; the weight planes are laid out in the same order).  The row
-// registers are refilled with the next tile's chunks as soon as they have been split (the state chunks after the epilogue, which compares
-// with them), the activation is a template parameter and every select that hipcc could turn into a branch is arithmetic.
-#ifndef TB_B6_WAVES
-#define TB_B6_WAVES 2
-#endif
+// ---- the forward Dense on the bf16 matrix cores ---------------------------------------------------------------------------------------
+// The matrix core is fed TRANSPOSED: the weights are the A operand, the input rows the B operand, so the result leaves lane (c, g) holding
+// Y[row c][16 ct + 4 g .. + 3] - four CONSECUTIVE columns of its own row: output, old state and stores share the row-major 16-byte layout.
+// A tile is 16 rows a wave, lane (c, g) = row c, 16-byte pieces at columns 16 q + 4 g; on v_mfma_f32_16x16x32_bf16 a k block is two chunks
+// (the lane's 8 values = its pieces of chunks 2 kb and 2 kb + 1; the weight planes are laid out in the same order).  The row registers are
+// refilled with the next tile's chunks as soon as they have been split (the state chunks after the epilogue, which compares with them),
+// the activation is a template parameter and every select that hipcc could turn into a branch is arithmetic.
+constexpr int TB_B6_WAVES = 2;           // waves per SIMD the register allocation is held to: one 8-wave workgroup per CU
 // One wait per trip.  hipcc counts a wave's loads and stores in one in-order counter and, with a store pending, waits for everything
 // issued before it - so a tile's stores directly in front of the next tile's first wait cost their whole round trip every trip (the
-// kernels above).  Here a trip is: wait for the tile's rows (requested a whole trip ago) -> split ALL of them to bf16 (60 registers)
+// f32 kernels this one replaced).  Here a trip is: wait for the tile's rows (requested a whole trip ago) -> split ALL of them to bf16 (60 registers)
 // and keep the state chunks for the predicate -> request the next tile's rows -> store the PREVIOUS tile's output (its activated values
 // waited in 16 registers) -> products -> activation, statistics, predicate.  Nothing the next wait covers is younger than most of a trip.
 template <int SQ, int ACT, bool ADD>
 __device__ __forceinline__ void train_fwd_b6_body(const TrainFwdArgs &a, const int bid, const int nblk) {
-    TB_MARK(0); TB_BLOCK_TIME(0);
     if (gate_closed(a.gate)) return;
     constexpr int XQ = ADD ? 0 : 2;                     // 16-column chunks of the constants line (ADD: none - TrainFwdArgs::addend stands in for their product)
     constexpr int NCT = SQ, HP = 16 * NCT, NQ = 2 * SQ + XQ, NKB = NQ / 2;
@@ -558,7 +355,6 @@ __device__ __forceinline__ void train_fwd_b6_body(const TrainFwdArgs &a, const i
     __syncthreads();                                     // (rowtab lives in `red`)
     for (int h = tid; h < HP; h += 64 * TB_WAVES) bias_l[h] = h < a.H ? a.bf[h] : 0.0f;
     __syncthreads();
-    TB_MARK(1);
 
     // windows of exactly the arrays' sizes: the rows past M of the last tile are out of range by themselves (they read 0), no select per load
     const __amdgpu_buffer_rsrc_t r_s = buf_rsrc_n(a.state, (unsigned)a.M * (unsigned)a.ld_state * 4u), r_a = buf_rsrc_n(a.agg, (unsigned)a.M * (unsigned)a.ld_agg * 4u),
@@ -590,7 +386,6 @@ __device__ __forceinline__ void train_fwd_b6_body(const TrainFwdArgs &a, const i
         }
     };
     const int t_step = nblk * TB_WAVES;
-    int trip_ = 0; (void)trip_;
     fetch(bid * TB_WAVES + wave);
     const u32x4 *Wv = reinterpret_cast<const u32x4 *>(Wl) + lane;
     f32x4 vP[NCT];                                      // the previous tile's output, stored one trip late
@@ -601,7 +396,6 @@ __device__ __forceinline__ void train_fwd_b6_body(const TrainFwdArgs &a, const i
     for (int t = bid * TB_WAVES + wave; t < n_tiles; t += t_step) {
         const int row = 16 * t + c;
         const bool in = row < a.M;
-        TB_STAMP(0);
         u32x4 xh[NKB], xm[NKB], xl[NKB];
         f32x4 old[SQ];
 #pragma unroll
@@ -624,7 +418,6 @@ __device__ __forceinline__ void train_fwd_b6_body(const TrainFwdArgs &a, const i
             __builtin_amdgcn_raw_buffer_store_b128(bits, r_y, inP ? offP + (int)((16u * ct + 4u * g) * 4u) : (int)BUF_OFF, 0, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
-        TB_STAMP_DEP(1, xh[NKB - 1]);
         // products in stages of (k block, CTG column tiles): a stage's weight fragments (3 planes x CTG) are read from LDS one stage ahead,
         // and inside a stage consecutive MFMAs go to different accumulators (left alone hipcc builds chains of six dependent MFMAs with
         // an LDS round trip in front of each: 14 000 cycles per tile)
@@ -651,7 +444,6 @@ __device__ __forceinline__ void train_fwd_b6_body(const TrainFwdArgs &a, const i
             __builtin_amdgcn_sched_barrier(0);
         }
         asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
-        TB_STAMP_DEP(2, acc[NCT - 1]);
         // (packed f32 arithmetic: two values an instruction; the rows past M of the last tile read zeros - their outputs are not stored and
         // `mask` / `in` keep them out of the statistics and the predicate)
         f32x4 d2v = {0.f, 0.f, 0.f, 0.f}, n2v = {0.f, 0.f, 0.f, 0.f};
@@ -661,7 +453,7 @@ __device__ __forceinline__ void train_fwd_b6_body(const TrainFwdArgs &a, const i
         for (int ct = 0; ct < NCT; ++ct) {
             f32x4 v = acc[ct];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = (TB_ABL & 16) ? v[e] : activate_b6<ACT>(v[e]);       // (H == 16 SQ: the launcher checks; a column mask here becomes a branch per element)
+            for (int e = 0; e < 4; ++e) v[e] = activate_b6<ACT>(v[e]);       // (H == 16 SQ: the launcher checks; a column mask here becomes a branch per element)
             vP[ct] = v;
             { const f32x4 dv = (v - *reinterpret_cast<const f32x4 *>(shift_l + 16 * ct + 4 * g)) * mask4; cs1[ct] += dv; cs2[ct] = fma4(dv, dv, cs2[ct]); }
             { const f32x4 dd = v - old[ct]; d2v = fma4(dd, dd, d2v); n2v = fma4(old[ct], old[ct], n2v); }
@@ -671,10 +463,7 @@ __device__ __forceinline__ void train_fwd_b6_body(const TrainFwdArgs &a, const i
         n2 += __shfl_xor(n2, 16, 64); n2 += __shfl_xor(n2, 32, 64);
         any |= (in && sqrtf(d2) > a.thr * sqrtf(n2)) ? 1 : 0;
         offP = (int)((unsigned)row * (unsigned)a.ldy * 4u); inP = in;
-        TB_STAMP_DEP(3, vP[NCT - 1]);
-        TB_TRIP_END();
     }
-    TB_MARK(2);
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) {                 // the last tile's output
         const u32x4 bits = {__float_as_uint(vP[ct][0]), __float_as_uint(vP[ct][1]), __float_as_uint(vP[ct][2]), __float_as_uint(vP[ct][3])};
@@ -696,7 +485,6 @@ __device__ __forceinline__ void train_fwd_b6_body(const TrainFwdArgs &a, const i
         for (int w_ = 0; w_ < TB_WAVES; ++w_) tsum += red[w_ * 2 * HP + tid];
         a.stat_part[(size_t)bid * 2 * HP + tid] = tsum;
     }
-    TB_MARK(3); TB_BLOCK_TIME(1);
     if (a.pred_flag && tid == 0) {
         if (any_s) atomicOr(a.pred_flag, 1);
         if (bid == 0 && a.pred_k) *a.pred_k = a.pred_kval;
@@ -717,9 +505,6 @@ inline size_t train_fwd_b6_lds() {
     constexpr int NQ = 2 * SQ + (ADD ? 0 : 2);
     return (size_t)(3 * (NQ / 2) * SQ * 64 * 8 * 2) + (size_t)(16 * SQ + TB_WAVES * 2 * 16 * SQ + 16 * SQ + 16 * NQ) * sizeof(float);
 }
-
-template <int SQ, int NCT>
-inline size_t train_fwd_lds() { return (size_t)(16 * (2 * SQ + 2) * 16 * NCT + 16 * NCT + TB_WAVES * 2 * 16 * NCT + 16 * NCT + 16 * (2 * SQ + 2)) * sizeof(float); }
 
 // ---- backward: d loss / d [state | agg] through the first Dense and its training-mode BatchNormalization ------------------------
 //   dy[m, j]  = sum_h dZ[m, h] W[row_j, h]                      (j < S: state column j, else agg column j - S)
@@ -743,100 +528,6 @@ struct TrainBwdArgs {
                                           // iteration's output).  The kernel then does not read the state rows at all (256 of 1536 bytes per row).
 };
 
-template <int HQ, int NCT>                 // NCT = 2 S / 16 output column tiles
-__global__ void __launch_bounds__(64 * TB_WAVES, 4) k_train_bwd_dx(TrainBwdArgs a) {
-    constexpr int HP = 16 * NCT;           // = 2 S
-    constexpr int SQ = NCT / 2;            // 16-column tiles of one half (state | agg)
-    extern __shared__ __attribute__((aligned(16))) float tb_smem[];
-    float *Wl = tb_smem;                    // [4 HQ k-steps][4 g][16 c][NCT]
-    float *coef = tb_smem + 16 * HQ * HP;   // [4][HP]: Ac, Cc, m1, mean
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int c = lane & 15, g = lane >> 4;
-    const int S = a.S;                      // == 8 NCT: the halves are whole 16-column tiles
-    for (int i = tid; i < 16 * HQ * HP; i += 64 * TB_WAVES) {
-        const int k = i / HP, j = i % HP;                                   // k = dZ column h, j = output column
-        const int row = j < S ? a.wrow_state + j : a.wrow_agg + (j - S);
-        const float v = k < a.H ? a.W[(size_t)row * a.ldw + k] : 0.0f;
-        const int q = k >> 4, rem = k & 15, gg = rem >> 2, e = rem & 3;
-        Wl[(((4 * q + e) * 4 + gg) * 16 + (j & 15)) * NCT + (j >> 4)] = v;
-    }
-    for (int j = tid; j < HP; j += 64 * TB_WAVES) {
-        float Ac = 1.0f, Cc = 0.0f, M1 = 0.0f, Mu = 0.0f;      // dx = Ac (dy - m1) + Cc (x - mean): the centred form - an Ac dy + Cc x + Bc with
-        if (a.gamma) {                                          // Bc = -Ac m1 - Cc mean rounds ONE constant per column whose error every row shares
-            const int k = j < S ? a.wrow_state + j : a.wrow_agg + (j - S);
-            const float rstd = 1.0f / sqrtf(a.var[k] + a.eps);
-            Ac = a.gamma[k] * rstd; Cc = -Ac * rstd * a.m2[k]; M1 = a.m1[k]; Mu = a.mean[k];
-            if (a.defer_state_bn && j < S) { Cc = 0.0f; M1 = 0.0f; Mu = 0.0f; }       // (see TrainBwdArgs::defer_state_bn)
-        }
-        coef[j] = Ac; coef[HP + j] = Cc; coef[2 * HP + j] = M1; coef[3 * HP + j] = Mu;
-    }
-    __syncthreads();
-    const __amdgpu_buffer_rsrc_t r_z = buf_rsrc(a.dZ), r_y = buf_rsrc(a.Y), r_s = buf_rsrc(a.defer_state_bn ? nullptr : a.state), r_a = buf_rsrc(a.agg), r_o = buf_rsrc(a.dx),
-                                 r_rs = buf_rsrc(a.agg_row_scale);
-    const int n_tiles = (a.M + 15) >> 4;
-#pragma unroll 1
-    for (int t = blockIdx.x * TB_WAVES + wave; t < n_tiles; t += gridDim.x * TB_WAVES) {
-        const int row = 16 * t + c;
-        const bool in = row < a.M;
-        // every load of the tile is issued here: the dZ row and - for the BatchNorm term - the layer's inputs x = [state | agg] of the
-        // same row, all as 16-byte chunks (columns 16 q + 4 g ..): the transposed product (see k_train_fwd) returns dy in that layout
-        f32x4 A[HQ], X[NCT], Yv[HQ];
-#pragma unroll
-        for (int q = 0; q < HQ; ++q) A[q] = buf_ld_f32x4(r_z, in ? ((unsigned)row * (unsigned)a.ldz + 16u * q + 4u * g) * 4u : BUF_OFF);
-        if (a.Y) {
-#pragma unroll
-            for (int q = 0; q < HQ; ++q) Yv[q] = buf_ld_f32x4(r_y, in ? ((unsigned)row * (unsigned)a.ldz + 16u * q + 4u * g) * 4u : BUF_OFF);
-        }
-        if (a.gamma) {
-#pragma unroll
-            for (int q = 0; q < SQ; ++q) {
-                X[q] = buf_ld_f32x4(r_s, in ? ((unsigned)row * (unsigned)a.ld_state + 16u * q + 4u * g) * 4u : BUF_OFF);
-                X[SQ + q] = buf_ld_f32x4(r_a, in ? ((unsigned)row * (unsigned)a.ld_agg + 16u * q + 4u * g) * 4u : BUF_OFF);
-            }
-        }
-        const float rs = a.agg_row_scale ? buf_ld_f32(r_rs, in ? (unsigned)row * 4u : BUF_OFF) : 1.0f;
-        if (a.Y) {
-#pragma unroll
-            for (int q = 0; q < HQ; ++q)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) A[q][e] *= activate_grad_from_output(a.act, Yv[q][e]);
-        }
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {                       // state half, then agg half (16 accumulator registers at a time)
-            f32x4 acc[SQ];
-#pragma unroll
-            for (int u = 0; u < SQ; ++u) acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int q = 0; q < HQ; ++q) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    BFrag<NCT> w;
-                    w.load(Wl + (((4 * q + e) * 4 + g) * 16 + c) * NCT);
-#pragma unroll
-                    for (int u = 0; u < SQ; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.v[half * SQ + u], A[q][e], acc[u], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            TB_MFMA_DRAIN();
-#pragma unroll
-            for (int u = 0; u < SQ; ++u) {
-                const int j0 = 16 * (half * SQ + u) + 4 * g;            // this lane's four output columns
-                f32x4 v = acc[u];
-                if (a.gamma) {
-                    const f32x4 Ac = *reinterpret_cast<const f32x4 *>(coef + j0), Cc = *reinterpret_cast<const f32x4 *>(coef + HP + j0),
-                                M1 = *reinterpret_cast<const f32x4 *>(coef + 2 * HP + j0), Mu = *reinterpret_cast<const f32x4 *>(coef + 3 * HP + j0);
-                    const f32x4 x = X[half * SQ + u];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaf(Ac[e], v[e] - M1[e], Cc[e] * (x[e] - Mu[e]));
-                }
-                if (half == 1) v *= rs;
-                const u32x4 bits = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
-                __builtin_amdgcn_raw_buffer_store_b128(bits, r_o, in ? (int)(((unsigned)row * (unsigned)a.ld_dx + (unsigned)j0) * 4u) : (int)BUF_OFF, 0, 0);
-            }
-        }
-    }
-}
-
 template <int ACT> __device__ __forceinline__ float activate_grad1(float y) {          // act'(z) from y = act(z), as kernels_train.hpp's switch
     if (ACT == GNN_ACT_RELU) return y > 0.0f ? 1.0f : 0.0f;
     if (ACT == GNN_ACT_SELU) return y > 0.0f ? 1.0507009873554805f : y + 1.0507009873554805f * 1.6732632423543772f;
@@ -847,10 +538,10 @@ template <int ACT> __device__ __forceinline__ float activate_grad1(float y) {   
     return 1.0f;
 }
 
-// k_train_bwd_dx on the bf16 matrix cores (the three-term split of k_train_fwd_b6: dZ rows are split as they arrive, W^T sits in LDS as
-// three bf16 planes in fragment order).  256-thread workgroups, two per CU; every row register is refilled with the NEXT tile's piece as
-// soon as its last reader has issued (dZ and Y after the split, the layer inputs x after the BatchNorm term of their column tile), so a
-// wave keeps 16 KB requested for a whole trip.  `a.Y == NULL` (dZ already formed): instantiate with ACT = LINEAR - the loads of Y then
+// d loss / d [state | agg] on the bf16 matrix cores (the three-term split of k_train_fwd_b6: dZ rows are split as they arrive, W^T sits in LDS
+// as three bf16 planes in fragment order, the transposed product returns dy in the row-major layout of the rows).  256-thread workgroups,
+// two per CU; every row register is refilled with the NEXT tile's piece as soon as its last reader has issued (dZ and Y after the split,
+// the layer inputs x after the BatchNorm term of their column tile), so a wave keeps 16 KB requested for a whole trip.  `a.Y == NULL` (dZ already formed): instantiate with ACT = LINEAR - the loads of Y then
 // fall out of range and return zeros, act'(0) = 1; no BatchNormalization: the x loads fall out of range the same way (Cc = m1 = mean = 0).
 template <int HQ, int ACT>
 __device__ __forceinline__ void train_bwd_dx_b6_body(const TrainBwdArgs &a, const int bid, const int nblk) {
@@ -884,8 +575,8 @@ __device__ __forceinline__ void train_bwd_dx_b6_body(const TrainBwdArgs &a, cons
         }
     }
     for (int j = tid; j < HP; j += 64 * NW) {
-        float Ac = 1.0f, Cc = 0.0f, M1 = 0.0f, Mu = 0.0f;      // (the centred form: see k_train_bwd_dx)
-        if (a.gamma) {
+        float Ac = 1.0f, Cc = 0.0f, M1 = 0.0f, Mu = 0.0f;      // dx = Ac (dy - m1) + Cc (x - mean): the centred form - an Ac dy + Cc x + Bc with
+        if (a.gamma) {                                          // Bc = -Ac m1 - Cc mean rounds ONE constant per column whose error every row shares
             const int k = j < S ? a.wrow_state + j : a.wrow_agg + (j - S);
             const float rstd = 1.0f / sqrtf(a.var[k] + a.eps);
             Ac = a.gamma[k] * rstd; Cc = -Ac * rstd * a.m2[k]; M1 = a.m1[k]; Mu = a.mean[k];
@@ -995,9 +686,6 @@ __global__ void __launch_bounds__(256, 2) k_train_bwd_dx_b6_types(TypeLaunch<Tra
 template <int HQ>
 inline size_t train_bwd_b6_lds() { return (size_t)(3 * ((HQ + 1) / 2) * 2 * HQ * 64 * 8 * 2) + (size_t)(4 * 32 * HQ) * sizeof(float); }
 
-template <int HQ, int NCT>
-inline size_t train_bwd_lds() { return (size_t)(16 * HQ * 16 * NCT + 4 * 16 * NCT) * sizeof(float); }
-
 // ---- weight gradient of the first Dense at large M: P = X^T dZ on the matrix cores, straight from memory ------------------------------------
 // X = [state | agg | constants] (the virtual concatenation, never materialised), dZ = G (.) act'(Y) formed as the rows arrive.  The
 // contraction runs over ROWS: for v_mfma_f32_16x16x4_f32 lane (c, g) supplies A[c][g] and B[g][c], i.e. one element of row r0 + g of each
@@ -1007,7 +695,8 @@ inline size_t train_bwd_lds() { return (size_t)(16 * HQ * 16 * NCT + 4 * 16 * NC
 // (2 SQ + 2) x SQ accumulator tiles (160 registers at S = 64) for its share of the rows, PD steps of loads in flight; the four waves' tiles
 // meet in LDS in wave order at the end and leave as one partial per workgroup in the layout of k_dense_grad_allk (k_reduce_partials /
 // k_first_layer_param_grads take it from there).  The constants line carries a 1 behind its Kc < 32 columns: its row of P is q = colsum(dZ).
-// 1 M rows, S = 64: k_dense_grad_allk 479 us + k_act_grad 127 us -> this kernel (profiles/r03_notes.txt).
+// 1 M rows, S = 64: k_dense_grad_allk 479 us + k_act_grad 127 us -> this kernel (profiles/r03_notes.txt).  The step runs it at S = 16
+// (k_train_wgrad<1>, dZ already formed: Y == NULL reads zeros, act = LINEAR); S = 32 / 64 take the bf16-split k_train_wgrad_b6 below.
 struct TrainWgradArgs {
     int M, rows_per_wg;
     const float *G, *Y; int act;          // [M, S] each
@@ -1036,9 +725,6 @@ template <> __device__ __forceinline__ Piece<2> ld_piece<2>(__amdgpu_buffer_rsrc
     typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
     const u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0);
     Piece<2> p; p.v[0] = __uint_as_float(t[0]); p.v[1] = __uint_as_float(t[1]); return p; }
-template <> __device__ __forceinline__ Piece<4> ld_piece<4>(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-    Piece<4> p; p.v[0] = __uint_as_float(t[0]); p.v[1] = __uint_as_float(t[1]); p.v[2] = __uint_as_float(t[2]); p.v[3] = __uint_as_float(t[3]); return p; }
 
 template <int SQ>
 __global__ void __launch_bounds__(256, 2) k_train_wgrad(TrainWgradArgs a) {
@@ -1129,8 +815,8 @@ __global__ void __launch_bounds__(256, 2) k_train_wgrad(TrainWgradArgs a) {
     }
 }
 
-// The 32x32 tiles of a workgroup's four waves -> its partial P (LDS, waves in order) -> a.part, by weight row (shared by the f32 and the
-// bf16-split forms of the kernel: v_mfma_f32_32x32x2_f32 and v_mfma_f32_32x32x16_bf16 leave their results in the same registers).
+// The 32x32 tiles of a workgroup's four waves -> its partial P (LDS, waves in order) -> a.part, by weight row (v_mfma_f32_32x32x16_bf16
+// leaves its results where v_mfma_f32_32x32x2_f32 does: lane (i = lane % 32, kk = lane / 32) holds tile rows 8 (v / 4) + 4 kk + v % 4 of column i).
 template <int NB, int XT = 1>                 // XT: 32-column tiles of the constants line (1: the 128-byte line; 2: 256 bytes, k_train_wgrad_b6<.., XT = 2>)
 __device__ __forceinline__ void wgrad32_store(const TrainWgradArgs &a, f32x16 (&acc)[2 * NB + XT][NB], float *Ps, const int bid) {
     constexpr int S = 32 * NB, RT = 2 * NB + XT, KV = 2 * S + 32 * XT;
@@ -1170,72 +856,6 @@ __device__ __forceinline__ void wgrad32_store(const TrainWgradArgs &a, f32x16 (&
     }
 }
 
-// The same contraction on v_mfma_f32_32x32x2_f32 (S = 32 NB): 156 TFLOP/s sustained against 104 .. 126 for the 16x16x4 form
-// (scripts/micro/mfma_peak.hip), and the weight gradient is the one dense training kernel that is almost all MFMA.  Lane (i = lane % 32,
-// kk = lane / 32) supplies one element of row r0 + kk of each operand: it loads the NB consecutive floats  X[r0 + kk][NB i ..]  (a
-// wave's load = two whole rows) and uses value e as the A operand of row tile e (tile row i is input column NB i + e); dZ pieces serve
-// as B operands the same way (tile column j is dZ column NB j + f).  A workgroup step is 8 rows, PD steps of loads in flight.
-#ifndef TB_WG32_PD
-#define TB_WG32_PD 6
-#define TB_WG32_WAVES 2
-#endif
-template <int NB, int ACT>
-__global__ void __launch_bounds__(256, TB_WG32_WAVES) k_train_wgrad32(TrainWgradArgs a) {
-    constexpr int S = 32 * NB, RT = 2 * NB + 1, KV = 2 * S + 32, PD = TB_WG32_PD;
-    __shared__ float Ps[KV * S];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = lane & 31, kk = lane >> 5;
-    const int m_beg = blockIdx.x * a.rows_per_wg, m_end = min(a.M, m_beg + a.rows_per_wg);
-    const int n_steps = (max(m_end - m_beg, 0) + 7) >> 3;            // a workgroup step = 8 rows: 2 per wave
-    const __amdgpu_buffer_rsrc_t r_g = buf_rsrc(a.G), r_y = buf_rsrc(a.Y), r_s = buf_rsrc(a.state), r_a = buf_rsrc(a.agg), r_c = buf_rsrc(a.xc);
-    f32x16 acc[RT][NB];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int f = 0; f < NB; ++f)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[rt][f][v] = 0.0f;
-    float mu_s[NB], mu_a[NB], mu_c;                     // the means of this lane's columns (0 without BatchNormalization, for the line's 1 and its padding)
-#pragma unroll
-    for (int e = 0; e < NB; ++e) { mu_s[e] = a.mean ? a.mean[a.wrow_state + NB * i + e] : 0.0f; mu_a[e] = a.mean ? a.mean[a.wrow_agg + NB * i + e] : 0.0f; }
-    { const int wr = wgrad_wrow(a, S, 2 * S + i); mu_c = (a.mean && wr >= 0) ? a.mean[wr] : 0.0f; }
-    struct Step { Piece<NB> xs, xa, gz, y; Piece<1> xc; };
-    Step buf[PD];
-    auto fetch = [&](Step &b, int s) {
-        const int row = m_beg + 8 * s + 2 * wave + kk;
-        const bool ok = s < n_steps && row < m_end;
-        const unsigned off = ok ? ((unsigned)row * (unsigned)S + (unsigned)(NB * i)) * 4u : BUF_OFF;
-        b.gz = ld_piece<NB>(r_g, off); b.y = ld_piece<NB>(r_y, off);
-        b.xs = ld_piece<NB>(r_s, off); b.xa = ld_piece<NB>(r_a, off);
-        b.xc = ld_piece<1>(r_c, ok ? ((unsigned)row * 32u + (unsigned)i) * 4u : BUF_OFF);
-    };
-#pragma unroll
-    for (int u = 0; u < PD; ++u) fetch(buf[u], u);
-#pragma unroll 1
-    for (int s0 = 0; s0 < n_steps; s0 += PD) {
-#pragma unroll
-        for (int u = 0; u < PD; ++u) {
-            {   // (no branch on s0 + u < n_steps, no switch on the activation: rows past the end load zeros, and hipcc drains the whole
-                //  load queue - s_waitcnt vmcnt(0) - wherever two blocks of the loop body meet)
-                Step &b = buf[u];
-                float dz[NB];
-#pragma unroll
-                for (int f = 0; f < NB; ++f) dz[f] = b.gz.v[f] * activate_grad1<ACT>(b.y.v[f]);
-#pragma unroll
-                for (int e = 0; e < NB; ++e)
-#pragma unroll
-                    for (int f = 0; f < NB; ++f) {
-                        acc[e][f] = __builtin_amdgcn_mfma_f32_32x32x2f32(b.xs.v[e] - mu_s[e], dz[f], acc[e][f], 0, 0, 0);
-                        acc[NB + e][f] = __builtin_amdgcn_mfma_f32_32x32x2f32(b.xa.v[e] - mu_a[e], dz[f], acc[NB + e][f], 0, 0, 0);
-                    }
-#pragma unroll
-                for (int f = 0; f < NB; ++f) acc[2 * NB][f] = __builtin_amdgcn_mfma_f32_32x32x2f32(b.xc.v[0] - mu_c, dz[f], acc[2 * NB][f], 0, 0, 0);
-                fetch(b, s0 + u + PD);
-            }
-        }
-    }
-    wgrad32_store<NB>(a, acc, Ps, blockIdx.x);
-}
 
 template <int J0, int J1, typename F> __device__ __forceinline__ void static_for(F &&f) {       // f(integral_constant<int, J0>) ... : loop indices that are constant expressions
     if constexpr (J0 < J1) { f(std::integral_constant<int, J0>{}); static_for<J0 + 1, J1>(f); }
@@ -1250,10 +870,10 @@ template <int OFF, typename V4> __device__ __forceinline__ void lds_read_b128(V4
 template <typename T> __device__ __forceinline__ void asm_tie(T &x) { asm volatile("" : "+v"(x)); }       // no instruction: orders the uses of x behind the volatile statements before it
 template <int OFF> __device__ __forceinline__ void lds_read_f32(float &v, unsigned addr) { asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF)); }
 
-// ... and on the bf16 matrix cores (round 5).  scripts/micro/mfma_bf16_valu_overlap.hip: on gfx950 a SIMD issues EITHER a matrix instruction
+// The same contraction for S = 32 / 64 on the bf16 matrix cores (round 5).  scripts/micro/mfma_bf16_valu_overlap.hip: on gfx950 a SIMD issues EITHER a matrix instruction
 // OR a VALU instruction - a wave's own VALU work does not run in the shadow of its MFMAs, nor does the other wave's (24 MFMAs + 96 v_fma a
 // trip: 516 ns in phases, 533 interleaved, 589 on specialised waves, against 336 + 212 alone) - so a dense kernel costs the SUM of its
-// matrix and VALU cycles, and k_train_wgrad32 is 64 cycles of v_mfma_f32_32x32x2_f32 for every 2 rows of every 32 x 32 tile: 5 120 cycles
+// matrix and VALU cycles, and the f32-input form of this contraction is 64 cycles of v_mfma_f32_32x32x2_f32 for every 2 rows of every 32 x 32 tile: 5 120 cycles
 // per 16 rows of S = 64.  v_mfma_f32_32x32x16_bf16 contracts 16 rows in 32 cycles: with both operands split into three bf16 terms
 // (split3_pk: exact, the products' sum is an f32 chain's to 2^-24) the same 16 rows cost 60 x 32 = 1 920 matrix cycles + ~1 400 of VALU.
 // Lane (i = lane % 32, kg = lane / 32) supplies 8 consecutive k of a tile row: the NB floats X[r0 + 8 kg + j][NB i ..] of EIGHT rows (j = 0
@@ -1329,10 +949,7 @@ __device__ __forceinline__ void train_wgrad_b6_body(const TrainWgradArgs &a, con
     auto split8 = [&](const float (&x)[8], u32x4 &h, u32x4 &m, u32x4 &l) {
         unsigned hh[4], mm[4], ll[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (TB_ABL & 64) { hh[q] = __float_as_uint(x[2 * q]); mm[q] = __float_as_uint(x[2 * q + 1]); ll[q] = hh[q] ^ mm[q]; }      // (ablation: no split)
-            else split3_pk((f32x2){x[2 * q], x[2 * q + 1]}, hh[q], mm[q], ll[q]);
-        }
+        for (int q = 0; q < 4; ++q) split3_pk((f32x2){x[2 * q], x[2 * q + 1]}, hh[q], mm[q], ll[q]);
         h = (u32x4){hh[0], hh[1], hh[2], hh[3]}; m = (u32x4){mm[0], mm[1], mm[2], mm[3]}; l = (u32x4){ll[0], ll[1], ll[2], ll[3]};
     };
     // Issue order: [line of s + 2 | rows of s + D] at the top of step s, the prologue in the same order - so that at the top of a step the
@@ -1385,12 +1002,7 @@ __device__ __forceinline__ void train_wgrad_b6_body(const TrainWgradArgs &a, con
             split8(x, xh, xm, xl);
             // small terms first; consecutive MFMAs go to different accumulators
 #define MF(xp_, zp_) _Pragma("unroll") for (int f = 0; f < NB; ++f) acc[rt][f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(B8(xp_), B8(zp_[f]), acc[rt][f], 0, 0, 0)
-            if (TB_ABL & 32) {           // (ablation of scripts/micro/rowgemm_bench.hip: no products)
-#pragma unroll
-                for (int f = 0; f < NB; ++f) acc[rt][f][0] += __uint_as_float(xl[0] ^ xm[1] ^ xh[2] ^ zh[f][3] ^ zm[f][0] ^ zl[f][1]);
-            } else {
-                MF(xl, zh); MF(xh, zl); MF(xm, zm); MF(xm, zh); MF(xh, zm); MF(xh, zh);
-            }
+            MF(xl, zh); MF(xh, zl); MF(xm, zm); MF(xm, zh); MF(xh, zm); MF(xh, zh);
 #undef MF
         }
     }
@@ -1656,7 +1268,7 @@ inline size_t train_wgrad_dx_b6_lds() {
 // iteration t - 1 begins with  dZ_{t-1} = G_{t-1} (.) act'(Y_{t-1}),  Y_{t-1} = state_t - formed twice, by the weight-gradient kernel and by
 // the input-gradient kernel, each reading G and Y (512 bytes per row each).  Here the aggregate's epilogue reads the state_t row once (it
 // has the node's output row in registers anyway) and
-//   * adds what k_train_bwd_dx left out of the state half's BatchNorm input gradient (TrainBwdArgs::defer_state_bn: that kernel then never
+//   * adds what k_train_bwd_dx_b6 left out of the state half's BatchNorm input gradient (TrainBwdArgs::defer_state_bn: that kernel then never
 //     reads state_t):  G = dx_state' + Adj . dx_agg + Cc (state_t - mean) - Ac m1,   Ac = gamma rstd,  Cc = - Ac rstd m2  (iteration t's);
 //   * writes dZ_{t-1} = G (.) act'(state_t).
 // The two dense kernels of iteration t - 1 then read dZ alone (their LINEAR instances, Y = NULL): per row and iteration 256 bytes more
@@ -1711,7 +1323,7 @@ k_aggregate_dz(int n_dst, const int *__restrict__ rowptr, const int *__restrict_
 //                     read once as 16-byte pieces; per-workgroup partials in the layout k_reduce_partials / k_first_layer_param_grads
 //                     take ([K x T] then [T]), row groups and workgroups added in a fixed order;
 //   k_head_dx<T>    - d loss / d state[m, j] = Ac_j (sum_h dZ[m, h] W[j, h] - m1_j) + Cc_j (state[m, j] - mean_j)  (the Dense input gradient with the
-//                     BatchNorm input gradient as per-column coefficients, as k_train_bwd_dx), WRITTEN into the state gradient: every
+//                     BatchNorm input gradient as per-column coefficients, as k_train_bwd_dx_b6), WRITTEN into the state gradient: every
 //                     row is an output row, so nothing is scattered or zero-filled.  The label columns' input gradient is never needed.
 struct HeadArgs {
     int M, S, L, T;
@@ -1804,7 +1416,7 @@ __global__ void __launch_bounds__(256) k_head_dx(HeadArgs a) {
     const int lpr = ns4 <= 4 ? 4 : ns4 <= 8 ? 8 : 16;
     const int l4 = threadIdx.x % lpr, groups = 256 / lpr;
     const bool act = l4 < ns4;
-    float w[4][T], Ac[4], Cc[4], M1[4], Mu[4];          // (the centred form: see k_train_bwd_dx)
+    float w[4][T], Ac[4], Cc[4], M1[4], Mu[4];          // (the centred form: see k_train_bwd_dx_b6)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const int j = 4 * l4 + e;

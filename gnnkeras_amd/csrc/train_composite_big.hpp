@@ -296,7 +296,6 @@ struct CBig {
 bool composite_big_applies(const gnn_train_args_t &ta, int N, int S, int W_comp, int *XT_out) {
     const gnn_loop_args_t &a = ta.loop;
     if (!composite_big_enabled() || N < train_big_min_nodes() || (S != 32 && S != 64)) return false;
-    if (!train_bf16x6_enabled() || !train_wgrad_b6_enabled() || !train_dz_enabled() || !train_wgrad_enabled()) return false;
     if ((size_t)N * 2 * S * 4 >= 0xFFFFFFF0ull || (size_t)a.adjacency.nnz * 4 >= 0xFFFFFFF0ull) return false;       // (4 GiB buffer windows)
     int XT = 1;
     for (int t = 0; t < a.n_types; ++t) {

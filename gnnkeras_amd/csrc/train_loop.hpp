@@ -107,11 +107,6 @@ inline int train_big_min_nodes() {
     return v;
 }
 constexpr int BIG_AGG_BLOCKS = 4096, BIG_FWD_BLOCKS = 1024, BIG_WGRAD_BLOCKS = 512, BIG_HEAD_BLOCKS = 2048;
-inline bool train_wgrad_enabled() {       // GNN_TRAIN_WGRAD=0: the round-2 weight-gradient kernels (k_act_grad + k_dense_grad_allk) at large M too
-    int v = -1;      // (read at every call: tests switch it inside one process)
-    { const char *e = getenv("GNN_TRAIN_WGRAD"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v != 0;
-}
 // The persistent small-graph kernels need every workgroup resident: one 64-node tile per CU (GNN_TRAIN_SMALL=0 switches them off).
 inline bool train_small_enabled() {
     int v = -1;      // (read at every call: tests switch it inside one process)
@@ -533,19 +528,8 @@ int rows_stats(const int *gate, const float *X, int ld, int F, int M, float *par
     return 0;
 }
 
-template <int SQ>
-int launch_train_fwd_sq(const gnn::TrainFwdArgs &fa, int grid, hipStream_t st) {
-    gnn::k_train_fwd<SQ, SQ><<<grid, 64 * gnn::TB_WAVES, gnn::train_fwd_lds<SQ, SQ>(), st>>>(fa);
-    return hipGetLastError() == hipSuccess ? 0 : fail("k_train_fwd launch failed");
-}
-
-// GNN_TRAIN_BF16X6=0: the exact-f32 MFMA kernels (k_train_fwd ..) instead of the three-term bf16 split on the bf16 matrix cores
-inline bool train_bf16x6_enabled() {
-    int v = -1;      // (read at every call: tests switch it inside one process)
-    { const char *e = getenv("GNN_TRAIN_BF16X6"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v != 0;
-}
-
+// ---- the large-graph step's dense kernels (kernels_train_big.hpp): one instance per shape, a shape without one is an error ----------------
+// the first Dense of the state network (H == S)
 template <int SQ, int ACT>
 int launch_train_fwd_b6_sa(const gnn::TrainFwdArgs &fa, int grid, hipStream_t st) {
     static bool attr = false;
@@ -569,182 +553,100 @@ int launch_train_fwd_b6_s(const gnn::TrainFwdArgs &fa, int grid, hipStream_t st)
         case GNN_ACT_SIGMOID: return launch_train_fwd_b6_sa<SQ, GNN_ACT_SIGMOID>(fa, grid, st);
         case GNN_ACT_ELU: return launch_train_fwd_b6_sa<SQ, GNN_ACT_ELU>(fa, grid, st);
         case GNN_ACT_SOFTPLUS: return launch_train_fwd_b6_sa<SQ, GNN_ACT_SOFTPLUS>(fa, grid, st);
-        default: return -1;                            // (softmax state networks are not on the large-graph path)
+        default: return fail("k_train_fwd_b6: no instance for activation %d", fa.act);      // (softmax state networks are not on the large-graph path)
     }
 }
 
 int launch_train_fwd(const gnn::TrainFwdArgs &fa, int S, hipStream_t st, int *grid_out) {
-    if (train_bf16x6_enabled() && fa.H == S) {
-        const int n_tiles16 = (fa.M + 15) / 16;
-        const int grid = std::max(1, std::min(std::min(device_cus(), BIG_FWD_BLOCKS), cdiv(n_tiles16, gnn::TB_WAVES)));     // one 8-wave workgroup per CU (192 registers)
-        int rc = -1;
-        switch (S) {
-            case 16: rc = launch_train_fwd_b6_s<1>(fa, grid, st); break;
-            case 32: rc = launch_train_fwd_b6_s<2>(fa, grid, st); break;
-            case 64: rc = launch_train_fwd_b6_s<4>(fa, grid, st); break;
-            default: break;
-        }
-        if (rc >= 0) { *grid_out = grid; return rc; }
-    }
-    const int n_tiles = (fa.M + 15) / 16;
-    const int grid = std::max(1, std::min(std::min(2 * device_cus(), BIG_FWD_BLOCKS), cdiv(n_tiles, gnn::TB_WAVES)));
+    if (fa.H != S) return fail("k_train_fwd_b6: %d units for state width %d", fa.H, S);
+    const int n_tiles16 = (fa.M + 15) / 16;
+    const int grid = std::max(1, std::min(std::min(device_cus(), BIG_FWD_BLOCKS), cdiv(n_tiles16, gnn::TB_WAVES)));     // one 8-wave workgroup per CU (192 registers)
     *grid_out = grid;
     switch (S) {
-        case 16: return launch_train_fwd_sq<1>(fa, grid, st);
-        case 32: return launch_train_fwd_sq<2>(fa, grid, st);
-        default: return launch_train_fwd_sq<4>(fa, grid, st);
+        case 16: return launch_train_fwd_b6_s<1>(fa, grid, st);
+        case 32: return launch_train_fwd_b6_s<2>(fa, grid, st);
+        case 64: return launch_train_fwd_b6_s<4>(fa, grid, st);
+        default: return fail("k_train_fwd_b6: no instance for state width %d", S);
     }
 }
 
-template <int HQ, int ACT>
-int launch_train_bwd_b6_ha(const gnn::TrainBwdArgs &ba, int grid, hipStream_t st) {
+// d loss / d [state | agg] from dZ (the LINEAR instance: the rows arrive with the activation's derivative applied)
+template <int HQ>
+int launch_train_bwd_dx_h(const gnn::TrainBwdArgs &ba, int grid, hipStream_t st) {
     static bool attr = false;
     const size_t lds = gnn::train_bwd_b6_lds<HQ>();
     if (!attr) {
-        if (hipFuncSetAttribute((const void *)gnn::k_train_bwd_dx_b6<HQ, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        if (hipFuncSetAttribute((const void *)gnn::k_train_bwd_dx_b6<HQ, GNN_ACT_LINEAR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return fail("k_train_bwd_dx_b6: cannot raise the dynamic LDS limit");
         attr = true;
     }
-    gnn::k_train_bwd_dx_b6<HQ, ACT><<<grid, 256, lds, st>>>(ba);
+    gnn::k_train_bwd_dx_b6<HQ, GNN_ACT_LINEAR><<<grid, 256, lds, st>>>(ba);
     return hipGetLastError() == hipSuccess ? 0 : fail("k_train_bwd_dx_b6 launch failed");
 }
 
-template <int HQ>
-int launch_train_bwd_b6_h(const gnn::TrainBwdArgs &ba, int grid, hipStream_t st) {
-    switch (ba.Y ? ba.act : GNN_ACT_LINEAR) {          // (dZ already formed: the kernel's Y loads fall out of range, act'(0) = 1)
-        case GNN_ACT_LINEAR: return launch_train_bwd_b6_ha<HQ, GNN_ACT_LINEAR>(ba, grid, st);
-        case GNN_ACT_RELU: return launch_train_bwd_b6_ha<HQ, GNN_ACT_RELU>(ba, grid, st);
-        case GNN_ACT_SELU: return launch_train_bwd_b6_ha<HQ, GNN_ACT_SELU>(ba, grid, st);
-        case GNN_ACT_TANH: return launch_train_bwd_b6_ha<HQ, GNN_ACT_TANH>(ba, grid, st);
-        case GNN_ACT_SIGMOID: return launch_train_bwd_b6_ha<HQ, GNN_ACT_SIGMOID>(ba, grid, st);
-        case GNN_ACT_ELU: return launch_train_bwd_b6_ha<HQ, GNN_ACT_ELU>(ba, grid, st);
-        case GNN_ACT_SOFTPLUS: return launch_train_bwd_b6_ha<HQ, GNN_ACT_SOFTPLUS>(ba, grid, st);
-        default: return -1;
+int launch_train_bwd_dx(const gnn::TrainBwdArgs &ba, int S, hipStream_t st) {
+    if (ba.Y || ba.H != S || ba.S != S || ba.ldz != S) return fail("k_train_bwd_dx_b6: the dZ form of a %d-unit layer only", S);
+    const int grid = std::max(1, std::min(2 * device_cus(), cdiv((ba.M + 15) / 16, 4)));       // 256-thread workgroups, two per CU
+    switch (S) {
+        case 16: return launch_train_bwd_dx_h<1>(ba, grid, st);
+        case 32: return launch_train_bwd_dx_h<2>(ba, grid, st);
+        case 64: return launch_train_bwd_dx_h<4>(ba, grid, st);
+        default: return fail("k_train_bwd_dx_b6: no instance for state width %d", S);
     }
 }
 
-// the weight gradient on v_mfma_f32_32x32x2_f32 (exact f32 like k_train_wgrad; S = 32 / 64): true when launched
+// the first layer's weight gradient P = X^T dZ, one partial per workgroup: k_train_wgrad_b6 (three-term splits, rows through an LDS ring;
+// rows_per_wg a multiple of 64, one workgroup per CU) at S = 32 / 64, k_train_wgrad<1> at S = 16
 template <int NB>
-bool launch_train_wgrad32_nb(const gnn::TrainWgradArgs &wa, int grid, hipStream_t st) {
-    switch (wa.act) {
-        case GNN_ACT_LINEAR: gnn::k_train_wgrad32<NB, GNN_ACT_LINEAR><<<grid, 256, 0, st>>>(wa); return true;
-        case GNN_ACT_RELU: gnn::k_train_wgrad32<NB, GNN_ACT_RELU><<<grid, 256, 0, st>>>(wa); return true;
-        case GNN_ACT_SELU: gnn::k_train_wgrad32<NB, GNN_ACT_SELU><<<grid, 256, 0, st>>>(wa); return true;
-        case GNN_ACT_TANH: gnn::k_train_wgrad32<NB, GNN_ACT_TANH><<<grid, 256, 0, st>>>(wa); return true;
-        case GNN_ACT_SIGMOID: gnn::k_train_wgrad32<NB, GNN_ACT_SIGMOID><<<grid, 256, 0, st>>>(wa); return true;
-        case GNN_ACT_ELU: gnn::k_train_wgrad32<NB, GNN_ACT_ELU><<<grid, 256, 0, st>>>(wa); return true;
-        case GNN_ACT_SOFTPLUS: gnn::k_train_wgrad32<NB, GNN_ACT_SOFTPLUS><<<grid, 256, 0, st>>>(wa); return true;
-        default: return false;
-    }
-}
-inline bool train_wgrad32_enabled() {       // GNN_TRAIN_WGRAD32=0: k_train_wgrad (16x16x4) at every width
-    int v = -1;      // (read at every call: tests switch it inside one process)
-    { const char *e = getenv("GNN_TRAIN_WGRAD32"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v != 0;
-}
-bool launch_train_wgrad32(const gnn::TrainWgradArgs &wa, int S, int grid, hipStream_t st) {
-    if (!train_wgrad32_enabled()) return false;
-    if (S == 64) return launch_train_wgrad32_nb<2>(wa, grid, st);
-    if (S == 32) return launch_train_wgrad32_nb<1>(wa, grid, st);
-    return false;
-}
-
-// ... and on the bf16 matrix cores (k_train_wgrad_b6: three-term splits, rows through an LDS ring; GNN_TRAIN_WGRAD_B6=0 keeps the f32-input
-// kernel): rows_per_wg must be a multiple of 64, one workgroup per CU
-template <int NB, int ACT>
-bool launch_train_wgrad_b6_na(const gnn::TrainWgradArgs &wa, int grid, hipStream_t st) {
+int launch_train_wgrad_b6_nb(const gnn::TrainWgradArgs &wa, int grid, hipStream_t st) {
     static bool attr = false;
-    const size_t lds = gnn::train_wgrad_b6_lds<NB, ACT>();
+    const size_t lds = gnn::train_wgrad_b6_lds<NB, GNN_ACT_LINEAR>();
     if (!attr) {
-        if (hipFuncSetAttribute((const void *)gnn::k_train_wgrad_b6<NB, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
+        if (hipFuncSetAttribute((const void *)gnn::k_train_wgrad_b6<NB, GNN_ACT_LINEAR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return fail("k_train_wgrad_b6: cannot raise the dynamic LDS limit");
         attr = true;
     }
-    gnn::k_train_wgrad_b6<NB, ACT><<<grid, 256, lds, st>>>(wa);
-    return true;
-}
-template <int NB>
-bool launch_train_wgrad_b6_nb(const gnn::TrainWgradArgs &wa, int grid, hipStream_t st) {
-    switch (wa.act) {
-        case GNN_ACT_LINEAR: return launch_train_wgrad_b6_na<NB, GNN_ACT_LINEAR>(wa, grid, st);
-        case GNN_ACT_RELU: return launch_train_wgrad_b6_na<NB, GNN_ACT_RELU>(wa, grid, st);
-        case GNN_ACT_SELU: return launch_train_wgrad_b6_na<NB, GNN_ACT_SELU>(wa, grid, st);
-        case GNN_ACT_TANH: return launch_train_wgrad_b6_na<NB, GNN_ACT_TANH>(wa, grid, st);
-        case GNN_ACT_SIGMOID: return launch_train_wgrad_b6_na<NB, GNN_ACT_SIGMOID>(wa, grid, st);
-        case GNN_ACT_ELU: return launch_train_wgrad_b6_na<NB, GNN_ACT_ELU>(wa, grid, st);
-        case GNN_ACT_SOFTPLUS: return launch_train_wgrad_b6_na<NB, GNN_ACT_SOFTPLUS>(wa, grid, st);
-        default: return false;
-    }
-}
-inline bool train_wgrad_b6_enabled() {
-    int v = -1;      // (read at every call: tests switch it inside one process)
-    { const char *e = getenv("GNN_TRAIN_WGRAD_B6"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v != 0 && train_bf16x6_enabled() && train_wgrad32_enabled();
-}
-bool launch_train_wgrad_b6(const gnn::TrainWgradArgs &wa, int S, int grid, hipStream_t st) {
-    if (S == 64) return launch_train_wgrad_b6_nb<2>(wa, grid, st);
-    if (S == 32) return launch_train_wgrad_b6_nb<1>(wa, grid, st);
-    return false;
+    gnn::k_train_wgrad_b6<NB, GNN_ACT_LINEAR><<<grid, 256, lds, st>>>(wa);
+    return hipGetLastError() == hipSuccess ? 0 : fail("k_train_wgrad_b6 launch failed");
 }
 
-// weight gradient and input gradient of an iteration in one pass over its rows (k_train_wgrad_dx_b6; the dZ form; GNN_TRAIN_FUSED_BWD=0: the two kernels)
-inline bool train_fused_bwd_enabled() {
-    int v = -1;      // (read at every call: tests switch it inside one process)
-    { const char *e = getenv("GNN_TRAIN_FUSED_BWD"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v != 0;
-}
+// ... and the input gradient with it, from one pass over the rows (k_train_wgrad_dx_b6, S = 32 / 64)
 template <int NB>
-bool launch_train_wgrad_dx_b6_nb(const gnn::TrainWgradArgs &wa, const gnn::TrainBwdArgs &ba, int grid, hipStream_t st) {
+int launch_train_wgrad_dx_b6_nb(const gnn::TrainWgradArgs &wa, const gnn::TrainBwdArgs &ba, int grid, hipStream_t st) {
     static bool attr = false;
     const size_t lds = gnn::train_wgrad_dx_b6_lds<NB>();
     if (!attr) {
-        if (hipFuncSetAttribute((const void *)gnn::k_train_wgrad_dx_b6<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
+        if (hipFuncSetAttribute((const void *)gnn::k_train_wgrad_dx_b6<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return fail("k_train_wgrad_dx_b6: cannot raise the dynamic LDS limit");
         attr = true;
     }
     gnn::k_train_wgrad_dx_b6<NB><<<grid, 256, lds, st>>>(wa, ba);
-    return true;
-}
-bool launch_train_wgrad_dx_b6(const gnn::TrainWgradArgs &wa, const gnn::TrainBwdArgs &ba, int S, int grid, hipStream_t st) {
-    // With BatchNormalization the input gradient needs m1 / m2 - column moments of dZ W^T that k_first_layer_param_grads derives from THIS
-    // iteration's finished P and q - so the two products cannot share a pass there (the kernel itself takes them as given: scripts/micro/
-    // rowgemm_check.hip checks it bit for bit against the two kernels on arbitrary m1 / m2).  Without it nothing global stands between them.
-    if (ba.gamma) return false;
-    if (wa.Y || wa.act != GNN_ACT_LINEAR || ba.Y) return false;           // the dZ form only
-    if (ba.H != S || ba.S != S || ba.ldz != S || ba.ld_state != S || ba.ld_agg != S || ba.M != wa.M || ba.dZ != wa.G || ba.agg != wa.agg) return false;
-    if ((size_t)wa.rows_per_wg * (size_t)ba.ld_dx * 4 >= 0xFFFFFFF0ull) return false;
-    if (S == 64) return launch_train_wgrad_dx_b6_nb<2>(wa, ba, grid, st);
-    if (S == 32) return launch_train_wgrad_dx_b6_nb<1>(wa, ba, grid, st);
-    return false;
+    return hipGetLastError() == hipSuccess ? 0 : fail("k_train_wgrad_dx_b6 launch failed");
 }
 
-int launch_train_bwd_dx(const gnn::TrainBwdArgs &ba, int S, hipStream_t st) {
-    if (train_bf16x6_enabled() && ba.H == S && ba.S == S && ba.ldz == S) {
-        const int grid = std::max(1, std::min(2 * device_cus(), cdiv((ba.M + 15) / 16, 4)));       // 256-thread workgroups, two per CU
-        int rc = -1;
-        switch (S) {
-            case 16: rc = launch_train_bwd_b6_h<1>(ba, grid, st); break;
-            case 32: rc = launch_train_bwd_b6_h<2>(ba, grid, st); break;
-            case 64: rc = launch_train_bwd_b6_h<4>(ba, grid, st); break;
-            default: break;
-        }
-        if (rc >= 0) return rc;
+// the weight gradient of the dZ form; ba != NULL: the input gradient in the same pass
+int launch_train_wgrad(const gnn::TrainWgradArgs &wa, const gnn::TrainBwdArgs *ba, int S, int grid, hipStream_t st) {
+    if (wa.Y || wa.act != GNN_ACT_LINEAR) return fail("k_train_wgrad: the dZ form only");
+    if (ba) {
+        // With BatchNormalization the input gradient needs m1 / m2 - column moments of dZ W^T that k_first_layer_param_grads derives from THIS
+        // iteration's finished P and q - so the two products cannot share a pass there (the kernel itself takes them as given: scripts/micro/
+        // rowgemm_check.hip checks it bit for bit against the two kernels on arbitrary m1 / m2).  Without it nothing global stands between them.
+        if (ba->gamma || ba->Y || ba->H != S || ba->S != S || ba->ldz != S || ba->ld_state != S || ba->ld_agg != S || ba->M != wa.M || ba->dZ != wa.G ||
+            ba->agg != wa.agg || (size_t)wa.rows_per_wg * (size_t)ba->ld_dx * 4 >= 0xFFFFFFF0ull)
+            return fail("k_train_wgrad_dx_b6: not for these arguments");
+        if (S == 64) return launch_train_wgrad_dx_b6_nb<2>(wa, *ba, grid, st);
+        if (S == 32) return launch_train_wgrad_dx_b6_nb<1>(wa, *ba, grid, st);
+        return fail("k_train_wgrad_dx_b6: no instance for state width %d", S);
     }
-    const int n_tiles = (ba.M + 15) / 16;
-    const int grid = std::max(1, std::min(2 * device_cus(), cdiv(n_tiles, gnn::TB_WAVES)));
     switch (S) {
-        case 16: gnn::k_train_bwd_dx<1, 2><<<grid, 64 * gnn::TB_WAVES, gnn::train_bwd_lds<1, 2>(), st>>>(ba); break;
-        case 32: gnn::k_train_bwd_dx<2, 4><<<grid, 64 * gnn::TB_WAVES, gnn::train_bwd_lds<2, 4>(), st>>>(ba); break;
-        default: gnn::k_train_bwd_dx<4, 8><<<grid, 64 * gnn::TB_WAVES, gnn::train_bwd_lds<4, 8>(), st>>>(ba); break;
+        case 16: gnn::k_train_wgrad<1><<<grid, 256, 0, st>>>(wa); LAUNCH_OK(); return 0;
+        case 32: return launch_train_wgrad_b6_nb<1>(wa, grid, st);
+        case 64: return launch_train_wgrad_b6_nb<2>(wa, grid, st);
+        default: return fail("k_train_wgrad: no instance for state width %d", S);
     }
-    LAUNCH_OK();
-    return 0;
 }
 
 // G_{t-1} -> dZ_{t-1} in the transposed aggregate's epilogue (kernels_train_big.hpp: k_aggregate_dz); false: no instance for this shape
-inline bool train_dz_enabled() {          // GNN_TRAIN_DZ=0: the round-4 flow (every dense kernel forms dZ itself, the last iteration's dx is still computed)
-    int v = -1;      // (read at every call: tests switch it inside one process)
-    { const char *e = getenv("GNN_TRAIN_DZ"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v != 0;
-}
 template <int LPR, bool HAS_W>
 bool launch_aggregate_dz_lw(const gnn_csr_t &c, const float *Xa, int ldx, float *out, int ldo, const float *addend, int ld_add, const gnn::AggDzArgs &z, int act,
                             int grid, hipStream_t st) {
@@ -1027,7 +929,7 @@ static int train_step_impl(const gnn_train_args_t &ta) {
             // (moments around the previous iteration's column means: one-pass sums, but nothing of the mean's size left to cancel)
             const float *prev = t > 0 ? p.stats_s + (size_t)(t - 1) * 2 * p.in_s : nullptr;
             TRY(launch_aggregate_stats(gate, a.adjacency, s_t, p.S, agg_t, p.part_a, stats + p.off_agg, stats + p.in_s + p.off_agg, prev ? prev + p.off_agg : nullptr, st));
-            if (t == 0) {          // (later iterations: k_train_fwd leaves the statistics of the state it writes)
+            if (t == 0) {          // (later iterations: k_train_fwd_b6 leaves the statistics of the state it writes)
                 int grid = 0;
                 TRY(rows_stats(gate, s_t, p.S, p.S, p.N, p.part_y, st, &grid));
                 gnn::k_stats_finish<<<p.S, 256, 0, st>>>(gate, p.part_y, grid, p.S, 1.0f / (float)p.N, stats, stats + p.in_s, s_t);
@@ -1176,7 +1078,7 @@ static int train_step_impl(const gnn_train_args_t &ta) {
         if (bn_o) {
             if (p.head_fast && bn_s && k >= 1) {
                 // Every node is an output row: the column statistics of [state_k | labels] are already on the tape - the state's were
-                // left by the launch that wrote it (k_train_fwd's epilogue, slot k), the labels' are the state network's constant
+                // left by the launch that wrote it (k_train_fwd_b6's epilogue, slot k), the labels' are the state network's constant
                 // BatchNorm columns S .. S + L (one pass over the packed constants line) - four small copies instead of four passes
                 // over a million rows (0.76 ms of a C4-size step).
                 const float *slot = p.stats_s + (size_t)k * 2 * p.in_s;
@@ -1225,9 +1127,10 @@ static int train_step_impl(const gnn_train_args_t &ta) {
     // ---- backward: output network, then the k iterations -----------------------------------------------------------------------------------
     // Large graphs (round 5): G_{t-1} leaves the transposed aggregate as dZ_{t-1} = G_{t-1} (.) act'(state_t) (k_aggregate_dz), so that the two
     // dense kernels of an iteration read dZ alone; the first dZ comes from the output head (k_head_dx, or one k_act_grad pass behind the
-    // general head).  And iteration 0 needs no input gradient at all: nothing consumes d loss / d state_0.
-    const bool dzpath = p.big && p.Kc > 0 && p.Kc < 32 && train_wgrad_enabled() && train_dz_enabled() && (p.S == 16 || p.S == 32 || p.S == 64) &&
-                        ns.activation[0] != GNN_ACT_SOFTMAX;
+    // general head).  And iteration 0 needs no input gradient at all: nothing consumes d loss / d state_0.  The weight gradient streams the
+    // rows with their constants line, whose 1 behind the Kc < 32 columns gives q = colsum(dZ): without constant inputs, or with 32, the
+    // general kernels (net_backward) take it and the plain transposed aggregate runs.
+    const bool dzpath = p.big && p.Kc > 0 && p.Kc < 32;
     if (!p.head_fast) HIP_OK(hipMemsetAsync(p.G_state, 0, sizeof(float) * (size_t)p.N * p.S, st));
     if (p.head_fast) {
         TRY(head_backward(p, a, state_k, out_nodes, G_out, bn_o ? p.stats_o : nullptr, st, (dzpath && k > 0) ? (int)ns.activation[0] : -1));
@@ -1297,12 +1200,10 @@ static int train_step_impl(const gnn_train_args_t &ta) {
         // 'average' / 'sum' / 'normalized' entries depend on the destination only (a.adjacency carries one scale per row): the large-
         // graph kernel scales the agg-half of a row's gradient once, and the transposed aggregate walks UNIT weights (no 4 bytes per arc)
         const bool unit_w = p.big && !a.adjacency.w;
-        const bool wgrad = p.big && p.Kc > 0 && p.Kc < 32 && train_wgrad_enabled();
         if (p.big) {
             gnn::TrainBwdArgs ba;                                    // d loss / d [state | agg] of this iteration (not taken at t == 0: nothing consumes it)
             memset(&ba, 0, sizeof(ba));
             ba.M = p.N; ba.dZ = p.G_state; ba.ldz = p.S;            // (net_backward: the activation gradient ran in place; dzpath: dZ arrived as such)
-            if (wgrad && !dzpath) { ba.Y = s_n; ba.act = ns.activation[0]; }   // (G is untouched: dZ is formed as the rows arrive)
             ba.W = ns.kernel[0]; ba.ldw = p.H1s; ba.H = p.H1s; ba.S = p.S; ba.wrow_state = 0; ba.wrow_agg = p.off_agg;
             ba.state = s_t; ba.ld_state = p.S; ba.agg = agg_t; ba.ld_agg = p.S;
             if (bn_s) { ba.gamma = ns.bn_gamma; ba.mean = stats; ba.var = stats + p.in_s; ba.m1 = p.cs.m1; ba.m2 = p.cs.m2; ba.eps = ns.bn_eps; }
@@ -1310,30 +1211,21 @@ static int train_step_impl(const gnn_train_args_t &ta) {
             ba.agg_row_scale = unit_w ? a.adjacency.row_scale : nullptr;
             ba.dx = p.dx_s_all; ba.ld_dx = p.kdx_s;
             bool dx_done = false;
-            if (wgrad) {
-                // P = X^T dZ and q on the matrix cores straight from the rows (dZ = G (.) act'(s_n) formed on the way), then the same
-                // reduction and parameter-gradient kernels as net_backward
+            if (dzpath) {
+                // P = X^T dZ and q on the matrix cores straight from the rows, then the same reduction and parameter-gradient kernels as net_backward
                 gnn::TrainWgradArgs wa;
                 memset(&wa, 0, sizeof(wa));
-                const bool wg_b6 = train_wgrad_b6_enabled() && (p.S == 64 || p.S == 32);
-                const int n_wg = std::min(std::min((wg_b6 ? 1 : 2) * device_cus(), BIG_WGRAD_BLOCKS), cdiv(p.N, 64));
-                wa.M = p.N; wa.rows_per_wg = wg_b6 ? cdiv(cdiv(p.N, n_wg), 64) * 64 : cdiv(cdiv(p.N, n_wg), 16) * 16;
-                wa.G = p.G_state; wa.Y = dzpath ? nullptr : s_n; wa.act = dzpath ? GNN_ACT_LINEAR : ns.activation[0];      // (dzpath: G_state holds dZ)
+                const bool b6 = p.S != 16;                             // (k_train_wgrad_b6 / k_train_wgrad_dx_b6: one workgroup per CU, 64-row steps)
+                const int n_wg = std::min(std::min((b6 ? 1 : 2) * device_cus(), BIG_WGRAD_BLOCKS), cdiv(p.N, 64));
+                wa.M = p.N; wa.rows_per_wg = b6 ? cdiv(cdiv(p.N, n_wg), 64) * 64 : cdiv(cdiv(p.N, n_wg), 16) * 16;
+                wa.G = p.G_state; wa.Y = nullptr; wa.act = GNN_ACT_LINEAR;      // (G_state holds dZ)
                 wa.state = s_t; wa.agg = agg_t; wa.xc = p.xc;
                 wa.K = p.in_s; wa.wrow_state = 0; wa.wrow_agg = p.off_agg; wa.Kc = p.Kc; wa.cs = p.cc;
                 wa.part = p.part_w;
                 wa.mean = stats;                       // (BatchNormalization: the rows are centred as they arrive, P arrives as P - mean q^T)
                 const int grid = cdiv(p.N, wa.rows_per_wg);
-                if (wg_b6 && dzpath && t > 0 && train_fused_bwd_enabled() && launch_train_wgrad_dx_b6(wa, ba, p.S, grid, st)) dx_done = true;    // both products from one pass over the rows
-                else if (wg_b6 && launch_train_wgrad_b6(wa, p.S, grid, st)) {
-                } else if (!launch_train_wgrad32(wa, p.S, grid, st)) {       // (S = 16, or an activation without an instance: the 16x16x4 kernel)
-                    switch (p.S) {
-                        case 16: gnn::k_train_wgrad<1><<<grid, 256, 0, st>>>(wa); break;
-                        case 32: gnn::k_train_wgrad<2><<<grid, 256, 0, st>>>(wa); break;
-                        default: gnn::k_train_wgrad<4><<<grid, 256, 0, st>>>(wa); break;
-                    }
-                }
-                LAUNCH_OK();
+                dx_done = b6 && t > 0 && !ba.gamma;                    // both products from one pass over the rows (no BatchNormalization)
+                TRY(launch_train_wgrad(wa, dx_done ? &ba : nullptr, p.S, grid, st));
                 const int nP = p.in_s * p.S + p.S;
                 gnn::k_reduce_partials<<<cdiv(nP, 64), 256, 0, st>>>(p.part_w, grid, nP, p.cs.P, 0, 1.0f, p.in_s * p.S, p.cs.q);
                 LAUNCH_OK();

@@ -1,5 +1,5 @@
 """Per-tensor errors of one large-graph training step (40 000 nodes, d = 64, BatchNorm, 4 iterations) against torch autograd in float64,
-in-library step and Python building blocks.  DBG_ACT=relu|selu|.., DBG_BN=0, DBG_DETAIL=1; GNN_TRAIN_BF16X6=0 / GNN_TRAIN_WGRAD32=0 for the f32 kernels.
+in-library step and Python building blocks.  DBG_ACT=relu|selu|.., DBG_BN=0, DBG_DETAIL=1.
 (profiles/r04_notes.txt sections 6-7 quote it.)"""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -32,7 +32,7 @@ for native in (True, False):
         for g_, r in zip(got, ref):
             errs.append(float(np.max(np.abs(g_.cpu().numpy() - r)) / max(float(np.max(np.abs(r))), 1e-12)))
     yp = float(np.max(np.abs(res['y_pred'].cpu().numpy() - want['y_pred'])))
-    print('native' if native else 'blocks', os.environ.get('GNN_TRAIN_BF16X6', '1'), 'k', res['k'], 'loss err', abs(float(res['loss']) - want['loss']), 'y_pred abs err', yp, 'grad rel errs', ['%.1e' % e for e in errs])
+    print('native' if native else 'blocks', 'k', res['k'], 'loss err', abs(float(res['loss']) - want['loss']), 'y_pred abs err', yp, 'grad rel errs', ['%.1e' % e for e in errs])
     if native and os.environ.get('DBG_DETAIL'):
         gk = tr.gs.gradients()[2].cpu().numpy(); rk = want['grads_state'][2]
         dk = np.abs(gk - rk)

@@ -20,12 +20,10 @@ def means(path, counter):
     return {k: (sum(v) / len(v), len(v)) for k, v in acc.items()}
 f, w = means(sys.argv[1], 'FETCH_SIZE'), means(sys.argv[2], 'WRITE_SIZE')
 N, E, S = 1e6, 1e7, 64
-import os
-dz = os.environ.get('GNN_TRAIN_DZ', '1') != '0'       # round 5: the dense kernels read dZ alone (no G + Y), k_train_bwd_dx skips the state rows
 alg = {'k_aggregate_stats': E * (4 + 4 * S) + N * (4 + 4 * S), 'k_aggregate_vec': E * (4 + 4 * S) + N * (4 + 3 * 4 * S),
        'k_aggregate_dz': E * (4 + 4 * S) + N * (4 + 4 * 4 * S),      # gathered dx_agg rows + source ids; per node row pointer, dx_state', state_t, dZ out
-       'k_train_fwd': N * (4 * S * 3 + 128), 'k_train_wgrad': N * (4 * S * (3 if dz else 4) + 128),
-       'k_train_bwd_dx': N * (4 * S * (2 if dz else 4) + 8 * S)}     # (substring match: also k_train_fwd_b6, k_train_wgrad32, k_train_bwd_dx_b6)
+       'k_train_fwd': N * (4 * S * 3 + 128), 'k_train_wgrad': N * (4 * S * 3 + 128),      # (the dense kernels read dZ alone, k_train_bwd_dx_b6
+       'k_train_bwd_dx': N * (4 * S * 2 + 8 * S)}     # skips the state rows; substring match: k_train_fwd_b6, k_train_wgrad_b6, k_train_bwd_dx_b6)
 print('# HBM bytes per launch from the PMC counters (KiB units; FETCH doubled: gfx950 tallies the 128-byte requests of 16-byte-per-lane reads at 64 bytes)')
 print('# kernel, launches, FETCH raw MB, 2 x FETCH + WRITE MB, algorithmic MB, ratio')
 for k in sorted(f):

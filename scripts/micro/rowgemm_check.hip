@@ -1,4 +1,5 @@
-// Correctness harness of k_train_bwd_dx / k_train_fwd against a CPU loop on random data (debug aid for kernels_train_big.hpp).
+// Correctness harness of the large-graph training kernels (k_train_fwd_b6, k_train_bwd_dx_b6, k_train_wgrad / k_train_wgrad_b6, k_train_wgrad_dx_b6)
+// against CPU loops on random data (debug aid for kernels_train_big.hpp).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -10,9 +11,9 @@
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s line %d\n", hipGetErrorString(e_), __LINE__); exit(1);} } while (0)
 template <typename T> T *up(const std::vector<T> &v) { T *d; CK(hipMalloc(&d, v.size() * sizeof(T))); CK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice)); return d; }
 
-template <int HQ, int NCT, bool B6 = false>
+template <int HQ>
 void check_bwd(int M, bool bn, bool scale) {
-    const int S = 8 * NCT, H = 16 * HQ, L = 7, K = 2 * S + 2 * L + 3, wa = S + L;
+    const int S = 16 * HQ, H = 16 * HQ, L = 7, K = 2 * S + 2 * L + 3, wa = S + L;
     std::mt19937 rng(1); std::normal_distribution<float> nd(0, 1);
     std::vector<float> dZ((size_t)M * H), W((size_t)K * H), st((size_t)M * S), ag((size_t)M * S), gm(K), mu(K), va(K), m1(K), m2(K), rs(M);
     for (auto *v : {&dZ, &W, &st, &ag, &gm, &mu, &m1, &m2}) for (auto &x : *v) x = nd(rng);
@@ -25,8 +26,8 @@ void check_bwd(int M, bool bn, bool scale) {
     if (bn) { a.gamma = up(gm); a.mean = up(mu); a.var = up(va); a.m1 = up(m1); a.m2 = up(m2); a.eps = 1e-3f; }
     if (scale) a.agg_row_scale = up(rs);
     a.dx = d_dx; a.ld_dx = 2 * S;
-    if constexpr (B6) gnn::k_train_bwd_dx_b6<HQ, GNN_ACT_LINEAR><<<64, 256, gnn::train_bwd_b6_lds<HQ>()>>>(a);
-    else gnn::k_train_bwd_dx<HQ, NCT><<<64, 64 * gnn::TB_WAVES, gnn::train_bwd_lds<HQ, NCT>()>>>(a);
+    CK(hipFuncSetAttribute((const void *)gnn::k_train_bwd_dx_b6<HQ, GNN_ACT_LINEAR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gnn::train_bwd_b6_lds<HQ>()));
+    gnn::k_train_bwd_dx_b6<HQ, GNN_ACT_LINEAR><<<64, 256, gnn::train_bwd_b6_lds<HQ>()>>>(a);
     CK(hipDeviceSynchronize());
     std::vector<float> got((size_t)M * 2 * S);
     CK(hipMemcpy(got.data(), d_dx, got.size() * 4, hipMemcpyDeviceToHost));
@@ -40,10 +41,10 @@ void check_bwd(int M, bool bn, bool scale) {
         if (scale && j >= S) v *= rs[m];
         worst = fmax(worst, fabs(v - got[(size_t)m * 2 * S + j]));
     }
-    printf("bwd<%d,%d>%s M=%d bn=%d scale=%d  max abs err %.3e\n", HQ, NCT, B6 ? " bf16x6" : "", M, bn, scale, worst);
+    printf("bwd<%d> M=%d bn=%d scale=%d  max abs err %.3e\n", HQ, M, bn, scale, worst);
 }
 
-template <int SQ, int W32 = 0>
+template <int SQ>
 void check_fwd(int M, bool pred, bool centred = false) {
     const int S = 16 * SQ, L = 7, A_ = 3, K = 2 * S + 2 * L + A_, wa = S + L;
     std::mt19937 rng(2); std::normal_distribution<float> nd(0, 1);
@@ -58,8 +59,8 @@ void check_fwd(int M, bool pred, bool centred = false) {
     a.act = GNN_ACT_TANH; a.Y = dY; a.ldy = S; a.thr = 1e9f; a.pred_flag = pred ? flag : nullptr; a.stat_part = part;
     std::vector<float> mu(K, 0.f);
     if (centred) { for (auto &x : mu) x = 0.4f + 0.2f * nd(rng); a.in_mean = up(mu); a.stat_shift = a.in_mean; }
-    if constexpr (W32 == 3) gnn::k_train_fwd_b6<SQ, GNN_ACT_TANH><<<64, 64 * gnn::TB_WAVES, gnn::train_fwd_b6_lds<SQ>()>>>(a);
-    else gnn::k_train_fwd<SQ, SQ><<<64, 64 * gnn::TB_WAVES, gnn::train_fwd_lds<SQ, SQ>()>>>(a);
+    CK(hipFuncSetAttribute((const void *)gnn::k_train_fwd_b6<SQ, GNN_ACT_TANH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gnn::train_fwd_b6_lds<SQ>()));
+    gnn::k_train_fwd_b6<SQ, GNN_ACT_TANH><<<64, 64 * gnn::TB_WAVES, gnn::train_fwd_b6_lds<SQ>()>>>(a);
     CK(hipDeviceSynchronize());
     std::vector<float> got((size_t)M * S), pt(64 * 2 * S);
     CK(hipMemcpy(got.data(), dY, got.size() * 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(pt.data(), part, pt.size() * 4, hipMemcpyDeviceToHost));
@@ -78,39 +79,38 @@ void check_fwd(int M, bool pred, bool centred = false) {
         ws = fmax(ws, fmax(fabs(a1 - s1[h]) / M, fabs(a2 - s2[h]) / M)); }
     int fl = -1; CK(hipMemcpy(&fl, flag, 4, hipMemcpyDeviceToHost));
     printf("   (mean error signed by the value's sign %.3e, mean |error| %.3e)\n", bias_sum / ((double)M * S), abs_sum / ((double)M * S));
-    printf("fwd<%d>%s M=%d pred=%d centred=%d  max abs err %.3e  stats err %.3e  flag %d\n", SQ, W32 == 3 ? " bf16x6" : W32 == 2 ? " 32x32p" : W32 ? " 32x32" : "", M, pred, centred, worst, ws, fl);
+    printf("fwd<%d> M=%d pred=%d centred=%d  max abs err %.3e  stats err %.3e  flag %d\n", SQ, M, pred, centred, worst, ws, fl);
 }
 
-
-template <int SQ, bool W32, bool B6 = false>
+// the weight gradient of the dZ form (G holds dZ): k_train_wgrad<1> at S = 16, k_train_wgrad_b6 at S = 32 / 64
+template <int SQ>
 void check_wgrad(int M, bool centred = false) {
+    constexpr bool B6 = SQ > 1;
     const int S = 16 * SQ, L = 7, A_ = 3, Kc = 2 * L + A_, K = 2 * S + Kc, wa = S + L;
     std::mt19937 rng(3); std::normal_distribution<float> nd(0, 1);
-    std::vector<float> G((size_t)M * S), Y((size_t)M * S), st((size_t)M * S), ag((size_t)M * S), xc((size_t)M * 32, 0.f);
+    std::vector<float> G((size_t)M * S), st((size_t)M * S), ag((size_t)M * S), xc((size_t)M * 32, 0.f);
     for (auto *v : {&G, &st, &ag}) for (auto &x : *v) x = nd(rng);
-    for (auto &x : Y) x = tanhf(nd(rng));
     for (int m = 0; m < M; ++m) { for (int j = 0; j < Kc; ++j) xc[(size_t)m * 32 + j] = nd(rng); xc[(size_t)m * 32 + Kc] = 1.f; }
     gnn::TrainWgradArgs a; memset(&a, 0, sizeof(a));
     const int n_wg = 37;
     a.M = M; a.rows_per_wg = B6 ? ((M + n_wg - 1) / n_wg + 63) / 64 * 64 : ((M + n_wg - 1) / n_wg + 15) / 16 * 16;
     const int grid = (M + a.rows_per_wg - 1) / a.rows_per_wg;
     float *part; CK(hipMalloc(&part, (size_t)grid * (K * S + S) * 4)); CK(hipMemset(part, 0, (size_t)grid * (K * S + S) * 4));
-    a.G = up(G); a.Y = up(Y); a.act = GNN_ACT_TANH; a.state = up(st); a.agg = up(ag); a.xc = up(xc);
+    a.G = up(G); a.Y = nullptr; a.act = GNN_ACT_LINEAR; a.state = up(st); a.agg = up(ag); a.xc = up(xc);
     a.K = K; a.wrow_state = 0; a.wrow_agg = wa; a.Kc = Kc; a.cs.n = 3; a.cs.width[0] = L; a.cs.wrow[0] = S; a.cs.width[1] = L; a.cs.wrow[1] = 2 * S + L; a.cs.width[2] = A_; a.cs.wrow[2] = 2 * S + 2 * L;
     a.part = part;
     std::vector<float> mu(K + 1, 0.f);
     if (centred) { for (int k = 0; k < K; ++k) mu[k] = 0.5f + 0.1f * nd(rng); a.mean = up(mu); }
     if constexpr (B6) {
-        CK(hipFuncSetAttribute((const void *)gnn::k_train_wgrad_b6<SQ / 2, GNN_ACT_TANH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gnn::train_wgrad_b6_lds<SQ / 2, GNN_ACT_TANH>()));
-        gnn::k_train_wgrad_b6<SQ / 2, GNN_ACT_TANH><<<grid, 256, gnn::train_wgrad_b6_lds<SQ / 2, GNN_ACT_TANH>()>>>(a);
-    }
-    else if constexpr (W32) gnn::k_train_wgrad32<SQ / 2, GNN_ACT_TANH><<<grid, 256>>>(a); else gnn::k_train_wgrad<SQ><<<grid, 256>>>(a);
+        CK(hipFuncSetAttribute((const void *)gnn::k_train_wgrad_b6<SQ / 2, GNN_ACT_LINEAR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gnn::train_wgrad_b6_lds<SQ / 2, GNN_ACT_LINEAR>()));
+        gnn::k_train_wgrad_b6<SQ / 2, GNN_ACT_LINEAR><<<grid, 256, gnn::train_wgrad_b6_lds<SQ / 2, GNN_ACT_LINEAR>()>>>(a);
+    } else gnn::k_train_wgrad<SQ><<<grid, 256>>>(a);
     CK(hipDeviceSynchronize());
     std::vector<float> pt((size_t)grid * (K * S + S));
     CK(hipMemcpy(pt.data(), part, pt.size() * 4, hipMemcpyDeviceToHost));
     std::vector<double> P((size_t)(K + 1) * S, 0.0);
     for (int m = 0; m < M; ++m) for (int h = 0; h < S; ++h) {
-        const double y = Y[(size_t)m * S + h], dz = G[(size_t)m * S + h] * (1.0 - y * y);
+        const double dz = G[(size_t)m * S + h];
         for (int j = 0; j < S; ++j) { P[(size_t)j * S + h] += (st[(size_t)m * S + j] - mu[j]) * dz; P[(size_t)(wa + j) * S + h] += (ag[(size_t)m * S + j] - mu[wa + j]) * dz; }
         for (int j = 0; j < L; ++j) { P[(size_t)(S + j) * S + h] += (xc[(size_t)m * 32 + j] - mu[S + j]) * dz; P[(size_t)(2 * S + L + j) * S + h] += (xc[(size_t)m * 32 + L + j] - mu[2 * S + L + j]) * dz; }
         for (int j = 0; j < A_; ++j) P[(size_t)(2 * S + 2 * L + j) * S + h] += (xc[(size_t)m * 32 + 2 * L + j] - mu[2 * S + 2 * L + j]) * dz;
@@ -118,7 +118,7 @@ void check_wgrad(int M, bool centred = false) {
     }
     double worst = 0, scale = 0;
     for (size_t idx = 0; idx < P.size(); ++idx) { double sum = 0; for (int b = 0; b < grid; ++b) sum += pt[(size_t)b * (K * S + S) + idx]; worst = fmax(worst, fabs(sum - P[idx])); scale = fmax(scale, fabs(P[idx])); }
-    printf("wgrad<%d>%s M=%d centred=%d  max abs err %.3e (scale %.3e)\n", SQ, B6 ? " bf16x6" : W32 ? " 32x32" : "", M, centred, worst, scale);
+    printf("wgrad<%d>%s M=%d centred=%d  max abs err %.3e (scale %.3e)\n", SQ, B6 ? " bf16x6" : "", M, centred, worst, scale);
 }
 
 // the one-pass kernel against the two kernels it replaces (both checked against CPU loops above): same bits expected
@@ -185,15 +185,10 @@ void check_fused(int M, bool bn, bool scale, int n_wg = 37) {
 
 int main(int argc, char **argv) {
     if (argc > 1) { for (int nw : {256, 625, 100}) for (int sc = 0; sc < 2; ++sc) { check_fused<1>(40000, false, sc, nw); check_fused<2>(40000, false, sc, nw); check_fused<1>(40000, true, sc, nw); } return 0; }
-    for (int M : {1000, 40000}) { check_fwd<1>(M, true, true); check_fwd<2>(M, true, true); check_fwd<4>(M, true, true); check_fwd<1, 3>(M, true, true); check_fwd<2, 3>(M, true, true); check_fwd<4, 3>(M, true, true); }
-    for (int M : {1000, 40000, 77}) { check_wgrad<2, false>(M); check_wgrad<4, false>(M); check_wgrad<2, true>(M); check_wgrad<4, true>(M);
-        check_wgrad<1, false>(M, true); check_wgrad<4, false>(M, true); check_wgrad<2, true>(M, true); check_wgrad<4, true>(M, true);
-        check_wgrad<2, true, true>(M); check_wgrad<4, true, true>(M); check_wgrad<2, true, true>(M, true); check_wgrad<4, true, true>(M, true); }
-    for (int M : {1000, 40000, 77}) for (int pr = 0; pr < 2; ++pr) { check_fwd<1>(M, pr); check_fwd<2>(M, pr); check_fwd<4>(M, pr); check_fwd<1, 3>(M, pr); check_fwd<2, 3>(M, pr); check_fwd<4, 3>(M, pr); }
-    for (int M : {1000, 40000}) for (int bn = 0; bn < 2; ++bn) for (int sc = 0; sc < 2; ++sc) {
-        check_bwd<1, 2>(M, bn, sc); check_bwd<2, 4>(M, bn, sc); check_bwd<4, 8>(M, bn, sc);
-        check_bwd<1, 2, true>(M, bn, sc); check_bwd<2, 4, true>(M, bn, sc); check_bwd<4, 8, true>(M, bn, sc);
-    }
+    for (int M : {1000, 40000}) { check_fwd<1>(M, true, true); check_fwd<2>(M, true, true); check_fwd<4>(M, true, true); }
+    for (int M : {1000, 40000, 77}) for (int c = 0; c < 2; ++c) { check_wgrad<1>(M, c); check_wgrad<2>(M, c); check_wgrad<4>(M, c); }
+    for (int M : {1000, 40000, 77}) for (int pr = 0; pr < 2; ++pr) { check_fwd<1>(M, pr); check_fwd<2>(M, pr); check_fwd<4>(M, pr); }
+    for (int M : {1000, 40000}) for (int bn = 0; bn < 2; ++bn) for (int sc = 0; sc < 2; ++sc) { check_bwd<1>(M, bn, sc); check_bwd<2>(M, bn, sc); check_bwd<4>(M, bn, sc); }
     for (int M : {1000, 40000, 77}) for (int bn = 0; bn < 2; ++bn) for (int sc = 0; sc < 2; ++sc) { check_fused<2>(M, bn, sc); check_fused<1>(M, bn, sc); }
     return 0;
 }

@@ -113,7 +113,7 @@ def test_group_and_set_tables_are_validated_without_gpu(lib):
         assert lib.gnn_loop_groups_supported(C.byref(a)) == 0
 
 
-def test_validation_paths_under_address_and_ub_sanitizers():
+def test_host_side_under_address_and_ub_sanitizers():
     """The host side of the library (argument validation, plan / workspace carving, table handling) built with
     -fsanitize=address,undefined (`make asan`: host code only, the device code is compiled as usual) and driven by the tests of
     this file in a child process - no GPU needed, SURVEY 5.  GPU AddressSanitizer is not available on this pool."""
@@ -132,10 +132,11 @@ def test_validation_paths_under_address_and_ub_sanitizers():
     assert 'ERROR: AddressSanitizer' not in res.stderr and 'runtime error' not in res.stderr, res.stderr[-3000:]
 
 
-def test_kernels_with_hand_counted_waits_use_no_scratch(tmp_path):
+def test_every_ring_kernel_with_hand_counted_waits_uses_no_scratch(tmp_path):
     """k_train_wgrad_b6 / k_train_wgrad_dx_b6 wait for their LDS-DMA loads with `s_waitcnt vmcnt(N)` counts written by hand (N = the loads of
     one ring slot: csrc/kernels_train_big.hpp).  A register spill is a scratch load / store on the same counter and would make those counts
-    wrong without any test on a small input noticing: every instantiation in the built library must have no scratch segment and no spill."""
+    wrong without any test on a small input noticing: every instantiation in the built library must have no scratch segment and no spill,
+    and every instantiation the library launches must be among those checked."""
     import re, shutil, subprocess
     llvm = '/opt/rocm/lib/llvm/bin'
     if not all(os.path.exists(os.path.join(llvm, t)) for t in ('llvm-objcopy', 'clang-offload-bundler', 'llvm-readelf')):
@@ -146,12 +147,15 @@ def test_kernels_with_hand_counted_waits_use_no_scratch(tmp_path):
     subprocess.run([os.path.join(llvm, 'clang-offload-bundler'), '--unbundle', '--type=o', f'--input={fat}', '--targets=hipv4-amdgcn-amd-amdhsa--gfx950',
                     f'--output={co}'], check=True, capture_output=True)
     notes = subprocess.run([os.path.join(llvm, 'llvm-readelf'), '--notes', co], check=True, capture_output=True, text=True).stdout
-    seen = 0
+    seen = set()
     for m in re.finditer(r'\.name:\s+(\S*(?:k_train_wgrad_b6|k_train_wgrad_dx_b6)\S*)\n(.*?)\.wavefront_size', notes, re.S):
         blk = m.group(2)
         scratch = int(re.search(r'\.private_segment_fixed_size:\s+(\d+)', blk).group(1))
         spills = int(re.search(r'\.vgpr_spill_count:\s+(\d+)', blk).group(1)) + int(re.search(r'\.sgpr_spill_count:\s+(\d+)', blk).group(1))
         dyn = re.search(r'\.uses_dynamic_stack:\s+(\w+)', blk).group(1)
         assert scratch == 0 and spills == 0 and dyn == 'false', (m.group(1), scratch, spills, dyn)
-        seen += 1
-    assert seen >= 16, seen          # 2 widths x 7 activations + the one-pass kernel's 2 widths
+        seen.add(re.search(r'(k_train_wgrad_\w+?)I(\w+?)EEEv', m.group(1)).groups())
+    # k_train_wgrad_b6<NB, LINEAR, XT> and its per-type launch: 2 widths x constants lines of 32 / 64 floats; the one-pass kernel's 2 widths
+    want = {(k, f'Li{nb}ELi0ELi{xt}') for k in ('k_train_wgrad_b6', 'k_train_wgrad_b6_types') for nb in (1, 2) for xt in (1, 2)}
+    want |= {('k_train_wgrad_dx_b6', f'Li{nb}') for nb in (1, 2)}
+    assert seen == want, sorted(seen ^ want)

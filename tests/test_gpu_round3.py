@@ -367,8 +367,8 @@ from test_gpu_training import prefetch_oracle
 @prefetch_oracle
 def test_large_graph_training_step_matches_autograd(d, bn, mode, thr):
     """From 32 768 nodes `gnn_train_step` runs an iteration on k_aggregate_stats (neighbour sum + its BatchNorm statistics),
-    k_train_fwd (rows straight into the matrix cores, statistics folded into the weights, predicate and the next iteration's
-    statistics in the epilogue) and k_train_bwd_dx (dZ . W^T with the BatchNorm input gradient and the 'average' row scale in the
+    k_train_fwd_b6 (rows straight into the matrix cores, statistics folded into the weights, predicate and the next iteration's
+    statistics in the epilogue) and k_train_bwd_dx_b6 (dZ . W^T with the BatchNorm input gradient and the 'average' row scale in the
     epilogue, unit-weight transposed aggregate): every gradient against torch autograd in float64, and against the Python
     building-block orchestration (which keeps the general kernels)."""
     from test_gpu_training import nets, check_step

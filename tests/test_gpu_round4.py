@@ -1023,9 +1023,9 @@ def test_starter_composite_py_defaults(mutag_graphs):
 @pytest.mark.parametrize('act,d', [('linear', 32), ('relu', 64), ('tanh', 32), ('sigmoid', 64), ('elu', 32), ('softplus', 32)])
 @prefetch_oracle
 def test_large_graph_training_kernels_for_every_activation(act, d):
-    """The large-graph dense kernels of round 4 (k_train_fwd_b6 / k_train_bwd_dx_b6: three-term bf16 splits on the bf16 matrix cores;
-    k_train_wgrad32) are instantiated per activation - 'selu' is what every other training test uses: one step on a 36 000-node graph
-    for each of the others against torch autograd in float64, both orchestrations."""
+    """The large-graph kernels k_train_fwd_b6 (three-term bf16 splits on the bf16 matrix cores) and k_aggregate_dz (which leaves dZ for the
+    weight- and input-gradient kernels) are instantiated per activation - 'selu' is what every other training test uses: one step on a
+    36 000-node graph for each of the others against torch autograd in float64, both orchestrations."""
     from test_gpu_training import nets, check_step
     rng = np.random.default_rng(11)
     N = 36_000
@@ -1057,21 +1057,6 @@ def test_large_graph_training_with_labels_far_from_zero():
     s0 = np.abs(rng.normal(0, 0.1, (N, 32))).astype(np.float32)
     model = GNNnodeBased(ns, no, 32, 3, 0.0)
     check_step(model, x, y, sw, s0)
-
-
-def test_large_graph_training_on_the_f32_mfma_kernels(monkeypatch):
-    """GNN_TRAIN_BF16X6=0 GNN_TRAIN_WGRAD32=0 (read at every call): the large-graph training step on the exact-f32 kernels the bf16-split
-    ones replaced by default (k_train_fwd / k_train_bwd_dx / k_train_wgrad: the same centred arithmetic; state width 16 runs them by
-    default) - one configuration per kernel instance and feature: widths 64 / 32 with and without BatchNormalization (early exit included),
-    an activation with a kink, labels far from zero, a thin head over every node.  Against the same float64 autograd oracle and bars."""
-    from test_gpu_round3 import test_large_graph_training_step_matches_autograd as step
-    monkeypatch.setenv('GNN_TRAIN_BF16X6', '0'); monkeypatch.setenv('GNN_TRAIN_WGRAD32', '0')
-    step(64, True, 'average', 0.0)
-    step(32, False, 'average', -1.0)
-    step(32, True, 'sum', 0.0)
-    test_large_graph_training_kernels_for_every_activation('relu', 64)
-    test_large_graph_training_with_labels_far_from_zero()
-    test_thin_output_head_over_every_node_matches_autograd(64, True, 'n', 2, 'categorical_crossentropy', 0.0)
 
 
 @pytest.mark.parametrize('dim_arc_label,bn', [(4, True), (4, False)])

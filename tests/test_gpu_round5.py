@@ -232,8 +232,8 @@ def start_train_oracle(test_names):
 
 def test_train_step_at_the_size_and_depth_the_bench_times_it(request):
     """`gnn_train_step` on the C4 graph (1 M nodes / 10 M arcs, d = 64, BatchNormalization, 10 iterations: bench.py's
-    `training.c4_d64_k10`, the row-streaming kernels of kernels_train_big.hpp - bf16 x 3 split products, the 1 M-row contraction of
-    k_train_wgrad32 in float32 MFMA accumulators) against torch autograd in float64: k, loss, training-mode predictions, the final state,
+    `training.c4_d64_k10`, the row-streaming kernels of kernels_train_big.hpp - bf16 x 3 split products accumulated in float32, the
+    1 M-row contraction of k_train_wgrad_b6 among them) against torch autograd in float64: k, loss, training-mode predictions, the final state,
     every gradient per tensor, the moving statistics - on the in-library step AND the building-block orchestration.  Prints the
     per-tensor errors (profiles/r05_train_c4_parity.txt is this test's output on the GPU box)."""
     from test_gpu_training import grad_rows, log_rows, BARS, Y_PRED_BAR
@@ -438,20 +438,6 @@ def test_composite_small_graph_training_persistent_kernels_match_autograd(focus,
 
 
 
-def test_large_graph_training_with_every_dense_kernel_forming_dz_itself(monkeypatch):
-    """GNN_TRAIN_DZ=0 (read at every call): the round-4 flow of the large-graph backward sweep - the weight-gradient and input-gradient
-    kernels each form dZ = G (.) act'(Y) from G and Y, k_train_bwd_dx applies the whole BatchNorm input gradient, the plain transposed
-    aggregate - which round 5 replaced by default with k_aggregate_dz (the aggregate's epilogue leaves dZ, the state half's BatchNorm
-    term is added there) and which models without constant inputs still take.  Both flows against the same float64 autograd oracle."""
-    from test_gpu_round3 import test_large_graph_training_step_matches_autograd as step
-    from test_gpu_round4 import test_thin_output_head_over_every_node_matches_autograd as head, test_large_graph_training_kernels_for_every_activation as act
-    monkeypatch.setenv('GNN_TRAIN_DZ', '0')
-    step(64, True, 'average', 0.0)
-    step(32, False, 'average', -1.0)
-    head(64, True, 'n', 2, 'categorical_crossentropy', 0.0)
-    act('relu', 64)
-
-
 @pytest.mark.parametrize('d', [64, 32])
 def test_large_graph_training_without_batchnorm_takes_both_gradients_in_one_pass(d):
     """Without BatchNormalization nothing global stands between an iteration's weight gradient and its input gradient: k_train_wgrad_dx_b6
@@ -461,16 +447,6 @@ def test_large_graph_training_without_batchnorm_takes_both_gradients_in_one_pass
     from test_gpu_round3 import test_large_graph_training_step_matches_autograd as run
     run(d, False, 'average', 0.0)
     run(d, False, 'sum', 0.0)
-
-
-def test_large_graph_training_on_the_kernels_before_the_lds_ring(monkeypatch):
-    """GNN_TRAIN_WGRAD_B6=0 GNN_TRAIN_FUSED_BWD=0 (read at every call): the weight gradient on the f32-input matrix instructions
-    (k_train_wgrad32) and the two-kernel backward pass stay selectable; the same tests against the same oracle."""
-    from test_gpu_round3 import test_large_graph_training_step_matches_autograd as step
-    monkeypatch.setenv('GNN_TRAIN_WGRAD_B6', '0'); monkeypatch.setenv('GNN_TRAIN_FUSED_BWD', '0')
-    step(64, True, 'average', 0.0)
-    step(32, True, 'sum', 0.0)
-    step(64, False, 'average', 0.0)
 
 
 @pytest.mark.parametrize('N,d,bn,mode', [(40_037, 64, True, 'average'), (33_001, 32, True, 'average'), (40_037, 64, False, 'average'),
