@@ -716,7 +716,10 @@ class GNNnodeBased(_LoopModel):
             from .training import LoopTrainer
             if getattr(self, '_trainer', None) is None: self._trainer = LoopTrainer(self)      # (one per model, shared with train_step)
             x_list = [nodes, arcs, dim_node_label, set_mask, output_mask, adjacency, arcnode, nodegraph]
-            if self._trainer._native_forward_applies():
+            # (no row in set_mask & output_mask - one graph of a serial LGNN propagation can have none: the in-library step wants at least
+            # one output row, the building blocks below skip the output network and leave its moving statistics alone)
+            has_rows = len(self._out_index(_squeeze_last(set_mask).to(nodes.device), _squeeze_last(output_mask).to(nodes.device))) > 0
+            if has_rows and self._trainer._native_forward_applies():
                 # one library call (include/gnnloop.h ABI 9, forward_only) instead of ~ 40 building-block calls: what a serial LGNN fit()
                 # runs on every single graph between its layers (reference LGNN.py:325-337)
                 try:

@@ -234,12 +234,34 @@ class LGNN(_LoopModel):
         return out
 
     # ---- fit: serial mode trains the layers one after another (reference LGNN.py:290-362) -----------------------------------
+    def _propagate(self, gnn, seq_now, seq_t0, state0s=None):
+        """What serial fit() hands from a trained layer to the next (reference LGNN.py:325-354): the states / outputs of every single
+        graph of `seq_now` (batch size 1, in order, training-mode forward: BatchNormalization on that graph's own statistics, the
+        moving averages moved per call) merged into copies of the t0 graphs of `seq_t0` (`update_graph`).  `state0s`: optional
+        per-graph initial states for state_vect_dim > 0 (drawn otherwise).  Returns (the relabelled sequencer, per-graph k)."""
+        seq_now.shuffle = False
+        seq_now.set_batch_size(1)
+        s0 = state0s if state0s is not None else [None] * len(seq_now)
+        results = [gnn.Loop(*gnn.process_inputs(seq_now[i][0]), training=True, state0=s0[i], node_level=True)
+                   for i in range(len(seq_now))]
+        new_seq = seq_t0.copy()
+        for g, (_, s, o) in zip(new_seq.data, results):
+            n, a, l = self.update_graph(g.nodes, g.arcs, g.DIM_NODE_LABEL, g.set_mask, g.output_mask,
+                                        s.cpu().numpy(), o.cpu().numpy())
+            g.nodes, g.arcs, g.DIM_NODE_LABEL = n, a, l
+        return new_seq, [int(float(k)) for k, _, _ in results]
+
     def fit(self, sequencer, epochs: int = 1, validation_data=None, verbose: int = 1, **kwargs):
         """'parallel' / 'residual': the usual loop.  'serial' (reference LGNN.py:290-362): the layers are trained one after
         another, each on the graphs relabelled with its predecessor's states / outputs; `callbacks`, when given, is a list of
         LAYERS callback lists - entry i goes to layer i's fit (reference :299-303)."""
         if self.training_mode != 'serial':
             return super().fit(sequencer, epochs=epochs, validation_data=validation_data, verbose=verbose, **kwargs)
+        from ..Sequencers.GraphSequencers import SingleGraphSequencer
+        if any(isinstance(s, SingleGraphSequencer) for s in (sequencer, validation_data)):
+            # (the reference cannot either: it zips the layer's results with `sequencer.data`, LGNN.py:330-331, one graph object there)
+            raise TypeError("serial LGNN fit() relabels a list of graphs one by one: a SingleGraphSequencer is not supported "
+                            "(use a MultiGraphSequencer, or training_mode 'parallel' / 'residual')")
         callbacks = kwargs.pop('callbacks', None)
         if callbacks is None: callbacks = [[] for _ in range(self.LAYERS)]
         assert len(callbacks) == self.LAYERS
@@ -250,26 +272,12 @@ class LGNN(_LoopModel):
         train_t0, valid_t0 = sequencer, validation_data
         training_sequence = view(train_t0)
         valid_sequence = view(valid_t0) if valid_t0 is not None else None
-
-        def propagate(gnn, seq_now, seq_t0):
-            """states / outputs of every single graph (batch size 1, training-mode forward as in the reference), merged
-            into the t0 graphs' labels."""
-            seq_now.shuffle = False
-            seq_now.set_batch_size(1)
-            results = [gnn.Loop(*gnn.process_inputs(seq_now[i][0]), training=True, node_level=True) for i in range(len(seq_now))]
-            new_seq = seq_t0.copy()
-            for g, (_, s, o) in zip(new_seq.data, results):
-                n, a, l = self.update_graph(g.nodes, g.arcs, g.DIM_NODE_LABEL, g.set_mask, g.output_mask,
-                                            s.cpu().numpy(), o.cpu().numpy())
-                g.nodes, g.arcs, g.DIM_NODE_LABEL = n, a, l
-            return new_seq
-
         for idx, gnn in enumerate(self.gnns[:-1]):
             if verbose: print(f'\\n\\n --- GNN {idx + 1}/{self.LAYERS} ---')
             histories.append(gnn.fit(view(training_sequence), epochs=epochs, verbose=verbose, callbacks=callbacks[idx],
                                      validation_data=view(valid_sequence) if valid_sequence is not None else None, **kwargs))
-            training_sequence = propagate(gnn, training_sequence, train_t0)
-            if valid_sequence is not None: valid_sequence = propagate(gnn, valid_sequence, valid_t0)
+            training_sequence = self._propagate(gnn, training_sequence, train_t0)[0]
+            if valid_sequence is not None: valid_sequence = self._propagate(gnn, valid_sequence, valid_t0)[0]
         if verbose: print(f'\\n\\n --- GNN {self.LAYERS}/{self.LAYERS} ---')
         histories.append(self.gnns[-1].fit(view(training_sequence), epochs=epochs, verbose=verbose, callbacks=callbacks[-1],
                                            validation_data=view(valid_sequence) if valid_sequence is not None else None, **kwargs))

@@ -240,6 +240,10 @@ class SingleGraphSequencer(MultiGraphSequencer):
         config["graph"] = config["graph"].copy()
         return self.from_config(config)
 
+    def _view(self):
+        """A second sequencer over the SAME graph object (its own batch size and order of the set_mask rows)."""
+        return self.from_config(self.get_config())
+
     def get_config(self):
         return {"graph": self.data, "focus": self.focus, "batch_size": self.batch_size, "shuffle": self.shuffle}
 

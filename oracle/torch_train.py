@@ -320,8 +320,23 @@ def composite_train_step(nodes, arcs, dim_node_label, type_mask, composite_adjac
                 kinks_state=[n.kinks for n in nets], kinks_output=no.kinks)
 
 
-def _homogeneous_forward(ns, no, X, lab, At, agg_arcs, d, max_iteration, state_threshold, state0, mask, focus, adjacency, NGt):
-    """One GNN layer with autograd-tracked inputs X (labels) / lab (arc labels): (k, state, node/arc-level out, task out)."""
+def _margin(dist, norm, state_threshold):
+    """How far one predicate evaluation `any(dist > thr * norm)` is from flipping: |max over rows of (dist - thr norm) / (thr norm)|."""
+    if state_threshold == 0: return float('inf')
+    with torch.no_grad():
+        return float(torch.max((dist - state_threshold * norm) / (state_threshold * norm)).abs())
+
+
+def _output_call(no, inp):
+    """The output network on the masked rows; no rows: no call (no moving-average update), an empty output."""
+    if inp.shape[0] == 0: return inp.new_zeros((0, no.W[-1].shape[1]))
+    return no(inp)
+
+
+def _homogeneous_forward(ns, no, X, lab, At, agg_arcs, d, max_iteration, state_threshold, state0, mask, focus, adjacency, NGt,
+                         margins=None):
+    """One GNN layer with autograd-tracked inputs X (labels) / lab (arc labels): (k, state, node/arc-level out, task out).
+    `margins`: a list that receives `_margin` of every predicate evaluation the threshold decides (k < max_iteration)."""
     if d > 0:
         state = state0
         agg_nodes = torch.sparse.mm(At, X)
@@ -334,6 +349,7 @@ def _homogeneous_forward(ns, no, X, lab, At, agg_arcs, d, max_iteration, state_t
     while True:
         dist = torch.sqrt(torch.sum(torch.square(state - state_old), dim=1))
         norm = torch.sqrt(torch.sum(torch.square(state_old), dim=1))
+        if margins is not None and k < max_iteration: margins.append(_margin(dist, norm, state_threshold))
         if not (bool(torch.any(dist > state_threshold * norm)) and k < max_iteration):
             break
         state, state_old, k = ns(torch.cat(comps(state), dim=1)), state, k + 1
@@ -343,7 +359,7 @@ def _homogeneous_forward(ns, no, X, lab, At, agg_arcs, d, max_iteration, state_t
         inp = torch.cat([sc[idx].reshape(lab.shape[0], 2 * sc.shape[1]), lab], dim=1)[mask]
     else:
         inp = sc[mask]
-    out = no(inp)
+    out = _output_call(no, inp)
     task = torch.sparse.mm(NGt, out) if focus == 'g' else out
     return k, state, out, task
 
@@ -396,8 +412,9 @@ def lgnn_train_step(nodes, arcs, adjacency, arcnode, nodegraph, mask, *, layers,
 
 
 def _composite_forward(nets, no, X, lab, dims, tm, At, ANt, CAts, d, max_iteration, state_threshold, state0, mask, focus,
-                       adjacency, NGt):
-    """One composite GNN layer with autograd-tracked labels X: (k, state, node/arc-level out, task out)."""
+                       adjacency, NGt, margins=None):
+    """One composite GNN layer with autograd-tracked labels X: (k, state, node/arc-level out, task out); `margins` as in
+    `_homogeneous_forward`."""
     agg_nodes = [torch.sparse.mm(ca, X[:, :dt]) for ca, dt in zip(CAts, dims)]
     agg_arcs = torch.sparse.mm(ANt, lab) if lab.shape[1] else torch.zeros((X.shape[0], 0), dtype=X.dtype)
     agg_comp = torch.cat(agg_nodes + [agg_arcs], dim=1)
@@ -407,6 +424,7 @@ def _composite_forward(nets, no, X, lab, dims, tm, At, ANt, CAts, d, max_iterati
     while True:
         dist = torch.sqrt(torch.sum(torch.square(state - state_old), dim=1))
         norm = torch.sqrt(torch.sum(torch.square(state_old), dim=1))
+        if margins is not None and k < max_iteration: margins.append(_margin(dist, norm, state_threshold))
         if not (bool(torch.any(dist > state_threshold * norm)) and k < max_iteration):
             break
         agg = torch.sparse.mm(At, state)
@@ -421,7 +439,7 @@ def _composite_forward(nets, no, X, lab, dims, tm, At, ANt, CAts, d, max_iterati
         inp = torch.cat([state[idx].reshape(lab.shape[0], 2 * state.shape[1]), lab], dim=1)[mask]
     else:
         inp = state[mask]
-    out = no(inp)
+    out = _output_call(no, inp)
     task = torch.sparse.mm(NGt, out) if focus == 'g' else out
     return k, state, out, task
 
@@ -472,3 +490,95 @@ def composite_lgnn_train_step(nodes, arcs, dim_node_label, type_mask, composite_
         if average_st_grads and k > 0: gs_ = [g / k for g in gs_]
         res.append(([npy(g) for g in gs_], [npy(g) for g in go_]))
     return dict(k=ks, loss=float(L.detach()), outs=[npy(o) for o in outs], grads=res)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# serial LGNN: the propagation between two layers (reference LGNN.py:325-354) and update_graph (LGNN.py:175-214)
+# ----------------------------------------------------------------------------------------------------------------------
+def update_graph(nodes, arcs, dim_node_label, set_mask, output_mask, state, output, *, get_state, get_output, arc_focus,
+                 dtype=np.float64):
+    """LGNN.update_graph (reference LGNN.py:175-214) on one graph: [state | output scattered on set_mask & output_mask | nodes];
+    an arc-focused layer's output goes IN FRONT of the arcs (ids included).  Returns (nodes, arcs, dim_node_label + plus)."""
+    nodes, arcs = np.asarray(nodes, dtype=dtype), np.asarray(arcs, dtype=dtype)
+    nodeplus, arcplus = [], []
+    if get_state: nodeplus.append(np.asarray(state, dtype=dtype))
+    if get_output:
+        mask = np.logical_and(np.asarray(set_mask, dtype=bool).reshape(-1), np.asarray(output_mask, dtype=bool).reshape(-1))
+        output = np.asarray(output, dtype=dtype)
+        out = np.zeros((len(mask), output.shape[1]), dtype=dtype)
+        out[mask] = output
+        (arcplus if arc_focus else nodeplus).append(out)
+    plus = sum(x.shape[1] for x in nodeplus)
+    return np.concatenate(nodeplus + [nodes], axis=1), np.concatenate(arcplus + [arcs], axis=1), np.asarray(dim_node_label) + plus
+
+
+def serial_layer(net_state, net_output, state_vect_dim, max_iteration, state_threshold, dtype=torch.float64):
+    """One layer of a serial LGNN: its networks as `Net`s (a list of state networks for a composite layer) - their moving statistics
+    are what `lgnn_serial_propagate` moves, from graph to graph and from call to call."""
+    from types import SimpleNamespace
+    composite = isinstance(net_state, list)
+    ns = [Net(*n, dtype=dtype) for n in net_state] if composite else Net(*net_state, dtype=dtype)
+    return SimpleNamespace(ns=ns, no=Net(*net_output, dtype=dtype), d=int(state_vect_dim), max_iteration=int(max_iteration),
+                           state_threshold=float(state_threshold), composite=composite, dtype=dtype)
+
+
+def _moving(net):
+    return (net.moving_mean.numpy().copy(), net.moving_var.numpy().copy()) if net.bn else None
+
+
+def lgnn_serial_propagate(graphs, layer, *, focus, get_state, get_output, state0s=None, dtype=None):
+    """The states / outputs a trained layer hands to the next one in a serial LGNN fit (reference LGNN.py:325-354): every graph ALONE,
+    in the given order, through the layer in TRAINING mode - BatchNormalization normalises with that graph's own statistics and moves
+    the moving averages once per executed call (k times for the state network, once for the output network) - and `update_graph`
+    merges the state and / or output into that graph's labels.
+
+    graphs: per-graph operands in sequencer order, dicts of numpy arrays: nodes, arcs, dim_node_label, set_mask, output_mask,
+            adjacency / arcnode (sparse triples) - plus type_mask [T, N] and composite_adjacencies for a composite layer - and, when
+            the labels to extend are not the inputs' own (layers > 1 relabel the ORIGINAL graphs), t0 = dict(nodes, arcs, dim_node_label).
+    layer:  `serial_layer(...)`; its moving statistics carry over from graph to graph and from one call to the next.
+    focus:  'g' and 'n' run node-level (the reference calls `GNNnodeBased.Loop` for a graph-focused stack), 'a' arc-level.
+    Returns dict(k, nodes, arcs, dim_node_label, margin: per graph; moving_state, moving_output: the statistics after the last graph).
+    margin: the smallest |dist - thr norm| / (thr norm) of the decisive row over the graph's threshold-decided predicate evaluations
+    (inf for threshold 0) - how far each k is from flipping.
+
+    Deliberate divergence: a graph without a single row in set_mask & output_mask skips the output network (no moving-average update,
+    an empty output), as the product's training forward does; the reference's Keras layer would take the moments of an empty batch."""
+    dtype = dtype or layer.dtype
+    arc_focus = focus == 'a'
+    fwd_focus = 'a' if arc_focus else 'n'
+    res = dict(k=[], nodes=[], arcs=[], dim_node_label=[], margin=[])
+    with torch.no_grad():
+        for gi, g in enumerate(graphs):
+            X = torch.tensor(np.asarray(g['nodes']), dtype=dtype)
+            lab = torch.tensor(np.asarray(g['arcs'])[:, 2:], dtype=dtype)
+            At, ANt = _sp(g['adjacency'], dtype), _sp(g['arcnode'], dtype)
+            mask = torch.from_numpy(np.logical_and(np.asarray(g['set_mask'], dtype=bool).reshape(-1),
+                                                   np.asarray(g['output_mask'], dtype=bool).reshape(-1)))
+            s0 = None if layer.d == 0 else torch.tensor(np.asarray(state0s[gi]), dtype=dtype)
+            margins = []
+            if layer.composite:
+                dims = [int(v) for v in np.asarray(g['dim_node_label']).reshape(-1)]
+                tm = torch.from_numpy(np.asarray(g['type_mask'], dtype=bool))
+                CAts = [_sp(ca, dtype) for ca in g['composite_adjacencies']]
+                k, state, out, _ = _composite_forward(layer.ns, layer.no, X, lab, dims, tm, At, ANt, CAts, layer.d, layer.max_iteration,
+                                                      layer.state_threshold, s0, mask, fwd_focus, g['adjacency'], None, margins)
+            else:
+                agg_arcs = torch.sparse.mm(ANt, lab) if lab.shape[1] else torch.zeros((X.shape[0], 0), dtype=dtype)
+                k, state, out, _ = _homogeneous_forward(layer.ns, layer.no, X, lab, At, agg_arcs, layer.d, layer.max_iteration,
+                                                        layer.state_threshold, s0, mask, fwd_focus, g['adjacency'], None, margins)
+            t0 = g.get('t0') or g
+            n, a, l = update_graph(t0['nodes'], t0['arcs'], t0['dim_node_label'], g['set_mask'], g['output_mask'], state.numpy(),
+                                   out.numpy(), get_state=get_state, get_output=get_output, arc_focus=arc_focus, dtype=np.float64)
+            res['k'].append(k); res['nodes'].append(n); res['arcs'].append(a); res['dim_node_label'].append(l)
+            res['margin'].append(min(margins) if margins else float('inf'))
+    res['moving_state'] = [_moving(n) for n in layer.ns] if layer.composite else _moving(layer.ns)
+    res['moving_output'] = _moving(layer.no)
+    return res
+
+
+def composite_lgnn_serial_propagate(graphs, layer, *, focus, get_state, get_output, state0s=None, dtype=None):
+    """`lgnn_serial_propagate` for a CompositeLGNN layer (`serial_layer` with one state network per node type): the per-graph forward is
+    `_composite_forward` (reference CompositeGNN.py:242-272), the relabelling the same `update_graph` - every type's label widens by
+    the same amount."""
+    if not layer.composite: raise TypeError('composite_lgnn_serial_propagate needs a composite serial_layer')
+    return lgnn_serial_propagate(graphs, layer, focus=focus, get_state=get_state, get_output=get_output, state0s=state0s, dtype=dtype)
