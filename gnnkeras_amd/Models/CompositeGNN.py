@@ -156,9 +156,11 @@ class CompositeGNNnodeBased(GNNnodeBased):
         return hit[0], hit[1]
 
     def Loop(self, nodes, arcs, dim_node_label, type_mask, set_mask, output_mask, composite_adjacencies, adjacency,
-             arcnode, nodegraph, training: bool = False, *, state0=None, seed=None, node_level: bool = False):
+             arcnode, nodegraph, training: bool = False, *, state0=None, seed=None, node_level: bool = False, groups=None):
         """(k, state, out) for one (merged) heterogeneous graph — reference CompositeGNN.py:242-272.
-        `state0` / `seed` / `node_level` as in `GNNnodeBased.Loop`."""
+        `state0` / `seed` / `node_level` as in `GNNnodeBased.Loop`; `groups`: convergence groups are not covered for composite models."""
+        if groups is not None:
+            raise NotImplementedError('convergence groups: composite (heterogeneous) models are not covered')
         focus = 'n' if (node_level and self._focus == 'g') else self._focus
         if training:
             from .training import LoopTrainer

@@ -699,7 +699,9 @@ class GNNnodeBased(_LoopModel):
              training: bool = False, *, state0=None, seed=None, node_level: bool = False, groups=None, group_sets=None):
         """(k, state, out) for one (merged) graph — reference GNN.py:245-274.
 
-        `groups` (additive; inference only): node offsets [G + 1] of G batches merged into this graph.  The loop then runs
+        `groups` (additive): node offsets [G + 1] of G batches merged into this graph (with `training=True`: G graphs computed as G
+        consecutive training-mode calls, in group order - BatchNormalization statistics, predicate and k per group - returns (k[G], state,
+        out); NotImplementedError where `gnn_train_groups_supported` says no).  In inference the loop runs
         as G independent loops in one launch - each batch has its own `condition` and stops on its own, exactly as if the
         reference had been called batch by batch - and k is a vector of G iteration counts (include/gnnloop.h,
         group_node_begin; `ops.loop_groups_supported` says whether a shape qualifies).  `group_sets` (first-group offsets [B + 1]):
@@ -712,10 +714,20 @@ class GNNnodeBased(_LoopModel):
         `GNNnodeBased.Loop` on a graph-based model inside LGNN, LGNN.py:225)."""
         focus = 'n' if (node_level and self._focus == 'g') else self._focus
         if training:
-            if groups is not None: raise ValueError('groups are an inference-only feature')
+            if group_sets is not None: raise ValueError('group_sets are an inference-only feature')
             from .training import LoopTrainer
             if getattr(self, '_trainer', None) is None: self._trainer = LoopTrainer(self)      # (one per model, shared with train_step)
             x_list = [nodes, arcs, dim_node_label, set_mask, output_mask, adjacency, arcnode, nodegraph]
+            if groups is not None:
+                # every group "as if it had been called alone", in group order (include/gnnloop.h ABI 10): k is a vector [G].  A shape the
+                # grouped kernels do not cover raises NotImplementedError (nothing launched, no moving statistic touched)
+                k, state, out = self._trainer.forward_native(x_list, state0=state0, seed=seed, node_level=node_level, groups=groups)
+                if bool((k < 0).any()):
+                    bad = torch.nonzero(k < 0).flatten().tolist()
+                    raise nat.NativeError(f'training-mode convergence groups: an arc of `adjacency` leaves its group (groups {bad[:8]}): '
+                                          'their results and the moving statistics are invalid')
+                self._last_k = k
+                return k, state, out
             # (no row in set_mask & output_mask - one graph of a serial LGNN propagation can have none: the in-library step wants at least
             # one output row, the building blocks below skip the output network and leave its moving statistics alone)
             has_rows = len(self._out_index(_squeeze_last(set_mask).to(nodes.device), _squeeze_last(output_mask).to(nodes.device))) > 0

@@ -27,6 +27,55 @@ from .GNN import GNNnodeBased, GNNarcBased, GNNgraphBased, _LoopModel, _metric_f
 from .training import LoopTrainer
 
 
+SERIAL_PROPAGATION = ('per_graph', 'grouped')
+
+
+def plan_runs(sizes, cap, max_nodes, max_graphs=1 << 20):
+    """How the grouped serial propagation walks a sequencer's graphs (node counts `sizes`, in order): a list of ('run', i0, i1) -
+    the consecutive graphs i0 .. i1 - 1 as the convergence groups of ONE library call, at most `max_nodes` nodes / `max_graphs` graphs
+    per run (the workspace) - and ('single', i) - a graph of more than `cap` nodes, which takes the per-graph call between two runs.
+    Every graph appears once, in order: the moving statistics are moved graph after graph whatever the cut."""
+    plan, i0, nodes = [], None, 0
+    for i, n in enumerate(int(v) for v in sizes):
+        if n > cap:
+            if i0 is not None: plan.append(('run', i0, i)); i0 = None
+            plan.append(('single', i))
+            continue
+        if i0 is not None and (nodes + n > max_nodes or i - i0 >= max_graphs): plan.append(('run', i0, i)); i0 = None
+        if i0 is None: i0, nodes = i, 0
+        nodes += n
+    if i0 is not None: plan.append(('run', i0, len(sizes)))
+    return plan
+
+
+def relabel_graphs(graphs, state, output, get_state: bool, get_output: bool, arc_focus: bool):
+    """`LGNN.update_graph` for a whole list of graphs at once: `state` [sum of nodes, S] and `output` [sum of rows of
+    set_mask & output_mask, T] are the per-graph results concatenated in list order; every graph's `nodes` / `arcs` / `DIM_NODE_LABEL`
+    are replaced by what `update_graph(g.nodes, g.arcs, g.DIM_NODE_LABEL, g.set_mask, g.output_mask, state_g, output_g)` returns (the same
+    bits, float32) - three array concatenations instead of one round of small tensor calls per graph."""
+    if not graphs: return
+    nodes0 = np.concatenate([np.asarray(g.nodes, dtype=np.float32) for g in graphs], axis=0)
+    n_begin = np.concatenate([[0], np.cumsum([g.nodes.shape[0] for g in graphs])])
+    a_begin = np.concatenate([[0], np.cumsum([g.arcs.shape[0] for g in graphs])])
+    nodeplus, arcs_new = [], None
+    if get_state: nodeplus.append(np.asarray(state, dtype=np.float32).reshape(nodes0.shape[0], -1))
+    if get_output:
+        mask = np.concatenate([np.logical_and(np.asarray(g.set_mask).reshape(-1).astype(bool), np.asarray(g.output_mask).reshape(-1).astype(bool))
+                               for g in graphs])
+        output = np.asarray(output, dtype=np.float32)
+        out = np.zeros((len(mask), output.shape[1]), dtype=np.float32)
+        out[mask] = output
+        if arc_focus: arcs_new = np.concatenate([out, np.concatenate([np.asarray(g.arcs, dtype=np.float32) for g in graphs], axis=0)], axis=1)
+        else: nodeplus.append(out)
+    plus = sum(x.shape[1] for x in nodeplus)
+    nodes_new = np.concatenate(nodeplus + [nodes0], axis=1)
+    for i, g in enumerate(graphs):
+        dnl = np.asarray(g.DIM_NODE_LABEL) + plus
+        g.nodes = nodes_new[n_begin[i]:n_begin[i + 1]]
+        g.arcs = arcs_new[a_begin[i]:a_begin[i + 1]] if arcs_new is not None else np.asarray(g.arcs, dtype=np.float32)
+        g.DIM_NODE_LABEL = dnl
+
+
 class LGNN(_LoopModel):
     """Layered GNN for node-, arc- or graph-focused problems (reference LGNN.py:11-362)."""
     _gnn_classes = {"node": GNNnodeBased, "arc": GNNarcBased, "graph": GNNgraphBased}
@@ -40,6 +89,10 @@ class LGNN(_LoopModel):
         self.get_state = bool(get_state)
         self.get_output = bool(get_output)
         self.training_mode = None
+        # how serial fit() hands a layer's results to the next one (`_propagate`): 'per_graph' = one training-mode call per graph,
+        # 'grouped' = runs of consecutive graphs as convergence groups of one call (same results, same order of the moving statistics)
+        self.serial_propagation = 'per_graph'
+        self.serial_run_bytes = 512 << 20          # workspace a grouped run may ask for (bounds the graphs per run)
         self._engine_init()
 
     # the class <-> name maps of the reference (`__gnnClass__`, `__gnnClassLoader__`)
@@ -86,10 +139,14 @@ class LGNN(_LoopModel):
         dirs = sorted((d for d in os.listdir(path) if os.path.isdir(f'{path}{d}')), key=lambda d: int(d[3:]))
         return cls(gnns=[gnn_class.load(f'{path}{d}') for d in dirs], **config)
 
-    def compile(self, *args, training_mode: str = 'parallel', average_st_grads: bool = False, **kwargs):
+    def compile(self, *args, training_mode: str = 'parallel', average_st_grads: bool = False, serial_propagation: str = 'per_graph', **kwargs):
         """`training_mode` in 'serial' (layers trained one after another), 'parallel' (loss = mean of the layers' losses),
-        'residual' (loss of the mean of the layers' outputs) — reference LGNN.py:133-152."""
+        'residual' (loss of the mean of the layers' outputs) — reference LGNN.py:133-152.  `serial_propagation` (additive; serial mode):
+        'per_graph' - between two layers every graph runs alone through the trained layer, one library call each - or 'grouped' - the
+        same arithmetic with the graphs as convergence groups of one call per run (docs/serial_propagation.md)."""
         if training_mode not in ('serial', 'parallel', 'residual'): raise ValueError('unknown training_mode')
+        if serial_propagation not in SERIAL_PROPAGATION: raise ValueError(f'serial_propagation must be one of {SERIAL_PROPAGATION}')
+        self.serial_propagation = serial_propagation
         super().compile(*args, average_st_grads=average_st_grads, **kwargs)
         for gnn in self.gnns: gnn.compile(*args, average_st_grads=average_st_grads, **kwargs)
         self.training_mode = training_mode
@@ -238,7 +295,13 @@ class LGNN(_LoopModel):
         """What serial fit() hands from a trained layer to the next (reference LGNN.py:325-354): the states / outputs of every single
         graph of `seq_now` (batch size 1, in order, training-mode forward: BatchNormalization on that graph's own statistics, the
         moving averages moved per call) merged into copies of the t0 graphs of `seq_t0` (`update_graph`).  `state0s`: optional
-        per-graph initial states for state_vect_dim > 0 (drawn otherwise).  Returns (the relabelled sequencer, per-graph k)."""
+        per-graph initial states for state_vect_dim > 0 (drawn otherwise).  Returns (the relabelled sequencer, per-graph k).
+        `self.serial_propagation` selects the route: 'per_graph' (below) or 'grouped' (`_propagate_grouped`)."""
+        if self.serial_propagation not in SERIAL_PROPAGATION: raise ValueError(f'serial_propagation must be one of {SERIAL_PROPAGATION}')
+        if self.serial_propagation == 'grouped':
+            done = self._propagate_grouped(gnn, seq_now, seq_t0, state0s)
+            if done is not None: return done
+        self.last_propagate = dict(route='per_graph', library_calls=len(seq_now.data), runs=0, fallback_graphs=len(seq_now.data))
         seq_now.shuffle = False
         seq_now.set_batch_size(1)
         s0 = state0s if state0s is not None else [None] * len(seq_now)
@@ -250,6 +313,95 @@ class LGNN(_LoopModel):
                                         s.cpu().numpy(), o.cpu().numpy())
             g.nodes, g.arcs, g.DIM_NODE_LABEL = n, a, l
         return new_seq, [int(float(k)) for k, _, _ in results]
+
+    def _grouped_applies(self, gnn, seq_now):
+        """May this layer's propagation merge graphs into runs?  (a plain multi-graph sequencer whose merge leaves every graph's operators as
+        they are - 'normalized' divides by the arc count of the merge - and a homogeneous layer; the library has the last word per run)"""
+        from ..Sequencers.GraphSequencers import MultiGraphSequencer
+        return type(seq_now) is MultiGraphSequencer and seq_now.aggregation_mode != 'normalized' and \
+            not isinstance(gnn.net_state, (list, tuple)) and len(seq_now.data) > 0
+
+    def _propagate_grouped(self, gnn, seq_now, seq_t0, state0s=None):
+        """`_propagate` with runs of consecutive graphs as the convergence groups of one `gnn_train_step(forward_only)` call each
+        (include/gnnloop.h ABI 10): per run one batch assembly, one library call, one copy of k / state / output rows to the host; all graphs
+        relabelled from the concatenated arrays at the end.  A graph above the library's group size takes the per-graph call between two runs;
+        a layer the grouped kernels do not cover returns None before anything ran (the caller takes the per-graph route for that layer)."""
+        from .training import LoopTrainer
+        from .. import _native as nat
+        if not self._grouped_applies(gnn, seq_now): return None
+        graphs = list(seq_now.data)
+        seq_now.shuffle = False
+        focus = gnn._focus
+        arc = focus == 'a'
+        d = gnn.state_vect_dim
+        L, A = int(graphs[0].nodes.shape[1]), int(graphs[0].arcs.shape[1]) - 2
+        S = d if d > 0 else L
+        SP = 16 if S <= 16 else 32 if S <= 32 else 64
+        in_s = 2 * S + (2 * L if d > 0 else 0) + A
+        in_o = int(gnn.net_output.input_dim)
+        sizes = [int(g.nodes.shape[0]) for g in graphs]
+        per_node = 4 * (2 * SP + L + A + 2) + 16
+        per_graph = 4 * (max(gnn.max_iteration, 1) * 2 * in_s + 2 * in_o) + 64
+        max_nodes = max(nat.TRAIN_GROUP_MAX_NODES, int(self.serial_run_bytes // (per_node + per_graph)))
+        plan = plan_runs(sizes, nat.TRAIN_GROUP_MAX_NODES, max_nodes)
+        if getattr(gnn, '_trainer', None) is None: gnn._trainer = LoopTrainer(gnn)
+        rows_of = lambda g: int(np.count_nonzero(np.logical_and(np.asarray(g.set_mask).reshape(-1), np.asarray(g.output_mask).reshape(-1))))
+        # (the sequencer's device-resident data set is looked up once: `_assemble_graphs` re-validates it against every graph per call)
+        ds = seq_now._device_dataset()
+        index = seq_now._dataset[2] if ds is not None else None
+        assemble = (lambda part: ds.assemble([index[id(g_)] for g_ in part])) if ds is not None else seq_now._assemble_graphs
+        states, outs, ks = [], [], []
+        calls = fallback = runs = 0
+        import time
+        sec = dict(assemble=0.0, library_calls=0.0, d2h=0.0, copy_graphs=0.0, relabel=0.0, new_sequencer=0.0)      # host wall time (the calls are asynchronous: d2h waits for them)
+        for entry in plan:
+            if entry[0] == 'run':
+                t0 = time.perf_counter()
+                part = graphs[entry[1]:entry[2]]
+                x = seq_now._x_list(assemble(part))
+                node_begin = np.concatenate([[0], np.cumsum(sizes[entry[1]:entry[2]])]).astype(np.int32)
+                out_begin = np.concatenate([[0], np.cumsum([rows_of(g) for g in part])]).astype(np.int32)
+                s0 = None
+                if d > 0 and state0s is not None:
+                    s0 = torch.cat([torch.as_tensor(state0s[i]).to(x[0].device, torch.float32) for i in range(entry[1], entry[2])], dim=0)
+                t1 = time.perf_counter()
+                try:
+                    k, state, out = gnn._trainer.forward_native(x, state0=s0, node_level=True, groups=node_begin, group_out_begin=out_begin)
+                except NotImplementedError:
+                    if calls: raise                  # (coverage is a property of the layer: it cannot change between two runs)
+                    return None
+                calls += 1; runs += 1
+                t2 = time.perf_counter()
+                k_h = k.cpu().numpy()                # one synchronisation per run
+                if (k_h < 0).any():
+                    raise nat.NativeError(f'grouped serial propagation: an arc leaves its graph (graphs {np.flatnonzero(k_h < 0)[:8] + entry[1]})')
+                ks += [int(v) for v in k_h]
+                if self.get_state: states.append(state.cpu().numpy())
+                if self.get_output: outs.append(out.cpu().numpy())
+                t3 = time.perf_counter()
+                sec['assemble'] += t1 - t0; sec['library_calls'] += t2 - t1; sec['d2h'] += t3 - t2
+            else:
+                i = entry[1]
+                x = seq_now._x_list(assemble([graphs[i]]))
+                k, state, out = gnn.Loop(*gnn.process_inputs(x), training=True, state0=None if state0s is None else state0s[i], node_level=True)
+                calls += 1; fallback += 1
+                ks.append(int(float(k)))
+                if self.get_state: states.append(state.cpu().numpy())
+                if self.get_output: outs.append(out.cpu().numpy())
+        # what `seq_t0.copy()` does, with the relabelling in front of the new sequencer's constructor: its batches are built once, from
+        # the relabelled graphs (the per-graph route builds them from the t0 labels and leaves them stale)
+        t0 = time.perf_counter()
+        config = seq_t0.get_config()
+        config['graphs'] = [g.copy() for g in config['graphs']]
+        t1 = time.perf_counter()
+        relabel_graphs(config['graphs'], np.concatenate(states, axis=0) if states else None, np.concatenate(outs, axis=0) if outs else None,
+                       self.get_state, self.get_output, arc)
+        t2 = time.perf_counter()
+        new_seq = seq_t0.from_config(config)
+        sec['copy_graphs'], sec['relabel'], sec['new_sequencer'] = t1 - t0, t2 - t1, time.perf_counter() - t2
+        self.last_propagate = dict(route='grouped', library_calls=calls, runs=runs, fallback_graphs=fallback)
+        self.last_propagate_seconds = sec
+        return new_seq, ks
 
     def fit(self, sequencer, epochs: int = 1, validation_data=None, verbose: int = 1, **kwargs):
         """'parallel' / 'residual': the usual loop.  'serial' (reference LGNN.py:290-362): the layers are trained one after

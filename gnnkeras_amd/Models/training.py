@@ -890,13 +890,22 @@ class LoopTrainer:
             if any(float(r) > 0 and int(q) == 0 for r, q in zip(n_.dropout_rate or [], n_.dropout_pos or [])): return False
         return True
 
-    def forward_native(self, x_list, state0=None, seed=None, node_level=False):
+    def forward_native(self, x_list, state0=None, seed=None, node_level=False, groups=None, group_out_begin=None):
         """The training-mode forward in one library call (include/gnnloop.h ABI 9, `forward_only`): (k, state, output rows) - the same
-        arithmetic as `forward()` on the building blocks, no tape kept.  `node_level`: a graph-focused model stops at its per-node outputs."""
-        r = self._train_step_native(x_list, None, None, state0, seed, False, forward_only=True, node_level=node_level)
+        arithmetic as `forward()` on the building blocks, no tape kept.  `node_level`: a graph-focused model stops at its per-node outputs.
+
+        `groups` (ABI 10): node offsets [G + 1] of G graphs merged into this one; every graph is then computed as if it had been called
+        alone, in group order (its own BatchNormalization statistics, predicate and k; the moving statistics moved graph after graph).
+        k comes back as a DEVICE vector [G] and the call does not synchronise: a negative entry says an arc left its group (the caller
+        raises when it reads k).  `group_out_begin`: the output rows of every group, [G + 1] offsets into the rows of
+        `set_mask & output_mask` (derived from the masks - one device-to-host copy - when absent).  A shape the grouped kernels do not
+        cover raises NotImplementedError before anything is launched."""
+        r = self._train_step_native(x_list, None, None, state0, seed, False, forward_only=True, node_level=node_level, groups=groups,
+                                    group_out_begin=group_out_begin)
         return r['k'], r['state'], r['y_pred']
 
-    def _train_step_native(self, x_list, y, sample_weight, state0, seed, apply, forward_only=False, node_level=False):
+    def _train_step_native(self, x_list, y, sample_weight, state0, seed, apply, forward_only=False, node_level=False, groups=None,
+                           group_out_begin=None):
         """One `gnn_train_step` call: training-mode forward, loss, BPTT; the tape and every scratch buffer live in one cached
         device allocation. Same results as the general path (same kernels for the arithmetic), ~2.5x fewer launches and no
         Python between them.  `forward_only`: the forward alone (no targets, no gradients; `Loop(..., training=True)`)."""
@@ -905,6 +914,14 @@ class LoopTrainer:
         m = self.model
         composite = isinstance(m.net_state, (list, tuple))
         nets_s = list(m.net_state) if composite else [m.net_state]
+        if groups is not None:
+            if not forward_only: raise NotImplementedError('training-mode convergence groups: the forward only (no grouped train_step)')
+            if composite: raise NotImplementedError('training-mode convergence groups: composite (heterogeneous) models are not covered')
+            if not self._native_forward_applies():
+                raise NotImplementedError('training-mode convergence groups: not covered (data parallelism, Dropout in front of a first Dense, '
+                                          'max_iteration < 1 or the in-library step switched off)')
+            if m._focus == 'g' and not node_level:
+                raise NotImplementedError('training-mode convergence groups: a graph-focused model is covered at node level only (node_level=True)')
         inputs = m.process_inputs(x_list)
         if composite:       # CompositeGNN.py:275-304: one state network per node type (csrc/train_composite.hpp)
             nodes, arcs, dim_node_label, type_mask, set_mask, output_mask, cas, adjacency, arcnode, nodegraph = inputs
@@ -1012,7 +1029,35 @@ class LoopTrainer:
         loss = p.new(1)
         k_host = C.c_int32(0)
         ta.y_pred, ta.state, ta.loss, ta.k_host = nat.ptr(y_pred), nat.ptr(state), nat.ptr(loss), C.pointer(k_host)
-        tiles = adjacency.tiles(64) if (self.use_tiles and not composite) else None      # a merged batch: graphs packed into tiles of <= 64 nodes
+        k_groups = None
+        if groups is not None:
+            gb = np.ascontiguousarray(np.asarray([int(v) for v in groups] if not isinstance(groups, np.ndarray) else groups, dtype=np.int32))
+            if gb.ndim != 1 or len(gb) < 2: raise ValueError('groups: node offsets [G + 1] expected')
+            G = len(gb) - 1
+            if group_out_begin is None:
+                # the group of every output row (node focus: the row's node; arc focus: the arc's source node), from the masks
+                rows = out_index.cpu().numpy().astype(np.int64)
+                if focus == 'a': rows = arcs[:, 0].cpu().numpy().astype(np.int64)[rows]
+                gid = np.searchsorted(gb.astype(np.int64), rows, side='right') - 1
+                if len(gid) and (np.any(np.diff(gid) < 0) or gid[0] < 0 or gid[-1] >= G):
+                    raise ValueError('groups: the output rows are not ordered by group (is this a merge of the groups, in order?)')
+                ob = np.searchsorted(gid, np.arange(G + 1), side='left').astype(np.int32)
+            else:
+                ob = np.ascontiguousarray(np.asarray(group_out_begin, dtype=np.int32))
+                if ob.shape != gb.shape: raise ValueError('group_out_begin: [G + 1] offsets expected')
+            k_groups = p.new(G)
+            keep += [gb, ob, k_groups]
+            ta.group_node_begin, ta.n_groups, ta.group_out_begin, ta.k_groups = gb.ctypes.data, G, ob.ctypes.data, nat.ptr(k_groups)
+            ans = nat.lib().gnn_train_groups_supported(C.byref(ta))
+            if ans == nat.TRAIN_GROUPS_MALFORMED:
+                raise ValueError('groups / group_out_begin must span [0, n_nodes] / [0, output rows] in ascending order, no empty group')
+            if ans == nat.TRAIN_GROUPS_UNCOVERED:
+                raise NotImplementedError('training-mode convergence groups do not cover this shape (one-layer state network of units == state '
+                                          'width <= 64, <= 32 constant columns, no softmax state, no Dropout; one-layer output network <= 64 units)')
+            if ans > 0:
+                raise NotImplementedError(f'training-mode convergence groups: group {ans - 1} has {int(gb[ans] - gb[ans - 1])} nodes '
+                                          f'(at most {nat.TRAIN_GROUP_MAX_NODES} per group)')
+        tiles = adjacency.tiles(64) if (self.use_tiles and not composite and groups is None) else None      # a merged batch: graphs packed into tiles of <= 64 nodes
         if tiles is not None and len(tiles) - 1 <= 256:
             ta.tile_node_begin, ta.n_tiles = tiles.ctypes.data, len(tiles) - 1
         nbytes = nat.lib().gnn_train_workspace_bytes(C.byref(ta))
@@ -1026,6 +1071,9 @@ class LoopTrainer:
         ta.tape, ta.tape_bytes = C.c_void_p(aligned), tape.numel() - (aligned - base)
         if forward_only:
             nat.check(nat.lib().gnn_train_step(C.byref(ta)))
+            if groups is not None:
+                self._keep_groups = keep                       # (the call did not synchronise: its operands live until the next one)
+                return {'k': k_groups, 'y_pred': y_pred, 'state': state}
             return {'k': int(k_host.value), 'y_pred': y_pred, 'state': state}
         # the validity word of this step's gradients (first word of the tape) and - for free, at the call's one synchronisation - the one
         # the previous step left there

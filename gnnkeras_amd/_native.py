@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, 'csrc')
 # GNNKERAS_AMD_LIB: load another build of the same sources (tests: the debug build whose in-launch waits expire at once)
 LIB_PATH = os.environ.get('GNNKERAS_AMD_LIB') or os.path.join(CSRC, 'libgnnloop.so')
 
-GNN_ABI_VERSION = 9
+GNN_ABI_VERSION = 10
 GNN_MAX_LAYERS = 8
 GNN_MAX_TYPES = 8
 
@@ -34,7 +34,7 @@ EXPORTS = ['gnn_last_error', 'gnn_last_kernel_name', 'gnn_abi_version', 'gnn_str
            'gnn_dense', 'gnn_fold_bn', 'gnn_dense_grad_workspace_bytes', 'gnn_dense_grad', 'gnn_act_grad',
            'gnn_colstats_workspace_bytes', 'gnn_colstats', 'gnn_first_layer_param_grads', 'gnn_bn_input_grad',
            'gnn_scatter_add_rows', 'gnn_axpby', 'gnn_loss_grad', 'gnn_dropout', 'gnn_adam_step', 'gnn_adam_multi', 'gnn_sgd_step',
-           'gnn_converged_gated', 'gnn_aggregate_gated', 'gnn_train_workspace_bytes', 'gnn_train_step', 'gnn_ragged_copy',
+           'gnn_converged_gated', 'gnn_aggregate_gated', 'gnn_train_workspace_bytes', 'gnn_train_step', 'gnn_train_groups_supported', 'gnn_ragged_copy',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_destroy', 'gnn_shard_loop']
 GNN_MAX_SEGMENTS = 6
 LOSSES = {'categorical_crossentropy': 0, 'cce': 0, 'binary_crossentropy': 1, 'bce': 1, 'mse': 2,
@@ -126,7 +126,14 @@ class TrainArgs(C.Structure):
                 # ABI 8: the networks' Dropout layers (positions >= 1) and the step's mask seed
                 ('drop_state', DropoutSpec * GNN_MAX_TYPES), ('drop_output', DropoutSpec), ('drop_seed', C.c_uint32),
                 # ABI 9: the training-mode forward alone (no loss, no gradients)
-                ('forward_only', C.c_int32)]
+                ('forward_only', C.c_int32),
+                # ABI 10: training-mode convergence groups (forward_only): host tables [n_groups + 1] of nodes / rows of out_index, k per group
+                ('group_node_begin', C.c_void_p), ('n_groups', C.c_int32), ('group_out_begin', C.c_void_p), ('k_groups', C.c_void_p)]
+
+
+# gnn_train_groups_supported(): 0 covered, -1 shape not covered, -2 malformed group arrays, g + 1 > 0: group g has too many nodes
+TRAIN_GROUPS_OK, TRAIN_GROUPS_UNCOVERED, TRAIN_GROUPS_MALFORMED = 0, -1, -2
+TRAIN_GROUP_MAX_NODES = 256
 
 
 class ShardLoopArgs(C.Structure):       # gnn_shard_loop_args_t (ABI 7): the sharded loop driven from native code (csrc/shard_loop.hpp)
@@ -268,6 +275,7 @@ def lib():
             'gnn_aggregate_gated': (C.c_int, [C.POINTER(CSR), vp, i32, i32, vp, i32, vp, vp]),
             'gnn_train_workspace_bytes': (sz, [C.POINTER(TrainArgs)]),
             'gnn_train_step': (C.c_int, [C.POINTER(TrainArgs)]),
+            'gnn_train_groups_supported': (C.c_int, [C.POINTER(TrainArgs)]),
             'gnn_ragged_copy': (C.c_int, [vp, i32, vp, i32, vp]),
             'gnn_comm_unique_id': (C.c_int, [vp]),
             'gnn_comm_create': (C.c_int, [i32, i32, vp, C.POINTER(vp)]),

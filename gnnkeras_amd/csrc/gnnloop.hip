@@ -1838,4 +1838,5 @@ int gnn_shard_output(const gnn_loop_args_t *args, const float *buf0_full, const 
 #include "shard_loop.hpp"
 #include "train_api.hpp"
 #include "train_loop.hpp"
+#include "train_group.hpp"
 #include "train_composite.hpp"

@@ -138,10 +138,12 @@ struct TypeConsts { ConstSegs cs[GNN_MAX_TYPES]; };          // backward: the co
 template <int SQ, bool HAS_W, bool LOCAL>
 struct TileCsr {
     static constexpr int S = 16 * SQ, LPR = S / 4, NPP = TS_NT / LPR, NPASS = 64 / NPP, IPL = 16 / LPR, PP = NPASS < 2 ? NPASS : 2;
-    int node[NPASS], beg[NPASS], end[NPASS], ids[NPASS][IPL];
-    float wts[NPASS][IPL], scl[NPASS];
+    // (the scalars in front of the per-pass arrays: with `scl` next to `src` the compiler kept that slice of the struct in memory -
+    // 32 bytes of scratch per lane at NPASS >= 2, scripts/kernel_resources.py)
     const int *src; const float *w; const int *inv;
     int n0, nt, q, l4, bad;
+    int node[NPASS], beg[NPASS], end[NPASS], ids[NPASS][IPL];
+    float wts[NPASS][IPL], scl[NPASS];
 
     // `node` = the row's POSITION in the tape (what the kernels address); heterogeneous models walk the nodes in type order: `perm[position]`
     // = the node's id in the caller's operators (row pointers, scales), `inv[id]` = its position (source ids)
@@ -153,12 +155,19 @@ struct TileCsr {
     }
     __device__ __forceinline__ void load(int n0_, int nt_, const int *rowptr, const int *src_, const float *w_, const float *row_scale,
                                          const int *perm = nullptr, const int *inv_ = nullptr) {
-        n0 = n0_; nt = nt_; src = src_; w = w_; bad = 0; inv = inv_;
+        bad = 0;
+        load_rows(n0_, nt_, n0_, nt_, rowptr, src_, w_, row_scale, perm, inv_);
+    }
+    // the rows [r0, r0 + nr) of a block of nodes [n0_, n0_ + nt_) that no arc leaves (LOCAL: ids are positions inside the BLOCK - a group
+    // of several 64-row tiles, kernels_train_group.hpp); `bad` is kept (the caller clears it once)
+    __device__ __forceinline__ void load_rows(int r0, int nr, int n0_, int nt_, const int *rowptr, const int *src_, const float *w_, const float *row_scale,
+                                              const int *perm = nullptr, const int *inv_ = nullptr) {
+        n0 = n0_; nt = nt_; src = src_; w = w_; inv = inv_;
         q = threadIdx.x / LPR; l4 = threadIdx.x % LPR;
 #pragma unroll
         for (int p = 0; p < NPASS; ++p) {
             const int r = p * NPP + q;
-            node[p] = r < nt ? n0 + r : -1;
+            node[p] = r < nr ? r0 + r : -1;
             beg[p] = end[p] = 0; scl[p] = 1.0f;
             if (node[p] >= 0) { const int o = perm ? perm[node[p]] : node[p]; beg[p] = rowptr[o]; end[p] = rowptr[o + 1]; if (row_scale) scl[p] = row_scale[o]; }
 #pragma unroll

@@ -1,0 +1,228 @@
+// Host side of the grouped training-mode forward (C ABI 10; kernels_train_group.hpp): coverage, group tables, workspace, launches.
+// Included behind train_loop.hpp in gnnloop.hip (shares its plan and helpers).
+#pragma once
+#include "kernels_train_group.hpp"
+
+namespace {
+
+static_assert(GNN_TRAIN_GROUP_MAX_NODES == gnn::GROUP_CAP, "include/gnnloop.h and kernels_train_group.hpp disagree on the group size");
+
+struct GroupPlan {
+    TrainPlan p;                 // dims only (planned without a workspace)
+    int G, max_nodes;
+    int *gbeg, *obeg;            // device copies of the host tables
+    float *agg_arcs, *agg_nodes, *cc, *agg, *stats_s, *stats_o;
+    int *isrc, *idst;
+    size_t bytes;
+};
+
+// what the grouped kernels cover (dims and network descriptions only)
+bool train_groups_covered(const gnn_train_args_t &ta, const TrainPlan &p) {
+    const gnn_loop_args_t &a = ta.loop;
+    const gnn_mlp_t &ns = a.net_state[0], &no = a.net_output;
+    if (a.composite || a.n_types > 1) return false;
+    if (ta.drop_state[0].n > 0 || ta.drop_output.n > 0) return false;
+    if (a.focus != GNN_FOCUS_NODE && a.focus != GNN_FOCUS_ARC) return false;
+    if (ns.n_layers != 1 || ns.units[0] != p.S || p.S > 64 || p.Kc > 32 || ns.activation[0] == GNN_ACT_SOFTMAX || p.K < 1) return false;
+    if (no.n_layers != 1 || no.units[0] > gnn::GROUP_HEAD_MAX_UNITS || no.in_dim > gnn::GROUP_HEAD_MAX_IN) return false;
+    return true;
+}
+
+// the host tables: 0 fine, -2 malformed (message set when `say`), g + 1: group g is too large
+int train_group_tables(const gnn_train_args_t &ta, const TrainPlan &p, bool say, int *max_nodes) {
+    const int G = ta.n_groups;
+    if (max_nodes) *max_nodes = 0;
+    if (!ta.group_node_begin || !ta.group_out_begin) { if (say) fail("group_node_begin / group_out_begin is NULL"); return GNN_TRAIN_GROUPS_MALFORMED; }
+    if (ta.group_node_begin[0] != 0 || ta.group_node_begin[G] != p.N) { if (say) fail("group_node_begin must span [0, n_nodes]"); return GNN_TRAIN_GROUPS_MALFORMED; }
+    if (ta.group_out_begin[0] != 0 || ta.group_out_begin[G] != p.M) { if (say) fail("group_out_begin must span [0, n_out]"); return GNN_TRAIN_GROUPS_MALFORMED; }
+    int too_large = 0, mx = 0;
+    for (int g = 0; g < G; ++g) {
+        const int n = ta.group_node_begin[g + 1] - ta.group_node_begin[g];
+        if (n <= 0) { if (say) fail("group %d is empty or group_node_begin is not ascending", g); return GNN_TRAIN_GROUPS_MALFORMED; }
+        if (ta.group_out_begin[g + 1] < ta.group_out_begin[g]) { if (say) fail("group_out_begin is not ascending at group %d", g); return GNN_TRAIN_GROUPS_MALFORMED; }
+        if (n > gnn::GROUP_CAP && !too_large) too_large = g + 1;
+        mx = std::max(mx, n);
+    }
+    if (max_nodes) *max_nodes = mx;
+    return too_large;
+}
+
+int make_group_plan(const gnn_train_args_t &ta, void *ws, GroupPlan &gp) {
+    TRY(make_train_plan(ta, nullptr, gp.p));
+    const TrainPlan &p = gp.p;
+    gp.G = ta.n_groups;
+    Carver c(ws);
+    gp.gbeg = c.take<int>((size_t)gp.G + 1); gp.obeg = c.take<int>((size_t)gp.G + 1);
+    gp.agg_arcs = c.take<float>((size_t)p.N * std::max(p.A, 1));
+    gp.agg_nodes = c.take<float>((size_t)p.N * std::max(p.L, 1));
+    gp.cc = c.take<float>((size_t)p.N * p.SPs);
+    gp.agg = c.take<float>((size_t)p.N * p.SPs);
+    gp.stats_s = c.take<float>((size_t)gp.G * p.K * 2 * p.in_s);
+    gp.stats_o = c.take<float>((size_t)gp.G * 2 * p.in_o);
+    gp.isrc = c.take<int>(std::max(p.M, 1)); gp.idst = c.take<int>(std::max(p.M, 1));
+    gp.bytes = (c.off + 255) & ~(size_t)255;
+    return 0;
+}
+
+size_t group_train_workspace_bytes(const gnn_train_args_t &ta) {
+    if (ta.n_groups < 0) { fail("n_groups < 0"); return 0; }
+    GroupPlan gp;
+    if (make_group_plan(ta, nullptr, gp)) return 0;
+    return gp.bytes;
+}
+
+template <int SQ>
+int launch_train_group_fwd_sq(const gnn::TrainGroupFwd &fa, int G, int max_nodes, bool has_w, hipStream_t st) {
+    const size_t lds = gnn::train_group_fwd_lds<SQ>(max_nodes);
+    auto go = [&](auto kern) -> int {
+        // (the limit is raised to what the largest group allowed needs, once per kernel)
+        static std::mutex m;
+        static bool raised = false;
+        {
+            std::lock_guard<std::mutex> lock(m);
+            if (!raised) {
+                HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gnn::train_group_fwd_lds<SQ>(gnn::GROUP_CAP)));
+                raised = true;
+            }
+        }
+        kern<<<G, gnn::TS_NT, lds, st>>>(fa);
+        LAUNCH_OK();
+        return 0;
+    };
+    return has_w ? go(&gnn::k_train_group_fwd<SQ, true>) : go(&gnn::k_train_group_fwd<SQ, false>);
+}
+
+int train_forward_groups(const gnn_train_args_t &ta) {
+    const gnn_loop_args_t &a = ta.loop;
+    if (!ta.forward_only) return fail("gnn_train_step: convergence groups need forward_only (a grouped training step is not implemented)");
+    if (ta.prev_grads_ok_host) return fail("gnn_train_step(forward_only): prev_grads_ok_host must be NULL");
+    if (ta.n_groups < 0) return fail("n_groups < 0");
+    GroupPlan gp;
+    TRY(make_group_plan(ta, ta.tape, gp));
+    const TrainPlan &p = gp.p;
+    if (!train_groups_covered(ta, p)) return fail("gnn_train_step: convergence groups do not cover this shape (gnn_train_groups_supported() == %d)", GNN_TRAIN_GROUPS_UNCOVERED);
+    const int tab = train_group_tables(ta, p, true, &gp.max_nodes);
+    if (tab < 0) return 1;
+    if (tab > 0) return fail("group %d has %d nodes (at most %d per convergence group: gnn_train_groups_supported())", tab - 1,
+                             ta.group_node_begin[tab] - ta.group_node_begin[tab - 1], gnn::GROUP_CAP);
+    if (ta.tape_bytes < gp.bytes) return fail("tape too small: %zu < %zu bytes", ta.tape_bytes, gp.bytes);
+    TRY(check_csr(a.adjacency, "adjacency", p.N, p.N));
+    TRY(check_csr(a.arcnode, "arcnode", p.N, p.E));
+    if (!a.nodes || (p.E > 0 && p.A > 0 && !a.arc_labels)) return fail("nodes / arc_labels is NULL");
+    if (a.state_dim > 0 && !a.state0) return fail("state0 is required when state_dim > 0");
+    if (p.M > 0 && !a.out_index) return fail("out_index is NULL");
+    if (a.focus == GNN_FOCUS_ARC && p.E > 0 && (!a.arc_src || !a.arc_dst)) return fail("arc focus needs arc_src / arc_dst");
+    if ((p.M > 0 && !ta.y_pred) || !ta.state || !ta.k_groups) return fail("y_pred / state / k_groups is NULL");
+    const gnn_mlp_t &ns = a.net_state[0], &no = a.net_output;
+    TRY(check_mlp(ns, "net_state", true));
+    TRY(check_mlp(no, "net_output", true));
+    const bool bn_s = ns.has_bn != 0, bn_o = no.has_bn != 0;
+    hipStream_t st = (hipStream_t)a.stream;
+    const int G = gp.G;
+    GNN_SET_KERNEL_NAME("train_step: grouped forward kernels");
+
+    // the group tables go to the device through a pinned staging buffer of this thread; its event says when the previous call's copy has left it
+    {
+        static thread_local struct { int *buf; size_t cap; hipEvent_t ev; } stage = {nullptr, 0, nullptr};
+        const size_t n_tab = 2 * ((size_t)G + 1);
+        if (stage.ev) HIP_OK(hipEventSynchronize(stage.ev));
+        else HIP_OK(hipEventCreateWithFlags(&stage.ev, hipEventDisableTiming));
+        if (stage.cap < n_tab) {
+            if (stage.buf) HIP_OK(hipHostFree(stage.buf));
+            stage.buf = nullptr; stage.cap = 0;
+            HIP_OK(hipHostMalloc((void **)&stage.buf, std::max<size_t>(n_tab, 4096) * sizeof(int), hipHostMallocDefault));
+            stage.cap = std::max<size_t>(n_tab, 4096);
+        }
+        memcpy(stage.buf, ta.group_node_begin, ((size_t)G + 1) * sizeof(int));
+        memcpy(stage.buf + G + 1, ta.group_out_begin, ((size_t)G + 1) * sizeof(int));
+        HIP_OK(hipMemcpyAsync(gp.gbeg, stage.buf, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(gp.obeg, stage.buf + G + 1, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_OK(hipEventRecord(stage.ev, st));
+    }
+    // aggregates of the constants over the merged graph (block-diagonal: a row sees its own group only)
+    if (p.A > 0) TRY(launch_aggregate(nullptr, a.arcnode, a.arc_labels, a.ld_arcs, p.A, gp.agg_arcs, p.A, st));
+    if (p.with_labels) TRY(launch_aggregate(nullptr, a.adjacency, a.nodes, a.ld_nodes, p.L, gp.agg_nodes, p.L, st));
+    gnn::ConstSegs cs;
+    memset(&cs, 0, sizeof(cs));
+    cs.n = p.cc.n;
+    for (int s = 0; s < cs.n; ++s) { cs.width[s] = p.cc.width[s]; cs.wrow[s] = p.cc.wrow[s]; }
+    if (p.with_labels) {
+        cs.ptr[0] = a.nodes; cs.ld[0] = a.ld_nodes;
+        cs.ptr[1] = gp.agg_nodes; cs.ld[1] = p.L;
+        cs.ptr[2] = gp.agg_arcs; cs.ld[2] = p.A;
+    } else { cs.ptr[0] = gp.agg_arcs; cs.ld[0] = p.A; }
+    gnn::k_train_group_const<<<G, 256, 0, st>>>(gp.gbeg, p.SPs, p.S, cs, ns.kernel[0], ns.bias[0], bn_s ? ns.bn_gamma : nullptr, ns.bn_beta, ns.bn_eps,
+                                                gp.cc, gp.stats_s, p.K, p.in_s);
+    LAUNCH_OK();
+    gnn::TrainGroupFwd fa;
+    memset(&fa, 0, sizeof(fa));
+    fa.S = p.SPs; fa.Sw = p.S; fa.K = p.K;
+    fa.rowptr = a.adjacency.rowptr; fa.src = a.adjacency.src; fa.w = a.adjacency.w; fa.row_scale = a.adjacency.row_scale;
+    fa.gbeg = gp.gbeg;
+    fa.state0 = a.state_dim > 0 ? a.state0 : a.nodes; fa.ld0 = a.state_dim > 0 ? p.S : a.ld_nodes;
+    fa.state_out = ta.state; fa.agg = gp.agg; fa.stats = gp.stats_s; fa.in_s = p.in_s; fa.off_agg = p.off_agg;
+    fa.W = ns.kernel[0]; fa.gamma = bn_s ? ns.bn_gamma : nullptr; fa.beta = ns.bn_beta; fa.eps = ns.bn_eps; fa.act = ns.activation[0];
+    fa.Cc = gp.cc; fa.thr = a.state_threshold; fa.k_groups = ta.k_groups;
+    switch (p.SPs) {
+        case 16: TRY(launch_train_group_fwd_sq<1>(fa, G, gp.max_nodes, a.adjacency.w != nullptr, st)); break;
+        case 32: TRY(launch_train_group_fwd_sq<2>(fa, G, gp.max_nodes, a.adjacency.w != nullptr, st)); break;
+        default: TRY(launch_train_group_fwd_sq<4>(fa, G, gp.max_nodes, a.adjacency.w != nullptr, st)); break;
+    }
+    if (bn_s) {
+        gnn::k_bn_moving_groups<<<cdiv(p.in_s, 64), 64, 0, st>>>(gp.stats_s, p.K, p.in_s, ta.k_groups, nullptr, G, const_cast<float *>(ns.bn_mean),
+                                                                const_cast<float *>(ns.bn_var), ta.bn_momentum);
+        LAUNCH_OK();
+    }
+    if (p.M > 0) {
+        gnn::TrainGroupHead h;
+        memset(&h, 0, sizeof(h));
+        int n = 0;
+        auto seg = [&](const float *ptr, const int *idx, int ld, int width) { h.sg.ptr[n] = ptr; h.sg.idx[n] = idx; h.sg.ld[n] = ld; h.sg.width[n] = width; ++n; };
+        if (a.focus == GNN_FOCUS_ARC) {
+            k_arc_endpoints<<<cdiv(p.M, 256), 256, 0, st>>>(a.out_index, a.arc_src, a.arc_dst, p.M, gp.isrc, gp.idst);
+            LAUNCH_OK();
+            const int *ends[2] = {gp.isrc, gp.idst};
+            for (int e = 0; e < 2; ++e) {
+                seg(ta.state, ends[e], p.S, p.S);
+                if (p.with_labels) seg(a.nodes, ends[e], a.ld_nodes, p.L);
+            }
+            if (p.A > 0) seg(a.arc_labels, a.out_index, a.ld_arcs, p.A);
+        } else {
+            seg(ta.state, a.out_index, p.S, p.S);
+            if (p.with_labels) seg(a.nodes, a.out_index, a.ld_nodes, p.L);
+        }
+        h.sg.n = n;
+        h.obeg = gp.obeg; h.in_o = p.in_o; h.T = p.T; h.act = no.activation[0];
+        h.W = no.kernel[0]; h.b = no.bias[0]; h.gamma = bn_o ? no.bn_gamma : nullptr; h.beta = no.bn_beta; h.eps = no.bn_eps;
+        h.stats_o = gp.stats_o; h.out = ta.y_pred;
+        const size_t lds = gnn::train_group_head_lds(p.in_o, p.T);
+        static std::mutex m;
+        static bool raised = false;
+        {
+            std::lock_guard<std::mutex> lock(m);
+            if (!raised) {
+                HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&gnn::k_train_group_head), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)gnn::train_group_head_lds(gnn::GROUP_HEAD_MAX_IN, gnn::GROUP_HEAD_MAX_UNITS)));
+                raised = true;
+            }
+        }
+        gnn::k_train_group_head<<<G, 256, lds, st>>>(h);
+        LAUNCH_OK();
+        if (bn_o) {
+            gnn::k_bn_moving_groups<<<cdiv(p.in_o, 64), 64, 0, st>>>(gp.stats_o, 1, p.in_o, ta.k_groups, gp.obeg, G, const_cast<float *>(no.bn_mean),
+                                                                    const_cast<float *>(no.bn_var), ta.bn_momentum);
+            LAUNCH_OK();
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int gnn_train_groups_supported(const gnn_train_args_t *args) {
+    if (!args || args->n_groups < 1 || !args->forward_only) return GNN_TRAIN_GROUPS_UNCOVERED;
+    TrainPlan p;
+    if (make_train_plan(*args, nullptr, p)) return GNN_TRAIN_GROUPS_UNCOVERED;
+    if (!train_groups_covered(*args, p)) return GNN_TRAIN_GROUPS_UNCOVERED;
+    return train_group_tables(*args, p, false, nullptr);
+}

@@ -797,6 +797,9 @@ int tile_table(const gnn_train_args_t &ta, const TrainPlan &p, gnn::TileTab &tt)
 // heterogeneous models: train_composite.hpp (behind this file in the same translation unit)
 int train_step_composite(const gnn_train_args_t &ta);
 size_t composite_train_workspace_bytes(const gnn_train_args_t &ta);
+// convergence groups of a training-mode forward (ABI 10): train_group.hpp (behind this file in the same translation unit)
+int train_forward_groups(const gnn_train_args_t &ta);
+size_t group_train_workspace_bytes(const gnn_train_args_t &ta);
 
 }  // namespace
 
@@ -804,6 +807,7 @@ extern "C" {
 
 size_t gnn_train_workspace_bytes(const gnn_train_args_t *args) {
     if (!args) { fail("args is NULL"); return 0; }
+    if (args->n_groups != 0) return group_train_workspace_bytes(*args);
     if (args->loop.composite) return composite_train_workspace_bytes(*args);
     TrainPlan p;
     if (make_train_plan(*args, nullptr, p)) return 0;
@@ -831,6 +835,7 @@ static int train_step_impl(const gnn_train_args_t &ta) {
     TrainPlan p;
     if (!ta.tape || ((uintptr_t)ta.tape & 255) != 0) return fail("tape must be a 256-byte aligned device buffer");
     const bool fwd_only = ta.forward_only != 0;                   // ABI 9: the training-mode forward alone (no loss, no gradients)
+    if (ta.n_groups != 0) return train_forward_groups(ta);         // ABI 10: independent convergence groups (train_group.hpp)
     if (a.composite) {
         if (fwd_only) return fail("gnn_train_step(forward_only): homogeneous models only");
         return train_step_composite(ta);                           // one state network per node type (train_composite.hpp)

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GNN_ABI_VERSION 9
+#define GNN_ABI_VERSION 10
 
 /* Keras activation names accepted by the reference MLP builder (GNN/Models/MLP.py:16). */
 enum gnn_activation {
@@ -549,6 +549,21 @@ typedef struct gnn_train_args {
      * touched (they may be NULL / zero; prev_grads_ok_host must be NULL - a forward has no step before it to judge).  y_pred, state and
      * k_host are written as by a step.  Homogeneous models only. */
     int32_t forward_only;
+    /* ABI 10: training-mode convergence GROUPS, valid only with forward_only != 0 (n_groups == 0: everything above, unchanged).  The graph
+     * is a merge of n_groups graphs - group g owns the nodes [group_node_begin[g], group_node_begin[g + 1]), no arc joins two groups - and
+     * the result equals n_groups consecutive forward_only calls on the groups alone, IN GROUP ORDER: BatchNormalization of both networks
+     * on the column statistics of the group's own rows (state network: all its nodes, every iteration; output network: its rows of
+     * out_index, [group_out_begin[g], group_out_begin[g + 1]) - a group without such a row skips the output network and leaves its
+     * moving statistics alone), its own predicate and its own iteration count k_groups[g]; the moving statistics are moved group after
+     * group, once per executed iteration (state network) and once per group with output rows (output network), by the literal
+     * recurrence.  state0 is [n_nodes, state_dim] for the merged graph.  focus NODE or ARC (a graph-focused model: its per-node outputs).
+     * The call does NOT synchronise the stream and does not write k_host: read k_groups with the state.  An arc that leaves its group is
+     * found on the device: k_groups[g] < 0, and every result of that group (and the moving statistics it would have moved: skipped) is
+     * invalid.  Covered shapes: gnn_train_groups_supported. */
+    const int32_t *group_node_begin;           /* HOST array [n_groups + 1], ascending, [0] = 0, [n_groups] = n_nodes  */
+    int32_t n_groups;
+    const int32_t *group_out_begin;            /* HOST array [n_groups + 1], non-descending, [0] = 0, [n_groups] = n_out */
+    float *k_groups;                           /* OUT, device float[n_groups]                                           */
 } gnn_train_args_t;
 /* Arithmetic: float32 throughout.  On graphs of >= GNN_TRAIN_BIG_MIN_NODES (32 768) nodes the first Dense's forward product and dZ . W^T run on
  * the bf16 matrix cores with every float32 operand split into three bf16 terms (six products, float32 accumulation: the accuracy of a
@@ -556,6 +571,21 @@ typedef struct gnn_train_args {
  * arrives. */
 size_t gnn_train_workspace_bytes(const gnn_train_args_t *args);
 int gnn_train_step(const gnn_train_args_t *args);
+/* May these arguments run as a grouped training-mode forward (ABI 10)?  Reads dims, network descriptions (no device memory) and the host
+ * group arrays only.
+ *   GNN_TRAIN_GROUPS_OK (0)           yes
+ *   GNN_TRAIN_GROUPS_UNCOVERED (-1)   the shape is not covered: anything but a homogeneous model with a one-layer state network of
+ *                                     units == state width <= 64, <= 32 constant input columns, no softmax state activation, no Dropout,
+ *                                     max_iteration >= 1, node / arc focus, and a one-layer output network of <= 64 units over <= 256
+ *                                     input columns without Dropout (BatchNormalization or not in both)
+ *   GNN_TRAIN_GROUPS_MALFORMED (-2)   the group arrays are missing or do not span [0, n_nodes] / [0, n_out] in ascending order
+ *   g + 1 > 0                         group g (the first such) has more than GNN_TRAIN_GROUP_MAX_NODES nodes: run that graph by a plain
+ *                                     forward_only call between two grouped calls (the order of the moving-statistics updates holds) */
+#define GNN_TRAIN_GROUPS_OK 0
+#define GNN_TRAIN_GROUPS_UNCOVERED (-1)
+#define GNN_TRAIN_GROUPS_MALFORMED (-2)
+#define GNN_TRAIN_GROUP_MAX_NODES 256
+int gnn_train_groups_supported(const gnn_train_args_t *args);
 
 #ifdef __cplusplus
 }
