@@ -16,7 +16,7 @@ import torch
 
 from .. import _native as nat
 from .. import ops
-from ..sparse import SparseMatrix
+from ..sparse import SparseMatrix, XC_MIN_NODES, xc_reuse_enabled
 from .MLP import Sequential
 
 
@@ -768,11 +768,20 @@ class GNNnodeBased(_LoopModel):
         if group_sets is not None:
             gs_ = np.asarray([int(v) for v in group_sets], dtype=np.int64)
             set_id = torch.as_tensor(np.repeat(np.arange(len(gs_) - 1), np.diff(gs_)), device=dev)
+        # a large graph keeps its constants line with the batch (sparse.py): the first call fills it, later ones read it
+        xc, xc_valid = None, False
+        if groups is None and N >= XC_MIN_NODES and xc_reuse_enabled() and \
+                ops.loop_xc_applies(N, nodes.shape[1], arcs.shape[1] - 2, self.net_state, self.net_output, self.state_vect_dim, self.max_iteration,
+                                    nat.FOCUS[focus], self.native_flags, len(out_index), adj):
+            xc, xc_valid = adjacency.constants_line(nodes, arcs, SparseMatrix.from_triple(arcnode), nodes.shape[1], self.state_vect_dim > 0, dev)
         # the whole Loop is ONE custom op: torch.ops.gnnkeras.loop_forward (csrc/torch_ops.cpp -> gnn_loop_forward)
         k, state, out = ops.loop_forward(nodes.to(torch.float32).contiguous(), arcs.to(torch.float32).contiguous(), adj, arcn, ng,
                                          self.net_state, self.net_output, state0, out_index, ends, self.state_vect_dim,
                                          self.max_iteration, self.state_threshold, nat.FOCUS[focus], self.native_flags,
-                                         loop_events=self.loop_events, groups=groups, group_sets=group_sets)
+                                         loop_events=self.loop_events, groups=groups, group_sets=group_sets, xc=xc, xc_valid=xc_valid,
+                                         # (ascending distinct node ids, N of them: 0 .. N - 1)
+                                         out_index_identity=focus != 'a' and len(out_index) == N and N > 0)
+        if xc is not None and not xc_valid: adjacency.constants_line_filled()
         if group_sets is not None:
             # one entry per set: its groups report the same k - or -1e9 where a member's wait for the others expired (any member: the
             # minimum keeps it, so _check_k / check_last_k see it)

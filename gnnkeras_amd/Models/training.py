@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from .. import _native as nat
-from ..sparse import SparseMatrix, CSRByDestination
+from ..sparse import SparseMatrix, CSRByDestination, XC_MIN_NODES, xc_reuse_enabled
 from .MLP import Sequential, BN_EPSILON, BN_MOMENTUM
 
 
@@ -1060,6 +1060,14 @@ class LoopTrainer:
         tiles = adjacency.tiles(64) if (self.use_tiles and not composite and groups is None) else None      # a merged batch: graphs packed into tiles of <= 64 nodes
         if tiles is not None and len(tiles) - 1 <= 256:
             ta.tile_node_begin, ta.n_tiles = tiles.ctypes.data, len(tiles) - 1
+        # a large graph keeps its constants line with the batch (sparse.py), shared with the inference forward: the first call fills it
+        xc_fill = False
+        if groups is None and not composite and N >= XC_MIN_NODES and xc_reuse_enabled() and nat.lib().gnn_train_xc_applies(C.byref(ta)):
+            caller_nodes, caller_arcs = inputs[0], inputs[1]          # (the objects the caller passed: what the line's key holds)
+            line, valid = adjacency.constants_line(caller_nodes, caller_arcs, arcnode, L, d > 0, dev)
+            a.xc, a.xc_mode = nat.ptr(line), (nat.XC_VALID if valid else nat.XC_FILL)
+            xc_fill = not valid
+            keep.append(line)
         nbytes = nat.lib().gnn_train_workspace_bytes(C.byref(ta))
         if nbytes == 0: nat.check(1)
         tape = getattr(self, '_tape', None)
@@ -1071,6 +1079,7 @@ class LoopTrainer:
         ta.tape, ta.tape_bytes = C.c_void_p(aligned), tape.numel() - (aligned - base)
         if forward_only:
             nat.check(nat.lib().gnn_train_step(C.byref(ta)))
+            if xc_fill: adjacency.constants_line_filled()
             if groups is not None:
                 self._keep_groups = keep                       # (the call did not synchronise: its operands live until the next one)
                 return {'k': k_groups, 'y_pred': y_pred, 'state': state}
@@ -1095,6 +1104,7 @@ class LoopTrainer:
                 prev_valid = bool(prev_ok.value) if (fetched_by_call and prev_ok.value >= 0) else (self._read_word(pend['view']) if fetched_by_call else prev_ok.value != 0)
                 if not prev_valid: self._recover_failed(pend)
             raise
+        if xc_fill: adjacency.constants_line_filled()
         for g_ in gs_all: g_.touched = k_host.value > 0          # (a type without nodes: the library zero-fills its gradients)
         go.touched = len(out_index) > 0
         view = tape[aligned - base:aligned - base + 4].view(torch.int32)

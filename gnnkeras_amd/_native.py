@@ -24,9 +24,11 @@ FOCUS = {'n': 0, 'a': 1, 'g': 2}
 FLAG_UNFUSED = 1
 FLAG_NO_EARLY_EXIT = 2
 FLAG_FUSED_GEN_MASK = 7 << 4
+XC_FILL, XC_VALID = 0, 1                # enum gnn_xc_mode
 FLAG_FUSED_GEN2, FLAG_FUSED_GEN4, FLAG_FUSED_GEN5, FLAG_FUSED_GEN6, FLAG_FUSED_GEN7 = 2 << 4, 4 << 4, 5 << 4, 6 << 4, 7 << 4     # pin the fused-kernel generation (tests, tuning)
 
 EXPORTS = ['gnn_last_error', 'gnn_last_kernel_name', 'gnn_abi_version', 'gnn_struct_size', 'gnn_loop_workspace_bytes', 'gnn_loop_forward', 'gnn_loop_groups_supported', 'gnn_aggregate',
+           'gnn_loop_xc_applies', 'gnn_train_xc_applies',
            'gnn_mlp_workspace_bytes', 'gnn_mlp_forward', 'gnn_converged', 'gnn_state_step', 'gnn_state_step_agg', 'gnn_state_ld', 'gnn_debug_occupy', 'gnn_debug_occupy_until', 'gnn_debug_expiry_beacon', 'gnn_debug_host_flag',
            'gnn_device_malloc', 'gnn_device_free', 'gnn_ipc_export', 'gnn_ipc_open', 'gnn_ipc_close', 'gnn_shard_iteration_peers', 'gnn_peer_wait', 'gnn_peer_publish', 'gnn_shard_iteration_split_rows',
            'gnn_shard_setup', 'gnn_shard_iteration', 'gnn_shard_output', 'gnn_gather_rows',
@@ -79,7 +81,9 @@ class LoopArgs(C.Structure):
                 ('n_heavy_segments', C.c_int32),
                 ('ev_loop_begin', C.c_void_p), ('ev_loop_end', C.c_void_p),
                 ('group_node_begin', C.c_void_p), ('n_groups', C.c_int32),
-                ('group_set_begin', C.c_void_p), ('n_group_sets', C.c_int32)]
+                ('group_set_begin', C.c_void_p), ('n_group_sets', C.c_int32),
+                # the constants line of the batch, owned by the caller ([n_nodes, 32] floats, 256-byte aligned) + enum gnn_xc_mode
+                ('xc', C.c_void_p), ('xc_mode', C.c_int32)]
 
 
 class DenseArgs(C.Structure):
@@ -276,6 +280,8 @@ def lib():
             'gnn_train_workspace_bytes': (sz, [C.POINTER(TrainArgs)]),
             'gnn_train_step': (C.c_int, [C.POINTER(TrainArgs)]),
             'gnn_train_groups_supported': (C.c_int, [C.POINTER(TrainArgs)]),
+            'gnn_loop_xc_applies': (C.c_int, [C.POINTER(LoopArgs)]),
+            'gnn_train_xc_applies': (C.c_int, [C.POINTER(TrainArgs)]),
             'gnn_ragged_copy': (C.c_int, [vp, i32, vp, i32, vp]),
             'gnn_comm_unique_id': (C.c_int, [vp]),
             'gnn_comm_create': (C.c_int, [i32, i32, vp, C.POINTER(vp)]),

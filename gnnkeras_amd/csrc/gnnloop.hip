@@ -568,7 +568,8 @@ int make_plan(const gnn_loop_args_t &a, void *ws, Plan &p, bool validate_ptrs) {
         if (!a.k_out) return fail("k_out is NULL");
         if (p.N > 0 && !a.state_out) return fail("state_out is NULL");
         if (!a.out && (a.focus == GNN_FOCUS_GRAPH ? a.nodegraph.n_dst : p.M) > 0) return fail("out is NULL");
-        if (p.M > 0 && !a.out_index) return fail("out_index is NULL");
+        // (NULL out_index: the identity - every node an output row, in node order)
+        if (p.M > 0 && !a.out_index && (a.focus == GNN_FOCUS_ARC || p.M != p.N)) return fail("out_index is NULL (the identity needs node / graph focus and n_out == n_nodes)");
         if (a.focus == GNN_FOCUS_ARC && p.E > 0 && (!a.arc_src || !a.arc_dst)) return fail("arc focus needs arc_src / arc_dst");
         if (a.focus == GNN_FOCUS_GRAPH) {
             if (a.nodegraph.n_src != p.M) return fail("graph focus: NodeGraph has %d rows but %d nodes pass the mask (the reference's matmul would fail too)", a.nodegraph.n_src, p.M);
@@ -720,14 +721,47 @@ int iteration_unfused(const gnn_loop_args_t &a, const Plan &p, const int *gate, 
 // `aggregated_nodes` / `aggregated_arcs` (GNN.py:217) or, column blocks of one matrix, `aggregated_component` (CompositeGNN.py:214)
 struct GivenAgg { const float *nodes; int ld_nodes; const float *arcs; int ld_arcs; };
 
+// The constants line of a homogeneous batch, xc[j] = [labels | Adjacency^T labels | ArcNode^T arc labels | 1 | 0 ..] (L0 = label columns the
+// state network sees: 0 when state_dim == 0), built in place: the aggregates write their columns of the line (the same launches, sums
+// and arc order as into arrays of their own), k_xc_own the rest - every element of `xc` is written.  Shared by gnn_loop_forward and the
+// large-graph training step: both build the same line, so a caller may keep ONE per batch (gnn_loop_args_t::xc).
+int fill_constants_line(const gnn_loop_args_t &a, int N, int L0, int A, float *xc, hipStream_t st) {
+    if (A > 0) TRY(launch_aggregate(nullptr, a.arcnode, a.arc_labels, a.ld_arcs, A, xc + 2 * L0, 32, st));
+    if (L0 > 0) TRY(launch_aggregate(nullptr, a.adjacency, a.nodes, a.ld_nodes, L0, xc + L0, 32, st));
+    gnn::k_xc_own<<<(int)std::min<long>(cdiv((long)N * 32, 256), 256 * 16), 256, 0, st>>>(N, a.nodes, a.ld_nodes, L0, 2 * L0 + A, xc);
+    LAUNCH_OK();
+    return 0;
+}
+// the caller's line, checked as far as it can be (GNN_XC_VALID itself is a promise)
+int check_xc_args(const gnn_loop_args_t &a) {
+    if (!a.xc) return 0;
+    if (((uintptr_t)a.xc & 255) != 0) return fail("xc must be 256-byte aligned");
+    if (a.xc_mode != GNN_XC_FILL && a.xc_mode != GNN_XC_VALID) return fail("unknown xc_mode %d", a.xc_mode);
+    return 0;
+}
+
+// `xc_line`: the iterations run on the XC form alone (skip_c) on a homogeneous graph - the line (p.Xc: the caller's or the workspace's) is
+// filled in place, or adopted as it is with `xc_valid`
 int setup_constants(const gnn_loop_args_t &a, const Plan &p, hipStream_t st, bool zero_loop_words = false, bool skip_c = false,
-                    const GivenAgg *given = nullptr) {
+                    const GivenAgg *given = nullptr, bool xc_line = false, bool xc_valid = false) {
     // BN folding of every first layer: one launch, which also zeroes the flag words / barrier counters and k
     FoldList fl;
     for (int t = 0; t < p.T; ++t) fl.add(a.net_state[t], p.tp[t].Wf, p.tp[t].bf);
     if (a.net_output.kernel[0]) fl.add(a.net_output, p.Wf_out, p.bf_out);      // absent for the standalone state step
     if (zero_loop_words) { fl.fa.zero_a = p.flags; fl.fa.n_a = a.max_iteration + GNN_LOOP_WORDS; fl.fa.zero_b = a.k_out; fl.fa.n_b = 1; }
     TRY(launch_fold_list(fl, st));
+    if (xc_line) {      // nothing but the line is read on this path: no aggregate arrays, no C
+        const TypePlan &tp = p.tp[0];
+        if (!xc_valid) TRY(fill_constants_line(a, p.N, a.state_dim > 0 ? p.L : 0, p.A, p.Xc, st));
+        gnn::PackSegs ps;
+        memset(&ps, 0, sizeof(ps));
+        ps.n = tp.ncseg;
+        for (int s2 = 0; s2 < tp.ncseg && s2 < 3; ++s2) { ps.width[s2] = tp.cseg[s2].width; ps.wrow[s2] = tp.cseg[s2].wrow; }
+        const int H = tp.net->units[0];
+        gnn::k_pack_wc<<<cdiv(32 * H, 256), 256, 0, st>>>(tp.Wf, tp.bf, H, ps, tp.Wc);
+        LAUNCH_OK();
+        return 0;
+    }
     // ArcNode scatter-add (GNN.py:254) and neighbour-label aggregates (GNN.py:258 / CompositeGNN.py:251)
     if (given) {
         if (p.A > 0) TRY(launch_copy2d(nullptr, given->arcs, given->ld_arcs, p.agg_arcs, p.A, p.N, p.A, p.A, st));
@@ -1273,6 +1307,23 @@ size_t gnn_struct_size(int which) {
     }
 }
 
+// every iteration on the XC form of the wave-specialised kernel (large homogeneous / composite graphs): C is never read
+bool xc_loop_applies(const gnn_loop_args_t &a, const Plan &p, int fz, bool soft, bool whole_loop) {
+    return p.xc_ok && !whole_loop && fz == 1 && (soft || !mid_applies(a, p)) && p.SP != 128 && !iter_adjacency(a, p).w &&
+           iteration_generation(a, p) == 4 && fused_generation(p.SP, p.N, a.flags) == 4;
+}
+
+int gnn_loop_xc_applies(const gnn_loop_args_t *args) {
+    if (!args) return 0;
+    Plan p;
+    if (make_plan(*args, nullptr, p, false)) return 0;
+    if (p.composite || p.N == 0 || p.n_groups > 0) return 0;
+    const int fz = fusable(*args, p);
+    const bool soft = state_softmax(*args, p);
+    const bool whole_loop = fz != 0 && !soft && persistent_applies(*args, p);
+    return xc_loop_applies(*args, p, fz, soft, whole_loop) ? 1 : 0;
+}
+
 size_t gnn_loop_workspace_bytes(const gnn_loop_args_t *args) {
     if (!args) { fail("args is NULL"); return 0; }
     Plan p;
@@ -1337,11 +1388,13 @@ int gnn_loop_forward(const gnn_loop_args_t *args) {
     const bool whole_loop = fz != 0 && !soft && persistent_applies(a, p);
     const bool small_setup = whole_loop && setup_small_applies(a, p);
     if (p.n_groups > 0 && !small_setup) return fail("convergence groups need the whole-loop kernel (gnn_loop_groups_supported() == 0 for these args)");
-    // every iteration on the XC form of the wave-specialised kernel (large homogeneous / composite graphs): C is never read
-    const bool xc_loop = p.xc_ok && !whole_loop && fz == 1 && (soft || !mid_applies(a, p)) && p.SP != 128 && !iter_adjacency(a, p).w &&
-                         iteration_generation(a, p) == 4 && fused_generation(p.SP, p.N, a.flags) == 4;
+    const bool xc_loop = xc_loop_applies(a, p, fz, soft, whole_loop);
+    // ... of a homogeneous graph: the line is filled in place, into the caller's buffer if there is one, or adopted from it (gnn_loop_args_t::xc)
+    const bool xc_line = xc_loop && !p.composite && p.N > 0;
+    if (xc_line && a.xc) { TRY(check_xc_args(a)); p.Xc = a.xc; }
     if (small_setup) TRY(setup_small(a, p, st));
-    else             TRY(setup_constants(a, p, st, /*zero_loop_words=*/true, /*skip_c=*/xc_loop));   // flags, barrier counters and k start from zero
+    else             TRY(setup_constants(a, p, st, /*zero_loop_words=*/true, /*skip_c=*/xc_loop, nullptr, xc_line,
+                                         xc_line && a.xc && a.xc_mode == GNN_XC_VALID));   // flags, barrier counters and k start from zero
 
     // state_0 (GNN.py:256-259) into the padded buffer; state_old_0 = ones is implicit in the first predicate (:261)
     // When the caller's state_0 already has the padded layout (d a multiple of 16, no hub rows behind the real ones) the

@@ -440,26 +440,28 @@ __global__ void __launch_bounds__(256) k_thin_dense(SegDenseArgs a, int K) {
             for (int h = 0; h < H; ++h)
 #pragma unroll
                 for (int off = 8; off >= 1; off >>= 1) acc[r][h] += __shfl_xor(acc[r][h], off, 16);
-        if (a.act == GNN_ACT_SOFTMAX) {                  // every lane holds all H sums: lane 0 finishes the whole row
-            if (l16 == 0) {
+        if (a.act == GNN_ACT_SOFTMAX) {                  // every lane holds all H sums of all TD_ROWS rows: lane r finishes row r (the same operations
+            float v[H];                                  // on the same values as one lane finishing them all, eight rows at a time, and the eight
+#pragma unroll                                           // rows leave as one contiguous piece instead of eight stores of lane 0)
+            for (int h = 0; h < H; ++h) v[h] = acc[0][h];
 #pragma unroll
-                for (int r = 0; r < TD_ROWS; ++r) {
-                    const long m = base + r;
-                    if (m >= a.M) continue;
-                    float v[H], mx = -3.4e38f, sum = 0.0f;
+            for (int r = 1; r < TD_ROWS; ++r)
 #pragma unroll
-                    for (int h = 0; h < H; ++h) {
-                        v[h] = acc[r][h];
-                        if (a.bias) v[h] += a.bias[h];
-                        if (a.addend) v[h] += a.addend[(size_t)(a.add_rowidx ? a.add_rowidx[m] : m) * a.ld_add + h];
-                        mx = fmaxf(mx, v[h]);
-                    }
+                for (int h = 0; h < H; ++h) v[h] = l16 == r ? acc[r][h] : v[h];
+            const long m = base + l16;
+            if (l16 < TD_ROWS && m < a.M) {
+                float mx = -3.4e38f, sum = 0.0f;
 #pragma unroll
-                    for (int h = 0; h < H; ++h) { v[h] = expf(v[h] - mx); sum += v[h]; }
-                    float *y = a.Y + (size_t)(a.out_rowidx ? a.out_rowidx[m] : m) * a.ldy;
-#pragma unroll
-                    for (int h = 0; h < H; ++h) y[h] = v[h] / sum;
+                for (int h = 0; h < H; ++h) {
+                    if (a.bias) v[h] += a.bias[h];
+                    if (a.addend) v[h] += a.addend[(size_t)(a.add_rowidx ? a.add_rowidx[m] : m) * a.ld_add + h];
+                    mx = fmaxf(mx, v[h]);
                 }
+#pragma unroll
+                for (int h = 0; h < H; ++h) { v[h] = expf(v[h] - mx); sum += v[h]; }
+                float *y = a.Y + (size_t)(a.out_rowidx ? a.out_rowidx[m] : m) * a.ldy;
+#pragma unroll
+                for (int h = 0; h < H; ++h) y[h] = v[h] / sum;
             }
         } else if (l16 < H) {                            // lane h of the group finishes output column h
 #pragma unroll
@@ -548,6 +550,19 @@ k_pack_xc(int count, const int *__restrict__ rows, PackSegs ps, float *__restric
         else if (c < Kc) v = ps.ptr[2][j * ps.ld[2] + (c - ps.width[0] - ps.width[1])];
         else if (c == Kc) v = 1.0f;
         Xc[j * 32 + c] = v;
+    }
+}
+// What is left of k_pack_xc on a homogeneous graph, where both aggregates write their columns [L0, Kc) of the line in place
+// (launch_aggregate with out = Xc + column, ldo = 32) instead of into arrays that are read back: the node's own labels in
+// front (L0 columns; 0 when the state network does not see them), the 1 that carries the bias in column Kc, zeros behind it.
+__global__ void __launch_bounds__(256)
+k_xc_own(int count, const float *__restrict__ nodes, int ld_nodes, int L0, int Kc, float *__restrict__ Xc) {
+    const size_t total = (size_t)count * 32;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t j = i >> 5;
+        const int c = (int)(i & 31);
+        if (c < L0) Xc[i] = nodes[j * ld_nodes + c];
+        else if (c >= Kc) Xc[i] = c == Kc ? 1.0f : 0.0f;
     }
 }
 __global__ void __launch_bounds__(256)

@@ -154,7 +154,8 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> loop_forward(
     const std::optional<at::Tensor> &arc_dst, int64_t state_dim, int64_t max_iteration, double state_threshold, int64_t focus, int64_t flags,
     const OptTensorList &hub, at::IntArrayRef hub_dims, const std::optional<at::Tensor> &type_nodes, at::IntArrayRef type_offsets,
     at::IntArrayRef type_dim_label, const OptTensorList &composite_adjacency, at::IntArrayRef composite_dims, at::IntArrayRef loop_events,
-    at::IntArrayRef group_node_begin, at::IntArrayRef group_set_begin) {
+    at::IntArrayRef group_node_begin, at::IntArrayRef group_set_begin, const std::optional<at::Tensor> &xc, bool xc_valid,
+    bool out_index_identity) {
     const at::Device dev = nodes.device();
     gnn_loop_args_t a{};
     fill_graph(a, nodes, arcs, adjacency, adjacency_dims, arcnode, arcnode_dims, hub, hub_dims, dev);
@@ -193,6 +194,10 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> loop_forward(
     a.focus = (int32_t)focus;
     a.out_index = i32(out_index, "out_index", dev);
     a.n_out = (int32_t)out_index.numel();
+    if (out_index_identity) {       // the caller knows that out_index is 0, 1, .. n_nodes - 1: the library then reads no index at all
+        TORCH_CHECK(focus != GNN_FOCUS_ARC && a.n_out == a.n_nodes, "out_index_identity needs node / graph focus and n_nodes entries");
+        a.out_index = nullptr;
+    }
     if (focus == GNN_FOCUS_ARC) {
         a.arc_src = i32(arc_src, "arc_src", dev); a.arc_dst = i32(arc_dst, "arc_dst", dev);
         TORCH_CHECK(a.n_arcs == 0 || (a.arc_src && a.arc_dst && arc_src->numel() == a.n_arcs && arc_dst->numel() == a.n_arcs),
@@ -213,6 +218,13 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> loop_forward(
     if (!sets.empty()) {
         TORCH_CHECK(!groups.empty() && sets.size() >= 2, "group_set_begin needs group_node_begin and at least one set");
         a.group_set_begin = sets.data(); a.n_group_sets = (int32_t)sets.size() - 1;
+    }
+
+    // the constants line of the batch, kept by the caller (gnn_loop_args_t::xc): filled by this call, or - xc_valid - read as it is
+    if (xc.has_value() && xc->defined()) {
+        TORCH_CHECK(xc->device() == dev && xc->scalar_type() == at::kFloat && xc->is_contiguous() && xc->dim() == 2 && xc->size(0) == a.n_nodes &&
+                    xc->size(1) == 32, "xc must be a contiguous float32 [n_nodes, 32] tensor on ", dev);
+        a.xc = xc->data_ptr<float>(); a.xc_mode = xc_valid ? GNN_XC_VALID : GNN_XC_FILL;
     }
 
     const auto opts = at::TensorOptions().dtype(at::kFloat).device(dev);
@@ -374,6 +386,25 @@ at::Tensor mlp_forward(at::TensorList weights, at::IntArrayRef spec, double bn_e
     return Y;
 }
 
+// Would `loop_forward` read / fill an `xc` line for a homogeneous graph of these shapes?  (shapes, flags and whether the adjacency carries
+// per-arc weights / hub segments: gnn_loop_xc_applies; no tensors)
+int64_t loop_xc_applies(int64_t n_nodes, int64_t dim_node_label, int64_t dim_arc_label, at::IntArrayRef net_state_spec, at::IntArrayRef net_output_spec,
+                        int64_t state_dim, int64_t max_iteration, int64_t focus, int64_t flags, int64_t n_out, bool per_arc_weights,
+                        int64_t n_heavy_segments) {
+    static const float some_w = 0.0f;           // (only its being non-NULL is read)
+    gnn_loop_args_t a{};
+    a.abi_version = GNN_ABI_VERSION;
+    a.n_nodes = (int32_t)n_nodes; a.dim_node_label = (int32_t)dim_node_label; a.dim_arc_label = (int32_t)dim_arc_label;
+    a.n_types = 1;
+    mlp_shape_of(a.net_state[0], net_state_spec, "net_state");
+    mlp_shape_of(a.net_output, net_output_spec, "net_output");
+    a.state_dim = (int32_t)state_dim; a.max_iteration = (int32_t)max_iteration; a.focus = (int32_t)focus; a.flags = (int32_t)flags;
+    a.n_out = (int32_t)n_out;
+    a.n_heavy_segments = (int32_t)n_heavy_segments;
+    if (per_arc_weights) a.adjacency.w = a.adjacency_light.w = &some_w;
+    return gnn_loop_xc_applies(&a);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(gnnkeras, m) {
@@ -382,7 +413,9 @@ TORCH_LIBRARY(gnnkeras, m) {
           "int[] net_output_spec, float bn_eps, Tensor? state0, Tensor out_index, Tensor? arc_src, Tensor? arc_dst, int state_dim, "
           "int max_iteration, float state_threshold, int focus, int flags, Tensor?[] hub, int[] hub_dims, Tensor? type_nodes, "
           "int[] type_offsets, int[] type_dim_label, Tensor?[] composite_adjacency, int[] composite_dims, int[] loop_events, "
-          "int[] group_node_begin=[], int[] group_set_begin=[]) -> (Tensor k, Tensor state, Tensor out)");
+          "int[] group_node_begin=[], int[] group_set_begin=[], Tensor(a!)? xc=None, bool xc_valid=False, bool out_index_identity=False) -> (Tensor k, Tensor state, Tensor out)");
+    m.def("loop_xc_applies(int n_nodes, int dim_node_label, int dim_arc_label, int[] net_state_spec, int[] net_output_spec, int state_dim, "
+          "int max_iteration, int focus, int flags, int n_out, bool per_arc_weights, int n_heavy_segments) -> int", &loop_xc_applies);
     m.def("loop_groups_supported(int n_nodes, int dim_node_label, int dim_arc_label, int[] net_state_spec, int[] net_output_spec, "
           "int state_dim, int max_iteration, int focus, int flags, int n_out, int[] group_node_begin, int[] group_set_begin=[]) -> int", &loop_groups_supported);
     m.def("aggregate(Tensor?[] csr, int[] dims, Tensor X) -> Tensor");

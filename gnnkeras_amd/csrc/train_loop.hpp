@@ -82,6 +82,7 @@ struct TrainPlan {
     int *grads_ok;               // FIRST word of the tape: validity of the step's gradients (gnn_train_args_t::grads_ok_dev)
     int *flags; float *k_dev;
     float *states, *agg, *agg_arcs, *agg_nodes;
+    int ld_agg_arcs, ld_agg_nodes;        // A / L for arrays of their own; 32 where they are columns of the constants line (big, Kc > 0)
     float *stats_s, *stats_tpl, *Wf_s, *bf_s;
     float *stats_o, *Wf_o, *bf_o;
     float *dx_s_all, *dx_o_all, *G_state, *G_out, *dpred, *loss_rows;
@@ -193,6 +194,7 @@ int make_train_plan(const gnn_train_args_t &ta, void *ws, TrainPlan &p) {
     p.agg = c.take<float>((size_t)(p.agg_taped ? std::max(p.K, 1) : 1) * p.N * p.ldS);
     p.agg_arcs = c.take<float>((size_t)p.N * std::max(p.A, 1));
     p.agg_nodes = c.take<float>((size_t)p.N * std::max(p.L, 1));
+    p.ld_agg_arcs = p.A; p.ld_agg_nodes = p.L;
     p.stats_s = c.take<float>((size_t)(std::max(p.K, 1) + 1) * 2 * p.in_s);      // (+ 1: the statistics of the LAST state, for the output head's BatchNormalization)
     p.stats_tpl = c.take<float>(2 * (size_t)p.in_s);
     p.Wf_s = c.take<float>((size_t)std::max(p.K, 1) * p.in_s * p.H1s);
@@ -225,6 +227,12 @@ int make_train_plan(const gnn_train_args_t &ta, void *ws, TrainPlan &p) {
         p.cc.width[0] = p.A; p.cc.wrow[0] = 2 * p.S;
     }
     p.xc = c.take<float>(p.big && p.Kc > 0 ? (size_t)p.N * 32 : 0);
+    if (p.big && p.Kc > 0) {       // the large-graph kernels read a node's constant inputs as one line (fill_constants_line), the caller's if there
+        if (ta.loop.xc) p.xc = ta.loop.xc;      // is one (gnn_loop_args_t::xc); whoever still wants an aggregate as a segment reads its columns of the line
+        const int L0 = p.with_labels ? p.L : 0;
+        p.agg_nodes = p.xc + L0; p.agg_arcs = p.xc + 2 * L0;
+        p.ld_agg_arcs = p.ld_agg_nodes = 32;
+    }
     p.part_a = c.take<float>(p.big ? (size_t)BIG_AGG_BLOCKS * 2 * p.S : 0);
     p.part_y = c.take<float>(p.big ? (size_t)BIG_FWD_BLOCKS * 2 * std::max(p.S, 32) : 0);      // (also the one-pass statistics of the 32-wide constants line)
     p.loss_part = c.take<float>(256);
@@ -480,8 +488,8 @@ int state_segs(const gnn_loop_args_t &a, const TrainPlan &p, int t, gnn::Seg *se
     segs[n++] = gnn::Seg{st_t, nullptr, p.ldS, p.S, col}; col += p.S;
     if (p.with_labels) { segs[n++] = gnn::Seg{a.nodes, nullptr, a.ld_nodes, p.L, col}; col += p.L; }
     segs[n++] = gnn::Seg{p.agg + (p.agg_taped ? (size_t)t * p.N * p.ldS : 0), nullptr, p.ldS, p.S, col}; col += p.S;
-    if (p.with_labels) { segs[n++] = gnn::Seg{p.agg_nodes, nullptr, p.L, p.L, col}; col += p.L; }
-    if (p.A > 0) { segs[n++] = gnn::Seg{p.agg_arcs, nullptr, p.A, p.A, col}; col += p.A; }
+    if (p.with_labels) { segs[n++] = gnn::Seg{p.agg_nodes, nullptr, p.ld_agg_nodes, p.L, col}; col += p.L; }
+    if (p.A > 0) { segs[n++] = gnn::Seg{p.agg_arcs, nullptr, p.ld_agg_arcs, p.A, col}; col += p.A; }
     return n;
 }
 
@@ -814,6 +822,13 @@ size_t gnn_train_workspace_bytes(const gnn_train_args_t *args) {
     return p.bytes;
 }
 
+int gnn_train_xc_applies(const gnn_train_args_t *args) {
+    if (!args || args->loop.composite || args->n_groups != 0) return 0;
+    TrainPlan p;
+    if (make_train_plan(*args, nullptr, p)) return 0;
+    return p.big && p.Kc > 0 ? 1 : 0;
+}
+
 static int train_step_impl(const gnn_train_args_t &ta);
 
 int gnn_train_step(const gnn_train_args_t *args) {
@@ -843,6 +858,7 @@ static int train_step_impl(const gnn_train_args_t &ta) {
     if (fwd_only && ta.prev_grads_ok_host) return fail("gnn_train_step(forward_only): prev_grads_ok_host must be NULL");
     TRY(make_train_plan(ta, ta.tape, p));
     if (ta.tape_bytes < p.bytes) return fail("tape too small: %zu < %zu bytes", ta.tape_bytes, p.bytes);
+    if (p.big && p.Kc > 0) TRY(check_xc_args(a));
     TRY(check_csr(a.adjacency, "adjacency", p.N, p.N));
     TRY(check_csr(a.arcnode, "arcnode", p.N, p.E));
     if (!fwd_only) TRY(check_csr(ta.adjacency_by_source, "adjacency_by_source", p.N, p.N));
@@ -881,21 +897,17 @@ static int train_step_impl(const gnn_train_args_t &ta) {
     }
     HIP_OK(hipMemsetAsync(p.flags, 0, sizeof(int) * (p.K + 8), st));
     HIP_OK(hipMemsetAsync(p.k_dev, 0, sizeof(float) * 4, st));
-    if (p.A > 0) TRY(launch_aggregate(nullptr, a.arcnode, a.arc_labels, a.ld_arcs, p.A, p.agg_arcs, p.A, st));
-    if (p.with_labels) TRY(launch_aggregate(nullptr, a.adjacency, a.nodes, a.ld_nodes, p.L, p.agg_nodes, p.L, st));
+    const bool xc_line = p.big && p.Kc > 0;      // the aggregates are columns of the constants line: filled in place, or adopted from the caller
+    if (xc_line) {
+        if (!(a.xc && a.xc_mode == GNN_XC_VALID)) TRY(fill_constants_line(a, p.N, p.with_labels ? p.L : 0, p.A, p.xc, st));
+    } else {
+        if (p.A > 0) TRY(launch_aggregate(nullptr, a.arcnode, a.arc_labels, a.ld_arcs, p.A, p.agg_arcs, p.A, st));
+        if (p.with_labels) TRY(launch_aggregate(nullptr, a.adjacency, a.nodes, a.ld_nodes, p.L, p.agg_nodes, p.L, st));
+    }
     if (a.state_dim > 0 && p.ldS == p.S) HIP_OK(hipMemcpyAsync(p.states, a.state0, sizeof(float) * NS, hipMemcpyDeviceToDevice, st));
     else if (a.state_dim > 0) TRY(launch_copy2d(nullptr, a.state0, p.S, p.states, p.ldS, p.N, p.S, p.ldS, st));
     else TRY(launch_copy2d(nullptr, a.nodes, a.ld_nodes, p.states, p.ldS, p.N, p.S, p.ldS, st));
     gnn::Seg segs[GNN_MAX_SEGS];
-    if (p.big && p.Kc > 0) {      // the constant inputs of a node as one 128-byte line: [labels | aggregated labels | aggregated arc labels | 1 | 0 ..]
-        gnn::PackSegs ps;
-        memset(&ps, 0, sizeof(ps));
-        const int n0 = state_segs(a, p, 0, segs);
-        for (int s = 0; s < n0; ++s)
-            if (segs[s].ptr != p.states && segs[s].ptr != p.agg) { ps.ptr[ps.n] = segs[s].ptr; ps.ld[ps.n] = segs[s].ld; ps.width[ps.n] = segs[s].width; ps.wrow[ps.n] = segs[s].wrow; ++ps.n; }
-        gnn::k_pack_xc<<<(int)std::min<long>(cdiv((long)p.N * 32, 256), 256 * 16), 256, 0, st>>>(p.N, nullptr, ps, p.xc);
-        LAUNCH_OK();
-    }
     if (bn_s && p.K > 0) {
         const int n = state_segs(a, p, 0, segs);
         gnn::Seg cst[GNN_MAX_SEGS]; int nc = 0;

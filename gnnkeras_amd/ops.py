@@ -57,13 +57,17 @@ def net_args(net, device, shape_only=False):
 
 
 def loop_forward(nodes, arcs, adjacency, arcnode, nodegraph, net_state, net_output, state0, out_index, arc_ends, state_dim,
-                 max_iteration, state_threshold, focus, flags, composite=None, loop_events=None, groups=None, group_sets=None):
+                 max_iteration, state_threshold, focus, flags, composite=None, loop_events=None, groups=None, group_sets=None,
+                 xc=None, xc_valid=False, out_index_identity=False):
     """`adjacency` / `arcnode` / `nodegraph`: device-CSR dicts (nodegraph None unless graph focus); `net_state`: one
     `Sequential`, or the list of per-type networks with `composite` = (type_nodes i32[N], type_offsets [T+1], type_dim_label
     [T], [device-CSR dict per type]); `arc_ends` = (arc_src, arc_dst) for arc focus; `loop_events` = (begin, end)
     `torch.cuda.Event`s recorded on the launch stream around the iteration launches; `groups` = node offsets [G + 1] of
     merged batches that run as independent loops of this one call (k is then [G]; ask `loop_groups_supported` first);
-    `group_sets` = first-group offsets [B + 1] when a batch was cut into several groups that share the loop's condition."""
+    `group_sets` = first-group offsets [B + 1] when a batch was cut into several groups that share the loop's condition;
+    `xc` = the batch's constants line (float32 [N, 32], `SparseMatrix.constants_line`): filled by this call, or - `xc_valid` - read
+    as an earlier call on the same batch left it (only where `loop_xc_applies` says the call takes it; ignored elsewhere);
+    `out_index_identity`: the caller knows `out_index` to be 0 .. N - 1 (node / graph focus) - the read-out then loads no index."""
     ops = load()
     dev = nodes.device
     adj_t, adj_d = csr_args(adjacency)
@@ -90,7 +94,18 @@ def loop_forward(nodes, arcs, adjacency, arcnode, nodegraph, net_state, net_outp
     return ops.loop_forward(nodes, arcs, adj_t, adj_d, an_t, an_d, ng_t, ng_d, sw, ss, ow, os_, BN_EPSILON, state0, out_index, es, ed,
                             int(state_dim), int(max_iteration), float(state_threshold), int(focus), int(flags), hub_t, hub_d,
                             type_nodes, type_offsets, type_dims, ca_t, ca_d, ev, [int(v) for v in groups] if groups is not None else [],
-                            [int(v) for v in group_sets] if group_sets is not None else [])
+                            [int(v) for v in group_sets] if group_sets is not None else [], xc, bool(xc_valid), bool(out_index_identity))
+
+
+def loop_xc_applies(n_nodes, dim_node_label, dim_arc_label, net_state, net_output, state_dim, max_iteration, focus, flags, n_out, adjacency):
+    """Does `loop_forward` on a homogeneous graph of these shapes read / fill the `xc` line?  (`adjacency`: the device-CSR dict - only
+    whether it carries per-arc weights and hub segments is looked at; include/gnnloop.h, gnn_loop_xc_applies)"""
+    _, ss = net_args(net_state, None, shape_only=True)
+    _, os_ = net_args(net_output, None, shape_only=True)
+    heavy = adjacency.get('heavy')
+    w = adjacency['w'] is not None or (heavy is not None and adjacency['light']['w'] is not None)
+    return bool(load().loop_xc_applies(int(n_nodes), int(dim_node_label), int(dim_arc_label), ss, os_, int(state_dim), int(max_iteration),
+                                       int(focus), int(flags), int(n_out), bool(w), int(heavy['n_seg']) if heavy is not None else 0))
 
 
 def loop_groups_supported(n_nodes, dim_node_label, dim_arc_label, net_state, net_output, state_dim, max_iteration, focus, flags,

@@ -9,6 +9,9 @@ triple for API compatibility and caches, built once per batch, what the HIP kern
 """
 from __future__ import annotations
 
+import os
+import weakref
+
 import numpy as np
 import torch
 
@@ -74,6 +77,38 @@ class CSRByDestination:
         elif uniform_rows:
             w = None
         return cls(rowptr.astype(np.int32), src, w, row_scale, n_src, n_dst)
+
+
+# ---- the constants line of a batch -------------------------------------------------------------------------------------------------
+# Large graphs read a node's constant inputs as one 128-byte line [labels | Adjacency^T labels | ArcNode^T arc labels | 1 | 0 ..]
+# (include/gnnloop.h, gnn_loop_args_t::xc).  It depends on the batch alone, and a large graph is one long-lived batch, so the line is
+# kept next to the cached device CSR of the batch's adjacency (`SparseMatrix.constants_line`) and every later forward / train step of
+# the batch reads it instead of running both aggregates again.
+XC_MIN_NODES = 4096        # below this no call takes the line (the library decides from this size on: ops.loop_xc_applies)
+
+
+def xc_reuse_enabled() -> bool:
+    """GNN_XC_REUSE=0: every call builds the line in its own workspace, as if nobody kept it (read at every call: tests switch it)."""
+    return os.environ.get('GNN_XC_REUSE', '1') != '0'
+
+
+def xc_key(nodes, arcs, arcnode, dim_node_label, with_labels, device) -> dict:
+    """What a constants line was computed from: the `nodes` / `arcs` tensor OBJECTS the caller passed (weak references; their address
+    alone would not do - the hot path converts with `.to(float32).contiguous()`, and the caching allocator hands the address of a freed
+    temporary out again with other contents), their `_version` (an in-place edit bumps it), shapes and dtypes, the ArcNode matrix
+    (identity), the label width, whether the state network sees the labels (state_vect_dim > 0: the line then starts with them) and
+    the device."""
+    return dict(nodes=weakref.ref(nodes), arcs=weakref.ref(arcs), arcnode=weakref.ref(arcnode),
+                versions=(nodes._version, arcs._version), shapes=(tuple(nodes.shape), tuple(arcs.shape)),
+                dtypes=(nodes.dtype, arcs.dtype), layout=(int(dim_node_label), bool(with_labels)), device=str(canonical_device(device)))
+
+
+def xc_key_matches(key: dict, nodes, arcs, arcnode, dim_node_label, with_labels, device) -> bool:
+    """Any mismatch - or a dead weak reference - is a miss."""
+    return (key['nodes']() is nodes and key['arcs']() is arcs and key['arcnode']() is arcnode and
+            key['versions'] == (nodes._version, arcs._version) and key['shapes'] == (tuple(nodes.shape), tuple(arcs.shape)) and
+            key['dtypes'] == (nodes.dtype, arcs.dtype) and key['layout'] == (int(dim_node_label), bool(with_labels)) and
+            key['device'] == str(canonical_device(device)))
 
 
 HEAVY_THRESHOLD = 512      # in-degree above which a destination row is aggregated by whole workgroups (hub nodes)
@@ -276,6 +311,23 @@ class SparseMatrix:
                 d['heavy'] = dict(seg_beg=up(heavy['seg_beg']), seg_end=up(heavy['seg_end']), n_seg=heavy['n_seg'])
             self._dev[key] = d
         return self._dev[key]
+
+    def constants_line(self, nodes, arcs, arcnode, dim_node_label, with_labels, device):
+        """(line, valid) for a call on this batch (`self` = its adjacency): `line` a float32 [n_nodes, 32] device tensor; `valid` True
+        when an earlier call filled it from these very inputs (`xc_key`) - the library then reads it as it is - else False: the call
+        fills it, and the caller reports `constants_line_filled()` once that call has been issued.  One line per batch."""
+        e = self.__dict__.get('_xc')
+        if e is not None and e['valid'] and xc_key_matches(e['key'], nodes, arcs, arcnode, dim_node_label, with_labels, device):
+            return e['line'], True
+        device = canonical_device(device)
+        line = e['line'] if e is not None else None
+        if line is None or line.device != device or line.shape[0] != nodes.shape[0]:
+            line = torch.empty((nodes.shape[0], 32), dtype=torch.float32, device=device)
+        self._xc = dict(key=xc_key(nodes, arcs, arcnode, dim_node_label, with_labels, device), line=line, valid=False)
+        return line, False
+
+    def constants_line_filled(self):
+        self._xc['valid'] = True
 
     def triple(self, device=None):
         """The `(indices, values[...,None], dense_shape)` tuple of `GraphSequencers.py:110`, carrying this matrix."""

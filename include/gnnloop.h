@@ -24,6 +24,8 @@
 extern "C" {
 #endif
 
+/* (the constants line - gnn_loop_args_t::xc, xc_mode - was appended to the end of gnn_loop_args_t under this number: a caller built
+ * against the shorter struct is told apart by gnn_struct_size(2), which every binding checks at load time) */
 #define GNN_ABI_VERSION 10
 
 /* Keras activation names accepted by the reference MLP builder (GNN/Models/MLP.py:16). */
@@ -113,7 +115,9 @@ typedef struct gnn_loop_args {
     /* output stage --------------------------------------------------------------------------------------------- */
     int32_t focus;            /* enum gnn_focus                                                                 */
     int32_t n_out;            /* rows that pass `set_mask & output_mask` (GNN.py:269)                           */
-    const int32_t *out_index; /* [n_out] ascending node ids (node/graph focus) or arc ids (arc focus)           */
+    const int32_t *out_index; /* [n_out] ascending node ids (node/graph focus) or arc ids (arc focus); gnn_loop_forward takes
+                                 NULL for the identity (node / graph focus, n_out == n_nodes: every node a row, no index
+                                 load in front of the read-out's row loads)                                      */
     const int32_t *arc_src;   /* [n_arcs] arc focus: adjacency.indices[:,0] in arcs order                       */
     const int32_t *arc_dst;   /* [n_arcs] arc focus: adjacency.indices[:,1]                                     */
     gnn_csr_t nodegraph;      /* graph focus: n_src = n_out, n_dst = #graphs                                    */
@@ -168,7 +172,23 @@ typedef struct gnn_loop_args {
      * (n_groups <= CUs) whenever some set has more than one group. */
     const int32_t *group_set_begin;    /* HOST array [n_group_sets + 1], ascending, [0] = 0, [n_group_sets] = n_groups    */
     int32_t n_group_sets;
+    /* the constants line of the batch (optional; NULL = it is built in the workspace at every call) ------------------------------
+     * Large graphs run their iterations on a kernel that reads a node's constant inputs as one 128-byte line,
+     *     xc[j] = [nodes[j] (state_dim > 0) | Adjacency^T nodes [j] (state_dim > 0) | ArcNode^T arc_labels [j] | 1 | 0 ..]   (32 floats),
+     * which depends on the BATCH (labels, arc labels, both operators) and on no weight and no state.  A caller that keeps a batch
+     * alive over many calls (every forward and every train step of a large graph) owns the line: `xc` = [n_nodes, 32] floats,
+     * 256-byte aligned, and
+     *     xc_mode = GNN_XC_FILL   the set-up runs and writes the line there (every element of it);
+     *     xc_mode = GNN_XC_VALID  the line is read as it is: no aggregate and no pack launch.
+     * GNN_XC_VALID is a promise the library CANNOT check: the buffer must have been filled by a call whose nodes, arc labels,
+     * adjacency, arcnode, dim_node_label, dim_arc_label and (state_dim > 0) were the same, and not written since.
+     * Where a call does not take that kernel (gnn_loop_xc_applies / gnn_train_xc_applies == 0: composite models, per-arc weights,
+     * padded width 128, small graphs, GNN_XC=0) both fields are ignored - the buffer is neither read nor written, the usual
+     * set-up runs.  gnn_train_step honours the same two fields of its `loop` member; both entry points build the same line. */
+    float *xc;
+    int32_t xc_mode;                   /* enum gnn_xc_mode                                                                 */
 } gnn_loop_args_t;
+enum gnn_xc_mode { GNN_XC_FILL = 0, GNN_XC_VALID = 1 };
 #define GNN_MAX_GROUPS 32                 /* groups of a call that spreads every group over several CUs                  */
 #define GNN_MAX_GROUPS_RESIDENT (1 << 20) /* groups of a call that keeps every group's state in the LDS of one CU        */
 
@@ -187,6 +207,9 @@ size_t gnn_loop_workspace_bytes(const gnn_loop_args_t *args);
 
 /* (k, state, out) = Loop(...)  — see gnn_loop_args. */
 int gnn_loop_forward(const gnn_loop_args_t *args);
+/* 1 when gnn_loop_forward would read / fill args->xc for these arguments, else 0.  Reads dims, network shapes, flags, the
+ * GNN_XC / GNN_XC_MIN_NODES environment, n_heavy_segments and WHETHER adjacency.w / adjacency_light.w are NULL; no device memory. */
+int gnn_loop_xc_applies(const gnn_loop_args_t *args);
 /* Non-zero when gnn_loop_forward accepts these args with n_groups > 0, else 0 (the caller then runs one call per batch).
  *   2: every group's state fits the LDS of one CU (nodes_g * padded width * 4 <= 156 KB, width <= 32, one-layer state network):
  *      one workgroup per group, any number of groups up to GNN_MAX_GROUPS_RESIDENT - the more the better, 256 run at once;
@@ -571,6 +594,9 @@ typedef struct gnn_train_args {
  * arrives. */
 size_t gnn_train_workspace_bytes(const gnn_train_args_t *args);
 int gnn_train_step(const gnn_train_args_t *args);
+/* 1 when gnn_train_step would read / fill args->loop.xc (the row-streaming kernels of large homogeneous graphs with at least one
+ * constant input column), else 0.  Reads dims and network shapes only. */
+int gnn_train_xc_applies(const gnn_train_args_t *args);
 /* May these arguments run as a grouped training-mode forward (ABI 10)?  Reads dims, network descriptions (no device memory) and the host
  * group arrays only.
  *   GNN_TRAIN_GROUPS_OK (0)           yes
