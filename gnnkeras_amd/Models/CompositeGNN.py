@@ -158,15 +158,28 @@ class CompositeGNNnodeBased(GNNnodeBased):
     def Loop(self, nodes, arcs, dim_node_label, type_mask, set_mask, output_mask, composite_adjacencies, adjacency,
              arcnode, nodegraph, training: bool = False, *, state0=None, seed=None, node_level: bool = False, groups=None):
         """(k, state, out) for one (merged) heterogeneous graph — reference CompositeGNN.py:242-272.
-        `state0` / `seed` / `node_level` as in `GNNnodeBased.Loop`; `groups`: convergence groups are not covered for composite models."""
+        `state0` / `seed` / `node_level` as in `GNNnodeBased.Loop`; `groups` is refused here: the convergence groups of composite models
+        are reached one level down, through `LoopTrainer.forward_native(groups=...)` (docs/serial_propagation.md)."""
         if groups is not None:
-            raise NotImplementedError('convergence groups: composite (heterogeneous) models are not covered')
+            raise NotImplementedError('convergence groups: composite (heterogeneous) models are not covered by Loop(groups=...); use LoopTrainer.forward_native(groups=...)')
         focus = 'n' if (node_level and self._focus == 'g') else self._focus
         if training:
             from .training import LoopTrainer
             if getattr(self, '_trainer', None) is None: self._trainer = LoopTrainer(self)
-            tp = self._trainer.forward([nodes, arcs, dim_node_label, type_mask, set_mask, output_mask, composite_adjacencies,
-                                        adjacency, arcnode, nodegraph], state0=state0, seed=seed, node_level=node_level)
+            x_list = [nodes, arcs, dim_node_label, type_mask, set_mask, output_mask, composite_adjacencies, adjacency, arcnode, nodegraph]
+            # (no row in set_mask & output_mask: the in-library forward wants an output row, the building blocks skip the output network)
+            has_rows = len(self._out_index(_squeeze_last(set_mask).to(nodes.device), _squeeze_last(output_mask).to(nodes.device))) > 0
+            if has_rows and self._trainer._native_forward_applies():
+                # one library call (include/gnnloop.h, forward_only on composite arguments) instead of one aggregate plus one training-mode
+                # MLP call per node type and iteration: what a serial CompositeLGNN fit() runs on every single graph between its layers
+                try:
+                    k, state, out = self._trainer.forward_native(x_list, state0=state0, seed=seed, node_level=node_level)
+                    return torch.tensor(float(k), device=state.device), state, out
+                except nat.NativeError as e:
+                    # an expired grid barrier of the persistent forward kernel (GPU shared with long-running work) or a shape the in-library
+                    # forward does not cover: nothing has been touched - the building blocks below have no cross-workgroup waits
+                    if not any(t in str(e) for t in ('grid barrier', 'cannot be resident', 'train through the building blocks', 'empty graph')): raise
+            tp = self._trainer.forward(x_list, state0=state0, seed=seed, node_level=node_level)
             return torch.tensor(float(tp.k), device=tp.dev), tp.state.clone(), tp.y_pred
         nat.require_device(nodes, 'nodes'); nat.require_device(arcs, 'arcs')
         dev = nodes.device

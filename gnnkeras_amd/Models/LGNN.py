@@ -316,10 +316,12 @@ class LGNN(_LoopModel):
 
     def _grouped_applies(self, gnn, seq_now):
         """May this layer's propagation merge graphs into runs?  (a plain multi-graph sequencer whose merge leaves every graph's operators as
-        they are - 'normalized' divides by the arc count of the merge - and a homogeneous layer; the library has the last word per run)"""
-        from ..Sequencers.GraphSequencers import MultiGraphSequencer
-        return type(seq_now) is MultiGraphSequencer and seq_now.aggregation_mode != 'normalized' and \
-            not isinstance(gnn.net_state, (list, tuple)) and len(seq_now.data) > 0
+        they are - 'normalized' divides by the arc count of the merge - with a homogeneous layer, or the composite multi-graph sequencer
+        with a composite layer; the library has the last word per run)"""
+        from ..Sequencers.GraphSequencers import MultiGraphSequencer, CompositeMultiGraphSequencer
+        composite = isinstance(gnn.net_state, (list, tuple))
+        return type(seq_now) is (CompositeMultiGraphSequencer if composite else MultiGraphSequencer) and \
+            seq_now.aggregation_mode != 'normalized' and len(seq_now.data) > 0
 
     def _propagate_grouped(self, gnn, seq_now, seq_t0, state0s=None):
         """`_propagate` with runs of consecutive graphs as the convergence groups of one `gnn_train_step(forward_only)` call each
@@ -337,11 +339,19 @@ class LGNN(_LoopModel):
         L, A = int(graphs[0].nodes.shape[1]), int(graphs[0].arcs.shape[1]) - 2
         S = d if d > 0 else L
         SP = 16 if S <= 16 else 32 if S <= 32 else 64
-        in_s = 2 * S + (2 * L if d > 0 else 0) + A
         in_o = int(gnn.net_output.input_dim)
         sizes = [int(g.nodes.shape[0]) for g in graphs]
-        per_node = 4 * (2 * SP + L + A + 2) + 16
-        per_graph = 4 * (max(gnn.max_iteration, 1) * 2 * in_s + 2 * in_o) + 64
+        if isinstance(gnn.net_state, (list, tuple)):
+            # one state network per node type over [labels[:, :d_t] | state | Adj^T state | aggregated_component]; the statistics slots are per type
+            dims = [int(v) for v in np.asarray(graphs[0].DIM_NODE_LABEL).reshape(-1)]
+            w_comp = sum(dims) + A
+            in_s = sum(d_t + 2 * S + w_comp for d_t in dims)
+            per_node = 4 * (2 * SP + w_comp + 2) + 16
+            per_graph = 4 * (max(gnn.max_iteration, 1) * 2 * in_s + 2 * in_o) + 64 + 4 * len(dims)
+        else:
+            in_s = 2 * S + (2 * L if d > 0 else 0) + A
+            per_node = 4 * (2 * SP + L + A + 2) + 16
+            per_graph = 4 * (max(gnn.max_iteration, 1) * 2 * in_s + 2 * in_o) + 64
         max_nodes = max(nat.TRAIN_GROUP_MAX_NODES, int(self.serial_run_bytes // (per_node + per_graph)))
         plan = plan_runs(sizes, nat.TRAIN_GROUP_MAX_NODES, max_nodes)
         if getattr(gnn, '_trainer', None) is None: gnn._trainer = LoopTrainer(gnn)

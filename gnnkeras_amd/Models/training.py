@@ -882,11 +882,12 @@ class LoopTrainer:
         return str(kind).lower() in nat.LOSSES
 
     def _native_forward_applies(self):
-        """May `Loop(..., training=True)` run as ONE `gnn_train_step(forward_only)` call?  (homogeneous models, no Dropout in front of a first
-        Dense, no data parallelism - what the in-library step covers, minus everything about the loss.)"""
+        """May `Loop(..., training=True)` run as ONE `gnn_train_step(forward_only)` call?  (homogeneous and composite models, no Dropout in
+        front of a first Dense, no data parallelism - what the in-library steps cover, minus everything about the loss.)"""
         m = self.model
-        if self.dp is not None or not self.use_native_step or isinstance(m.net_state, (list, tuple)) or m.max_iteration < 1: return False
-        for n_ in (m.net_state, m.net_output):
+        if self.dp is not None or not self.use_native_step or m.max_iteration < 1: return False
+        nets = list(m.net_state) if isinstance(m.net_state, (list, tuple)) else [m.net_state]
+        for n_ in nets + [m.net_output]:
             if any(float(r) > 0 and int(q) == 0 for r, q in zip(n_.dropout_rate or [], n_.dropout_pos or [])): return False
         return True
 
@@ -916,7 +917,6 @@ class LoopTrainer:
         nets_s = list(m.net_state) if composite else [m.net_state]
         if groups is not None:
             if not forward_only: raise NotImplementedError('training-mode convergence groups: the forward only (no grouped train_step)')
-            if composite: raise NotImplementedError('training-mode convergence groups: composite (heterogeneous) models are not covered')
             if not self._native_forward_applies():
                 raise NotImplementedError('training-mode convergence groups: not covered (data parallelism, Dropout in front of a first Dense, '
                                           'max_iteration < 1 or the in-library step switched off)')
@@ -1011,8 +1011,9 @@ class LoopTrainer:
         m._dropout_step = getattr(m, '_dropout_step', 0) + 1
         self.drop_seed = _mix32(0x5EED, int(seed)) if seed is not None else _mix32(id(m) & 0xFFFFFFFF, m._dropout_step)
         ta.drop_seed = self.drop_seed
-        drop_nets = [self._cached_grads('state', m.net_state, p), self._cached_grads('output', m.net_output, p)] if forward_only else None
-        if forward_only: gs_all, go = [drop_nets[0]], drop_nets[1]           # (the holders know the networks' Dropout layers; their buffers stay untouched)
+        if forward_only:            # (the holders know the networks' Dropout layers; their buffers stay untouched)
+            gs_all = [self._cached_grads(f'state{i}' if composite else 'state', n_, p) for i, n_ in enumerate(nets_s)]
+            go = self._cached_grads('output', m.net_output, p)
         for i, g_ in enumerate(gs_all): g_.net_id = i
         go.net_id = 1000
         for spec, g_ in [(ta.drop_state[i], g_) for i, g_ in enumerate(gs_all)] + [(ta.drop_output, go)]:
@@ -1052,8 +1053,9 @@ class LoopTrainer:
             if ans == nat.TRAIN_GROUPS_MALFORMED:
                 raise ValueError('groups / group_out_begin must span [0, n_nodes] / [0, output rows] in ascending order, no empty group')
             if ans == nat.TRAIN_GROUPS_UNCOVERED:
-                raise NotImplementedError('training-mode convergence groups do not cover this shape (one-layer state network of units == state '
-                                          'width <= 64, <= 32 constant columns, no softmax state, no Dropout; one-layer output network <= 64 units)')
+                raise NotImplementedError('training-mode convergence groups do not cover this shape (one-layer state network' + (' per type' if composite else '') +
+                                          ' of units == state width <= 64, <= ' + ('64 constant columns per type' if composite else '32 constant columns') +
+                                          ', no softmax state, no Dropout; one-layer output network <= 64 units over <= 256 columns)')
             if ans > 0:
                 raise NotImplementedError(f'training-mode convergence groups: group {ans - 1} has {int(gb[ans] - gb[ans - 1])} nodes '
                                           f'(at most {nat.TRAIN_GROUP_MAX_NODES} per group)')

@@ -1891,5 +1891,5 @@ int gnn_shard_output(const gnn_loop_args_t *args, const float *buf0_full, const 
 #include "shard_loop.hpp"
 #include "train_api.hpp"
 #include "train_loop.hpp"
-#include "train_group.hpp"
 #include "train_composite.hpp"
+#include "train_group.hpp"      // (behind train_composite.hpp: its heterogeneous half plans with make_cplan)

@@ -393,15 +393,17 @@ __global__ void __launch_bounds__(256) k_train_group_head(TrainGroupHead a) {
 // moving <- momentum moving + (1 - momentum) batch for g = 0 .. G - 1, slot after slot: `slots` = K, steps of group g = k_groups[g] (state
 // network) - or slots = 1 with one step where the group has output rows (output network, obeg given).  A group whose k is negative
 // (invalid) moves nothing.  The literal recurrence: the result does not depend on how the graphs were cut into calls.
+// `rows_k_steps` (with obeg; heterogeneous state networks, obeg = the type's rows per group): k_groups[g] steps where the group has rows of
+// the type, none where it has not.
 __global__ void __launch_bounds__(64)
 k_bn_moving_groups(const float *__restrict__ stats, int slots, int ncols, const float *__restrict__ k_groups, const int *__restrict__ obeg, int G,
-                   float *moving_mean, float *moving_var, float momentum) {
+                   float *moving_mean, float *moving_var, float momentum, int rows_k_steps = 0) {
     const int col = blockIdx.x * blockDim.x + threadIdx.x;
     if (col >= ncols) return;
     float mm = moving_mean[col], mv = moving_var[col];
     for (int g = 0; g < G; ++g) {
         const int kg = (int)k_groups[g];
-        const int steps = kg < 0 ? 0 : obeg ? (obeg[g + 1] > obeg[g] ? 1 : 0) : min(kg, slots);
+        const int steps = kg < 0 ? 0 : obeg ? (obeg[g + 1] > obeg[g] ? (rows_k_steps ? min(kg, slots) : 1) : 0) : min(kg, slots);
         const float *sl = stats + (size_t)g * slots * 2 * ncols;
         for (int t = 0; t < steps; ++t) {
             mm = mm * momentum + sl[(size_t)t * 2 * ncols + col] * (1.0f - momentum);

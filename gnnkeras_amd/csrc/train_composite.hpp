@@ -268,7 +268,7 @@ int composite_big_setup(const gnn_train_args_t &ta, CPlan &p, hipStream_t st) {
     k_invert_perm<<<std::min(cdiv(p.N, 256), 1024), 256, 0, st>>>(a.type_nodes, p.N, p.inv);
     LAUNCH_OK();
     TRY(build_pos_csr(a.adjacency, a.type_nodes, p.inv, p.N, B.d, B.scan_tmp, st));
-    TRY(build_pos_csr(ta.adjacency_by_source, a.type_nodes, p.inv, p.N, B.s, B.scan_tmp, st));
+    if (!ta.forward_only) TRY(build_pos_csr(ta.adjacency_by_source, a.type_nodes, p.inv, p.N, B.s, B.scan_tmp, st));      // (the backward's walk)
     if (a.state_dim > 0) TRY(gather_rows(a.state0, p.S, a.type_nodes, p.N, p.S, p.states, p.S, st));
     else TRY(gather_rows(a.nodes, a.ld_nodes, a.type_nodes, p.N, p.S, p.states, p.S, st));
     for (int q = 0; q < p.n_types; ++q) {
@@ -526,14 +526,16 @@ size_t composite_train_workspace_bytes(const gnn_train_args_t &ta) {
 int train_step_composite(const gnn_train_args_t &ta) {
     const gnn_loop_args_t &a = ta.loop;
     CPlan p;
+    const bool fwd_only = ta.forward_only != 0;         // the training-mode forward alone: no loss, no gradients, the validity word untouched
+    if (fwd_only && ta.prev_grads_ok_host) return fail("gnn_train_step(forward_only): prev_grads_ok_host must be NULL");
     TRY(make_cplan(ta, ta.tape, p));
     if (!ta.tape || ta.tape_bytes < p.bytes) return fail("tape too small: %zu < %zu bytes", ta.tape_bytes, p.bytes);
     TRY(check_csr(a.adjacency, "adjacency", p.N, p.N));
     TRY(check_csr(a.arcnode, "arcnode", p.N, p.E));
-    TRY(check_csr(ta.adjacency_by_source, "adjacency_by_source", p.N, p.N));
+    if (!fwd_only) TRY(check_csr(ta.adjacency_by_source, "adjacency_by_source", p.N, p.N));
     for (int t = 0; t < p.n_types; ++t) {
         TRY(check_csr(a.composite_adjacency[t], "composite_adjacency", p.N, p.N));
-        TRY(check_grads(*p.ty[t].m, p.ty[t].g, "grad_state_types"));
+        if (!fwd_only) TRY(check_grads(*p.ty[t].m, p.ty[t].g, "grad_state_types"));
     }
     if (!a.nodes || !a.type_nodes) return fail("nodes / type_nodes is NULL");
     if (a.state_dim > 0 && !a.state0) return fail("state0 is required when state_dim > 0");
@@ -543,12 +545,12 @@ int train_step_composite(const gnn_train_args_t &ta) {
     if (p.pooled) {
         if (a.nodegraph.n_src != p.M) return fail("graph focus: NodeGraph has %d rows but %d nodes pass the mask", a.nodegraph.n_src, p.M);
         TRY(check_csr(a.nodegraph, "nodegraph", p.G, p.M));
-        TRY(check_csr(ta.nodegraph_by_source, "nodegraph_by_source", p.M, p.G));
+        if (!fwd_only) TRY(check_csr(ta.nodegraph_by_source, "nodegraph_by_source", p.M, p.G));
     }
-    if (p.R > 0 && !ta.targets) return fail("targets is NULL");
-    if (ta.loss_kind < 0 || ta.loss_kind > 3) return fail("unknown loss kind %d", ta.loss_kind);
-    if (!ta.y_pred || !ta.loss || !ta.k_host || !ta.state) return fail("y_pred / loss / k_host / state is NULL");
-    TRY(check_grads(a.net_output, ta.grad_output, "grad_output"));
+    if (!fwd_only && p.R > 0 && !ta.targets) return fail("targets is NULL");
+    if (!fwd_only && (ta.loss_kind < 0 || ta.loss_kind > 3)) return fail("unknown loss kind %d", ta.loss_kind);
+    if ((p.R > 0 && !ta.y_pred) || (!fwd_only && !ta.loss) || !ta.k_host || !ta.state) return fail("y_pred / loss / k_host / state is NULL");
+    if (!fwd_only) TRY(check_grads(a.net_output, ta.grad_output, "grad_output"));
     const gnn_mlp_t &no = a.net_output;
     const bool bn_o = no.has_bn != 0;
     hipStream_t st = (hipStream_t)a.stream;
@@ -556,10 +558,12 @@ int train_step_composite(const gnn_train_args_t &ta) {
 
     // ---- setup: transposes, aggregated_component (CompositeGNN.py:251-253), state_0, the constant columns' statistics ------------
     if (ta.prev_grads_ok_host) HIP_OK(hipMemcpyAsync(ta.prev_grads_ok_host, p.grads_ok, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemsetAsync(p.grads_ok, 0, sizeof(int) * 4, st));
-    if (ta.grads_ok_dev) *ta.grads_ok_dev = p.grads_ok;
-    for (int t = 0; t < p.n_types; ++t) TRY(transposes(p.ty[t].nc, st));
-    TRY(transposes(p.co, st));
+    if (!fwd_only) {               // (a forward leaves the word of the last STEP on this tape as it is)
+        HIP_OK(hipMemsetAsync(p.grads_ok, 0, sizeof(int) * 4, st));
+        if (ta.grads_ok_dev) *ta.grads_ok_dev = p.grads_ok;
+        for (int t = 0; t < p.n_types; ++t) TRY(transposes(p.ty[t].nc, st));
+        TRY(transposes(p.co, st));
+    }
     HIP_OK(hipMemsetAsync(p.flags, 0, sizeof(int) * (p.K + 8), st));
     HIP_OK(hipMemsetAsync(p.k_dev, 0, sizeof(float) * 4, st));
     {
@@ -758,6 +762,18 @@ int train_step_composite(const gnn_train_args_t &ta) {
         TRY(forward_layers(no, osegs, nos, p.M, W0, b0, ohs, nullptr, st, nullptr, nullptr, bn_o ? p.stats_o : nullptr, &dro));
     }
     if (p.pooled) TRY(launch_aggregate(nullptr, a.nodegraph, out_nodes, p.T, p.T, ta.y_pred, p.T, st));
+    if (fwd_only) {
+        // the forward alone: the moving averages the persistent small-graph path keeps back for the step's validity word are due now
+        if (p.small) {
+            TRY(moving_state(nullptr));
+            if (bn_o && p.M > 0) {
+                gnn::k_bn_moving_multi<<<cdiv(no.in_dim, 256), 256, 0, st>>>(p.stats_o, 2 * no.in_dim, 1, no.in_dim, const_cast<float *>(no.bn_mean),
+                                                                            const_cast<float *>(no.bn_var), ta.bn_momentum);
+                LAUNCH_OK();
+            }
+        }
+        return 0;
+    }
     gnn::k_loss_grad<<<cdiv(std::max(p.R, 1), 256), 256, 0, st>>>(ta.loss_kind, ta.targets, ta.y_pred, ta.sample_weight, p.R, p.T, p.dpred, p.loss_rows);
     LAUNCH_OK();
     if (p.R > 65536) {

@@ -1,7 +1,9 @@
 // Host side of the grouped training-mode forward (C ABI 10; kernels_train_group.hpp): coverage, group tables, workspace, launches.
-// Included behind train_loop.hpp in gnnloop.hip (shares its plan and helpers).
+// Included behind train_loop.hpp and train_composite.hpp in gnnloop.hip (shares their plans and helpers).  Heterogeneous models (one state
+// network per node type) take the *_types kernels of kernels_train_group_types.hpp: the second half of this file.
 #pragma once
 #include "kernels_train_group.hpp"
+#include "kernels_train_group_types.hpp"
 
 namespace {
 
@@ -29,12 +31,12 @@ bool train_groups_covered(const gnn_train_args_t &ta, const TrainPlan &p) {
 }
 
 // the host tables: 0 fine, -2 malformed (message set when `say`), g + 1: group g is too large
-int train_group_tables(const gnn_train_args_t &ta, const TrainPlan &p, bool say, int *max_nodes) {
+int train_group_tables(const gnn_train_args_t &ta, int N, int M, bool say, int *max_nodes) {
     const int G = ta.n_groups;
     if (max_nodes) *max_nodes = 0;
     if (!ta.group_node_begin || !ta.group_out_begin) { if (say) fail("group_node_begin / group_out_begin is NULL"); return GNN_TRAIN_GROUPS_MALFORMED; }
-    if (ta.group_node_begin[0] != 0 || ta.group_node_begin[G] != p.N) { if (say) fail("group_node_begin must span [0, n_nodes]"); return GNN_TRAIN_GROUPS_MALFORMED; }
-    if (ta.group_out_begin[0] != 0 || ta.group_out_begin[G] != p.M) { if (say) fail("group_out_begin must span [0, n_out]"); return GNN_TRAIN_GROUPS_MALFORMED; }
+    if (ta.group_node_begin[0] != 0 || ta.group_node_begin[G] != N) { if (say) fail("group_node_begin must span [0, n_nodes]"); return GNN_TRAIN_GROUPS_MALFORMED; }
+    if (ta.group_out_begin[0] != 0 || ta.group_out_begin[G] != M) { if (say) fail("group_out_begin must span [0, n_out]"); return GNN_TRAIN_GROUPS_MALFORMED; }
     int too_large = 0, mx = 0;
     for (int g = 0; g < G; ++g) {
         const int n = ta.group_node_begin[g + 1] - ta.group_node_begin[g];
@@ -64,8 +66,11 @@ int make_group_plan(const gnn_train_args_t &ta, void *ws, GroupPlan &gp) {
     return 0;
 }
 
+size_t group_types_workspace_bytes(const gnn_train_args_t &ta);
+
 size_t group_train_workspace_bytes(const gnn_train_args_t &ta) {
     if (ta.n_groups < 0) { fail("n_groups < 0"); return 0; }
+    if (ta.loop.composite) return group_types_workspace_bytes(ta);
     GroupPlan gp;
     if (make_group_plan(ta, nullptr, gp)) return 0;
     return gp.bytes;
@@ -92,8 +97,28 @@ int launch_train_group_fwd_sq(const gnn::TrainGroupFwd &fa, int G, int max_nodes
     return has_w ? go(&gnn::k_train_group_fwd<SQ, true>) : go(&gnn::k_train_group_fwd<SQ, false>);
 }
 
+int train_forward_groups_types(const gnn_train_args_t &ta);
+
+int launch_train_group_head(const gnn::TrainGroupHead &h, int G, hipStream_t st) {
+    const size_t lds = gnn::train_group_head_lds(h.in_o, h.T);
+    static std::mutex m;
+    static bool raised = false;
+    {
+        std::lock_guard<std::mutex> lock(m);
+        if (!raised) {
+            HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&gnn::k_train_group_head), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)gnn::train_group_head_lds(gnn::GROUP_HEAD_MAX_IN, gnn::GROUP_HEAD_MAX_UNITS)));
+            raised = true;
+        }
+    }
+    gnn::k_train_group_head<<<G, 256, lds, st>>>(h);
+    LAUNCH_OK();
+    return 0;
+}
+
 int train_forward_groups(const gnn_train_args_t &ta) {
     const gnn_loop_args_t &a = ta.loop;
+    if (a.composite) return train_forward_groups_types(ta);
     if (!ta.forward_only) return fail("gnn_train_step: convergence groups need forward_only (a grouped training step is not implemented)");
     if (ta.prev_grads_ok_host) return fail("gnn_train_step(forward_only): prev_grads_ok_host must be NULL");
     if (ta.n_groups < 0) return fail("n_groups < 0");
@@ -101,7 +126,7 @@ int train_forward_groups(const gnn_train_args_t &ta) {
     TRY(make_group_plan(ta, ta.tape, gp));
     const TrainPlan &p = gp.p;
     if (!train_groups_covered(ta, p)) return fail("gnn_train_step: convergence groups do not cover this shape (gnn_train_groups_supported() == %d)", GNN_TRAIN_GROUPS_UNCOVERED);
-    const int tab = train_group_tables(ta, p, true, &gp.max_nodes);
+    const int tab = train_group_tables(ta, p.N, p.M, true, &gp.max_nodes);
     if (tab < 0) return 1;
     if (tab > 0) return fail("group %d has %d nodes (at most %d per convergence group: gnn_train_groups_supported())", tab - 1,
                              ta.group_node_begin[tab] - ta.group_node_begin[tab - 1], gnn::GROUP_CAP);
@@ -195,22 +220,214 @@ int train_forward_groups(const gnn_train_args_t &ta) {
         h.obeg = gp.obeg; h.in_o = p.in_o; h.T = p.T; h.act = no.activation[0];
         h.W = no.kernel[0]; h.b = no.bias[0]; h.gamma = bn_o ? no.bn_gamma : nullptr; h.beta = no.bn_beta; h.eps = no.bn_eps;
         h.stats_o = gp.stats_o; h.out = ta.y_pred;
-        const size_t lds = gnn::train_group_head_lds(p.in_o, p.T);
+        TRY(launch_train_group_head(h, G, st));
+        if (bn_o) {
+            gnn::k_bn_moving_groups<<<cdiv(p.in_o, 64), 64, 0, st>>>(gp.stats_o, 1, p.in_o, ta.k_groups, gp.obeg, G, const_cast<float *>(no.bn_mean),
+                                                                    const_cast<float *>(no.bn_var), ta.bn_momentum);
+            LAUNCH_OK();
+        }
+    }
+    return 0;
+}
+
+
+// ---- heterogeneous models ---------------------------------------------------------------------------------------------------------------------
+struct GroupTypesPlan {
+    CPlan p;                     // dims only (planned without a workspace)
+    int G, max_nodes, SPs;
+    int *gbeg, *obeg, *tbeg;     // device: the host tables, and the rows of every type per group [n_types][G + 1]
+    float *agg_comp, *cc, *agg, *stats_t[GNN_MAX_TYPES], *stats_o;
+    int *isrc, *idst;
+    size_t bytes;
+};
+
+// what the *_types kernels cover (dims and network descriptions only).  BatchNormalization may differ between the types: every (group, type)
+// is normalised on its own.
+bool train_groups_types_covered(const gnn_train_args_t &ta, const CPlan &p) {
+    const gnn_loop_args_t &a = ta.loop;
+    const gnn_mlp_t &no = a.net_output;
+    if (!a.composite || p.n_types < 1 || p.n_types > GNN_MAX_TYPES) return false;
+    if (a.focus != GNN_FOCUS_NODE && a.focus != GNN_FOCUS_ARC) return false;
+    if (p.S > 64 || p.K < 1 || ta.drop_output.n > 0) return false;
+    for (int t = 0; t < p.n_types; ++t) {
+        const gnn_mlp_t &ns = a.net_state[t];
+        if (ta.drop_state[t].n > 0) return false;
+        if (ns.n_layers != 1 || ns.units[0] != p.S || ns.activation[0] == GNN_ACT_SOFTMAX) return false;
+        if (a.type_dim_label[t] + p.W_comp > gnn::GROUP_TYPES_MAX_KC) return false;
+    }
+    if (no.n_layers != 1 || no.units[0] > gnn::GROUP_HEAD_MAX_UNITS || no.in_dim > gnn::GROUP_HEAD_MAX_IN) return false;
+    return true;
+}
+
+int make_group_types_plan(const gnn_train_args_t &ta, void *ws, GroupTypesPlan &gp) {
+    TRY(make_cplan(ta, nullptr, gp.p));
+    const CPlan &p = gp.p;
+    gp.G = ta.n_groups;
+    gp.SPs = p.S <= 16 ? 16 : p.S <= 32 ? 32 : 64;
+    Carver c(ws);
+    gp.gbeg = c.take<int>((size_t)gp.G + 1); gp.obeg = c.take<int>((size_t)gp.G + 1);
+    gp.tbeg = c.take<int>((size_t)p.n_types * (gp.G + 1));
+    gp.agg_comp = c.take<float>((size_t)p.N * std::max(p.W_comp, 1));
+    gp.cc = c.take<float>((size_t)p.N * gp.SPs);
+    gp.agg = c.take<float>((size_t)p.N * gp.SPs);
+    for (int t = 0; t < p.n_types; ++t) gp.stats_t[t] = c.take<float>((size_t)gp.G * p.K * 2 * p.ty[t].in_dim);
+    gp.stats_o = c.take<float>((size_t)gp.G * 2 * ta.loop.net_output.in_dim);
+    gp.isrc = c.take<int>(std::max(p.M, 1)); gp.idst = c.take<int>(std::max(p.M, 1));
+    gp.bytes = (c.off + 255) & ~(size_t)255;
+    return 0;
+}
+
+size_t group_types_workspace_bytes(const gnn_train_args_t &ta) {
+    GroupTypesPlan gp;
+    if (make_group_types_plan(ta, nullptr, gp)) return 0;
+    return gp.bytes;
+}
+
+template <int SQ>
+int launch_train_group_fwd_types_sq(const gnn::TrainGroupFwdTypes &fa, int G, int max_nodes, bool has_w, hipStream_t st) {
+    const size_t lds = gnn::train_group_fwd_types_lds<SQ>(max_nodes);
+    auto go = [&](auto kern) -> int {
+        // (the limit is raised to what the largest group allowed needs, once per kernel)
         static std::mutex m;
         static bool raised = false;
         {
             std::lock_guard<std::mutex> lock(m);
             if (!raised) {
-                HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&gnn::k_train_group_head), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)gnn::train_group_head_lds(gnn::GROUP_HEAD_MAX_IN, gnn::GROUP_HEAD_MAX_UNITS)));
+                HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gnn::train_group_fwd_types_lds<SQ>(gnn::GROUP_CAP)));
                 raised = true;
             }
         }
-        gnn::k_train_group_head<<<G, 256, lds, st>>>(h);
+        kern<<<G, gnn::TS_NT, lds, st>>>(fa);
         LAUNCH_OK();
+        return 0;
+    };
+    return has_w ? go(&gnn::k_train_group_fwd_types<SQ, true>) : go(&gnn::k_train_group_fwd_types<SQ, false>);
+}
+
+int train_forward_groups_types(const gnn_train_args_t &ta) {
+    const gnn_loop_args_t &a = ta.loop;
+    if (!ta.forward_only) return fail("gnn_train_step: convergence groups need forward_only (a grouped training step is not implemented)");
+    if (ta.prev_grads_ok_host) return fail("gnn_train_step(forward_only): prev_grads_ok_host must be NULL");
+    if (ta.n_groups < 0) return fail("n_groups < 0");
+    GroupTypesPlan gp;
+    TRY(make_group_types_plan(ta, ta.tape, gp));
+    const CPlan &p = gp.p;
+    if (!train_groups_types_covered(ta, p)) return fail("gnn_train_step: convergence groups do not cover this shape (gnn_train_groups_supported() == %d)", GNN_TRAIN_GROUPS_UNCOVERED);
+    const int tab = train_group_tables(ta, p.N, p.M, true, &gp.max_nodes);
+    if (tab < 0) return 1;
+    if (tab > 0) return fail("group %d has %d nodes (at most %d per convergence group: gnn_train_groups_supported())", tab - 1,
+                             ta.group_node_begin[tab] - ta.group_node_begin[tab - 1], gnn::GROUP_CAP);
+    if (ta.tape_bytes < gp.bytes) return fail("tape too small: %zu < %zu bytes", ta.tape_bytes, gp.bytes);
+    TRY(check_csr(a.adjacency, "adjacency", p.N, p.N));
+    TRY(check_csr(a.arcnode, "arcnode", p.N, p.E));
+    for (int t = 0; t < p.n_types; ++t) {
+        TRY(check_csr(a.composite_adjacency[t], "composite_adjacency", p.N, p.N));
+        TRY(check_mlp(a.net_state[t], "net_state", true));
+    }
+    if (!a.nodes || !a.type_nodes) return fail("nodes / type_nodes is NULL");
+    if (p.E > 0 && p.A > 0 && !a.arc_labels) return fail("arc_labels is NULL");
+    if (a.state_dim > 0 && !a.state0) return fail("state0 is required when state_dim > 0");
+    if (p.M > 0 && !a.out_index) return fail("out_index is NULL");
+    if (a.focus == GNN_FOCUS_ARC && p.E > 0 && (!a.arc_src || !a.arc_dst)) return fail("arc focus needs arc_src / arc_dst");
+    if ((p.M > 0 && !ta.y_pred) || !ta.state || !ta.k_groups) return fail("y_pred / state / k_groups is NULL");
+    const gnn_mlp_t &no = a.net_output;
+    TRY(check_mlp(no, "net_output", true));
+    const bool bn_o = no.has_bn != 0;
+    hipStream_t st = (hipStream_t)a.stream;
+    const int G = gp.G, SPs = gp.SPs;
+    GNN_SET_KERNEL_NAME("train_step: grouped forward kernels (types)");
+
+    // the group tables go to the device through a pinned staging buffer of this thread; its event says when the previous call's copy has left it
+    {
+        static thread_local struct { int *buf; size_t cap; hipEvent_t ev; } stage = {nullptr, 0, nullptr};
+        const size_t n_tab = 2 * ((size_t)G + 1);
+        if (stage.ev) HIP_OK(hipEventSynchronize(stage.ev));
+        else HIP_OK(hipEventCreateWithFlags(&stage.ev, hipEventDisableTiming));
+        if (stage.cap < n_tab) {
+            if (stage.buf) HIP_OK(hipHostFree(stage.buf));
+            stage.buf = nullptr; stage.cap = 0;
+            HIP_OK(hipHostMalloc((void **)&stage.buf, std::max<size_t>(n_tab, 4096) * sizeof(int), hipHostMallocDefault));
+            stage.cap = std::max<size_t>(n_tab, 4096);
+        }
+        memcpy(stage.buf, ta.group_node_begin, ((size_t)G + 1) * sizeof(int));
+        memcpy(stage.buf + G + 1, ta.group_out_begin, ((size_t)G + 1) * sizeof(int));
+        HIP_OK(hipMemcpyAsync(gp.gbeg, stage.buf, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(gp.obeg, stage.buf + G + 1, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_OK(hipEventRecord(stage.ev, st));
+    }
+    // the rows of every type per group: groups are contiguous node ranges, a type's row list ascends
+    {
+        gnn::TypeOffsets to;
+        for (int t = 0; t <= GNN_MAX_TYPES; ++t) to.off[t] = t <= p.n_types ? a.type_offsets[t] : p.N;
+        gnn::k_group_type_begin<<<cdiv(p.n_types * (G + 1), 256), 256, 0, st>>>(a.type_nodes, to, p.n_types, gp.gbeg, G, gp.tbeg);
+        LAUNCH_OK();
+    }
+    // aggregated_component over the merged graph (block-diagonal: a row sees its own group only), as train_step_composite builds it
+    {
+        int col = 0;
+        for (int t = 0; t < p.n_types; ++t) {
+            const int dt = a.type_dim_label[t];
+            if (dt > 0) TRY(launch_aggregate(nullptr, a.composite_adjacency[t], a.nodes, a.ld_nodes, dt, gp.agg_comp + col, p.W_comp, st));
+            col += dt;
+        }
+        if (p.A > 0) TRY(launch_aggregate(nullptr, a.arcnode, a.arc_labels, a.ld_arcs, p.A, gp.agg_comp + col, p.W_comp, st));
+    }
+    gnn::TrainGroupConstTypes ca;
+    gnn::TrainGroupFwdTypes fa;
+    memset(&ca, 0, sizeof(ca)); memset(&fa, 0, sizeof(fa));
+    for (int t = 0; t < p.n_types; ++t) {
+        const CType &y = p.ty[t];
+        const gnn_mlp_t &ns = a.net_state[t];
+        gnn::GroupTypeNet &n = ca.net[t];
+        n.W = ns.kernel[0]; n.b = ns.bias[0]; n.gamma = ns.has_bn ? ns.bn_gamma : nullptr; n.beta = ns.bn_beta; n.eps = ns.bn_eps;
+        n.act = ns.activation[0]; n.d_t = y.d_t; n.in_dim = y.in_dim; n.off_state = y.off_state; n.off_agg = y.off_agg; n.off_comp = y.off_comp;
+        n.stats = gp.stats_t[t];
+        fa.net[t] = n;
+    }
+    ca.n_types = p.n_types; ca.G = G; ca.S = SPs; ca.Sw = p.S; ca.K = p.K; ca.W_comp = p.W_comp;
+    ca.tbeg = gp.tbeg; ca.type_nodes = a.type_nodes; ca.nodes = a.nodes; ca.ld_nodes = a.ld_nodes; ca.agg_comp = gp.agg_comp; ca.Cc = gp.cc;
+    gnn::k_train_group_const_types<<<G, 256, 0, st>>>(ca);
+    LAUNCH_OK();
+    fa.S = SPs; fa.Sw = p.S; fa.K = p.K; fa.n_types = p.n_types; fa.G = G;
+    fa.rowptr = a.adjacency.rowptr; fa.src = a.adjacency.src; fa.w = a.adjacency.w; fa.row_scale = a.adjacency.row_scale;
+    fa.gbeg = gp.gbeg; fa.tbeg = gp.tbeg; fa.type_nodes = a.type_nodes;
+    fa.state0 = a.state_dim > 0 ? a.state0 : a.nodes; fa.ld0 = a.state_dim > 0 ? p.S : a.ld_nodes;
+    fa.state_out = ta.state; fa.agg = gp.agg; fa.Cc = gp.cc; fa.thr = a.state_threshold; fa.k_groups = ta.k_groups;
+    switch (SPs) {
+        case 16: TRY(launch_train_group_fwd_types_sq<1>(fa, G, gp.max_nodes, a.adjacency.w != nullptr, st)); break;
+        case 32: TRY(launch_train_group_fwd_types_sq<2>(fa, G, gp.max_nodes, a.adjacency.w != nullptr, st)); break;
+        default: TRY(launch_train_group_fwd_types_sq<4>(fa, G, gp.max_nodes, a.adjacency.w != nullptr, st)); break;
+    }
+    // the moving statistics of network t: k_g steps for every group with rows of type t, group after group
+    for (int t = 0; t < p.n_types; ++t) {
+        const gnn_mlp_t &ns = a.net_state[t];
+        if (!ns.has_bn) continue;
+        const int in_t = p.ty[t].in_dim;
+        gnn::k_bn_moving_groups<<<cdiv(in_t, 64), 64, 0, st>>>(gp.stats_t[t], p.K, in_t, ta.k_groups, gp.tbeg + (size_t)t * (G + 1), G, const_cast<float *>(ns.bn_mean),
+                                                              const_cast<float *>(ns.bn_var), ta.bn_momentum, 1);
+        LAUNCH_OK();
+    }
+    if (p.M > 0) {
+        // composite models filter on the state alone: [state] (node focus), [state_src | state_dst | arc label] (arc focus)
+        gnn::TrainGroupHead h;
+        memset(&h, 0, sizeof(h));
+        int n = 0;
+        auto seg = [&](const float *ptr, const int *idx, int ld, int width) { h.sg.ptr[n] = ptr; h.sg.idx[n] = idx; h.sg.ld[n] = ld; h.sg.width[n] = width; ++n; };
+        if (a.focus == GNN_FOCUS_ARC) {
+            k_arc_endpoints<<<cdiv(p.M, 256), 256, 0, st>>>(a.out_index, a.arc_src, a.arc_dst, p.M, gp.isrc, gp.idst);
+            LAUNCH_OK();
+            seg(ta.state, gp.isrc, p.S, p.S);
+            seg(ta.state, gp.idst, p.S, p.S);
+            if (p.A > 0) seg(a.arc_labels, a.out_index, a.ld_arcs, p.A);
+        } else seg(ta.state, a.out_index, p.S, p.S);
+        h.sg.n = n;
+        h.obeg = gp.obeg; h.in_o = no.in_dim; h.T = p.T; h.act = no.activation[0];
+        h.W = no.kernel[0]; h.b = no.bias[0]; h.gamma = bn_o ? no.bn_gamma : nullptr; h.beta = no.bn_beta; h.eps = no.bn_eps;
+        h.stats_o = gp.stats_o; h.out = ta.y_pred;
+        TRY(launch_train_group_head(h, G, st));
         if (bn_o) {
-            gnn::k_bn_moving_groups<<<cdiv(p.in_o, 64), 64, 0, st>>>(gp.stats_o, 1, p.in_o, ta.k_groups, gp.obeg, G, const_cast<float *>(no.bn_mean),
-                                                                    const_cast<float *>(no.bn_var), ta.bn_momentum);
+            gnn::k_bn_moving_groups<<<cdiv(no.in_dim, 64), 64, 0, st>>>(gp.stats_o, 1, no.in_dim, ta.k_groups, gp.obeg, G, const_cast<float *>(no.bn_mean),
+                                                                      const_cast<float *>(no.bn_var), ta.bn_momentum, 0);
             LAUNCH_OK();
         }
     }
@@ -221,8 +438,14 @@ int train_forward_groups(const gnn_train_args_t &ta) {
 
 extern "C" int gnn_train_groups_supported(const gnn_train_args_t *args) {
     if (!args || args->n_groups < 1 || !args->forward_only) return GNN_TRAIN_GROUPS_UNCOVERED;
+    if (args->loop.composite) {
+        CPlan cp;
+        if (make_cplan(*args, nullptr, cp)) return GNN_TRAIN_GROUPS_UNCOVERED;
+        if (!train_groups_types_covered(*args, cp)) return GNN_TRAIN_GROUPS_UNCOVERED;
+        return train_group_tables(*args, cp.N, cp.M, false, nullptr);
+    }
     TrainPlan p;
     if (make_train_plan(*args, nullptr, p)) return GNN_TRAIN_GROUPS_UNCOVERED;
     if (!train_groups_covered(*args, p)) return GNN_TRAIN_GROUPS_UNCOVERED;
-    return train_group_tables(*args, p, false, nullptr);
+    return train_group_tables(*args, p.N, p.M, false, nullptr);
 }

@@ -851,10 +851,7 @@ static int train_step_impl(const gnn_train_args_t &ta) {
     if (!ta.tape || ((uintptr_t)ta.tape & 255) != 0) return fail("tape must be a 256-byte aligned device buffer");
     const bool fwd_only = ta.forward_only != 0;                   // ABI 9: the training-mode forward alone (no loss, no gradients)
     if (ta.n_groups != 0) return train_forward_groups(ta);         // ABI 10: independent convergence groups (train_group.hpp)
-    if (a.composite) {
-        if (fwd_only) return fail("gnn_train_step(forward_only): homogeneous models only");
-        return train_step_composite(ta);                           // one state network per node type (train_composite.hpp)
-    }
+    if (a.composite) return train_step_composite(ta);             // one state network per node type (train_composite.hpp); honours forward_only
     if (fwd_only && ta.prev_grads_ok_host) return fail("gnn_train_step(forward_only): prev_grads_ok_host must be NULL");
     TRY(make_train_plan(ta, ta.tape, p));
     if (ta.tape_bytes < p.bytes) return fail("tape too small: %zu < %zu bytes", ta.tape_bytes, p.bytes);
