@@ -156,12 +156,17 @@ class CompositeGNNnodeBased(GNNnodeBased):
         return hit[0], hit[1]
 
     def Loop(self, nodes, arcs, dim_node_label, type_mask, set_mask, output_mask, composite_adjacencies, adjacency,
-             arcnode, nodegraph, training: bool = False, *, state0=None, seed=None, node_level: bool = False, groups=None):
+             arcnode, nodegraph, training: bool = False, *, state0=None, seed=None, node_level: bool = False, groups=None, group_sets=None):
         """(k, state, out) for one (merged) heterogeneous graph — reference CompositeGNN.py:242-272.
-        `state0` / `seed` / `node_level` as in `GNNnodeBased.Loop`; `groups` is refused here: the convergence groups of composite models
-        are reached one level down, through `LoopTrainer.forward_native(groups=...)` (docs/serial_propagation.md)."""
-        if groups is not None:
-            raise NotImplementedError('convergence groups: composite (heterogeneous) models are not covered by Loop(groups=...); use LoopTrainer.forward_native(groups=...)')
+        `state0` / `seed` / `node_level` as in `GNNnodeBased.Loop`.  `groups` / `group_sets` (inference only): node offsets [G + 1] of G
+        merged batches that run as independent loops of one launch, k is then [G] (one entry per set with `group_sets`) - as for
+        homogeneous models, on the typed one-CU-per-group kernel; a shape it does not cover raises `NativeError` ('convergence groups ..',
+        `ops.loop_groups_supported(..., type_dims=...)` != 2).  With `training=True` groups are refused here: the training-mode
+        convergence groups of composite models are reached one level down, through `LoopTrainer.forward_native(groups=...)`
+        (docs/serial_propagation.md)."""
+        if groups is not None and training:
+            raise NotImplementedError('convergence groups: composite (heterogeneous) models are not covered by Loop(training=True, groups=...); use LoopTrainer.forward_native(groups=...)')
+        if group_sets is not None and groups is None: raise ValueError('group_sets needs groups')
         focus = 'n' if (node_level and self._focus == 'g') else self._focus
         if training:
             from .training import LoopTrainer
@@ -191,7 +196,8 @@ class CompositeGNNnodeBased(GNNnodeBased):
         T = len(dims)
         if T != len(self.net_state): raise ValueError(f'{T} node types but {len(self.net_state)} state networks')
         if T > nat.GNN_MAX_TYPES: raise ValueError(f'at most {nat.GNN_MAX_TYPES} node types are supported')
-        type_mask = _squeeze_last(type_mask).to(dev)
+        # (T, N, 1) as the sequencers hand it over, or (T, N) after process_inputs - which for a graph of ONE node must not lose its node axis too
+        type_mask = (_squeeze_last(type_mask) if type_mask.dim() == 3 else type_mask).to(dev)
         set_mask, output_mask = _squeeze_last(set_mask).to(dev), _squeeze_last(output_mask).to(dev)
         out_index = self._out_index(set_mask, output_mask)
         type_nodes, offsets = self._type_lists(type_mask)
@@ -213,10 +219,19 @@ class CompositeGNNnodeBased(GNNnodeBased):
             state0 = None
         ends = _arc_endpoints(adjacency, dev) if focus == 'a' else None
         ng = SparseMatrix.from_triple(nodegraph).device_csr(dev) if focus == 'g' else None
+        # (the first group of every set, uploaded BEFORE the launch: a pageable host-to-device copy behind it would block the host)
+        set_id = None
+        if group_sets is not None:
+            gs_ = np.asarray([int(v) for v in group_sets], dtype=np.int64)
+            set_id = torch.as_tensor(np.repeat(np.arange(len(gs_) - 1), np.diff(gs_)), device=dev)
         # one custom op for the whole heterogeneous Loop: torch.ops.gnnkeras.loop_forward with the per-type lists
         k, state, out = ops.loop_forward(nodes, arcs, adj, arcn, ng, self.net_state, self.net_output, state0, out_index, ends,
                                          self.state_vect_dim, self.max_iteration, self.state_threshold, nat.FOCUS[focus],
-                                         self.native_flags, composite=(type_nodes, offsets, dims, cas), loop_events=self.loop_events)
+                                         self.native_flags, composite=(type_nodes, offsets, dims, cas), loop_events=self.loop_events,
+                                         groups=groups, group_sets=group_sets)
+        self._last_k_groups = k         # (one entry per GROUP, before the sets are folded)
+        if group_sets is not None:      # one entry per set: its groups report the same k (or -1e9 where a member's wait expired: the minimum keeps it)
+            k = torch.full((len(group_sets) - 1,), float('inf'), device=dev).scatter_reduce_(0, set_id, k, 'amin')
         self._last_k = k
         return k, state, out
 

@@ -355,21 +355,27 @@ class _LoopModel:
         yield from self._batches_concurrently(len(plan), launch, device, width, lane=lane)
 
     def _group_plan(self, sequencer, device):
-        """[[batch, ...], ...]: the batches each launch merges, or None when grouping does not apply (composite model, CPU,
-        'normalized', unsupported shape, a sequencer that does not keep a list of merged batches).  Batches whose state fits the
+        """[[batch, ...], ...]: the batches each launch merges, or None when grouping does not apply (CPU, 'normalized',
+        unsupported shape, a sequencer that does not keep a list of merged batches).  Batches whose state fits the
         LDS of one CU go together - one workgroup each, any number of them per launch; the others in runs of at most 32 whose
-        64-node tiles are all resident at once."""
+        64-node tiles are all resident at once.  Composite models (a list of state networks): resident launches only."""
         if not self.group_batches or device.type != 'cuda' or not hasattr(sequencer, 'merged_batches'): return None
         if not isinstance(getattr(sequencer, 'graph_tensors', None), list): return None          # opt-in: Multi* sequencers only
-        if not isinstance(getattr(self, 'net_state', None), Sequential) or not hasattr(self, 'state_vect_dim'): return None
+        nets = getattr(self, 'net_state', None)
+        composite = isinstance(nets, (list, tuple))
+        if composite:
+            if not nets or not all(isinstance(n_, Sequential) for n_ in nets): return None
+        elif not isinstance(nets, Sequential): return None
+        if not hasattr(self, 'state_vect_dim'): return None
         if sequencer.merged_batches(0, 1) is None: return None
+        nets = list(nets) if composite else [nets]
         # the plan depends on the batches (rebuilt batches = a new graph_tensors list) and on the model's shape only: kept
         key = (id(sequencer.graph_tensors), len(sequencer), self.state_vect_dim, self.max_iteration, self.native_flags, self._focus,
-               tuple(self.net_state.units), tuple(self.net_state.activations), self.net_state.input_dim, str(device))
+               tuple(tuple(n_.units) for n_ in nets), tuple(tuple(n_.activations) for n_ in nets), tuple(n_.input_dim for n_ in nets), composite, str(device))
         cache = self.__dict__.setdefault('_plan_cache', {})
         hit = cache.get(key)
         if hit is not None and hit[0] is sequencer.graph_tensors: return hit[1]
-        plan = self._make_group_plan(sequencer, device)
+        plan = self._make_composite_group_plan(sequencer, device) if composite else self._make_group_plan(sequencer, device)
         if len(cache) >= 4: cache.clear()
         cache[key] = (sequencer.graph_tensors, plan)
         return plan
@@ -451,6 +457,62 @@ class _LoopModel:
         if run: plan.append(_Launch(run))
         for bs in plan:
             if len(bs) >= 2 and not getattr(bs, 'parts', None) and not supported(bs): return None
+        return plan
+
+    def _make_composite_group_plan(self, sequencer, device):
+        """The group plan of a composite model: resident launches only (one workgroup per batch with its typed rows in LDS, gnn_loop_groups_supported
+        == 2).  A batch above the library's group size (`ops.loop_group_max_nodes`: it shrinks with the number of node types) is cut along
+        graph boundaries into parts that share the loop's condition (group sets).  None - the walk stays batch by batch - when any
+        batch can be neither taken whole nor cut, or the library refuses a launch.
+
+        Two differences from `_make_group_plan`, both on the cautious side.  A batch with hub rows (in-degree above
+        sparse.HEAVY_THRESHOLD; they take the per-iteration kernels) makes this planner give up on the WHOLE sequencer, where the homogeneous
+        one launches such a batch alone and groups the rest: a mixed plan would need the spread form for what is left, which composite
+        models do not have.  And there is no `long_loop`-style rule that cuts batches further to fill the CUs: a rule of that kind (or one
+        that leaves a configuration ungrouped because it measures no faster) belongs before the `for b in range(n)` loop below, decided
+        from max_iteration x largest batch x padded width as there; scripts/composite_predict_perf.py is the measurement to base it on."""
+        try:
+            n = len(sequencer)
+            sizes = [int(sequencer[i][0][0].shape[0]) for i in range(n)]
+            n_out = [int(sequencer[i][1].shape[0]) for i in range(n)]
+            x0 = sequencer[0][0]
+            L, A = int(x0[0].shape[1]), int(x0[1].shape[1]) - 2
+            dims = [int(d) for d in x0[2].reshape(-1).tolist()]
+            # (the hub probe uploads every batch's adjacency CSR just to look at 'heavy' - as the homogeneous planner does; the upload is
+            # cached on the matrix, so the walk that follows finds it there)
+            hub = any(SparseMatrix.from_triple(sequencer[i][0][7]).device_csr(device).get('heavy') is not None for i in range(n))
+        except Exception:
+            return None
+        if hub or len(dims) != len(self.net_state): return None
+        focus = nat.FOCUS[self._focus]
+        limit = ops.loop_group_max_nodes(L, A, self.net_state, self.net_output, self.state_vect_dim, self.max_iteration, focus, dims)
+        if limit < 1: return None
+        parts = {}
+        for b in range(n):
+            if sizes[b] <= limit: continue
+            cut = self._cut_batch(sequencer, b, limit)
+            if cut is None: return None
+            parts[b] = cut
+        cus = torch.cuda.get_device_properties(device).multi_processor_count
+        plan, chunk, n_grp = [], [], 0
+        def flush():
+            nonlocal chunk, n_grp
+            if chunk:
+                entry = _Launch(chunk, resident=True, parts={b: parts[b] for b in chunk if b in parts})
+                begin, sets = entry.groups_and_sets(sizes)
+                if len(chunk) == 1 and not entry.parts: entry = _Launch(chunk)      # (a lone batch: an ordinary call)
+                elif ops.loop_groups_supported(begin[-1], L, A, self.net_state, self.net_output, self.state_vect_dim, self.max_iteration, focus,
+                                               self.native_flags, sum(n_out[b] for b in chunk), begin, sets, dims) != 2:
+                    return False
+                plan.append(entry)
+            chunk, n_grp = [], 0
+            return True
+        for b in range(n):
+            g_b = len(parts.get(b, [0]))
+            if chunk and n_grp + g_b > (cus if parts else 1024):
+                if not flush(): return None
+            chunk.append(b); n_grp += g_b
+        if not flush(): return None
         return plan
 
     @staticmethod

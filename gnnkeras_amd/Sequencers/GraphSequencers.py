@@ -99,8 +99,10 @@ class MultiGraphSequencer:
         independent loops of one launch - each batch converges and stops on its own, as if called alone - which is how
         predict() / evaluate() fill the GPU with small batches.  None when a bigger merge would change the operands:
         'normalized' divides by the number of arcs of the merged graph (graph_class.py buildArcNode).  Cached
-        until the batches are rebuilt."""
-        if self.aggregation_mode == 'normalized' or type(self).merge.__func__ is not MultiGraphSequencer.merge.__func__: return None
+        until the batches are rebuilt.  `CompositeMultiGraphSequencer` answers with the composite merge of the same graphs (host
+        merge + upload); sequencers with a merge of their own answer None."""
+        if self.aggregation_mode == 'normalized': return None
+        if type(self).merge.__func__ not in (MultiGraphSequencer.merge.__func__, CompositeMultiGraphSequencer.merge.__func__): return None
         batches = [int(b) for b in i0] if i1 is None else list(range(int(i0), int(i1)))
         key = tuple(batches)                                    # (a range and the list of its members are the same merge)
         cache = self.__dict__.setdefault('_merged', {})

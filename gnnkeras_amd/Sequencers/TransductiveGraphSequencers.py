@@ -42,6 +42,10 @@ class TransductiveMultiGraphSequencer(CompositeMultiGraphSequencer):
 
     __str__ = __repr__
 
+    def merged_batches(self, i0, i1=None):
+        """The batches are merges of a split that is re-drawn at every epoch end: not merged across batches."""
+        return None
+
     def on_epoch_end(self):
         """Re-draw the transductive split of every graph, then reshuffle / re-merge (reference :56-59)."""
         self.data = [self.get_transduction(g, self.transductive_rate, self.focus, self.dtype) for g in self.graph_objects]

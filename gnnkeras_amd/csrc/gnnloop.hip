@@ -26,6 +26,7 @@
 #include "kernel_state_small.hpp"
 #include "kernel_state_mid.hpp"
 #include "kernel_state_lds.hpp"
+#include "kernel_state_lds_types.hpp"
 #include "kernel_state_wide.hpp"
 #include "kernels_batch.hpp"
 #include "kernels_setup.hpp"
@@ -442,7 +443,9 @@ struct Plan {
     int *d_group_tabs;               // device copies of group_node_begin / 64-node-tile offsets / set first group / set size, [n_groups + 1] each
     unsigned long long *set_bar;     // two flag-exchange counters per group set (indexed by the set's first group), zeroed per call
     bool has_sets;                   // some set has more than one group
-    int *pred0;                      // state_0's predicate, one word per 64-node tile (written by k_setup_small, read by k_state_small)
+    int *pred0;                      // state_0's predicate, one word per 64-node tile (written by k_setup_small, read by k_state_small);
+                                     // composite groups: one word per group (k_pred0_groups)
+    int *tbeg;                       // composite groups: rows of every type per group, positions in type_nodes [n_types][n_groups + 1]
     int *err;                        // sticky "an in-launch wait expired" word of the fused kernels, folded into k at the end
     float *agg_arcs, *agg_nodes; int ld_agg_nodes;
     float *C; int ldC;
@@ -502,7 +505,6 @@ int make_plan(const gnn_loop_args_t &a, void *ws, Plan &p, bool validate_ptrs) {
     p.n_groups = a.n_groups;
     if (a.n_groups < 0 || a.n_groups > GNN_MAX_GROUPS_RESIDENT) return fail("n_groups %d out of [0,%d]", a.n_groups, GNN_MAX_GROUPS_RESIDENT);
     if (a.n_groups > 0) {
-        if (p.composite) return fail("convergence groups are not supported for composite graphs");
         if (!a.group_node_begin) return fail("group_node_begin is NULL");
         if (a.group_node_begin[0] != 0 || a.group_node_begin[a.n_groups] != a.n_nodes) return fail("group_node_begin must span [0, n_nodes]");
         p.gt.n = a.n_groups <= GNN_MAX_GROUPS ? a.n_groups : 0;
@@ -620,7 +622,9 @@ int make_plan(const gnn_loop_args_t &a, void *ws, Plan &p, bool validate_ptrs) {
     // hub segments: virtual rows for padded widths up to 128; wider states walk the plain adjacency (the un-fused aggregate
     // handles any degree), so the caller may always pass the split
     p.n_heavy = (a.n_heavy_segments > 0 && p.SP <= 128) ? a.n_heavy_segments : 0;
-    p.buf[0] = c.take<float>((size_t)(p.N + p.n_heavy) * p.SP + 64);
+    // composite groups: the staging rows of the one-CU-per-group kernel in position order, every (group, type) range padded to 16 rows
+    const size_t pad_rows = (p.composite && a.n_groups > 0) ? (size_t)15 * p.T * a.n_groups : 0;
+    p.buf[0] = c.take<float>((size_t)(p.N + p.n_heavy + pad_rows) * p.SP + 64);
     p.buf[1] = c.take<float>((size_t)(p.N + p.n_heavy) * p.SP + 64);
     p.agg = c.take<float>((size_t)p.N * p.SP);
     p.Wx = c.take<float>((p.SP > 128 && p.S <= 256) ? gnn::xwide_weight_floats(p.S, p.SP) : 0);
@@ -633,6 +637,7 @@ int make_plan(const gnn_loop_args_t &a, void *ws, Plan &p, bool validate_ptrs) {
     p.out_nodes = c.take<float>((size_t)p.M * p.Tout);
     p.idx_src = c.take<int>(std::max(p.M, 1));
     p.idx_dst = c.take<int>(std::max(p.M, 1));
+    p.tbeg = c.take<int>((p.composite && a.n_groups > 0) ? (size_t)p.T * ((size_t)a.n_groups + 1) : 0);
     p.bytes = (c.off + 255) & ~(size_t)255;
 
     // ---- per-type first-layer layout ----
@@ -1188,6 +1193,46 @@ int loop_lds(const gnn_loop_args_t &a, const Plan &p, hipStream_t st) {
     return rc;
 }
 
+// ... of a heterogeneous model (kernel_state_lds_types.hpp): every type's state network one Dense layer; the largest group must fit with
+// every (group, type) range padded to 16 rows - decided from the shapes alone (type_nodes is a device array): rows <= n_g + 15 n_types.
+bool lds_types_applies(const gnn_loop_args_t &a, const Plan &p) {
+    const int pinned = (a.flags & GNN_FLAG_FUSED_GEN_MASK) >> 4;
+    static int env = -1;
+    if (env < 0) { const char *e = getenv("GNN_FUSED_KERNEL"); env = e ? atoi(e) : 0; }
+    if ((pinned != 0 && pinned != 7) || (pinned == 0 && env != 0 && env != 7)) return false;
+    if (p.n_groups < 1 || !p.composite || p.T < 1 || p.T > GNN_MAX_TYPES || p.n_heavy != 0 || a.n_heavy_segments > 0 || a.nodes_src) return false;
+    if (a.max_iteration < 1 || (p.SP != 16 && p.SP != 32) || (a.flags & GNN_FLAG_UNFUSED)) return false;
+    for (int t = 0; t < p.T; ++t)
+        if (a.net_state[t].n_layers != 1 || a.net_state[t].activation[0] == GNN_ACT_SOFTMAX || (int)a.net_state[t].units[0] != p.S) return false;
+    if (p.has_sets && p.n_groups > device_cus()) return false;      // groups that wait for each other must all be resident
+    if ((size_t)(p.N + (size_t)15 * p.T * p.n_groups) * p.SP * 4 >= ((size_t)1 << 32)) return false;      // the staging rows: 32-bit byte offsets
+    return gnn::lds_types_group_fits(p.group_max_nodes, p.T, p.SP);
+}
+
+int loop_lds_types(const gnn_loop_args_t &a, const Plan &p, hipStream_t st) {
+    gnn::LdsTypesArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    gnn::LdsArgs &la = ta.l;
+    la.node_begin = p.d_group_tabs;
+    la.set_first = p.d_group_tabs + 2 * (p.n_groups + 1); la.set_size = p.d_group_tabs + 3 * (p.n_groups + 1);
+    la.set_bar = p.has_sets ? p.set_bar : nullptr;
+    la.pred0 = p.pred0;
+    la.rowptr = a.adjacency.rowptr; la.src = a.adjacency.src; la.w = a.adjacency.w; la.row_scale = a.adjacency.row_scale;
+    la.state0 = a.state_dim > 0 ? a.state0 : a.nodes; la.ld_s0 = a.state_dim > 0 ? p.S : a.ld_nodes;
+    la.C = p.C; la.ldC = p.ldC;
+    la.S = p.S; la.max_iteration = a.max_iteration; la.no_exit = (a.flags & GNN_FLAG_NO_EARLY_EXIT) != 0;
+    la.thr = a.state_threshold;
+    la.stage = p.buf[0];
+    la.state_out = a.state_out; la.k_out = a.k_out;
+    ta.n_types = p.T; ta.n_groups = p.n_groups;
+    ta.type_nodes = a.type_nodes; ta.tbeg = p.tbeg;
+    for (int t = 0; t < p.T; ++t)
+        ta.tp[t] = gnn::LdsTypeNet{p.tp[t].Wf, p.tp[t].wrow_state, p.tp[t].wrow_agg, (int)a.net_state[t].activation[0]};
+    const int rc = gnn::launch_lds_types(ta, p.SP, p.group_max_nodes, st);
+    if (rc == 1) return fail("LDS-resident loop kernel (types): launch failed (%s)", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
 // 0: un-fused kernels; 1: any fused kernel; 2: two-layer state networks - only the wave-specialised kernel and the
 // persistent whole-loop kernel carry the second Dense; 3: state width 65 .. 128 - the wide kernel, whatever generation is pinned.
 int fusable(const gnn_loop_args_t &a, const Plan &p) {
@@ -1331,6 +1376,39 @@ size_t gnn_loop_workspace_bytes(const gnn_loop_args_t *args) {
     return p.bytes;
 }
 
+// The tables of a one-CU-per-group launch on the device: group_node_begin / 64-node-tile offsets / first group and size of every group's set.
+static int upload_group_tabs(const gnn_loop_args_t &a, const Plan &p, hipStream_t st) {
+    // the group tables go to the device through a pinned staging buffer of this thread (an asynchronous copy out of pageable
+    // memory would have to outlive this call); its event says when the previous call's copy has left it
+    static thread_local struct { int *buf; size_t cap; hipEvent_t ev; } stage = {nullptr, 0, nullptr};
+    const size_t n_tab = 4 * ((size_t)p.n_groups + 1);
+    if (stage.ev) HIP_OK(hipEventSynchronize(stage.ev));
+    else HIP_OK(hipEventCreateWithFlags(&stage.ev, hipEventDisableTiming));
+    if (stage.cap < n_tab) {
+        if (stage.buf) HIP_OK(hipHostFree(stage.buf));
+        stage.buf = nullptr; stage.cap = 0;
+        HIP_OK(hipHostMalloc((void **)&stage.buf, std::max<size_t>(n_tab, 4096) * sizeof(int), hipHostMallocDefault));
+        stage.cap = std::max<size_t>(n_tab, 4096);
+    }
+    int *tabs = stage.buf;
+    int tiles = 0;
+    for (int g = 0; g <= p.n_groups; ++g) {
+        tabs[g] = a.group_node_begin[g];
+        tabs[p.n_groups + 1 + g] = tiles;
+        tabs[2 * (p.n_groups + 1) + g] = g; tabs[3 * (p.n_groups + 1) + g] = 1;       // its own set unless listed below
+        if (g < p.n_groups) tiles += (a.group_node_begin[g + 1] - a.group_node_begin[g] + 63) / 64;
+    }
+    for (int s2 = 0; s2 < a.n_group_sets; ++s2)
+        for (int g = a.group_set_begin[s2]; g < a.group_set_begin[s2 + 1]; ++g) {
+            tabs[2 * (p.n_groups + 1) + g] = a.group_set_begin[s2];
+            tabs[3 * (p.n_groups + 1) + g] = a.group_set_begin[s2 + 1] - a.group_set_begin[s2];
+        }
+    HIP_OK(hipMemcpyAsync(p.d_group_tabs, tabs, n_tab * sizeof(int), hipMemcpyHostToDevice, st));
+    if (p.has_sets) HIP_OK(hipMemsetAsync(p.set_bar, 0, sizeof(unsigned long long) * 2 * (size_t)p.n_groups, st));
+    HIP_OK(hipEventRecord(stage.ev, st));
+    return 0;
+}
+
 int gnn_loop_forward(const gnn_loop_args_t *args) {
     if (!args) return fail("args is NULL");
     const gnn_loop_args_t &a = *args;
@@ -1345,40 +1423,34 @@ int gnn_loop_forward(const gnn_loop_args_t *args) {
     const int fz = fusable(a, p);
     // Groups that fit the LDS of one CU: set-up launch, one workgroup per group, output stage.
     if (p.n_groups > 0 && fz == 1 && lds_applies(a, p) && setup_small_applies(a, p)) {
-        // the group tables go to the device through a pinned staging buffer of this thread (an asynchronous copy out of pageable
-        // memory would have to outlive this call); its event says when the previous call's copy has left it
-        static thread_local struct { int *buf; size_t cap; hipEvent_t ev; } stage = {nullptr, 0, nullptr};
-        const size_t n_tab = 4 * ((size_t)p.n_groups + 1);
-        if (stage.ev) HIP_OK(hipEventSynchronize(stage.ev));
-        else HIP_OK(hipEventCreateWithFlags(&stage.ev, hipEventDisableTiming));
-        if (stage.cap < n_tab) {
-            if (stage.buf) HIP_OK(hipHostFree(stage.buf));
-            stage.buf = nullptr; stage.cap = 0;
-            HIP_OK(hipHostMalloc((void **)&stage.buf, std::max<size_t>(n_tab, 4096) * sizeof(int), hipHostMallocDefault));
-            stage.cap = std::max<size_t>(n_tab, 4096);
-        }
-        int *tabs = stage.buf;
-        int tiles = 0;
-        for (int g = 0; g <= p.n_groups; ++g) {
-            tabs[g] = a.group_node_begin[g];
-            tabs[p.n_groups + 1 + g] = tiles;
-            tabs[2 * (p.n_groups + 1) + g] = g; tabs[3 * (p.n_groups + 1) + g] = 1;       // its own set unless listed below
-            if (g < p.n_groups) tiles += (a.group_node_begin[g + 1] - a.group_node_begin[g] + 63) / 64;
-        }
-        for (int s2 = 0; s2 < a.n_group_sets; ++s2)
-            for (int g = a.group_set_begin[s2]; g < a.group_set_begin[s2 + 1]; ++g) {
-                tabs[2 * (p.n_groups + 1) + g] = a.group_set_begin[s2];
-                tabs[3 * (p.n_groups + 1) + g] = a.group_set_begin[s2 + 1] - a.group_set_begin[s2];
-            }
-        HIP_OK(hipMemcpyAsync(p.d_group_tabs, tabs, n_tab * sizeof(int), hipMemcpyHostToDevice, st));
-        if (p.has_sets) HIP_OK(hipMemsetAsync(p.set_bar, 0, sizeof(unsigned long long) * 2 * (size_t)p.n_groups, st));
-        HIP_OK(hipEventRecord(stage.ev, st));
+        TRY(upload_group_tabs(a, p, st));
         Plan q = p;
         q.gt.n = 0;                                 // the set-up kernel reads the device tables
         TRY(setup_small(a, q, st));
         if (a.ev_loop_begin) HIP_OK(hipEventRecord((hipEvent_t)a.ev_loop_begin, st));
         const int rc = loop_lds(a, p, st);
         if (rc != 0) return rc == 2 ? fail("LDS-resident loop kernel does not cover this shape") : 1;
+        if (a.ev_loop_end) HIP_OK(hipEventRecord((hipEvent_t)a.ev_loop_end, st));
+        return output_stage(a, p, st);
+    }
+    // ... of a heterogeneous model: the general set-up (constants per type), the type-begin table and state_0's predicate per group, then
+    // one workgroup per group on the typed kernel.  Nothing else runs composite groups: what is not covered fails here, before any launch.
+    if (p.n_groups > 0 && p.composite) {
+        if (fz != 1 || !lds_types_applies(a, p))
+            return fail("convergence groups of a composite graph need the one-CU-per-group kernel (gnn_loop_groups_supported() != 2 for these args)");
+        TRY(upload_group_tabs(a, p, st));
+        TRY(setup_constants(a, p, st, /*zero_loop_words=*/true));
+        HIP_OK(hipMemsetAsync(a.k_out, 0, sizeof(float) * (size_t)p.n_groups, st));
+        gnn::TypeOffsets to;
+        for (int t = 0; t <= GNN_MAX_TYPES; ++t) to.off[t] = a.type_offsets[std::min(t, p.T)];
+        gnn::k_group_type_begin<<<cdiv(p.T * (p.n_groups + 1), 256), 256, 0, st>>>(a.type_nodes, to, p.T, p.d_group_tabs, p.n_groups, p.tbeg);
+        LAUNCH_OK();
+        gnn::k_pred0_groups<<<p.n_groups, 256, 0, st>>>(p.d_group_tabs, a.state_dim > 0 ? a.state0 : a.nodes, a.state_dim > 0 ? p.S : a.ld_nodes, p.S,
+                                                        a.state_threshold, p.pred0);
+        LAUNCH_OK();
+        if (a.ev_loop_begin) HIP_OK(hipEventRecord((hipEvent_t)a.ev_loop_begin, st));
+        const int rc = loop_lds_types(a, p, st);
+        if (rc != 0) return rc == 2 ? fail("LDS-resident loop kernel does not cover these convergence groups") : 1;
         if (a.ev_loop_end) HIP_OK(hipEventRecord((hipEvent_t)a.ev_loop_end, st));
         return output_stage(a, p, st);
     }
@@ -1460,9 +1532,21 @@ int gnn_loop_groups_supported(const gnn_loop_args_t *args) {
     Plan p;
     if (make_plan(*args, nullptr, p, false)) return 0;
     const int fz = fusable(*args, p);
+    if (p.composite) return fz == 1 && lds_types_applies(*args, p) ? 2 : 0;      // (the spread form: homogeneous models only)
     if (fz == 1 && lds_applies(*args, p) && setup_small_applies(*args, p)) return 2;
     if (args->n_groups > GNN_MAX_GROUPS) return 0;
     return fz != 0 && !state_softmax(*args, p) && persistent_applies(*args, p) && setup_small_applies(*args, p) ? 1 : 0;
+}
+
+int gnn_loop_group_max_nodes(const gnn_loop_args_t *args) {
+    if (!args) return 0;
+    gnn_loop_args_t a = *args;
+    a.n_groups = 0; a.group_node_begin = nullptr; a.n_group_sets = 0; a.group_set_begin = nullptr;      // (shapes only: any tables)
+    Plan p;
+    if (make_plan(a, nullptr, p, false)) return 0;
+    if (p.SP != 16 && p.SP != 32) return 0;
+    if (p.composite) return gnn::lds_types_max_nodes(p.T, p.SP);
+    return (int)std::min<size_t>(gnn::LDS_BUDGET_BYTES / gnn::lds_state_bytes(1, p.SP), 65535);
 }
 
 int gnn_aggregate(const gnn_csr_t *csr, const float *X, int32_t ldx, int32_t F, float *out, int32_t ldo, void *stream) {

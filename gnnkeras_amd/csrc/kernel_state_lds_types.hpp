@@ -1,0 +1,424 @@
+// The one-CU-per-group whole-loop kernel (kernel_state_lds.hpp) for HETEROGENEOUS models: one state network per node type
+// (gnn_loop_args_t::composite with group_node_begin).  k_state_lds feeds the matrix core with the folded first-layer weights as the A
+// operand and 16 node rows as the B operand of v_mfma_f32_16x16x4_f32, so the 16 rows of a tile share ONE weight matrix: with a network
+// per type a tile must hold rows of one type only.
+//
+//   * the group's state sits in LDS in POSITION order: the rows of type 0 first, then type 1, .. - each (group, type) range padded to a
+//     multiple of 16 rows.  A group is a contiguous node range and type t's row list (type_nodes) is ascending, so the rows of type t in
+//     group g are the slice type_nodes[tbeg[t][g] .. tbeg[t][g + 1]) (k_group_type_begin, shared with the training-mode group kernels).
+//     positions <= n_g + 15 n_types: what the host's "fits" test and the staging rows are sized by;
+//   * Orig[position] = local node id (-1: pad row), Inv[local node] = position, both in LDS: the neighbour ids of the per-node record are
+//     translated to positions when the records are built, the ids of rows with more than 4 arcs (read from the CSR) as they are read;
+//   * pad rows are zero, are never a neighbour, never enter the predicate and are not written back;
+//   * a wave owns a CONTIGUOUS run of tiles and holds the weights of its current tile's type in registers: they are reloaded (from L2,
+//     32 dwords per lane at width 32) only when the walk crosses into another type - at most n_types - 1 + 16 reloads per iteration over
+//     the whole workgroup, none at all in a group of one type.  (All types' blocks in LDS instead would take 8 KB per type at width 32 and
+//     one LDS read per weight register and TILE: 32 ds_read_b32 against the tile's 32 MFMAs.);
+//   * the per-node constant C (setup_constants writes it per type, indexed by node), state_0 and the per-arc weights are read by original
+//     node id; the result goes back to state_out in node order;
+//   * predicate, activation (per type), no_exit, k, group sets, the double-buffered form: as in k_state_lds.  state_0's predicate comes
+//     from k_pred0_groups, one word per GROUP (the arithmetic of k_converge, row by row).
+#pragma once
+#include "kernel_state_lds.hpp"
+
+namespace gnn {
+
+struct TypeOffsets { int off[GNN_MAX_TYPES + 1]; };
+
+// tbeg[t][g] = first position in type_nodes, at or behind type t's begin, whose node id is >= gbeg[g]
+__global__ void __launch_bounds__(256)
+k_group_type_begin(const int *__restrict__ type_nodes, TypeOffsets to, int n_types, const int *__restrict__ gbeg, int G, int *__restrict__ tbeg) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_types * (G + 1)) return;
+    const int t = i / (G + 1), g = i % (G + 1);
+    const int key = gbeg[g];
+    int lo = to.off[t], hi = to.off[t + 1];
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (type_nodes[mid] < key) lo = mid + 1; else hi = mid; }
+    tbeg[i] = lo;
+}
+
+// pred0[g] = does any node of group g still move between state_old = ones and state_0?  (16 lanes per node, as k_converge)
+__global__ void __launch_bounds__(256)
+k_pred0_groups(const int *__restrict__ node_begin, const float *__restrict__ s, int ld_s, int S, float thr, int *__restrict__ pred0) {
+    const int g = blockIdx.x, nb = node_begin[g], ne = node_begin[g + 1];
+    const int lane = threadIdx.x & 15;
+    int any = 0;
+    for (int j0 = nb; j0 < ne; j0 += 16) {
+        const int j = j0 + threadIdx.x / 16;
+        float d2 = 0.0f, n2 = 0.0f;
+        if (j < ne) {
+            for (int f = lane; f < S; f += 16) {
+                const float d = s[(size_t)j * ld_s + f] - 1.0f;
+                d2 = fmaf(d, d, d2);
+                n2 = fmaf(1.0f, 1.0f, n2);
+            }
+        }
+#pragma unroll
+        for (int off = 8; off >= 1; off >>= 1) {
+            d2 += __shfl_xor(d2, off, 16);
+            n2 += __shfl_xor(n2, off, 16);
+        }
+        if (j < ne && sqrtf(d2) > thr * sqrtf(n2)) any = 1;
+    }
+    any = __syncthreads_or(any);
+    if (threadIdx.x == 0) pred0[g] = any;
+}
+
+constexpr unsigned LDS_TYPES_NO_ROW = 0xFFFFu;      // a record's neighbour id for an arc whose source is not a row of the group
+
+struct LdsTypeNet { const float *Wf; int wrow_state, wrow_agg, act; };
+
+struct LdsTypesArgs {
+    LdsArgs l;                      // as for k_state_lds; unused: tile64_begin, Wf, wrow_*, H, act.  pred0: one word per GROUP
+    LdsTypeNet tp[GNN_MAX_TYPES];
+    int n_types;
+    const int *type_nodes;          // device [N]: node ids grouped by type, ascending inside a type
+    const int *tbeg;                // device [n_types][n_groups + 1] (k_group_type_begin)
+    int n_groups;
+};
+
+// LDS of a group of n nodes in at most `rows` positions: state rows (twice: DB), records, Orig per position; Inv per node
+inline int lds_types_rows(int n_nodes, int n_types) { return n_nodes + 15 * n_types; }
+inline size_t lds_types_bytes(int n_nodes, int n_types, int SP, bool db = false) {
+    return (size_t)lds_types_rows(n_nodes, n_types) * ((db ? 2 : 1) * SP * sizeof(float) + sizeof(LdsRec) + sizeof(int)) + (size_t)n_nodes * sizeof(int);
+}
+inline bool lds_types_group_fits(int n_nodes, int n_types, int SP) {
+    return lds_types_bytes(n_nodes, n_types, SP) <= LDS_BUDGET_BYTES && lds_types_rows(n_nodes, n_types) < 65536;
+}
+inline bool lds_types_group_fits_twice(int n_nodes, int n_types, int SP) { return lds_types_bytes(n_nodes, n_types, SP, true) <= LDS_BUDGET_BYTES; }
+// the largest group (in nodes) that fits
+inline int lds_types_max_nodes(int n_types, int SP) {
+    const size_t per_row = SP * sizeof(float) + sizeof(LdsRec) + sizeof(int), fixed = (size_t)15 * n_types * per_row;
+    if (fixed >= LDS_BUDGET_BYTES) return 0;
+    return (int)((LDS_BUDGET_BYTES - fixed) / (per_row + sizeof(int)));
+}
+
+template <int SP, bool HAS_W, bool DB>
+__global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds_types(LdsTypesArgs ta) {
+    constexpr int NQ = SP / 16;
+    constexpr int NCT = SP / 16;
+    constexpr int KS = 2 * SP / 4;
+    constexpr int CPB = 5;
+    extern __shared__ __attribute__((aligned(16))) char smem_lds[];
+    __shared__ int moving_s[3];
+    __shared__ int set_go;
+    __shared__ int pb_s[GNN_MAX_TYPES + 1];       // first position of every type (multiples of 16); [n_types] = positions of the group
+    __shared__ int cnt_s[GNN_MAX_TYPES];          // rows of every type in this group
+    __shared__ int tb_s[GNN_MAX_TYPES];           // ... and where they begin in type_nodes
+    __shared__ LdsTypeNet net_s[GNN_MAX_TYPES];
+
+    const LdsArgs &a = ta.l;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, g = lane >> 4;
+    const int grp = blockIdx.x;
+    const int nb = a.node_begin[grp], ne = a.node_begin[grp + 1], n = ne - nb;
+    const int S = a.S, T = ta.n_types;
+
+    // ---- the group's rows per type, their positions --------------------------------------------------------------------------------------
+#pragma unroll
+    for (int t = 0; t < GNN_MAX_TYPES; ++t)
+        if (tid == t && t < T) {
+            const int b0 = ta.tbeg[t * (ta.n_groups + 1) + grp], b1 = ta.tbeg[t * (ta.n_groups + 1) + grp + 1];
+            tb_s[t] = b0; cnt_s[t] = b1 - b0;
+            net_s[t] = ta.tp[t];
+        }
+    if (tid == 0) { moving_s[0] = 0; moving_s[1] = 0; moving_s[2] = 0; }
+    __syncthreads();
+    if (tid == 0) {
+        int p0 = 0;
+        for (int t = 0; t < T; ++t) { pb_s[t] = p0; p0 += (cnt_s[t] + 15) & ~15; }
+        pb_s[T] = p0;
+    }
+    __syncthreads();
+    const int P = pb_s[T];                        // positions of this group (<= n + 15 T), a multiple of 16
+    if (P > n + 15 * T) {                         // type lists that name a node twice: more rows than LDS and staging are sized for
+        if (tid == 0) a.k_out[grp] = -1.0e9f;
+        return;
+    }
+    const int n_tiles = P >> 4;
+    float *St = reinterpret_cast<float *>(smem_lds);                                 // [P][SP] (DB: two of them)
+    LdsRec *Rec = reinterpret_cast<LdsRec *>(St + (size_t)(DB ? 2 : 1) * P * SP);    // [P]
+    int *Orig = reinterpret_cast<int *>(Rec + P);                                    // [P]: local node of a position, -1 = pad row
+    int *Inv = Orig + P;                                                             // [n]: position of a local node
+    float *const St_base = St;
+
+    for (int i = tid; i < n; i += 64 * LDS_NW) Inv[i] = 0;      // (a node that no type lists: never a row; as a neighbour it reads position 0)
+    __syncthreads();
+    for (int t = 0; t < T; ++t) {
+        const int p0 = pb_s[t], c = cnt_s[t], b0 = tb_s[t], cp = (c + 15) & ~15;
+        for (int i = tid; i < cp; i += 64 * LDS_NW) {
+            int j = -1;
+            if (i < c) {
+                const unsigned l = (unsigned)(ta.type_nodes[b0 + i] - nb);
+                if (l < (unsigned)n) { j = (int)l; Inv[j] = p0 + i; }
+            }
+            Orig[p0 + i] = j;
+        }
+    }
+    __syncthreads();
+    // ---- state_0 and the CSR records into LDS, by position ----------------------------------------------------------------------------------
+    for (int i = tid; i < P * SP; i += 64 * LDS_NW) {
+        const int ps = i / SP, c = i % SP, j = Orig[ps];
+        St[i] = (j >= 0 && c < S) ? a.state0[(size_t)(nb + j) * a.ld_s0 + c] : 0.0f;
+        if (DB) St[(size_t)P * SP + i] = 0.0f;
+    }
+    for (int ps = tid; ps < P; ps += 64 * LDS_NW) {
+        const int j = Orig[ps];
+        LdsRec rec = LdsRec{0u, 0u, 0, 1.0f};
+        if (j >= 0) {
+            const int beg = a.rowptr[nb + j], end = a.rowptr[nb + j + 1];
+            unsigned id[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const unsigned l = beg + u < end ? (unsigned)(a.src[beg + u] - nb) : 0u;
+                id[u] = beg + u >= end ? 0u : (l < (unsigned)n ? (unsigned)Inv[l] : LDS_TYPES_NO_ROW);      // (positions stay below 65535)
+            }
+            rec = LdsRec{id[0] | (id[1] << 16), id[2] | (id[3] << 16), end - beg, a.row_scale ? a.row_scale[nb + j] : 1.0f};
+        }
+        Rec[ps] = rec;
+    }
+    const int set_lo = a.set_bar ? a.set_first[grp] : grp, set_n = a.set_bar ? a.set_size[grp] : 1;
+    unsigned moved_seen[2] = {0u, 0u};
+    int timed_out = 0;
+    int run = a.no_exit;
+    if (!run) {
+        int v = 0;
+        for (int i = set_lo + lane; i < set_lo + set_n; i += 64) v |= a.pred0[i];
+        run = __any(v != 0);
+    }
+    __syncthreads();
+
+    // rows of the staging buffer: group g's begin behind the padded sizes of the groups before it (bounded by 15 n_types each)
+    const __amdgpu_buffer_rsrc_t r_C = buf_rsrc(a.C + (size_t)nb * a.ldC), r_stage = buf_rsrc(a.stage + ((size_t)nb + (size_t)15 * T * grp) * SP);
+    auto load_c = [&](int t, f32x4 *c) {            // C of tile t by original node: row Orig[16 t + r], columns 16 ct + 4 g ..
+        const int j = Orig[16 * t + r];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) {
+            const int col = 16 * ct + 4 * g;
+            c[ct] = buf_ld_f32x4(r_C, (j >= 0 && col < S) ? ((unsigned)j * (unsigned)a.ldC + (unsigned)col) * 4u : BUF_OFF);
+        }
+    };
+
+    // a wave's tiles: a contiguous run, so that it crosses from one type into the next as rarely as possible
+    const int per = (n_tiles + LDS_NW - 1) / LDS_NW;
+    const int t_lo = min(wave * per, n_tiles), t_hi = min(t_lo + per, n_tiles);
+    float wreg[KS][NCT];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) wreg[ks][ct] = 0.0f;
+    int cur_ty = -1, act = 0;
+
+    int k_done = 0;
+    for (int it = 0; run && it < a.max_iteration; ++it) {
+        float *Snew = St_base;
+        if (DB) { St = St_base + (size_t)(it & 1) * P * SP; Snew = St_base + (size_t)((it + 1) & 1) * P * SP; }
+        f32x4 cn[NCT];
+        int any = 0;
+        if (t_lo < t_hi) load_c(t_lo, cn);
+#pragma unroll 1
+        for (int t = t_lo; t < t_hi; ++t) {
+            f32x4 c[NCT];
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) c[ct] = cn[ct];
+            if (t + 1 < t_hi) load_c(t + 1, cn);
+            // the tile's type (wave-uniform): the weights change hands only when it differs from the previous tile's
+            int ty = 0;
+            for (int u = 1; u < T; ++u) ty += (16 * t >= pb_s[u]) ? 1 : 0;
+            ty = __builtin_amdgcn_readfirstlane(ty);
+            if (ty != cur_ty) {
+                cur_ty = ty;
+                const LdsTypeNet nt = net_s[ty];
+                const float *Wf = static_cast<const float *>(uniform_ptr(nt.Wf));
+                const int ws = __builtin_amdgcn_readfirstlane(nt.wrow_state), wa = __builtin_amdgcn_readfirstlane(nt.wrow_agg);
+                act = __builtin_amdgcn_readfirstlane(nt.act);
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    const int half = ks / (SP / 4), qe = ks % (SP / 4);
+                    const int kcol = 16 * (qe / 4) + 4 * g + (qe & 3);
+#pragma unroll
+                    for (int ct = 0; ct < NCT; ++ct) {
+                        const int ncol = 16 * ct + r;
+                        wreg[ks][ct] = (kcol < S && ncol < S) ? Wf[(size_t)((half ? wa : ws) + kcol) * S + ncol] : 0.0f;
+                    }
+                }
+            }
+            const int ps = 16 * t + r;                                         // position of this lane's row
+            const int jo = Orig[ps];
+            const bool on = jo >= 0;
+            const LdsRec rec = Rec[ps];                                        // (pad rows: degree 0)
+            f32x4 own[NQ], agg[NQ];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                own[q] = on ? *reinterpret_cast<const f32x4 *>(St + ps * SP + 16 * q + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
+                agg[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
+            const unsigned ids4[4] = {rec.id01 & 0xFFFFu, rec.id01 >> 16, rec.id23 & 0xFFFFu, rec.id23 >> 16};
+            float w4[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+            if (HAS_W && on) {
+                const int b0 = a.rowptr[nb + jo];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) w4[u] = u < rec.deg ? a.w[b0 + u] : 0.0f;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (u < rec.deg && ids4[u] != LDS_TYPES_NO_ROW) {               // (an arc from outside the group adds nothing)
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) {
+                        const f32x4 x = *reinterpret_cast<const f32x4 *>(St + ids4[u] * SP + 16 * q + 4 * g);
+                        if (HAS_W) agg[q] += w4[u] * x; else agg[q] += x;
+                    }
+                }
+            }
+            if (__any(rec.deg > 4)) {                                          // rows with more than 4 arcs: the rest from the CSR in global memory
+                const int b0 = on ? a.rowptr[nb + jo] : 0, e1 = b0 + rec.deg;
+                for (int e = b0 + 4; __any(e < e1); e += 4) {
+                    int id[4]; float wv[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const bool ok = e + u < e1;
+                        const unsigned l = ok ? (unsigned)(a.src[e + u] - nb) : 0u;
+                        const bool in = ok && l < (unsigned)n;
+                        id[u] = in ? Inv[l] : 0;
+                        wv[u] = in ? (HAS_W ? a.w[e + u] : 1.0f) : 0.0f;
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        if (e + u < e1) {
+#pragma unroll
+                            for (int q = 0; q < NQ; ++q) {
+                                const f32x4 x = *reinterpret_cast<const f32x4 *>(St + id[u] * SP + 16 * q + 4 * g);
+                                agg[q] += wv[u] * x;                           // (wv = 0: an arc from outside the group adds nothing)
+                            }
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) agg[q] *= rec.scale;
+            f32x4 c2[NCT];
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) c2[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int qe = 0; qe < SP / 4; ++qe) {
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct) {
+                    c[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[qe][ct], own[qe / 4][qe & 3], c[ct], 0, 0, 0);
+                    c2[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[SP / 4 + qe][ct], agg[qe / 4][qe & 3], c2[ct], 0, 0, 0);
+                }
+            }
+            float d2 = 0.0f, n2 = 0.0f;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+                f32x4 v = c[ct] + c2[ct];
+                activate4(act, v);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[e] = (on && 16 * ct + 4 * g + e < S) ? v[e] : 0.0f;      // pad rows stay zero
+                    const float o = own[ct][e], d = v[e] - o;
+                    d2 = fmaf(d, d, d2); n2 = fmaf(o, o, n2);
+                }
+                if (DB) {
+                    *reinterpret_cast<f32x4 *>(Snew + ps * SP + 16 * ct + 4 * g) = v;
+                } else {
+                    const u32x4 bits = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+                    __builtin_amdgcn_raw_buffer_store_b128(bits, r_stage, (int)(((unsigned)ps * SP + 16u * ct + 4u * g) * 4u), 0, 0);
+                }
+            }
+            d2 += __shfl_xor(d2, 16, 64); d2 += __shfl_xor(d2, 32, 64);
+            n2 += __shfl_xor(n2, 16, 64); n2 += __shfl_xor(n2, 32, 64);
+            if (on && sqrtf(d2) > a.thr * sqrtf(n2)) any = 1;
+        }
+        int mv_slot = it & 1;
+        if (DB) {
+            mv_slot = it % 3;
+            if (any) moving_s[mv_slot] = 1;
+            __syncthreads();
+            if (tid == 0) moving_s[(it + 2) % 3] = 0;
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (tid == 0) moving_s[(it + 1) & 1] = 0;
+            if (any) moving_s[it & 1] = 1;
+            {
+                const __amdgpu_buffer_rsrc_t rs = r_stage;
+                const int total = P * (SP / 4);
+                for (int i0 = tid; i0 < total; i0 += 64 * LDS_NW * CPB) {
+                    u32x4 v[CPB];
+#pragma unroll
+                    for (int u = 0; u < CPB; ++u) {
+                        const int i = i0 + u * 64 * LDS_NW;
+                        v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, i < total ? i * 16 : (int)BUF_OFF, 0, 16);
+                    }
+#pragma unroll
+                    for (int u = 0; u < CPB; ++u) {
+                        const int i = i0 + u * 64 * LDS_NW;
+                        if (i < total) *reinterpret_cast<u32x4 *>(St + 4 * i) = v[u];
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        if (DB) St = Snew;
+        k_done = it + 1;
+        if (set_n > 1) {
+            if (tid == 0) {
+                unsigned long long *ctr = a.set_bar + 2 * set_lo + (it & 1);
+                __hip_atomic_fetch_add(ctr, 1ull + ((unsigned long long)(moving_s[mv_slot] ? 1u : 0u) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const unsigned target = (unsigned)(it / 2 + 1) * (unsigned)set_n;
+                unsigned long long v = 0;
+                if (!wait_until(a.wait_ticks, [&]() { v = __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return (unsigned)v >= target; }))
+                    timed_out = 1;
+                const unsigned moved = (unsigned)(v >> 32);
+                set_go = timed_out ? -1 : ((moved != moved_seen[it & 1]) ? 1 : 0);
+                moved_seen[it & 1] = moved;
+            }
+            __syncthreads();
+            if (set_go < 0) break;
+            if (!a.no_exit && set_go == 0) break;
+        } else if (!a.no_exit && moving_s[mv_slot] == 0) break;
+    }
+    // ---- result rows to the caller's compact buffer in node order, k of this group ------------------------------------------------------
+    for (int i = tid; i < P * S; i += 64 * LDS_NW) {
+        const int ps = i / S, c = i % S, j = Orig[ps];
+        if (j >= 0) a.state_out[(size_t)(nb + j) * S + c] = St[ps * SP + c];
+    }
+    if (tid == 0) a.k_out[grp] = timed_out ? -1.0e9f : (float)k_done;
+}
+
+template <int SP, bool HAS_W, bool DB>
+int launch_lds_types_one(const LdsTypesArgs &la_in, size_t lds_bytes, hipStream_t st) {
+    static bool attr = false;
+    if (!attr) {
+        if (hipFuncSetAttribute((const void *)k_state_lds_types<SP, HAS_W, DB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET_BYTES) != hipSuccess) return 1;
+        attr = true;
+    }
+    LdsTypesArgs la = la_in;
+    la.l.wait_ticks = wait_ticks();
+    if (la.l.set_bar) {          // groups of a set wait for each other: every workgroup of the launch must be resident at once
+        int dev = 0, n_cu = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 1;
+        if (!persistent_fits((const void *)k_state_lds_types<SP, HAS_W, DB>, 64 * LDS_NW, lds_bytes, la.n_groups, n_cu)) return 2;
+    }
+    GNN_SET_KERNEL_NAME("k_state_lds_types<%d,%s,%s>", SP, HAS_W ? "true" : "false", DB ? "true" : "false");
+    k_state_lds_types<SP, HAS_W, DB><<<la.n_groups, 64 * LDS_NW, lds_bytes, st>>>(la);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+// max_nodes: nodes of the largest group (every workgroup requests LDS for its bound of positions)
+inline int launch_lds_types(const LdsTypesArgs &la, int SP, int max_nodes, hipStream_t st) {
+    const bool db = lds_types_group_fits_twice(max_nodes, la.n_types, SP);
+    const size_t bytes = std::max<size_t>(lds_types_bytes(max_nodes, la.n_types, SP, db), 90 * 1024);      // one workgroup per CU either way
+#define LDS_TYPES_CASE(SPV)                                                                                                        \
+    case SPV:                                                                                                                      \
+        if (db) return la.l.w ? launch_lds_types_one<SPV, true, true>(la, bytes, st) : launch_lds_types_one<SPV, false, true>(la, bytes, st); \
+        return la.l.w ? launch_lds_types_one<SPV, true, false>(la, bytes, st) : launch_lds_types_one<SPV, false, false>(la, bytes, st);
+    switch (SP) {
+        LDS_TYPES_CASE(16)
+        LDS_TYPES_CASE(32)
+        default: return 2;
+    }
+#undef LDS_TYPES_CASE
+}
+
+}  // namespace gnn

@@ -18,23 +18,13 @@
 // fits next to a 256-row state at width 64 (138 KB), eight do not.  A group whose rows are all of one type loads it once.
 #pragma once
 #include "kernels_train_group.hpp"
+#include "kernel_state_lds_types.hpp"
 
 namespace gnn {
 
 constexpr int GROUP_TYPES_MAX_KC = 64;   // constant input columns of one type's network (labels of the type + aggregated component)
 
-struct TypeOffsets { int off[GNN_MAX_TYPES + 1]; };
-
-__global__ void __launch_bounds__(256)
-k_group_type_begin(const int *__restrict__ type_nodes, TypeOffsets to, int n_types, const int *__restrict__ gbeg, int G, int *__restrict__ tbeg) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_types * (G + 1)) return;
-    const int t = i / (G + 1), g = i % (G + 1);
-    const int key = gbeg[g];
-    int lo = to.off[t], hi = to.off[t + 1];
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (type_nodes[mid] < key) lo = mid + 1; else hi = mid; }
-    tbeg[i] = lo;
-}
+// (TypeOffsets and k_group_type_begin: kernel_state_lds_types.hpp - the inference groups of heterogeneous models build the same table)
 
 // ---- constants ---------------------------------------------------------------------------------------------------------------------------
 struct GroupTypeNet {

@@ -250,15 +250,33 @@ void mlp_shape_of(gnn_mlp_t &m, at::IntArrayRef spec, const char *name) {
     for (int l = 0; l < m.n_layers; ++l) { m.units[l] = (int32_t)spec[3 + l]; m.activation[l] = (int32_t)spec[3 + m.n_layers + l]; }
 }
 
+// dims and state network shapes of a homogeneous (`type_dim_label` empty) or composite call: `net_state_spec` holds one spec per type in a row
+void fill_shape(gnn_loop_args_t &a, int64_t n_nodes, int64_t dim_node_label, int64_t dim_arc_label, at::IntArrayRef net_state_spec,
+                at::IntArrayRef type_dim_label) {
+    a.abi_version = GNN_ABI_VERSION;
+    a.n_nodes = (int32_t)n_nodes; a.dim_node_label = (int32_t)dim_node_label; a.dim_arc_label = (int32_t)dim_arc_label;
+    const int T = (int)type_dim_label.size();
+    TORCH_CHECK(T <= GNN_MAX_TYPES, "at most ", GNN_MAX_TYPES, " node types");
+    a.composite = T > 0; a.n_types = T > 0 ? T : 1;
+    size_t pos = 0;
+    for (int t = 0; t < a.n_types; ++t) {
+        TORCH_CHECK(net_state_spec.size() >= pos + 3, "net_state: ", a.n_types, " spec(s) expected");
+        const size_t len = 3 + 2 * (size_t)std::max<int64_t>(net_state_spec[pos + 2], 0);
+        TORCH_CHECK(net_state_spec.size() >= pos + len, "net_state: malformed spec");
+        mlp_shape_of(a.net_state[t], net_state_spec.slice(pos, len), "net_state");
+        pos += len;
+        if (a.composite) a.type_dim_label[t] = (int32_t)type_dim_label[t];
+    }
+    TORCH_CHECK(pos == net_state_spec.size(), "net_state: surplus spec entries");
+    if (a.composite) a.type_offsets[T] = a.n_nodes;      // (only the span is looked at without device arrays)
+}
+
 // May `loop_forward(..., group_node_begin)` run these batches as independent loops of one call?  (shapes only, no tensors)
 int64_t loop_groups_supported(int64_t n_nodes, int64_t dim_node_label, int64_t dim_arc_label, at::IntArrayRef net_state_spec,
                            at::IntArrayRef net_output_spec, int64_t state_dim, int64_t max_iteration, int64_t focus, int64_t flags,
-                           int64_t n_out, at::IntArrayRef group_node_begin, at::IntArrayRef group_set_begin) {
+                           int64_t n_out, at::IntArrayRef group_node_begin, at::IntArrayRef group_set_begin, at::IntArrayRef type_dim_label) {
     gnn_loop_args_t a{};
-    a.abi_version = GNN_ABI_VERSION;
-    a.n_nodes = (int32_t)n_nodes; a.dim_node_label = (int32_t)dim_node_label; a.dim_arc_label = (int32_t)dim_arc_label;
-    a.n_types = 1;
-    mlp_shape_of(a.net_state[0], net_state_spec, "net_state");
+    fill_shape(a, n_nodes, dim_node_label, dim_arc_label, net_state_spec, type_dim_label);
     mlp_shape_of(a.net_output, net_output_spec, "net_output");
     a.state_dim = (int32_t)state_dim; a.max_iteration = (int32_t)max_iteration; a.focus = (int32_t)focus; a.flags = (int32_t)flags;
     a.n_out = (int32_t)n_out;
@@ -268,6 +286,16 @@ int64_t loop_groups_supported(int64_t n_nodes, int64_t dim_node_label, int64_t d
     std::vector<int32_t> sets(group_set_begin.begin(), group_set_begin.end());
     if (sets.size() >= 2) { a.group_set_begin = sets.data(); a.n_group_sets = (int32_t)sets.size() - 1; }
     return gnn_loop_groups_supported(&a);
+}
+
+// Nodes of the largest group the one-CU-per-group form holds for these shapes (gnn_loop_group_max_nodes)
+int64_t loop_group_max_nodes(int64_t dim_node_label, int64_t dim_arc_label, at::IntArrayRef net_state_spec, at::IntArrayRef net_output_spec,
+                             int64_t state_dim, int64_t max_iteration, int64_t focus, at::IntArrayRef type_dim_label) {
+    gnn_loop_args_t a{};
+    fill_shape(a, 0, dim_node_label, dim_arc_label, net_state_spec, type_dim_label);
+    mlp_shape_of(a.net_output, net_output_spec, "net_output");
+    a.state_dim = (int32_t)state_dim; a.max_iteration = (int32_t)max_iteration; a.focus = (int32_t)focus;
+    return gnn_loop_group_max_nodes(&a);
 }
 
 at::Tensor aggregate(const OptTensorList &csr, at::IntArrayRef dims, const at::Tensor &X) {
@@ -417,7 +445,9 @@ TORCH_LIBRARY(gnnkeras, m) {
     m.def("loop_xc_applies(int n_nodes, int dim_node_label, int dim_arc_label, int[] net_state_spec, int[] net_output_spec, int state_dim, "
           "int max_iteration, int focus, int flags, int n_out, bool per_arc_weights, int n_heavy_segments) -> int", &loop_xc_applies);
     m.def("loop_groups_supported(int n_nodes, int dim_node_label, int dim_arc_label, int[] net_state_spec, int[] net_output_spec, "
-          "int state_dim, int max_iteration, int focus, int flags, int n_out, int[] group_node_begin, int[] group_set_begin=[]) -> int", &loop_groups_supported);
+          "int state_dim, int max_iteration, int focus, int flags, int n_out, int[] group_node_begin, int[] group_set_begin=[], int[] type_dim_label=[]) -> int", &loop_groups_supported);
+    m.def("loop_group_max_nodes(int dim_node_label, int dim_arc_label, int[] net_state_spec, int[] net_output_spec, int state_dim, int max_iteration, "
+          "int focus, int[] type_dim_label=[]) -> int", &loop_group_max_nodes);
     m.def("aggregate(Tensor?[] csr, int[] dims, Tensor X) -> Tensor");
     m.def("pool(Tensor?[] nodegraph, int[] dims, Tensor out_nodes) -> Tensor");
     m.def("converged(Tensor state, Tensor? state_old, float threshold) -> Tensor");

@@ -263,7 +263,8 @@ class DataParallel:
         a plan: batch i to rank i % world)."""
         m = self.model
         n = len(sequencer)
-        plan = m._group_plan(sequencer, device) if n > 1 else None
+        # (composite models keep the batch-by-batch walk here: their grouped launches are planned for one GPU only)
+        plan = m._group_plan(sequencer, device) if n > 1 and not isinstance(getattr(m, 'net_state', None), (list, tuple)) else None
         owner = self._owner_of(n, plan)
         my_batches = [i for i in range(n) if owner[i] == self.rank]
         my_launches = None if plan is None else [plan[li] for li in range(len(plan)) if li % self.world == self.rank]

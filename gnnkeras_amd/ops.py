@@ -108,15 +108,30 @@ def loop_xc_applies(n_nodes, dim_node_label, dim_arc_label, net_state, net_outpu
                                        int(focus), int(flags), int(n_out), bool(w), int(heavy['n_seg']) if heavy is not None else 0))
 
 
+def _state_specs(net_state):
+    """The shape spec of one `Sequential`, or of the per-type list of a composite model, one after the other."""
+    ss = []
+    for n_ in (list(net_state) if isinstance(net_state, (list, tuple)) else [net_state]): ss += net_args(n_, None, shape_only=True)[1]
+    return ss
+
+
 def loop_groups_supported(n_nodes, dim_node_label, dim_arc_label, net_state, net_output, state_dim, max_iteration, focus, flags,
-                          n_out, groups, group_sets=None):
+                          n_out, groups, group_sets=None, type_dims=None):
     """May these merged batches run as independent loops of ONE call?  0 no, 1 spread over the CUs (<= 32 groups), 2 one CU
-    per group with its state in LDS (any number of groups).  (shapes only: include/gnnloop.h, gnn_loop_groups_supported)"""
-    _, ss = net_args(net_state, None, shape_only=True)
+    per group with its state in LDS (any number of groups).  (shapes only: include/gnnloop.h, gnn_loop_groups_supported)
+    Composite models: `net_state` = the per-type list, `type_dims` = the label width of every type; the answer is 2 or 0."""
     _, os_ = net_args(net_output, None, shape_only=True)
-    return int(load().loop_groups_supported(int(n_nodes), int(dim_node_label), int(dim_arc_label), ss, os_, int(state_dim),
+    return int(load().loop_groups_supported(int(n_nodes), int(dim_node_label), int(dim_arc_label), _state_specs(net_state), os_, int(state_dim),
                                              int(max_iteration), int(focus), int(flags), int(n_out), [int(v) for v in groups],
-                                             [int(v) for v in group_sets] if group_sets is not None else []))
+                                             [int(v) for v in group_sets] if group_sets is not None else [],
+                                             [int(v) for v in type_dims] if type_dims is not None else []))
+
+
+def loop_group_max_nodes(dim_node_label, dim_arc_label, net_state, net_output, state_dim, max_iteration, focus, type_dims=None):
+    """Nodes of the largest group the one-CU-per-group form holds for these shapes (include/gnnloop.h, gnn_loop_group_max_nodes)."""
+    _, os_ = net_args(net_output, None, shape_only=True)
+    return int(load().loop_group_max_nodes(int(dim_node_label), int(dim_arc_label), _state_specs(net_state), os_, int(state_dim),
+                                            int(max_iteration), int(focus), [int(v) for v in type_dims] if type_dims is not None else []))
 
 
 def aggregate(csr, X):

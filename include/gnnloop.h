@@ -160,6 +160,7 @@ typedef struct gnn_loop_args {
      * once - each group has its own predicate, its own iteration counter (k_out is [n_groups]) and stops on its own -
      * so many small batches fill the GPU in one launch instead of one underfilled launch each.  Results per group equal
      * a separate call on that batch alone.  Supported where the whole-loop kernel applies (gnn_loop_groups_supported);
+     * composite (heterogeneous) models: the one-CU-per-group form only, one workgroup per group with typed rows;
      * everything before and after the loop (constants, output network, pooling) is per node / per graph anyway. */
     const int32_t *group_node_begin;   /* HOST array [n_groups + 1], ascending, [0] = 0, [n_groups] = n_nodes         */
     int32_t n_groups;                  /* see gnn_loop_groups_supported                                                */
@@ -212,11 +213,18 @@ int gnn_loop_forward(const gnn_loop_args_t *args);
 int gnn_loop_xc_applies(const gnn_loop_args_t *args);
 /* Non-zero when gnn_loop_forward accepts these args with n_groups > 0, else 0 (the caller then runs one call per batch).
  *   2: every group's state fits the LDS of one CU (nodes_g * padded width * 4 <= 156 KB, width <= 32, one-layer state network):
- *      one workgroup per group, any number of groups up to GNN_MAX_GROUPS_RESIDENT - the more the better, 256 run at once;
+ *      one workgroup per group, any number of groups up to GNN_MAX_GROUPS_RESIDENT - the more the better, 256 run at once.
+ *      Composite models (composite != 0, 1 .. GNN_MAX_TYPES types) get this answer or 0: every type's state network one layer of
+ *      the state's width and not softmax, padded width 16 or 32, no hub rows, no nodes_src, max_iteration >= 1, not GNN_FLAG_UNFUSED,
+ *      and the largest group fits with every type's rows padded to 16: nodes_g <= gnn_loop_group_max_nodes();
  *   1: homogeneous model, one- or two-layer state network of width <= 64, at most GNN_MAX_GROUPS groups whose 64-node tiles are
  *      all resident at once: sum_g ceil(nodes_g / 64) <= CUs.
  * Reads dims, flags and the host group array only. */
 int gnn_loop_groups_supported(const gnn_loop_args_t *args);
+/* The largest group, in nodes, the one-CU-per-group form (answer 2 above) holds for a call of these shapes (state width, composite,
+ * n_types; the group tables of `args` are not read); 0 when the padded state width is neither 16 nor 32.  It shrinks with the number
+ * of node types of a composite model: a group's rows are sorted by type and every type's range is padded to 16 rows. */
+int gnn_loop_group_max_nodes(const gnn_loop_args_t *args);
 
 /* out[j, 0:F] = sum_{e in row j} w_e * X[src_e, 0:F]   == tf.sparse.sparse_dense_matmul(A, X, adjoint_a=True)
  * (ArcNode scatter-add GNN.py:254, label aggregate :258, state aggregate :228, graph pooling :345). */
