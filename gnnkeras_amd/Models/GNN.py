@@ -404,7 +404,7 @@ class _LoopModel:
             # the loop's condition (group sets): still ONE launch, and no batch is left to the spread form
             parts = {}
             S_w = self.state_vect_dim if self.state_vect_dim > 0 else L
-            limit = (158 * 1024) // (4 * (16 if S_w <= 16 else 32) + 16)          # kernel_state_lds.hpp: LDS_BUDGET_BYTES / (row + CSR record)
+            limit = ops.loop_group_max_nodes(L, A, self.net_state, self.net_output, self.state_vect_dim, self.max_iteration, focus)
             for b in rest:
                 if b in fits: continue
                 cut = self._cut_batch(sequencer, b, limit)

@@ -1160,34 +1160,45 @@ int loop_mid(const gnn_loop_args_t &a, const Plan &p, const float *first, float 
     return rc;
 }
 
-// Groups whose whole state fits the LDS of one CU: one workgroup per group, no grid barrier (kernel_state_lds.hpp).
-bool lds_applies(const gnn_loop_args_t &a, const Plan &p) {
+// Groups whose whole state fits the LDS of one CU: one workgroup per group, no grid barrier (kernel_state_lds.hpp, generation 7).
+// May this call take that form, by its pinned generation / GNN_FUSED_KERNEL?
+bool lds_generation_allowed(const gnn_loop_args_t &a) {
     const int pinned = (a.flags & GNN_FLAG_FUSED_GEN_MASK) >> 4;
     static int env = -1;
     if (env < 0) { const char *e = getenv("GNN_FUSED_KERNEL"); env = e ? atoi(e) : 0; }
-    if ((pinned != 0 && pinned != 7) || (pinned == 0 && env != 0 && env != 7)) return false;
+    return !((pinned != 0 && pinned != 7) || (pinned == 0 && env != 0 && env != 7));
+}
+
+bool lds_applies(const gnn_loop_args_t &a, const Plan &p) {
+    if (!lds_generation_allowed(a)) return false;
     if (p.n_groups < 1 || p.composite || p.n_heavy != 0 || a.max_iteration < 1 || (p.SP != 16 && p.SP != 32)) return false;
     if (a.net_state[0].n_layers != 1 || a.net_state[0].activation[0] == GNN_ACT_SOFTMAX || (a.flags & GNN_FLAG_UNFUSED)) return false;
     if (p.has_sets && p.n_groups > device_cus()) return false;      // groups that wait for each other must all be resident
     return gnn::lds_group_fits(p.group_max_nodes, p.SP);
 }
 
-int loop_lds(const gnn_loop_args_t &a, const Plan &p, hipStream_t st) {
-    gnn::LdsArgs la;
-    memset(&la, 0, sizeof(la));
-    la.node_begin = p.d_group_tabs; la.tile64_begin = p.d_group_tabs + (p.n_groups + 1);
+// what both one-CU-per-group kernels are told alike (la: zeroed); tile64_begin and the state network(s) are the caller's
+void fill_lds_args(gnn::LdsArgs &la, const gnn_loop_args_t &a, const Plan &p) {
+    la.node_begin = p.d_group_tabs;
     la.set_first = p.d_group_tabs + 2 * (p.n_groups + 1); la.set_size = p.d_group_tabs + 3 * (p.n_groups + 1);
     la.set_bar = p.has_sets ? p.set_bar : nullptr;
     la.pred0 = p.pred0;
     la.rowptr = a.adjacency.rowptr; la.src = a.adjacency.src; la.w = a.adjacency.w; la.row_scale = a.adjacency.row_scale;
     la.state0 = a.state_dim > 0 ? a.state0 : a.nodes; la.ld_s0 = a.state_dim > 0 ? p.S : a.ld_nodes;
     la.C = p.C; la.ldC = p.ldC;
-    la.Wf = p.tp[0].Wf; la.wrow_state = p.tp[0].wrow_state; la.wrow_agg = p.tp[0].wrow_agg;
-    la.H = a.net_state[0].units[0]; la.act = a.net_state[0].activation[0];
     la.S = p.S; la.max_iteration = a.max_iteration; la.no_exit = (a.flags & GNN_FLAG_NO_EARLY_EXIT) != 0;
     la.thr = a.state_threshold;
     la.stage = p.buf[0];
     la.state_out = a.state_out; la.k_out = a.k_out;
+}
+
+int loop_lds(const gnn_loop_args_t &a, const Plan &p, hipStream_t st) {
+    gnn::LdsArgs la;
+    memset(&la, 0, sizeof(la));
+    fill_lds_args(la, a, p);
+    la.tile64_begin = p.d_group_tabs + (p.n_groups + 1);
+    la.Wf = p.tp[0].Wf; la.wrow_state = p.tp[0].wrow_state; la.wrow_agg = p.tp[0].wrow_agg;
+    la.H = a.net_state[0].units[0]; la.act = a.net_state[0].activation[0];
     const int rc = gnn::launch_lds(la, p.SP, p.n_groups, p.group_max_nodes, st);
     if (rc == 1) return fail("LDS-resident loop kernel: launch failed (%s)", hipGetErrorString(hipGetLastError()));
     return rc;
@@ -1196,10 +1207,7 @@ int loop_lds(const gnn_loop_args_t &a, const Plan &p, hipStream_t st) {
 // ... of a heterogeneous model (kernel_state_lds_types.hpp): every type's state network one Dense layer; the largest group must fit with
 // every (group, type) range padded to 16 rows - decided from the shapes alone (type_nodes is a device array): rows <= n_g + 15 n_types.
 bool lds_types_applies(const gnn_loop_args_t &a, const Plan &p) {
-    const int pinned = (a.flags & GNN_FLAG_FUSED_GEN_MASK) >> 4;
-    static int env = -1;
-    if (env < 0) { const char *e = getenv("GNN_FUSED_KERNEL"); env = e ? atoi(e) : 0; }
-    if ((pinned != 0 && pinned != 7) || (pinned == 0 && env != 0 && env != 7)) return false;
+    if (!lds_generation_allowed(a)) return false;
     if (p.n_groups < 1 || !p.composite || p.T < 1 || p.T > GNN_MAX_TYPES || p.n_heavy != 0 || a.n_heavy_segments > 0 || a.nodes_src) return false;
     if (a.max_iteration < 1 || (p.SP != 16 && p.SP != 32) || (a.flags & GNN_FLAG_UNFUSED)) return false;
     for (int t = 0; t < p.T; ++t)
@@ -1212,18 +1220,7 @@ bool lds_types_applies(const gnn_loop_args_t &a, const Plan &p) {
 int loop_lds_types(const gnn_loop_args_t &a, const Plan &p, hipStream_t st) {
     gnn::LdsTypesArgs ta;
     memset(&ta, 0, sizeof(ta));
-    gnn::LdsArgs &la = ta.l;
-    la.node_begin = p.d_group_tabs;
-    la.set_first = p.d_group_tabs + 2 * (p.n_groups + 1); la.set_size = p.d_group_tabs + 3 * (p.n_groups + 1);
-    la.set_bar = p.has_sets ? p.set_bar : nullptr;
-    la.pred0 = p.pred0;
-    la.rowptr = a.adjacency.rowptr; la.src = a.adjacency.src; la.w = a.adjacency.w; la.row_scale = a.adjacency.row_scale;
-    la.state0 = a.state_dim > 0 ? a.state0 : a.nodes; la.ld_s0 = a.state_dim > 0 ? p.S : a.ld_nodes;
-    la.C = p.C; la.ldC = p.ldC;
-    la.S = p.S; la.max_iteration = a.max_iteration; la.no_exit = (a.flags & GNN_FLAG_NO_EARLY_EXIT) != 0;
-    la.thr = a.state_threshold;
-    la.stage = p.buf[0];
-    la.state_out = a.state_out; la.k_out = a.k_out;
+    fill_lds_args(ta.l, a, p);
     ta.n_types = p.T; ta.n_groups = p.n_groups;
     ta.type_nodes = a.type_nodes; ta.tbeg = p.tbeg;
     for (int t = 0; t < p.T; ++t)
@@ -1545,8 +1542,7 @@ int gnn_loop_group_max_nodes(const gnn_loop_args_t *args) {
     Plan p;
     if (make_plan(a, nullptr, p, false)) return 0;
     if (p.SP != 16 && p.SP != 32) return 0;
-    if (p.composite) return gnn::lds_types_max_nodes(p.T, p.SP);
-    return (int)std::min<size_t>(gnn::LDS_BUDGET_BYTES / gnn::lds_state_bytes(1, p.SP), 65535);
+    return p.composite ? gnn::lds_types_max_nodes(p.T, p.SP) : gnn::lds_max_nodes(p.SP);
 }
 
 int gnn_aggregate(const gnn_csr_t *csr, const float *X, int32_t ldx, int32_t F, float *out, int32_t ldo, void *stream) {

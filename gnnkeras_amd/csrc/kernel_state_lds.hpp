@@ -26,6 +26,10 @@
 //     registers, the new rows leave as 16-byte stores: a quarter of the epilogue's instructions (it was two thirds of an iteration);
 //   * predicate, activation and iteration count as everywhere else; k_out[g] is written once at the end.
 // Used when every group fits (n_g * (4 SP + 16) <= LDS_BUDGET_BYTES), SP is 16 or 32 and the state network has one layer.
+//
+// The body of the loop is written ONCE, as __forceinline__ pieces over a compile-time row policy (below: lds_fill_wreg, lds_load_c, lds_tile,
+// lds_iter_end, lds_leaves): k_state_lds here and k_state_lds_types (kernel_state_lds_types.hpp, one state network per node type) are a
+// prologue, a walk over tiles and a result copy around them, and both launch through launch_lds_family.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernel_state_fused2.hpp"
@@ -69,15 +73,237 @@ __device__ __forceinline__ float row16_sum_to_lane15(float x) {
 // One node's CSR row as the loop needs it, 16 bytes in LDS: in-degree, row scale, the first 4 source ids (local, 16 bit each).
 struct LdsRec { unsigned id01, id23; int deg; float scale; };
 
+// ---- The pieces both one-CU-per-group kernels are made of: k_state_lds below and k_state_lds_types (kernel_state_lds_types.hpp).  The two
+// differ only in which LDS row holds which node; a ROW POLICY (compile time, no branch on "which kernel am I") says so:
+//     PAD_ROWS           LDS rows that are no node exist (and stay zero); otherwise such rows are not memory of the state at all
+//     ALL_ARCS_ARE_ROWS  every arc's source is a row of the group; otherwise a packed id may be LDS_NO_ROW and the CSR tail masks by weight
+//     node(row)          local node of an LDS row (what rowptr / w / C / state0 / state_out are indexed by, behind the group's begin)
+//     on(row, node)      is the row a node at all?
+//     has_row(l)         is local node id l (from the CSR; any integer) a row of this group?
+//     row_of(l)          ... and which one
+struct LdsRowsLocal {           // k_state_lds: LDS row = local node.  Rows at or past n are the Rec array: never read as state, never written
+    static constexpr bool PAD_ROWS = false, ALL_ARCS_ARE_ROWS = true;
+    int n;
+    __device__ __forceinline__ int node(int row) const { return row; }
+    __device__ __forceinline__ bool on(int row, int) const { return row < n; }
+    __device__ __forceinline__ bool has_row(int) const { return true; }
+    __device__ __forceinline__ int row_of(int l) const { return l; }
+};
+constexpr unsigned LDS_NO_ROW = 0xFFFFu;            // a record's neighbour id for an arc whose source is not a row of the group
+
+// W1 as B fragments in registers: k-step (half, q, e) supplies column kcol = 16 q + 4 g + e of that half.  `ld`: the folded block's row
+// stride and column bound
+template <int SP>
+__device__ __forceinline__ void lds_fill_wreg(float (&wreg)[2 * SP / 4][SP / 16], const float *Wf, int wrow_state, int wrow_agg, int S, int ld, int r, int g) {
+#pragma unroll
+    for (int ks = 0; ks < 2 * SP / 4; ++ks) {
+        const int half = ks / (SP / 4), qe = ks % (SP / 4);
+        const int kcol = 16 * (qe / 4) + 4 * g + (qe & 3);
+#pragma unroll
+        for (int ct = 0; ct < SP / 16; ++ct) {
+            const int ncol = 16 * ct + r;
+            wreg[ks][ct] = (kcol < S && ncol < ld) ? Wf[(size_t)((half ? wrow_agg : wrow_state) + kcol) * ld + ncol] : 0.0f;
+        }
+    }
+}
+
+// the per-node constant C of one tile row, row-major: local node j (`on`: there is one), columns 16 ct + 4 g .. + 3 below `cols`
+template <int SP>
+__device__ __forceinline__ void lds_load_c(f32x4 (&c)[SP / 16], __amdgpu_buffer_rsrc_t r_C, bool on, int j, int cols, int ldC, int g) {
+#pragma unroll
+    for (int ct = 0; ct < SP / 16; ++ct) {
+        const int col = 16 * ct + 4 * g;
+        c[ct] = buf_ld_f32x4(r_C, (on && col < cols) ? ((unsigned)j * (unsigned)ldC + (unsigned)col) * 4u : BUF_OFF);
+    }
+}
+
+// does the loop run at all?  state_0's predicate words [lo, hi) of the group (or of its whole set)
+__device__ __forceinline__ int lds_run0(const LdsArgs &a, int lo, int hi, int lane) {
+    if (a.no_exit) return a.no_exit;
+    int v = 0;
+    for (int i = lo + lane; i < hi; i += 64) v |= a.pred0[i];
+    return __any(v != 0);
+}
+
+// One 16-row tile of an iteration: lane (r, g) of the wave updates LDS row 16 t + r.  c: the tile's constant C on entry (lds_load_c);
+// wreg / act: the weights and activation of the tile's rows; St: the state this iteration reads; the new rows go to Snew (DB) or to
+// the staging rows behind r_stage.  Sets `any` when a row of the tile still moves.
+template <int SP, bool HAS_W, bool DB, class Rows>
+__device__ __forceinline__ void lds_tile(const LdsArgs &a, const Rows &rows, int nb, int t, int r, int g, const float *St, float *Snew, const LdsRec *Rec,
+                                         __amdgpu_buffer_rsrc_t r_stage, const float (&wreg)[2 * SP / 4][SP / 16], f32x4 (&c)[SP / 16], int act, int &any) {
+    constexpr int NQ = SP / 16;                   // 16-byte chunks of a row owned by one lane
+    constexpr int NCT = SP / 16;                  // 16-column output tiles
+    const int S = a.S;
+    const int row = 16 * t + r;                                            // LDS row of this lane
+    const int jn = rows.node(row);                                         // ... and its local node
+    const bool on = rows.on(row, jn);
+    const bool mem = Rows::PAD_ROWS || on;                                 // the row exists in LDS and in the staging buffer (pad rows: degree 0)
+    const LdsRec rec = mem ? Rec[row] : LdsRec{0u, 0u, 0, 1.0f};
+    // own row chunks and the neighbour sum, both in fragment order
+    f32x4 own[NQ], agg[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        own[q] = on ? *reinterpret_cast<const f32x4 *>(St + row * SP + 16 * q + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        agg[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    const unsigned ids4[4] = {rec.id01 & 0xFFFFu, rec.id01 >> 16, rec.id23 & 0xFFFFu, rec.id23 >> 16};
+    float w4[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+    if (HAS_W && on) {
+        const int b0 = a.rowptr[nb + jn];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) w4[u] = u < rec.deg ? a.w[b0 + u] : 0.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        if (u < rec.deg && (Rows::ALL_ARCS_ARE_ROWS || ids4[u] != LDS_NO_ROW)) {      // (an arc from outside the group adds nothing)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const f32x4 x = *reinterpret_cast<const f32x4 *>(St + ids4[u] * SP + 16 * q + 4 * g);
+                if (HAS_W) agg[q] += w4[u] * x; else agg[q] += x;
+            }
+        }
+    }
+    if (__any(rec.deg > 4)) {                                              // rows with more than 4 arcs: the rest from the CSR in global memory
+        const int b0 = on ? a.rowptr[nb + jn] : 0, e1 = b0 + rec.deg;
+        for (int e = b0 + 4; __any(e < e1); e += 4) {
+            int id[4]; float wv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const bool ok = e + u < e1;
+                const int l = ok ? a.src[e + u] - nb : 0;
+                const bool in = ok && rows.has_row(l);
+                id[u] = in ? rows.row_of(l) : 0;
+                wv[u] = in ? (HAS_W ? a.w[e + u] : 1.0f) : 0.0f;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (e + u < e1) {
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) {
+                        const f32x4 x = *reinterpret_cast<const f32x4 *>(St + id[u] * SP + 16 * q + 4 * g);
+                        if (HAS_W || !Rows::ALL_ARCS_ARE_ROWS) agg[q] += wv[u] * x;      // (wv = 0: an arc from outside the group adds nothing)
+                        else agg[q] += x;
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) agg[q] *= rec.scale;
+    // two independent MFMA chains per column tile: the state half accumulates onto C, the agg half onto zero, summed at the end.
+    // Operands swapped (weights = A, rows = B): the result is row-major - lane (r, g) gets columns 16 ct + 4 g .. + 3 of row r.
+    f32x4 c2[NCT];
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct) c2[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int qe = 0; qe < SP / 4; ++qe) {
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) {
+            c[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[qe][ct], own[qe / 4][qe & 3], c[ct], 0, 0, 0);
+            c2[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[SP / 4 + qe][ct], agg[qe / 4][qe & 3], c2[ct], 0, 0, 0);
+        }
+    }
+    // activation + predicate against the old row chunks (still in registers); the new rows leave for the other buffer / the staging buffer
+    float d2 = 0.0f, n2 = 0.0f;
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct) {
+        f32x4 v = c[ct] + c2[ct];
+        activate4(act, v);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            v[e] = (on && 16 * ct + 4 * g + e < S) ? v[e] : 0.0f;          // pad columns - and pad rows - stay zero
+            const float o = own[ct][e], d = v[e] - o;
+            d2 = fmaf(d, d, d2); n2 = fmaf(o, o, n2);
+        }
+        if (DB) {
+            if (mem) *reinterpret_cast<f32x4 *>(Snew + row * SP + 16 * ct + 4 * g) = v;
+        } else {
+            const u32x4 bits = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+            __builtin_amdgcn_raw_buffer_store_b128(bits, r_stage, mem ? (int)(((unsigned)row * SP + 16u * ct + 4u * g) * 4u) : (int)BUF_OFF, 0, 0);
+        }
+    }
+    d2 += __shfl_xor(d2, 16, 64); d2 += __shfl_xor(d2, 32, 64);            // the four lane groups of a row
+    n2 += __shfl_xor(n2, 16, 64); n2 += __shfl_xor(n2, 32, 64);
+    if (on && sqrtf(d2) > a.thr * sqrtf(n2)) any = 1;
+}
+
+// The end of iteration `it`, after a wave's last tile: publishes `any` in moving_s (workgroup-shared, zero before the loop), makes the
+// `rows` new rows the state of the next iteration (single-buffered: staged rows back into St) and returns the word of moving_s that
+// says - to every thread, after the barriers in here - whether some node of the group still moves.
+template <int SP, bool DB>
+__device__ __forceinline__ int lds_iter_end(int *moving_s, int any, int it, float *St, __amdgpu_buffer_rsrc_t r_stage, int rows, int tid) {
+    constexpr int CPB = 5;                        // 16-byte chunks a thread copies back per trip (all in flight together)
+    if (DB) {
+        // three rotating flag words: iteration it sets [it % 3] before the barrier and reads it after; the word of iteration it + 2
+        // is cleared after this barrier - its last readers (iteration it - 1) are behind every wave, its next writers two barriers away
+        const int mv_slot = it % 3;
+        if (any) moving_s[mv_slot] = 1;                                    // benign race: every writer stores 1
+        __syncthreads();                                                   // new rows complete, old rows no longer read
+        if (tid == 0) moving_s[(it + 2) % 3] = 0;
+        return mv_slot;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // this wave's staged rows are in L2
+    __syncthreads();                                                       // every wave is done reading the old state
+    // two flag words: the one of the NEXT iteration is cleared here - every wave has read it (end of the previous iteration)
+    // before it arrived at the barrier above, and the barrier below orders the clear before the next iteration's stores
+    if (tid == 0) moving_s[(it + 1) & 1] = 0;
+    if (any) moving_s[it & 1] = 1;                                         // benign race: every writer stores 1
+    // staged rows back into LDS: sc1 loads, served by the L2 the stores went to (the CU's L1 may still hold last iteration's
+    // lines of the staging buffer).  All of a thread's loads are issued before the first is stored (they are independent;
+    // one at a time they cost a round trip to L2 each: up to nine per iteration).
+    const int total = rows * (SP / 4);
+    for (int i0 = tid; i0 < total; i0 += 64 * LDS_NW * CPB) {
+        u32x4 v[CPB];
+#pragma unroll
+        for (int u = 0; u < CPB; ++u) {
+            const int i = i0 + u * 64 * LDS_NW;
+            v[u] = __builtin_amdgcn_raw_buffer_load_b128(r_stage, i < total ? i * 16 : (int)BUF_OFF, 0, 16);
+        }
+#pragma unroll
+        for (int u = 0; u < CPB; ++u) {
+            const int i = i0 + u * 64 * LDS_NW;
+            if (i < total) *reinterpret_cast<u32x4 *>(St + 4 * i) = v[u];
+        }
+    }
+    __syncthreads();
+    return it & 1;
+}
+
+// Does the group leave the loop after iteration `it`?  The groups [set_lo, set_lo + set_n) of a set leave together: one flag exchange per
+// iteration.  moved_seen (zero before the loop) / timed_out (a wait has expired: reported through k): thread 0's memory of the exchange.
+// (uniform per workgroup; called by every thread: barriers inside)
+__device__ __forceinline__ bool lds_leaves(const LdsArgs &a, const int *moving_s, int *set_go, int mv_slot, int it, int set_lo, int set_n,
+                                           unsigned (&moved_seen)[2], int &timed_out, int tid) {
+    if (set_n > 1) {
+        // one 64-bit add carries this group's arrival and "some node of mine still moves"; the set's total tells every member
+        // whether ANY of them moves (k_state_small's grid barrier, over the set's few workgroups and without any state rows)
+        if (tid == 0) {
+            unsigned long long *ctr = a.set_bar + 2 * set_lo + (it & 1);
+            __hip_atomic_fetch_add(ctr, 1ull + ((unsigned long long)(moving_s[mv_slot] ? 1u : 0u) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned target = (unsigned)(it / 2 + 1) * (unsigned)set_n;
+            unsigned long long v = 0;
+            if (!wait_until(a.wait_ticks, [&]() { v = __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return (unsigned)v >= target; }))
+                timed_out = 1;                                             // a member never arrived (not resident?): reported through k
+            const unsigned moved = (unsigned)(v >> 32);
+            *set_go = timed_out ? -1 : ((moved != moved_seen[it & 1]) ? 1 : 0);
+            moved_seen[it & 1] = moved;
+        }
+        __syncthreads();
+        // an expired wait ends this group's loop at once: its result is void (k < 0), and waiting out the bound again in each of the
+        // remaining iterations would hold the CU - and every member queued behind it - for max_iteration x the bound
+        if (*set_go < 0) return true;
+        return !a.no_exit && *set_go == 0;
+    }
+    return !a.no_exit && moving_s[mv_slot] == 0;                           // uniform: read after the barrier
+}
+
 // DB (round 3): the group's state fits LDS TWICE (n (8 SP + 16) <= 158 KB: 594 nodes at 32-wide rows - what the planner's balanced
 // cuts produce when there are CUs to spare): iteration it reads buffer it & 1 and writes the other one with 16-byte LDS stores.
 // No staging buffer in L2, no store drain, no copy back, ONE workgroup barrier per iteration instead of two.
 template <int SP, bool HAS_W, bool DB>
 __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds(LdsArgs a) {
-    constexpr int NQ = SP / 16;                   // 16-byte chunks of a row owned by one lane
     constexpr int NCT = SP / 16;                  // 16-column output tiles
     constexpr int KS = 2 * SP / 4;                // MFMA k-steps over [state | agg]
-    constexpr int CPB = 5;                        // 16-byte chunks a thread copies back per trip (all in flight together)
     extern __shared__ __attribute__((aligned(16))) char smem_lds[];
     __shared__ int moving_s[3];                   // "some node of this group still moves": iteration it uses [it % 3] (DB) / [it & 1]
     __shared__ int set_go;                        // group sets: does any group of the set still move?
@@ -91,19 +317,10 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds(LdsArgs a) {
     float *St = reinterpret_cast<float *>(smem_lds);                        // [n][SP] (DB: two of them, iteration it reads the one at (it & 1) n SP)
     LdsRec *Rec = reinterpret_cast<LdsRec *>(St + (size_t)(DB ? 2 : 1) * n * SP);   // [n]
     float *const St_base = St;
+    const LdsRowsLocal rows{n};
 
-    // ---- W1 as B fragments in registers: k-step (half, q, e) supplies column kcol = 16 q + 4 g + e of that half ----------------
-    float wreg[KS][NCT];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-        const int half = ks / (SP / 4), qe = ks % (SP / 4);
-        const int kcol = 16 * (qe / 4) + 4 * g + (qe & 3);
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) {
-            const int ncol = 16 * ct + r;
-            wreg[ks][ct] = (kcol < S && ncol < a.H) ? a.Wf[(size_t)((half ? a.wrow_agg : a.wrow_state) + kcol) * a.H + ncol] : 0.0f;
-        }
-    }
+    float wreg[KS][NCT];                                                    // the one state network's W1: loaded once
+    lds_fill_wreg<SP>(wreg, a.Wf, a.wrow_state, a.wrow_agg, S, a.H, r, g);
     // ---- state_0 and the CSR records into LDS ------------------------------------------------------------------------------------------
     for (int i = tid; i < n * SP; i += 64 * LDS_NW) {
         const int j = i / SP, c = i % SP;
@@ -117,29 +334,17 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds(LdsArgs a) {
         Rec[j] = LdsRec{id[0] | (id[1] << 16), id[2] | (id[3] << 16), end - beg, a.row_scale ? a.row_scale[nb + j] : 1.0f};
     }
     if (tid == 0) { moving_s[0] = 0; moving_s[1] = 0; moving_s[2] = 0; }
-    // the groups of a set leave the loop together: state_0's predicate over the tiles of the whole set, one flag exchange per iteration
+    // the groups of a set leave the loop together: state_0's predicate over the 64-node tiles of the whole set
     const int set_lo = a.set_bar ? a.set_first[grp] : grp, set_n = a.set_bar ? a.set_size[grp] : 1;
     unsigned moved_seen[2] = {0u, 0u};
     int timed_out = 0;
-    int run = a.no_exit;
-    if (!run) {
-        const int t0 = a.tile64_begin[set_lo], t1 = a.tile64_begin[set_lo + set_n];
-        int v = 0;
-        for (int i = t0 + lane; i < t1; i += 64) v |= a.pred0[i];
-        run = __any(v != 0);
-    }
+    const int run = lds_run0(a, a.tile64_begin[set_lo], a.tile64_begin[set_lo + set_n], lane);
     __syncthreads();
 
     // (the kernel is bound by its instruction count, not by the matrix pipe: 32-bit offsets off scalar bases, predicated-off
     // loads, 16-byte accesses everywhere, one activation switch per 4 values)
     const __amdgpu_buffer_rsrc_t r_C = buf_rsrc(a.C + (size_t)nb * a.ldC), r_stage = buf_rsrc(a.stage + (size_t)nb * SP);
-    auto load_c = [&](int t, f32x4 *c) {            // the per-node constant C of tile t, row-major: row 16 t + r, columns 16 ct + 4 g ..
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) {
-            const int rl = 16 * t + r, col = 16 * ct + 4 * g;
-            c[ct] = buf_ld_f32x4(r_C, (rl < n && col < a.H) ? ((unsigned)rl * (unsigned)a.ldC + (unsigned)col) * 4u : BUF_OFF);
-        }
-    };
+    auto load_c = [&](int t, f32x4 (&c)[NCT]) { lds_load_c<SP>(c, r_C, 16 * t + r < n, 16 * t + r, a.H, a.ldC, g); };
 
     int k_done = 0;
     for (int it = 0; run && it < a.max_iteration; ++it) {
@@ -149,156 +354,17 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds(LdsArgs a) {
         int any = 0;
         if (wave < n_tiles) load_c(wave, cn);
 #pragma unroll 1
-        for (int t = wave; t < n_tiles; t += LDS_NW) {
+        for (int t = wave; t < n_tiles; t += LDS_NW) {                         // a wave's tiles: wave, wave + 16, ..
             f32x4 c[NCT];
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct) c[ct] = cn[ct];
             if (t + LDS_NW < n_tiles) load_c(t + LDS_NW, cn);
-            const int jl = 16 * t + r;                                         // local node of this lane's row
-            const bool on = jl < n;
-            const LdsRec rec = on ? Rec[jl] : LdsRec{0u, 0u, 0, 1.0f};
-            // own row chunks and the neighbour sum, both in fragment order
-            f32x4 own[NQ], agg[NQ];
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                own[q] = on ? *reinterpret_cast<const f32x4 *>(St + jl * SP + 16 * q + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
-                agg[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            }
-            const unsigned ids4[4] = {rec.id01 & 0xFFFFu, rec.id01 >> 16, rec.id23 & 0xFFFFu, rec.id23 >> 16};
-            float w4[4] = {1.0f, 1.0f, 1.0f, 1.0f};
-            if (HAS_W && on) {
-                const int b0 = a.rowptr[nb + jl];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) w4[u] = u < rec.deg ? a.w[b0 + u] : 0.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (u < rec.deg) {
-#pragma unroll
-                    for (int q = 0; q < NQ; ++q) {
-                        const f32x4 x = *reinterpret_cast<const f32x4 *>(St + ids4[u] * SP + 16 * q + 4 * g);
-                        if (HAS_W) agg[q] += w4[u] * x; else agg[q] += x;
-                    }
-                }
-            }
-            if (__any(rec.deg > 4)) {                                          // rows with more than 4 arcs: the rest from the CSR in global memory
-                const int b0 = on ? a.rowptr[nb + jl] : 0, e1 = b0 + rec.deg;
-                for (int e = b0 + 4; __any(e < e1); e += 4) {
-                    int id[4]; float wv[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const bool ok = e + u < e1;
-                        id[u] = ok ? a.src[e + u] - nb : 0;
-                        wv[u] = ok ? (HAS_W ? a.w[e + u] : 1.0f) : 0.0f;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        if (e + u < e1) {
-#pragma unroll
-                            for (int q = 0; q < NQ; ++q) {
-                                const f32x4 x = *reinterpret_cast<const f32x4 *>(St + id[u] * SP + 16 * q + 4 * g);
-                                if (HAS_W) agg[q] += wv[u] * x; else agg[q] += x;
-                            }
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) agg[q] *= rec.scale;
-            // two independent MFMA chains per column tile: the state half accumulates onto C, the agg half onto zero, summed at the end.
-            // Operands swapped (weights = A, rows = B): the result is row-major - lane (r, g) gets columns 16 ct + 4 g .. + 3 of row r.
-            f32x4 c2[NCT];
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) c2[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int qe = 0; qe < SP / 4; ++qe) {
-#pragma unroll
-                for (int ct = 0; ct < NCT; ++ct) {
-                    c[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[qe][ct], own[qe / 4][qe & 3], c[ct], 0, 0, 0);
-                    c2[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[SP / 4 + qe][ct], agg[qe / 4][qe & 3], c2[ct], 0, 0, 0);
-                }
-            }
-            // activation + predicate against the old row chunks (still in registers); the new rows leave for the staging buffer
-            float d2 = 0.0f, n2 = 0.0f;
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) {
-                f32x4 v = c[ct] + c2[ct];
-                activate4(a.act, v);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = (on && 16 * ct + 4 * g + e < S) ? v[e] : 0.0f;
-                    const float o = own[ct][e], d = v[e] - o;
-                    d2 = fmaf(d, d, d2); n2 = fmaf(o, o, n2);
-                }
-                if (DB) {
-                    if (on) *reinterpret_cast<f32x4 *>(Snew + jl * SP + 16 * ct + 4 * g) = v;
-                } else {
-                    const u32x4 bits = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
-                    __builtin_amdgcn_raw_buffer_store_b128(bits, r_stage, on ? (int)(((unsigned)jl * SP + 16u * ct + 4u * g) * 4u) : (int)BUF_OFF, 0, 0);
-                }
-            }
-            d2 += __shfl_xor(d2, 16, 64); d2 += __shfl_xor(d2, 32, 64);        // the four lane groups of a row
-            n2 += __shfl_xor(n2, 16, 64); n2 += __shfl_xor(n2, 32, 64);
-            if (on && sqrtf(d2) > a.thr * sqrtf(n2)) any = 1;
+            lds_tile<SP, HAS_W, DB>(a, rows, nb, t, r, g, St, Snew, Rec, r_stage, wreg, c, a.act, any);
         }
-        int mv_slot = it & 1;
-        if (DB) {
-            // three rotating flag words: iteration it sets [it % 3] before the barrier and reads it after; the word of iteration it + 2
-            // is cleared after this barrier - its last readers (iteration it - 1) are behind every wave, its next writers two barriers away
-            mv_slot = it % 3;
-            if (any) moving_s[mv_slot] = 1;                                    // benign race: every writer stores 1
-            __syncthreads();                                                   // new rows complete, old rows no longer read
-            if (tid == 0) moving_s[(it + 2) % 3] = 0;
-        } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // this wave's staged rows are in L2
-        __syncthreads();                                                       // every wave is done reading the old state
-        // two flag words: the one of the NEXT iteration is cleared here - every wave has read it (end of the previous iteration)
-        // before it arrived at the barrier above, and the barrier below orders the clear before the next iteration's stores
-        if (tid == 0) moving_s[(it + 1) & 1] = 0;
-        if (any) moving_s[it & 1] = 1;                                         // benign race: every writer stores 1
-        {   // staged rows back into LDS: sc1 loads, served by the L2 the stores went to (the CU's L1 may still hold last iteration's
-            // lines of the staging buffer).  All of a thread's loads are issued before the first is stored (they are independent;
-            // one at a time they cost a round trip to L2 each: up to nine per iteration).
-            const __amdgpu_buffer_rsrc_t rs = r_stage;
-            const int total = n * (SP / 4);
-            for (int i0 = tid; i0 < total; i0 += 64 * LDS_NW * CPB) {
-                u32x4 v[CPB];
-#pragma unroll
-                for (int u = 0; u < CPB; ++u) {
-                    const int i = i0 + u * 64 * LDS_NW;
-                    v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, i < total ? i * 16 : (int)BUF_OFF, 0, 16);
-                }
-#pragma unroll
-                for (int u = 0; u < CPB; ++u) {
-                    const int i = i0 + u * 64 * LDS_NW;
-                    if (i < total) *reinterpret_cast<u32x4 *>(St + 4 * i) = v[u];
-                }
-            }
-        }
-        __syncthreads();
-        }
+        const int mv_slot = lds_iter_end<SP, DB>(moving_s, any, it, St, r_stage, n, tid);
         if (DB) St = Snew;                                                     // (what the result copy below reads if the loop ends here)
         k_done = it + 1;
-        if (set_n > 1) {                                                       // (uniform per workgroup)
-            // one 64-bit add carries this group's arrival and "some node of mine still moves"; the set's total tells every member
-            // whether ANY of them moves (k_state_small's grid barrier, over the set's few workgroups and without any state rows)
-            if (tid == 0) {
-                unsigned long long *ctr = a.set_bar + 2 * set_lo + (it & 1);
-                __hip_atomic_fetch_add(ctr, 1ull + ((unsigned long long)(moving_s[mv_slot] ? 1u : 0u) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned target = (unsigned)(it / 2 + 1) * (unsigned)set_n;
-                unsigned long long v = 0;
-                if (!wait_until(a.wait_ticks, [&]() { v = __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return (unsigned)v >= target; }))
-                    timed_out = 1;                                             // a member never arrived (not resident?): reported through k
-                const unsigned moved = (unsigned)(v >> 32);
-                set_go = timed_out ? -1 : ((moved != moved_seen[it & 1]) ? 1 : 0);
-                moved_seen[it & 1] = moved;
-            }
-            __syncthreads();
-            // an expired wait ends this group's loop at once: its result is void (k < 0), and waiting out the bound again in each of the
-            // remaining iterations would hold the CU - and every member queued behind it - for max_iteration x the bound
-            if (set_go < 0) break;
-            if (!a.no_exit && set_go == 0) break;
-        } else if (!a.no_exit && moving_s[mv_slot] == 0) break;                // uniform: read after the barrier
+        if (lds_leaves(a, moving_s, &set_go, mv_slot, it, set_lo, set_n, moved_seen, timed_out, tid)) break;
     }
     // ---- result rows to the caller's compact buffer, k of this group ------------------------------------------------------------------
     for (int i = tid; i < n * S; i += 64 * LDS_NW) {
@@ -311,40 +377,60 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds(LdsArgs a) {
 inline size_t lds_state_bytes(int n_nodes, int SP, bool db = false) { return (size_t)n_nodes * ((db ? 2 : 1) * SP * sizeof(float) + sizeof(LdsRec)); }
 inline bool lds_group_fits(int n_nodes, int SP) { return lds_state_bytes(n_nodes, SP) <= LDS_BUDGET_BYTES && n_nodes < 65536; }
 inline bool lds_group_fits_twice(int n_nodes, int SP) { return lds_state_bytes(n_nodes, SP, true) <= LDS_BUDGET_BYTES; }
+// the largest group (in nodes) that fits
+inline int lds_max_nodes(int SP) { return (int)std::min<size_t>(LDS_BUDGET_BYTES / lds_state_bytes(1, SP), 65535); }
 
-template <int SP, bool HAS_W, bool DB>
-int launch_lds_one(const LdsArgs &la_in, int n_groups, size_t lds_bytes, hipStream_t st) {
+// ---- One launcher for both kernels.  A kernel family F names its argument struct, the LdsArgs inside it, and its instantiations:
+//     using Args; static LdsArgs &common(Args &); static constexpr const char *name; template <int SP, bool HAS_W, bool DB> static constexpr void (*fn)(Args)
+struct LdsKernel {
+    using Args = LdsArgs;
+    static LdsArgs &common(Args &a) { return a; }
+    static constexpr const char *name = "k_state_lds";
+    template <int SP, bool HAS_W, bool DB> static constexpr void (*fn)(Args) = k_state_lds<SP, HAS_W, DB>;
+};
+
+template <class F, int SP, bool HAS_W, bool DB>
+int launch_lds_one(const typename F::Args &la_in, int n_groups, size_t lds_bytes, hipStream_t st) {
+    constexpr auto kernel = F::template fn<SP, HAS_W, DB>;
     static bool attr = false;
     if (!attr) {
-        if (hipFuncSetAttribute((const void *)k_state_lds<SP, HAS_W, DB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET_BYTES) != hipSuccess) return 1;
+        if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET_BYTES) != hipSuccess) return 1;
         attr = true;
     }
-    LdsArgs la = la_in;
-    la.wait_ticks = wait_ticks();
-    if (la.set_bar) {            // groups of a set wait for each other: every workgroup of the launch must be resident at once
+    typename F::Args la = la_in;
+    F::common(la).wait_ticks = wait_ticks();
+    if (F::common(la).set_bar) {            // groups of a set wait for each other: every workgroup of the launch must be resident at once
         int dev = 0, n_cu = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 1;
-        if (!persistent_fits((const void *)k_state_lds<SP, HAS_W, DB>, 64 * LDS_NW, lds_bytes, n_groups, n_cu)) return 2;
+        if (!persistent_fits((const void *)kernel, 64 * LDS_NW, lds_bytes, n_groups, n_cu)) return 2;
     }
-    GNN_SET_KERNEL_NAME("k_state_lds<%d,%s,%s>", SP, HAS_W ? "true" : "false", DB ? "true" : "false");
-    k_state_lds<SP, HAS_W, DB><<<n_groups, 64 * LDS_NW, lds_bytes, st>>>(la);
+    GNN_SET_KERNEL_NAME("%s<%d,%s,%s>", F::name, SP, HAS_W ? "true" : "false", DB ? "true" : "false");
+    kernel<<<n_groups, 64 * LDS_NW, lds_bytes, st>>>(la);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
-// max_nodes: nodes of the largest group (every workgroup requests LDS for that one); the double-buffered form where it fits twice
-inline int launch_lds(const LdsArgs &la, int SP, int n_groups, int max_nodes, hipStream_t st) {
-    const bool db = lds_group_fits_twice(max_nodes, SP);
-    const size_t bytes = std::max<size_t>(lds_state_bytes(max_nodes, SP, db), 90 * 1024);     // one workgroup per CU either way
-#define LDS_CASE(SPV)                                                                                                            \
-    case SPV:                                                                                                                    \
-        if (db) return la.w ? launch_lds_one<SPV, true, true>(la, n_groups, bytes, st) : launch_lds_one<SPV, false, true>(la, n_groups, bytes, st); \
-        return la.w ? launch_lds_one<SPV, true, false>(la, n_groups, bytes, st) : launch_lds_one<SPV, false, false>(la, n_groups, bytes, st);
+template <class F, int SP>
+int launch_lds_sp(const typename F::Args &la, bool has_w, bool db, int n_groups, size_t lds_bytes, hipStream_t st) {
+    if (db) return has_w ? launch_lds_one<F, SP, true, true>(la, n_groups, lds_bytes, st) : launch_lds_one<F, SP, false, true>(la, n_groups, lds_bytes, st);
+    return has_w ? launch_lds_one<F, SP, true, false>(la, n_groups, lds_bytes, st) : launch_lds_one<F, SP, false, false>(la, n_groups, lds_bytes, st);
+}
+
+// state_bytes: LDS of the largest group (every workgroup requests that much), in the double-buffered form when db
+template <class F>
+int launch_lds_family(typename F::Args la, int SP, bool db, int n_groups, size_t state_bytes, hipStream_t st) {
+    const size_t bytes = std::max<size_t>(state_bytes, 90 * 1024);            // one workgroup per CU either way
+    const bool has_w = F::common(la).w != nullptr;
     switch (SP) {
-        LDS_CASE(16)
-        LDS_CASE(32)
+        case 16: return launch_lds_sp<F, 16>(la, has_w, db, n_groups, bytes, st);
+        case 32: return launch_lds_sp<F, 32>(la, has_w, db, n_groups, bytes, st);
         default: return 2;
     }
-#undef LDS_CASE
+}
+
+// max_nodes: nodes of the largest group; the double-buffered form where it fits twice
+inline int launch_lds(const LdsArgs &la, int SP, int n_groups, int max_nodes, hipStream_t st) {
+    const bool db = lds_group_fits_twice(max_nodes, SP);
+    return launch_lds_family<LdsKernel>(la, SP, db, n_groups, lds_state_bytes(max_nodes, SP, db), st);
 }
 
 }  // namespace gnn

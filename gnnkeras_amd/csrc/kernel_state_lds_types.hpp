@@ -16,8 +16,11 @@
 //     one LDS read per weight register and TILE: 32 ds_read_b32 against the tile's 32 MFMAs.);
 //   * the per-node constant C (setup_constants writes it per type, indexed by node), state_0 and the per-arc weights are read by original
 //     node id; the result goes back to state_out in node order;
-//   * predicate, activation (per type), no_exit, k, group sets, the double-buffered form: as in k_state_lds.  state_0's predicate comes
-//     from k_pred0_groups, one word per GROUP (the arithmetic of k_converge, row by row).
+//   * what is this kernel's own: the prologue (rows per type, positions, Orig / Inv, records by position), the row policy LdsRowsTyped, the
+//     walk over a contiguous run of tiles with the weight reload, and the result copy in node order.  The update of a tile, the end of an
+//     iteration (flag words, copy back), group sets, no_exit, k and the launcher are kernel_state_lds.hpp's pieces, instantiated with that
+//     policy - the double-buffered form included.  state_0's predicate comes from k_pred0_groups, one word per GROUP (the arithmetic of
+//     k_converge, row by row).
 #pragma once
 #include "kernel_state_lds.hpp"
 
@@ -64,7 +67,16 @@ k_pred0_groups(const int *__restrict__ node_begin, const float *__restrict__ s, 
     if (threadIdx.x == 0) pred0[g] = any;
 }
 
-constexpr unsigned LDS_TYPES_NO_ROW = 0xFFFFu;      // a record's neighbour id for an arc whose source is not a row of the group
+// The row policy of the typed kernel (kernel_state_lds.hpp): LDS rows are POSITIONS; Orig / Inv translate.  Pad rows exist and stay zero,
+// and an arc's source may be no row of the group (a node that no type lists, a source outside the group's range).
+struct LdsRowsTyped {
+    static constexpr bool PAD_ROWS = true, ALL_ARCS_ARE_ROWS = false;
+    const int *Orig, *Inv; int n;
+    __device__ __forceinline__ int node(int row) const { return Orig[row]; }
+    __device__ __forceinline__ bool on(int, int j) const { return j >= 0; }
+    __device__ __forceinline__ bool has_row(int l) const { return (unsigned)l < (unsigned)n; }
+    __device__ __forceinline__ int row_of(int l) const { return Inv[l]; }
+};
 
 struct LdsTypeNet { const float *Wf; int wrow_state, wrow_agg, act; };
 
@@ -95,10 +107,8 @@ inline int lds_types_max_nodes(int n_types, int SP) {
 
 template <int SP, bool HAS_W, bool DB>
 __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds_types(LdsTypesArgs ta) {
-    constexpr int NQ = SP / 16;
     constexpr int NCT = SP / 16;
     constexpr int KS = 2 * SP / 4;
-    constexpr int CPB = 5;
     extern __shared__ __attribute__((aligned(16))) char smem_lds[];
     __shared__ int moving_s[3];
     __shared__ int set_go;
@@ -171,32 +181,24 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds_types(LdsTypesArgs
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const unsigned l = beg + u < end ? (unsigned)(a.src[beg + u] - nb) : 0u;
-                id[u] = beg + u >= end ? 0u : (l < (unsigned)n ? (unsigned)Inv[l] : LDS_TYPES_NO_ROW);      // (positions stay below 65535)
+                id[u] = beg + u >= end ? 0u : (l < (unsigned)n ? (unsigned)Inv[l] : LDS_NO_ROW);      // (positions stay below 65535)
             }
             rec = LdsRec{id[0] | (id[1] << 16), id[2] | (id[3] << 16), end - beg, a.row_scale ? a.row_scale[nb + j] : 1.0f};
         }
         Rec[ps] = rec;
     }
+    const LdsRowsTyped rows{Orig, Inv, n};
     const int set_lo = a.set_bar ? a.set_first[grp] : grp, set_n = a.set_bar ? a.set_size[grp] : 1;
     unsigned moved_seen[2] = {0u, 0u};
     int timed_out = 0;
-    int run = a.no_exit;
-    if (!run) {
-        int v = 0;
-        for (int i = set_lo + lane; i < set_lo + set_n; i += 64) v |= a.pred0[i];
-        run = __any(v != 0);
-    }
+    const int run = lds_run0(a, set_lo, set_lo + set_n, lane);             // state_0's predicate: one word per group of the set
     __syncthreads();
 
     // rows of the staging buffer: group g's begin behind the padded sizes of the groups before it (bounded by 15 n_types each)
     const __amdgpu_buffer_rsrc_t r_C = buf_rsrc(a.C + (size_t)nb * a.ldC), r_stage = buf_rsrc(a.stage + ((size_t)nb + (size_t)15 * T * grp) * SP);
-    auto load_c = [&](int t, f32x4 *c) {            // C of tile t by original node: row Orig[16 t + r], columns 16 ct + 4 g ..
+    auto load_c = [&](int t, f32x4 (&c)[NCT]) {     // C of tile t by original node
         const int j = Orig[16 * t + r];
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) {
-            const int col = 16 * ct + 4 * g;
-            c[ct] = buf_ld_f32x4(r_C, (j >= 0 && col < S) ? ((unsigned)j * (unsigned)a.ldC + (unsigned)col) * 4u : BUF_OFF);
-        }
+        lds_load_c<SP>(c, r_C, j >= 0, j, S, a.ldC, g);
     };
 
     // a wave's tiles: a contiguous run, so that it crosses from one type into the next as rarely as possible
@@ -232,151 +234,14 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds_types(LdsTypesArgs
                 const float *Wf = static_cast<const float *>(uniform_ptr(nt.Wf));
                 const int ws = __builtin_amdgcn_readfirstlane(nt.wrow_state), wa = __builtin_amdgcn_readfirstlane(nt.wrow_agg);
                 act = __builtin_amdgcn_readfirstlane(nt.act);
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    const int half = ks / (SP / 4), qe = ks % (SP / 4);
-                    const int kcol = 16 * (qe / 4) + 4 * g + (qe & 3);
-#pragma unroll
-                    for (int ct = 0; ct < NCT; ++ct) {
-                        const int ncol = 16 * ct + r;
-                        wreg[ks][ct] = (kcol < S && ncol < S) ? Wf[(size_t)((half ? wa : ws) + kcol) * S + ncol] : 0.0f;
-                    }
-                }
+                lds_fill_wreg<SP>(wreg, Wf, ws, wa, S, S, r, g);             // (the host checked units[0] == S)
             }
-            const int ps = 16 * t + r;                                         // position of this lane's row
-            const int jo = Orig[ps];
-            const bool on = jo >= 0;
-            const LdsRec rec = Rec[ps];                                        // (pad rows: degree 0)
-            f32x4 own[NQ], agg[NQ];
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                own[q] = on ? *reinterpret_cast<const f32x4 *>(St + ps * SP + 16 * q + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
-                agg[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            }
-            const unsigned ids4[4] = {rec.id01 & 0xFFFFu, rec.id01 >> 16, rec.id23 & 0xFFFFu, rec.id23 >> 16};
-            float w4[4] = {1.0f, 1.0f, 1.0f, 1.0f};
-            if (HAS_W && on) {
-                const int b0 = a.rowptr[nb + jo];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) w4[u] = u < rec.deg ? a.w[b0 + u] : 0.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (u < rec.deg && ids4[u] != LDS_TYPES_NO_ROW) {               // (an arc from outside the group adds nothing)
-#pragma unroll
-                    for (int q = 0; q < NQ; ++q) {
-                        const f32x4 x = *reinterpret_cast<const f32x4 *>(St + ids4[u] * SP + 16 * q + 4 * g);
-                        if (HAS_W) agg[q] += w4[u] * x; else agg[q] += x;
-                    }
-                }
-            }
-            if (__any(rec.deg > 4)) {                                          // rows with more than 4 arcs: the rest from the CSR in global memory
-                const int b0 = on ? a.rowptr[nb + jo] : 0, e1 = b0 + rec.deg;
-                for (int e = b0 + 4; __any(e < e1); e += 4) {
-                    int id[4]; float wv[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const bool ok = e + u < e1;
-                        const unsigned l = ok ? (unsigned)(a.src[e + u] - nb) : 0u;
-                        const bool in = ok && l < (unsigned)n;
-                        id[u] = in ? Inv[l] : 0;
-                        wv[u] = in ? (HAS_W ? a.w[e + u] : 1.0f) : 0.0f;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        if (e + u < e1) {
-#pragma unroll
-                            for (int q = 0; q < NQ; ++q) {
-                                const f32x4 x = *reinterpret_cast<const f32x4 *>(St + id[u] * SP + 16 * q + 4 * g);
-                                agg[q] += wv[u] * x;                           // (wv = 0: an arc from outside the group adds nothing)
-                            }
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) agg[q] *= rec.scale;
-            f32x4 c2[NCT];
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) c2[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int qe = 0; qe < SP / 4; ++qe) {
-#pragma unroll
-                for (int ct = 0; ct < NCT; ++ct) {
-                    c[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[qe][ct], own[qe / 4][qe & 3], c[ct], 0, 0, 0);
-                    c2[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[SP / 4 + qe][ct], agg[qe / 4][qe & 3], c2[ct], 0, 0, 0);
-                }
-            }
-            float d2 = 0.0f, n2 = 0.0f;
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) {
-                f32x4 v = c[ct] + c2[ct];
-                activate4(act, v);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = (on && 16 * ct + 4 * g + e < S) ? v[e] : 0.0f;      // pad rows stay zero
-                    const float o = own[ct][e], d = v[e] - o;
-                    d2 = fmaf(d, d, d2); n2 = fmaf(o, o, n2);
-                }
-                if (DB) {
-                    *reinterpret_cast<f32x4 *>(Snew + ps * SP + 16 * ct + 4 * g) = v;
-                } else {
-                    const u32x4 bits = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
-                    __builtin_amdgcn_raw_buffer_store_b128(bits, r_stage, (int)(((unsigned)ps * SP + 16u * ct + 4u * g) * 4u), 0, 0);
-                }
-            }
-            d2 += __shfl_xor(d2, 16, 64); d2 += __shfl_xor(d2, 32, 64);
-            n2 += __shfl_xor(n2, 16, 64); n2 += __shfl_xor(n2, 32, 64);
-            if (on && sqrtf(d2) > a.thr * sqrtf(n2)) any = 1;
+            lds_tile<SP, HAS_W, DB>(a, rows, nb, t, r, g, St, Snew, Rec, r_stage, wreg, c, act, any);
         }
-        int mv_slot = it & 1;
-        if (DB) {
-            mv_slot = it % 3;
-            if (any) moving_s[mv_slot] = 1;
-            __syncthreads();
-            if (tid == 0) moving_s[(it + 2) % 3] = 0;
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) moving_s[(it + 1) & 1] = 0;
-            if (any) moving_s[it & 1] = 1;
-            {
-                const __amdgpu_buffer_rsrc_t rs = r_stage;
-                const int total = P * (SP / 4);
-                for (int i0 = tid; i0 < total; i0 += 64 * LDS_NW * CPB) {
-                    u32x4 v[CPB];
-#pragma unroll
-                    for (int u = 0; u < CPB; ++u) {
-                        const int i = i0 + u * 64 * LDS_NW;
-                        v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, i < total ? i * 16 : (int)BUF_OFF, 0, 16);
-                    }
-#pragma unroll
-                    for (int u = 0; u < CPB; ++u) {
-                        const int i = i0 + u * 64 * LDS_NW;
-                        if (i < total) *reinterpret_cast<u32x4 *>(St + 4 * i) = v[u];
-                    }
-                }
-            }
-            __syncthreads();
-        }
+        const int mv_slot = lds_iter_end<SP, DB>(moving_s, any, it, St, r_stage, P, tid);
         if (DB) St = Snew;
         k_done = it + 1;
-        if (set_n > 1) {
-            if (tid == 0) {
-                unsigned long long *ctr = a.set_bar + 2 * set_lo + (it & 1);
-                __hip_atomic_fetch_add(ctr, 1ull + ((unsigned long long)(moving_s[mv_slot] ? 1u : 0u) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned target = (unsigned)(it / 2 + 1) * (unsigned)set_n;
-                unsigned long long v = 0;
-                if (!wait_until(a.wait_ticks, [&]() { v = __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return (unsigned)v >= target; }))
-                    timed_out = 1;
-                const unsigned moved = (unsigned)(v >> 32);
-                set_go = timed_out ? -1 : ((moved != moved_seen[it & 1]) ? 1 : 0);
-                moved_seen[it & 1] = moved;
-            }
-            __syncthreads();
-            if (set_go < 0) break;
-            if (!a.no_exit && set_go == 0) break;
-        } else if (!a.no_exit && moving_s[mv_slot] == 0) break;
+        if (lds_leaves(a, moving_s, &set_go, mv_slot, it, set_lo, set_n, moved_seen, timed_out, tid)) break;
     }
     // ---- result rows to the caller's compact buffer in node order, k of this group ------------------------------------------------------
     for (int i = tid; i < P * S; i += 64 * LDS_NW) {
@@ -386,39 +251,17 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds_types(LdsTypesArgs
     if (tid == 0) a.k_out[grp] = timed_out ? -1.0e9f : (float)k_done;
 }
 
-template <int SP, bool HAS_W, bool DB>
-int launch_lds_types_one(const LdsTypesArgs &la_in, size_t lds_bytes, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void *)k_state_lds_types<SP, HAS_W, DB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET_BYTES) != hipSuccess) return 1;
-        attr = true;
-    }
-    LdsTypesArgs la = la_in;
-    la.l.wait_ticks = wait_ticks();
-    if (la.l.set_bar) {          // groups of a set wait for each other: every workgroup of the launch must be resident at once
-        int dev = 0, n_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 1;
-        if (!persistent_fits((const void *)k_state_lds_types<SP, HAS_W, DB>, 64 * LDS_NW, lds_bytes, la.n_groups, n_cu)) return 2;
-    }
-    GNN_SET_KERNEL_NAME("k_state_lds_types<%d,%s,%s>", SP, HAS_W ? "true" : "false", DB ? "true" : "false");
-    k_state_lds_types<SP, HAS_W, DB><<<la.n_groups, 64 * LDS_NW, lds_bytes, st>>>(la);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
-}
+struct LdsTypesKernel {         // (launch_lds_one, kernel_state_lds.hpp)
+    using Args = LdsTypesArgs;
+    static LdsArgs &common(Args &a) { return a.l; }
+    static constexpr const char *name = "k_state_lds_types";
+    template <int SP, bool HAS_W, bool DB> static constexpr void (*fn)(Args) = k_state_lds_types<SP, HAS_W, DB>;
+};
 
 // max_nodes: nodes of the largest group (every workgroup requests LDS for its bound of positions)
 inline int launch_lds_types(const LdsTypesArgs &la, int SP, int max_nodes, hipStream_t st) {
     const bool db = lds_types_group_fits_twice(max_nodes, la.n_types, SP);
-    const size_t bytes = std::max<size_t>(lds_types_bytes(max_nodes, la.n_types, SP, db), 90 * 1024);      // one workgroup per CU either way
-#define LDS_TYPES_CASE(SPV)                                                                                                        \
-    case SPV:                                                                                                                      \
-        if (db) return la.l.w ? launch_lds_types_one<SPV, true, true>(la, bytes, st) : launch_lds_types_one<SPV, false, true>(la, bytes, st); \
-        return la.l.w ? launch_lds_types_one<SPV, true, false>(la, bytes, st) : launch_lds_types_one<SPV, false, false>(la, bytes, st);
-    switch (SP) {
-        LDS_TYPES_CASE(16)
-        LDS_TYPES_CASE(32)
-        default: return 2;
-    }
-#undef LDS_TYPES_CASE
+    return launch_lds_family<LdsTypesKernel>(la, SP, db, la.n_groups, lds_types_bytes(max_nodes, la.n_types, SP, db), st);
 }
 
 }  // namespace gnn

@@ -1166,6 +1166,91 @@ def test_starter_configuration_runs_grouped(mutag_graphs):
     assert rel_err(p1, p0) <= TOL and abs(e1['loss'] - e0['loss']) <= 1e-5 and abs(e1['accuracy'] - e0['accuracy']) <= 1e-6
 
 
+def _graph_with_long_rows(rng, n, L, A):
+    """n nodes, ~2 n random arcs, and on top of them rows of in-degree 5 .. 8 and 9 .. 12: the one-CU-per-group kernel keeps 4 source
+    ids per row in LDS and reads the rest from the CSR four at a time - one trip and two trips of that tail loop."""
+    ends = [rng.integers(0, n, size=(2 * n, 2))]
+    for j, deg in ((1, 5), (n // 2, 7), (3, 9), (n - 2, 11)):
+        ends.append(np.stack([rng.choice([v for v in range(n) if v != j], size=deg, replace=False), np.full(deg, j)], axis=1))
+    ends = np.concatenate(ends)
+    ends = np.unique(ends[ends[:, 0] != ends[:, 1]], axis=0)
+    indeg = np.bincount(ends[:, 1], minlength=n)
+    assert np.any((indeg >= 5) & (indeg <= 8)) and np.any((indeg >= 9) & (indeg <= 12)), indeg
+    arcs = np.concatenate([ends, rng.normal(size=(len(ends), A))], axis=1)
+    return GraphObject(nodes=rng.normal(size=(n, L)), arcs=arcs, targets=rng.normal(size=(n, 2)), focus='n', aggregation_mode='sum')
+
+
+def _with_arc_weights(g, w):
+    """The batch tensors of ONE graph object with user-supplied per-arc weights (as test_per_arc_weights_path)."""
+    an = g.getArcNode(); an.data = np.asarray(w, np.float32)
+    m = GraphObject(nodes=g.nodes, arcs=g.arcs, targets=g.targets, focus='n', ArcNode=an, NodeGraph=g.NodeGraph)
+    assert np.array_equal(m.arcs, g.arcs)
+    seq = MultiGraphSequencer([m], 'n', 'sum', 1, shuffle=False)
+    # the sequencer's merge re-derives ArcNode for its mode: put the custom operands back on the batch
+    seq.graph_tensors[0].ArcNode = SparseMatrix.from_scipy(m.ArcNode)
+    seq.graph_tensors[0].Adjacency = SparseMatrix.from_scipy(m.Adjacency)
+    seq._items = [None]
+    x = seq[0][0]
+    assert x[5].matrix.csr().w is not None
+    return x
+
+
+# sizes of the groups, state width, threshold, max_iteration, seed, the kernel's last template argument (double-buffered?)
+LDS_WEIGHTED_CASES = {
+    'w16_thr0':        ((20, 70, 45), 6, 0.0, 5, 0, 'true'),
+    'w32_thr0':        ((20, 70, 45), 20, 0.0, 5, 1, 'true'),
+    'w32_thr0_single': ((20, 620, 45), 20, 0.0, 4, 2, 'false'),       # 620 nodes do not fit LDS twice (594 at 32-wide rows)
+    'w32_thr':         ((20, 70, 45), 20, 0.02, 12, 3, 'true'),
+}
+
+
+@pytest.mark.parametrize('case', list(LDS_WEIGHTED_CASES))
+def test_groups_with_per_arc_weights_and_long_rows_in_lds(case):
+    """k_state_lds<.., HAS_W = true, ..>: convergence groups of a homogeneous model whose adjacency carries per-arc weights, with rows
+    above 4 arcs in every group (the weighted CSR tail), double- and single-buffered.  Per group against the float64 oracle; k exact -
+    with a threshold only after the float64 k was seen not to move at threshold x (1 +- K_MARGIN), as tests/test_gpu_composite_groups.py."""
+    from test_gpu_composite_groups import K_MARGIN
+    sizes, d, thr, iters, seed, db = LDS_WEIGHTED_CASES[case]
+    L, A = 5, 3
+    rng = np.random.default_rng(100 + seed)
+    gl = [_graph_with_long_rows(rng, n, L, A) for n in sizes]
+    ws = [rng.uniform(0.2, 1.0, g.arcs.shape[0]) / (4.0 if thr > 0 else 1.0) for g in gl]
+    s0s = [rng.normal(0, 0.1 * (1 + i), (n, d)).astype(np.float32) for i, n in enumerate(sizes)]
+    m = GraphObject.merge(gl, 'n', 'sum')
+    begin = [0] + [int(v) for v in np.cumsum(sizes)]
+    for i, g in enumerate(gl):      # the merged arcs are the graphs' arcs one after the other: so are the weights
+        e0 = sum(h.arcs.shape[0] for h in gl[:i])
+        assert np.array_equal(m.arc_ids[e0:e0 + g.arcs.shape[0]] - begin[i], g.arc_ids)
+    x = _with_arc_weights(m, np.concatenate(ws))
+    ns, no = starter_nets('n', d, L=L, A=A, scale=0.3)
+    model = GNNnodeBased(ns, no, d, iters, thr)
+    k, st, o = model.Loop(*model.process_inputs(x), state0=dev(np.concatenate(s0s)), groups=begin)
+    name = _last_kernel()
+    torch.cuda.synchronize()
+    assert name == f'k_state_lds<{16 if d <= 16 else 32},true,{db}>', name
+    assert k.shape == (len(sizes),)
+    k, st, o = k.cpu().numpy(), st.cpu().numpy(), o.cpu().numpy()
+    assert np.all(np.isfinite(st)) and np.all(np.isfinite(o))
+    ks = []
+    for i, g in enumerate(gl):
+        xg = _with_arc_weights(g, ws[i])
+        k64, st64, o64 = oracle_loop(model, xg, s0s[i], np.float64)
+        if thr > 0:
+            try:
+                for f in (1 - K_MARGIN, 1 + K_MARGIN):
+                    model.state_threshold = thr * f
+                    assert float(oracle_loop(model, xg, s0s[i], np.float64)[0]) == float(k64), 'borderline k in float64: choose another seed'
+            finally:
+                model.state_threshold = thr
+        e_st, e_o = rel_err(st[begin[i]:begin[i + 1]], st64), rel_err(o[begin[i]:begin[i + 1]], o64)
+        print(f'{case} group {i}: n = {sizes[i]}, k = {k[i]} (float64 {float(k64)}), rel_err state {e_st:.2e} out {e_o:.2e}')
+        assert float(k[i]) == float(k64), (case, i, float(k[i]), float(k64))
+        assert e_st <= TOL and e_o <= TOL, (case, i, e_st, e_o)
+        ks.append(float(k64))
+    if thr == 0: assert ks == [float(iters)] * len(sizes), ks
+    else: assert min(ks) < iters, ('the groups were meant to stop early', ks)
+
+
 @pytest.mark.parametrize('d,state_dim0,mode', [(64, False, 'average'), (32, False, 'sum'), (20, True, 'average')])
 def test_constant_inputs_on_the_matrix_cores_variant(d, state_dim0, mode):
     """From ~200 k nodes the wave-specialised kernel no longer reads the per-node constant C (4 H bytes per node and
