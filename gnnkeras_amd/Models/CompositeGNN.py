@@ -140,6 +140,10 @@ class CompositeGNNnodeBased(GNNnodeBased):
 
     def _type_lists(self, type_mask: torch.Tensor):
         """(node ids grouped by type int32 [N] on device, host offsets [T+1]); cached per type_mask tensor."""
+        if type_mask.is_cuda:
+            from ..device_batch import lookup_type_lists           # batches assembled on the device bring their lists along
+            pre = lookup_type_lists(type_mask)
+            if pre is not None: return pre
         key = (type_mask.data_ptr(), type_mask._version, tuple(type_mask.shape))
         hit = self._type_cache.get(key)
         if hit is None:

@@ -33,7 +33,8 @@ class MultiGraphSequencer:
                  device=None, assemble: str = 'auto'):
         """`assemble` (additive): where batches are merged — 'host' (numpy `GraphObject.merge`, then upload), 'device' (the data
         set is uploaded once, a batch is ONE ragged-copy launch: `gnnkeras_amd/device_batch.py`) or 'auto' = device on a GPU
-        for homogeneous data sets it supports, host otherwise. Same arrays either way."""
+        for the data sets it supports (homogeneous, and heterogeneous ones of `CompositeMultiGraphSequencer`), host otherwise.
+        Same arrays either way."""
         self.data = graphs if isinstance(graphs, list) else [graphs]
         self.focus = focus
         self.aggregation_mode = aggregation_mode
@@ -48,22 +49,25 @@ class MultiGraphSequencer:
 
     def _device_dataset(self):
         """The device-resident data set, or None when batches are merged on the host."""
-        if self.assemble == 'host' or self.device.type != 'cuda' or type(self).merge.__func__ is not MultiGraphSequencer.merge.__func__:
-            if self.assemble == 'device': raise ValueError('device assembly needs a GPU and a homogeneous data set')
+        merge = type(self).merge.__func__
+        kind = 'DeviceDataset' if merge is MultiGraphSequencer.merge.__func__ else \
+            'CompositeDeviceDataset' if merge is CompositeMultiGraphSequencer.merge.__func__ else None      # (a merge of one's own: host)
+        if self.assemble == 'host' or self.device.type != 'cuda' or kind is None:
+            if self.assemble == 'device': raise ValueError("device assembly needs a GPU and a multi-graph sequencer's own merge")
             return None
         # the data set on the device is valid as long as the graphs still hold the arrays it was built from (LGNN's serial fit
         # REPLACES the label arrays of a sequencer's graphs: reference LGNN.py:318-333); edits made IN PLACE inside an array are
         # not seen - call refresh() after such an edit
-        arrays = lambda g: (id(g.nodes), id(g.arcs), id(g.targets), id(g.set_mask), id(g.output_mask))
+        arrays = lambda g: (id(g.nodes), id(g.arcs), id(g.targets), id(g.set_mask), id(g.output_mask), id(getattr(g, 'type_mask', None)))
         # (the signature is keyed by graph OBJECT: order-independent, so shuffling keeps it valid; a list that holds the same
         # object twice has fewer keys than entries, which is fine - compare against the number of distinct objects)
         stale = self._dataset is None or len(self._dataset[1]) != len({id(g) for g in self.data}) or \
             any(self._dataset[1].get(id(g)) != arrays(g) for g in self.data)
         if stale:
             sig = {id(g): arrays(g) for g in self.data}
-            from ..device_batch import DeviceDataset
+            from .. import device_batch
             try:
-                ds = DeviceDataset(self.data, self.focus, self.aggregation_mode, self.device)
+                ds = getattr(device_batch, kind)(self.data, self.focus, self.aggregation_mode, self.device)
             except ValueError:
                 if self.assemble == 'device': raise
                 ds = None
@@ -99,8 +103,8 @@ class MultiGraphSequencer:
         independent loops of one launch - each batch converges and stops on its own, as if called alone - which is how
         predict() / evaluate() fill the GPU with small batches.  None when a bigger merge would change the operands:
         'normalized' divides by the number of arcs of the merged graph (graph_class.py buildArcNode).  Cached
-        until the batches are rebuilt.  `CompositeMultiGraphSequencer` answers with the composite merge of the same graphs (host
-        merge + upload); sequencers with a merge of their own answer None."""
+        until the batches are rebuilt.  `CompositeMultiGraphSequencer` answers with the composite merge of the same graphs;
+        sequencers with a merge of their own answer None."""
         if self.aggregation_mode == 'normalized': return None
         if type(self).merge.__func__ not in (MultiGraphSequencer.merge.__func__, CompositeMultiGraphSequencer.merge.__func__): return None
         batches = [int(b) for b in i0] if i1 is None else list(range(int(i0), int(i1)))

@@ -25,11 +25,12 @@ class TransductiveMultiGraphSequencer(CompositeMultiGraphSequencer):
         self.graph_objects = graphs if isinstance(graphs, list) else [graphs]
         self.transductive_rate = transductive_rate
         gs = [self.get_transduction(g, transductive_rate, focus, 'float32') for g in self.graph_objects]
-        super().__init__(gs, focus, aggregation_mode, batch_size, shuffle, device=device)
+        # (the split is re-drawn at every epoch end - new graph objects each time: a device-resident data set would be rebuilt per epoch)
+        super().__init__(gs, focus, aggregation_mode, batch_size, shuffle, device=device, assemble='host')
 
     def get_config(self):
         config = super().get_config()
-        config.pop("assemble", None)                               # (composite batches are merged on the host)
+        config.pop("assemble", None)                               # (transductive batches are merged on the host)
         config["graphs"] = self.graph_objects                      # from_config must see the homogeneous originals
         config["transductive_rate"] = self.transductive_rate
         return config

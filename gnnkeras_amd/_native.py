@@ -154,7 +154,7 @@ class RaggedDesc(C.Structure):
                 ('fval', C.c_float), ('width', C.c_int32)]
 
 
-RC_COPY_F32, RC_COPY_I32_ADD, RC_COPY_ROWS_ADD2, RC_FILL_F32, RC_FILL_I32, RC_IOTA_I32, RC_COPY_U8 = range(7)
+RC_COPY_F32, RC_COPY_I32_ADD, RC_COPY_ROWS_ADD2, RC_FILL_F32, RC_FILL_I32, RC_IOTA_I32, RC_COPY_U8, RC_TYPE_ROWS_U8 = range(8)
 RC_CHUNK = 2048
 
 

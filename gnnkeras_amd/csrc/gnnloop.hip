@@ -1726,6 +1726,16 @@ int gnn_ragged_copy(const gnn_ragged_desc_t *desc, int32_t n_desc, const int32_t
     if (n_desc == 0 || n_blocks == 0) return 0;
     if (!desc || !blk_begin) return fail("desc / blk_begin is NULL");
     static_assert(gnn::RC_CHUNK == GNN_RC_CHUNK, "chunk size of the header and the kernel differ");
+    // the table lives on the device: its kinds are checked there, the verdict lands in a host-mapped word
+    static thread_local int *bad = nullptr;
+    if (!bad) HIP_OK(hipHostMalloc((void **)&bad, 64, hipHostMallocMapped | hipHostMallocPortable));
+    int *bad_dev = nullptr;
+    HIP_OK(hipHostGetDevicePointer((void **)&bad_dev, bad, 0));
+    *bad = 0;
+    gnn::k_ragged_check<<<cdiv(n_desc, 256), 256, 0, (hipStream_t)stream>>>(desc, n_desc, bad_dev);
+    LAUNCH_OK();
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+    if (*bad != 0) return fail("gnn_ragged_copy: unknown kind %d (kinds are 0 .. %d); nothing was written", *bad, GNN_RC_KIND_MAX);
     gnn::k_ragged_copy<<<n_blocks, 256, 0, (hipStream_t)stream>>>(desc, n_desc, blk_begin);
     LAUNCH_OK();
     return 0;

@@ -53,8 +53,24 @@ k_ragged_copy(const gnn_ragged_desc_t *__restrict__ desc, int n_desc, const int 
             const unsigned char *s = (const unsigned char *)d.src; unsigned char *o = (unsigned char *)d.dst;
             for (long i = base + threadIdx.x; i < end; i += 256) o[i] = s[i];
         } break;
-        default: break;
+        case GNN_RC_TYPE_ROWS_U8: {            // src = a type id per node: all `width` rows of a (width, iadd) one-hot byte mask, columns [0, count)
+            const unsigned char *s = (const unsigned char *)d.src; unsigned char *o = (unsigned char *)d.dst;
+            for (long i = base + threadIdx.x; i < end; i += 256) {
+                const int type = s[i];
+                for (int t = 0; t < d.width; ++t) o[(long)t * d.iadd + i] = (unsigned char)(type == t);
+            }
+        } break;
+        default: break;                        // (gnn_ragged_copy has refused the table before this launch: k_ragged_check)
     }
+}
+
+// an unknown kind anywhere in the table -> *bad = that kind (host-mapped word; any one of several will do)
+__global__ void __launch_bounds__(256)
+k_ragged_check(const gnn_ragged_desc_t *__restrict__ desc, int n_desc, int *bad) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_desc) return;
+    const int kind = desc[i].kind;
+    if (kind < 0 || kind > GNN_RC_KIND_MAX) *bad = kind < 0 ? -1 : kind;
 }
 
 }  // namespace gnn

@@ -467,7 +467,8 @@ int gnn_aggregate_gated(const gnn_csr_t *csr, const float *X, int32_t ldx, int32
  * segments of the dataset's device-resident arrays, with a per-segment offset added to node / arc ids.  gnn_ragged_copy executes
  * a table of such segment operations in ONE launch.  `desc` and `blk_begin` are DEVICE arrays (the caller uploads them with one
  * small copy per batch): blk_begin[d] = first workgroup of descriptor d (GNN_RC_CHUNK elements per workgroup), blk_begin[n_desc]
- * = n_blocks. */
+ * = n_blocks.  A table that holds a kind outside the enum is refused with a status before anything is written: the kinds are read
+ * on the device, so the call waits for `stream` once (it cannot be part of a stream capture). */
 enum gnn_ragged_kind {
     GNN_RC_COPY_F32 = 0,        /* dst[i] = src[i]                                 (float32)                          */
     GNN_RC_COPY_I32_ADD = 1,    /* dst[i] = src[i] + iadd                          (int32: ids, row pointers)          */
@@ -475,8 +476,11 @@ enum gnn_ragged_kind {
     GNN_RC_FILL_F32 = 3,        /* dst[i] = fval                                                                       */
     GNN_RC_FILL_I32 = 4,        /* dst[i] = iadd                                                                       */
     GNN_RC_IOTA_I32 = 5,        /* dst[i] = iadd + i                                                                   */
-    GNN_RC_COPY_U8 = 6          /* dst[i] = src[i]                                 (bytes: bool masks)                 */
+    GNN_RC_COPY_U8 = 6,         /* dst[i] = src[i]                                 (bytes: bool masks)                 */
+    GNN_RC_TYPE_ROWS_U8 = 7     /* dst[t * iadd + i] = (src[i] == t), t < width    (bytes: src = a type id per node, dst = all
+                                 * `width` rows of a one-hot type mask whose rows are `iadd` bytes apart; count = nodes)       */
 };
+#define GNN_RC_KIND_MAX 7
 #define GNN_RC_CHUNK 2048
 typedef struct gnn_ragged_desc {
     const void *src;          /* NULL for fills                                                                        */
@@ -485,7 +489,7 @@ typedef struct gnn_ragged_desc {
     int32_t kind;             /* enum gnn_ragged_kind                                                                  */
     int32_t iadd;
     float fval;
-    int32_t width;            /* GNN_RC_COPY_ROWS_ADD2: columns per row                                                */
+    int32_t width;            /* GNN_RC_COPY_ROWS_ADD2: columns per row; GNN_RC_TYPE_ROWS_U8: number of types (rows)    */
 } gnn_ragged_desc_t;
 int gnn_ragged_copy(const gnn_ragged_desc_t *desc, int32_t n_desc, const int32_t *blk_begin, int32_t n_blocks, void *stream);
 
