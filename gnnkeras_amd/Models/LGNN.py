@@ -28,6 +28,7 @@ from .training import LoopTrainer
 
 
 SERIAL_PROPAGATION = ('per_graph', 'grouped')
+JOINT_STEP = ('auto', 'library', 'blocks')
 
 
 def plan_runs(sizes, cap, max_nodes, max_graphs=1 << 20):
@@ -93,6 +94,10 @@ class LGNN(_LoopModel):
         # 'grouped' = runs of consecutive graphs as convergence groups of one call (same results, same order of the moving statistics)
         self.serial_propagation = 'per_graph'
         self.serial_run_bytes = 512 << 20          # workspace a grouped run may ask for (bounds the graphs per run)
+        # how a joint step ('parallel' / 'residual') runs: 'library' = every layer as two library calls (`gnn_train_step_ex` phases 1 and 2,
+        # docs/joint_lgnn_step.md), 'blocks' = the building blocks driven from here, 'auto' = 'library' where it applies
+        self.joint_step = 'auto'
+        self.last_joint_route = None
         self._engine_init()
 
     # the class <-> name maps of the reference (`__gnnClass__`, `__gnnClassLoader__`)
@@ -139,12 +144,17 @@ class LGNN(_LoopModel):
         dirs = sorted((d for d in os.listdir(path) if os.path.isdir(f'{path}{d}')), key=lambda d: int(d[3:]))
         return cls(gnns=[gnn_class.load(f'{path}{d}') for d in dirs], **config)
 
-    def compile(self, *args, training_mode: str = 'parallel', average_st_grads: bool = False, serial_propagation: str = 'per_graph', **kwargs):
+    def compile(self, *args, training_mode: str = 'parallel', average_st_grads: bool = False, serial_propagation: str = 'per_graph',
+                joint_step: str = 'auto', **kwargs):
         """`training_mode` in 'serial' (layers trained one after another), 'parallel' (loss = mean of the layers' losses),
         'residual' (loss of the mean of the layers' outputs) — reference LGNN.py:133-152.  `serial_propagation` (additive; serial mode):
         'per_graph' - between two layers every graph runs alone through the trained layer, one library call each - or 'grouped' - the
-        same arithmetic with the graphs as convergence groups of one call per run (docs/serial_propagation.md)."""
+        same arithmetic with the graphs as convergence groups of one call per run (docs/serial_propagation.md).  `joint_step` (additive;
+        'parallel' / 'residual'): 'library' - every layer's forward and backward as one library call each, 'blocks' - the building blocks,
+        'auto' - 'library' where it applies; `last_joint_route` records what a step took (docs/joint_lgnn_step.md)."""
         if training_mode not in ('serial', 'parallel', 'residual'): raise ValueError('unknown training_mode')
+        if joint_step not in JOINT_STEP: raise ValueError(f'joint_step must be one of {JOINT_STEP}')
+        self.joint_step = joint_step
         if serial_propagation not in SERIAL_PROPAGATION: raise ValueError(f'serial_propagation must be one of {SERIAL_PROPAGATION}')
         self.serial_propagation = serial_propagation
         super().compile(*args, average_st_grads=average_st_grads, **kwargs)
@@ -228,8 +238,17 @@ class LGNN(_LoopModel):
         i_set = 4 if len(x) == 10 else 3                           # composite lists carry type_mask at [3]
         nodes_0, arcs_0, dim0, set_mask, output_mask = x[0], x[1], x[2], x[i_set], x[i_set + 1]
         s0 = state0 if state0 is not None else [None] * self.LAYERS
-        trainers = [LoopTrainer(g) for g in self.gnns]
         for g in self.gnns: g.loss = self.loss
+        if self.joint_step not in JOINT_STEP: raise ValueError(f'joint_step must be one of {JOINT_STEP}')
+        why = None if self.joint_step == 'blocks' else self._joint_library_refusal(x)
+        if self.joint_step == 'library' and why is not None:
+            raise NotImplementedError(f"joint_step='library' does not apply here: {why}")
+        if self.joint_step != 'blocks' and why is None:
+            self.last_joint_route = 'library'
+            return self._train_step_library(x, y, sample_weight, s0, seed, apply)
+        self.last_joint_route = 'blocks'
+        self.resolve_joint_pending()
+        trainers = [LoopTrainer(g) for g in self.gnns]
         graph_based = self.GNN_CLASS is self._gnn_classes['graph']
         arc_based = self.GNN_CLASS is self._gnn_classes['arc']
         tapes, outs = [], []
@@ -283,6 +302,126 @@ class LGNN(_LoopModel):
             self._optimizer_obj().apply_gradients(gv)
         self._last_tapes = tapes
         out = {'loss': loss, 'k': [tp.k for tp in tapes]}
+        yd = y.to(outs[-1].device)
+        sw = torch.ones(yd.shape[0], device=yd.device) if sample_weight is None else sample_weight.to(yd.device)
+        for mtr in self.metrics_spec:
+            n, f = _metric_fn(mtr, yd.shape[-1])
+            out[n] = (f(yd, outs[-1]) * sw).sum() / sw.sum()
+        return out
+
+    # ---- the joint step inside the library (docs/joint_lgnn_step.md) --------------------------------------------------------------------------
+    def _joint_trainers(self):
+        """One trainer per layer, kept across steps: its tape, gradient holders and the optimizer's pointer tables with it."""
+        tr = getattr(self, '_joint_trs', None)
+        if tr is None or len(tr) != self.LAYERS or any(t.model is not g for t, g in zip(tr, self.gnns)):
+            tr = self._joint_trs = [LoopTrainer(g) for g in self.gnns]
+        return tr
+
+    def _joint_library_refusal(self, x):
+        """None when this batch can take the library route, else the reason (a joint step takes one route or the other, never a mix)."""
+        from .. import _native as nat
+        if len(x) != 8 or any(isinstance(g.net_state, (list, tuple)) for g in self.gnns): return 'composite layers train through the building blocks'
+        if self.LAYERS > 16: return 'more than 16 layers'
+        nodes, arcs = x[0], x[1]
+        if not (isinstance(nodes, torch.Tensor) and nodes.is_cuda): return 'the batch is not on the device'
+        N, E, L, A = int(nodes.shape[0]), int(arcs.shape[0]), int(nodes.shape[1]), int(arcs.shape[1]) - 2
+        arc_based = self.GNN_CLASS is self._gnn_classes['arc']
+        for tr, g in zip(self._joint_trainers(), self.gnns):
+            if not tr._native_phases_apply(N, E, L, A, 1):      # (coverage depends on the dims and the networks, not on the rows of the mask)
+                return 'a layer is not covered by the phased in-library step (Dropout in front of a first Dense, a loss without a device gradient, ' \
+                       'max_iteration < 1, or a batch of the row-streaming size)'
+            S = g.state_vect_dim if g.state_vect_dim > 0 else L
+            T = int(g.net_output.units[-1])
+            L, A = nodes.shape[1] + (S if self.get_state else 0) + (T if self.get_output and not arc_based else 0), \
+                arcs.shape[1] - 2 + (T if self.get_output and arc_based else 0)
+        return None
+
+    def resolve_joint_pending(self, failed=None):
+        """Settle the last applied joint step of the library route: was its update gated off on the device (a barrier wait of a persistent
+        backward launch expired)?  `failed` None: read the gate word (one synchronisation) - what `fit()` does behind its last step and
+        `train_step` when a tape was reallocated; else what the layers' phase-1 calls fetched for free.  A discarded update had been
+        counted on the host: the count is taken back, with a RuntimeWarning.  The batch is not trained again."""
+        import warnings
+        pending, self._joint_pending = getattr(self, '_joint_pending', False), False
+        if not pending: return
+        if failed is None:
+            gate = getattr(self, '_joint_gate', None)
+            failed = gate is not None and int(gate.item()) == 0
+        if failed:
+            warnings.warn('the previous joint LGNN step was discarded on the device (a persistent backward kernel could not keep its workgroups '
+                          'resident): weights and optimizer slots untouched', RuntimeWarning, stacklevel=3)
+            opt = self._optimizer_obj()
+            if isinstance(getattr(opt, 'iterations', None), int) and opt.iterations > 0: opt.iterations -= 1
+
+    def _train_step_library(self, x, y, sample_weight, s0, seed, apply):
+        """The joint step as LAYERS phase-1 calls followed by LAYERS phase-2 calls (`LoopTrainer.forward_phase` / `backward_phase`): the same
+        arithmetic and the same column bookkeeping as the building-block route of `train_step`, the label gradients computed by the library.
+        The optimizer update is all or nothing: one gate word over every layer's validity word; the moving statistics of a layer are gated
+        by that layer's own word."""
+        import ctypes as C
+        import warnings
+        from .. import _native as nat
+        from .training import Adam, SGD
+        i_set = 3
+        nodes_0, arcs_0, dim0, set_mask, output_mask = x[0], x[1], x[2], x[i_set], x[i_set + 1]
+        trainers = self._joint_trainers()
+        arc_based = self.GNN_CLASS is self._gnn_classes['arc']
+        Lyr = self.LAYERS
+        hs, nodes, arcs, dnl = [], nodes_0, arcs_0, dim0
+        for i, tr in enumerate(trainers):
+            h = tr.forward_phase(self._layer_x(x, nodes, arcs, dnl), state0=s0[i], seed=seed)
+            hs.append(h)
+            if i < Lyr - 1: nodes, arcs, dnl = self.update_graph(nodes_0, arcs_0, dnl, set_mask, output_mask, h.state, h.out_nodes)
+        # the previous applied joint step: every phase 1 above fetched its layer's word for free at its synchronisation; a layer whose tape
+        # was reallocated in between fetched nothing, and the gate word itself is read then (before this step overwrites it)
+        fetched = [h.prev_ok for h in hs if h.prev_ok is not None]
+        self.resolve_joint_pending(failed=(any(ok is False for ok in fetched) if len(fetched) == Lyr else None))
+        outs = [h.y_pred for h in hs]
+        dmean = None
+        if self.training_mode == 'residual':
+            mean_out = sum(outs) / Lyr
+            loss, dmean = trainers[-1].loss_and_grad(hs[-1], mean_out, y, sample_weight)
+            dmean = dmean / Lyr
+        d_state_extra, d_out_extra = None, None
+        for i in range(Lyr - 1, -1, -1):
+            h, tr = hs[i], trainers[i]
+            arc_out = arc_based and self.get_output and i > 0        # the layer below wrote its output into the ARC labels
+            if dmean is None:
+                tr.backward_phase(h, y, sample_weight, loss_scale=1.0 / Lyr, d_out_extra=d_out_extra, d_state_extra=d_state_extra,
+                                  want_label_grads=i > 0, want_arc_label_grads=arc_out)
+            else:
+                tr.backward_phase(h, None, None, d_pred_extra=dmean, d_out_extra=d_out_extra, d_state_extra=d_state_extra,
+                                  want_label_grads=i > 0, want_arc_label_grads=arc_out)
+            d_state_extra = d_out_extra = None
+            if i > 0:                                               # (the column bookkeeping of `train_step`)
+                prev, d_nodes = hs[i - 1], h.d_nodes
+                col = 0
+                if self.get_state:
+                    d_state_extra = d_nodes[:, :prev.S].contiguous(); col = prev.S
+                if self.get_output and not arc_based:
+                    d_out_extra = d_nodes[:, col:col + prev.T].index_select(0, prev.out_index.long()).contiguous()
+                elif arc_out:
+                    d_out_extra = torch.zeros((prev.M, prev.T), dtype=torch.float32, device=h.dev)
+                    if prev.T > 2:
+                        d_out_extra[:, 2:] = h.d_arc_labels[:, :prev.T - 2].index_select(0, prev.out_index.long())
+        if dmean is None: loss = sum(h.loss[0] for h in hs) / Lyr
+        for h, tr in zip(hs, trainers): tr.finish(h, apply=False)
+        if apply:
+            gv = [pair for h in hs for pair in LoopTrainer.grads_and_vars(h)]
+            opt = self._optimizer_obj()
+            if isinstance(opt, (Adam, SGD)):
+                dev = hs[0].dev
+                gate = getattr(self, '_joint_gate', None)
+                if gate is None or gate.device != dev: gate = self._joint_gate = torch.zeros(1, dtype=torch.int32, device=dev)
+                words = (C.c_void_p * Lyr)(*[h.grads_ok for h in hs])
+                nat.check(nat.lib().gnn_gate_all(words, Lyr, nat.ptr(gate), nat.current_stream(dev)))
+                opt.apply_gradients(gv, gate=gate.data_ptr())
+                for h, tr in zip(hs, trainers): tr._joint_word_tape = h.tape      # the next phase 1 on this tape reads the word for free
+                self._joint_pending = True
+            elif all(LoopTrainer._read_word(h.grads_ok_view) for h in hs):      # a foreign optimizer knows nothing of the gate: read the words
+                opt.apply_gradients(gv)
+        self._last_tapes = hs
+        out = {'loss': loss, 'k': [h.k for h in hs]}
         yd = y.to(outs[-1].device)
         sw = torch.ones(yd.shape[0], device=yd.device) if sample_weight is None else sample_weight.to(yd.device)
         for mtr in self.metrics_spec:
@@ -418,7 +557,8 @@ class LGNN(_LoopModel):
         another, each on the graphs relabelled with its predecessor's states / outputs; `callbacks`, when given, is a list of
         LAYERS callback lists - entry i goes to layer i's fit (reference :299-303)."""
         if self.training_mode != 'serial':
-            return super().fit(sequencer, epochs=epochs, validation_data=validation_data, verbose=verbose, **kwargs)
+            try: return super().fit(sequencer, epochs=epochs, validation_data=validation_data, verbose=verbose, **kwargs)
+            finally: self.resolve_joint_pending()          # (the last step's gate word: nothing follows it that would fetch it)
         from ..Sequencers.GraphSequencers import SingleGraphSequencer
         if any(isinstance(s, SingleGraphSequencer) for s in (sequencer, validation_data)):
             # (the reference cannot either: it zips the layer's results with `sequencer.data`, LGNN.py:330-331, one graph object there)

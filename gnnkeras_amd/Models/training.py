@@ -906,7 +906,7 @@ class LoopTrainer:
         return r['k'], r['state'], r['y_pred']
 
     def _train_step_native(self, x_list, y, sample_weight, state0, seed, apply, forward_only=False, node_level=False, groups=None,
-                           group_out_begin=None):
+                           group_out_begin=None, phase_forward=False):
         """One `gnn_train_step` call: training-mode forward, loss, BPTT; the tape and every scratch buffer live in one cached
         device allocation. Same results as the general path (same kernels for the arithmetic), ~2.5x fewer launches and no
         Python between them.  `forward_only`: the forward alone (no targets, no gradients; `Loop(..., training=True)`)."""
@@ -937,7 +937,7 @@ class LoopTrainer:
         focus = 'n' if (forward_only and node_level and m._focus == 'g') else m._focus
         for n_ in nets_s: n_.to(dev)
         m.net_output.to(dev)
-        if forward_only: self.resolve_pending()                  # (the tape is shared with the steps: nothing of theirs may be pending on it)
+        if forward_only or phase_forward: self.resolve_pending()   # (the tape is shared with the steps: nothing of theirs may be pending on it)
         # gnn_train_step OVERWRITES every gradient buffer: the holders of the previous step are reused as they are (eight zero-fill
         # launches and their allocations per step otherwise; the optimizer's pointer tables stay valid too)
         gs_all = [] if forward_only else [self._cached_grads(f'state{i}' if composite else 'state', n_, p) for i, n_ in enumerate(nets_s)]
@@ -998,7 +998,7 @@ class LoopTrainer:
             n_rows = ng['n_dst']
         a.stream = p.stream()
         ta.forward_only = int(bool(forward_only))
-        if not forward_only:
+        if not forward_only and not phase_forward:
             yd = y.to(dev, torch.float32).contiguous()
             if yd.shape[0] != n_rows: raise ValueError(f'targets have {yd.shape[0]} rows, the model outputs {n_rows}')
             sw = None if sample_weight is None else sample_weight.to(dev, torch.float32).contiguous()
@@ -1079,6 +1079,32 @@ class LoopTrainer:
         base = tape.data_ptr()
         aligned = (base + 255) & ~255
         ta.tape, ta.tape_bytes = C.c_void_p(aligned), tape.numel() - (aligned - base)
+        if phase_forward:
+            # phase 1 of `gnn_train_step_ex` (include/gnnloop.h): everything up to the output network and the pooling, the tape kept for
+            # `backward_phase`.  The handle carries the argument blocks (phase 2 runs on the SAME ones) and what an LGNN layer hands on.
+            if nat.lib().gnn_train_phases_supported(C.byref(ta)) != 0:
+                raise NotImplementedError('the phased in-library step does not cover this shape (gnn_train_phases_supported)')
+            ps, px = nat.TrainPhaseState(), nat.TrainPhaseArgs()
+            px.phase, px.phase_state = nat.TRAIN_PHASE_FORWARD, C.pointer(ps)
+            out_nodes = y_pred
+            if focus == 'g':
+                out_nodes = p.new(len(out_index), T)
+                px.node_out = nat.ptr(out_nodes)
+            ok_ptr, prev_ok = C.c_void_p(0), C.c_int32(1)
+            ta.grads_ok_dev = C.pointer(ok_ptr)
+            fetched = getattr(self, '_joint_word_tape', None) is tape      # the word of the last applied joint step on this tape, for free
+            self._joint_word_tape = None
+            if fetched:
+                prev_ok.value = -1
+                ta.prev_grads_ok_host = C.pointer(prev_ok)
+            nat.check(nat.lib().gnn_train_step_ex(C.byref(ta), C.byref(px)))
+            ta.prev_grads_ok_host = C.POINTER(C.c_int32)()
+            view = tape[aligned - base:aligned - base + 4].view(torch.int32)
+            E, A = int(arcs.shape[0]), int(arcs.shape[1]) - 2
+            return SimpleNamespace(ta=ta, px=px, ps=ps, keep=keep + [k_host, ok_ptr, y_pred, state, loss, out_nodes, tiles], gs=gs_all, go=go, k=int(k_host.value),
+                                   y_pred=y_pred, state=state, out_nodes=out_nodes, loss=loss, grads_ok=ok_ptr.value, grads_ok_view=view,
+                                   prev_ok=(None if not fetched or prev_ok.value < 0 else bool(prev_ok.value)), tape=tape, dev=dev, p=p,
+                                   N=N, L=L, S=S, T=T, M=len(out_index), E=E, A=A, out_index=out_index, arcnode=arcnode, n_rows=n_rows)
         if forward_only:
             nat.check(nat.lib().gnn_train_step(C.byref(ta)))
             if xc_fill: adjacency.constants_line_filled()
@@ -1120,6 +1146,74 @@ class LoopTrainer:
         res['grads_ok'] = view                                   # device int32[1]: 1 when the gradients / the update of this step are valid
         if failed_prev: self._recover_failed(pend, uncount=False)      # the PREVIOUS step's batch, one step late
         return res
+
+    # ---- the step in two phases (gnn_train_step_ex): what a joint LGNN step is made of (docs/joint_lgnn_step.md) ---------------------------------
+    def _native_phases_apply(self, n_nodes, n_arcs, dim_node_label, dim_arc_label, n_out):
+        """May a batch of these dims run as `forward_phase` + `backward_phase`?  Today's `_native_step_applies` conditions (no data
+        parallelism, no Dropout in front of a first Dense, a loss with a device gradient), a homogeneous model, and the library's own answer
+        (`gnn_train_phases_supported`: dims and network descriptions only, nothing is launched)."""
+        m = self.model
+        if isinstance(m.net_state, (list, tuple)) or m.max_iteration < 1: return False
+        if not self._native_step_applies(True): return False
+        ta = nat.TrainArgs()
+        a = ta.loop
+        a.abi_version, a.n_types = nat.GNN_ABI_VERSION, 1
+        a.n_nodes, a.n_arcs, a.dim_node_label, a.dim_arc_label = int(n_nodes), int(n_arcs), int(dim_node_label), int(dim_arc_label)
+        a.state_dim, a.max_iteration, a.state_threshold = m.state_vect_dim, m.max_iteration, float(m.state_threshold)
+        for dst, net in ((a.net_state[0], m.net_state), (a.net_output, m.net_output)):
+            units = [int(u) for u in net.units]
+            dst.in_dim, dst.n_layers = int(net.input_dim), len(units)
+            for i, (u, act) in enumerate(zip(units, net.activations)): dst.units[i], dst.activation[i] = u, nat.ACTIVATIONS[act]
+        a.focus, a.n_out = nat.FOCUS[m._focus], int(n_out)
+        return nat.lib().gnn_train_phases_supported(C.byref(ta)) == 0
+
+    def forward_phase(self, x_list, state0=None, seed=None):
+        """Phase 1: the training-mode forward of one batch inside the library with the tape kept - y_pred, state, k and the per-node /
+        per-arc outputs before the pooling (`out_nodes`) are there when it returns (the step's one synchronisation).  Returns the handle
+        `backward_phase` takes; the trainer's tape belongs to it until then.  `prev_ok`: validity of the last applied joint step on this
+        tape (None: nothing to report).  A shape the library does not cover raises NotImplementedError before anything is launched."""
+        return self._train_step_native(x_list, None, None, state0, seed, False, phase_forward=True)
+
+    def backward_phase(self, h, y=None, sample_weight=None, loss_scale=1.0, d_pred_extra=None, d_out_extra=None, d_state_extra=None,
+                       want_label_grads=False, want_arc_label_grads=False):
+        """Phase 2 on the handle of `forward_phase`: the loss of `y` (None: no loss of its own, `GNN_LOSS_NONE`) times `loss_scale`, plus
+        the upstream gradients `d_pred_extra` [rows, T] (task level), `d_out_extra` [M, T] (per-node / per-arc outputs) and `d_state_extra`
+        [N, S]; back-propagation through the tape.  The parameter gradients land in `h.gs[0]` / `h.go` (overwritten), `h.loss` holds the
+        unscaled loss; `want_label_grads` / `want_arc_label_grads` leave d loss / d nodes in `h.d_nodes` [N, L] and d loss / d arc labels
+        in `h.d_arc_labels` [E, A].  Does not synchronise; `h.grads_ok` is the step's validity word."""
+        m, p, ta, px = self.model, h.p, h.ta, h.px
+        dev = h.dev
+        px.phase = nat.TRAIN_PHASE_BACKWARD
+        if y is None:
+            ta.loss_kind = nat.LOSS_NONE
+        else:
+            yd = y.to(dev, torch.float32).contiguous()
+            if yd.shape[0] != h.n_rows: raise ValueError(f'targets have {yd.shape[0]} rows, the model outputs {h.n_rows}')
+            sw = None if sample_weight is None else sample_weight.to(dev, torch.float32).contiguous()
+            ta.targets, ta.sample_weight = nat.ptr(yd), nat.ptr(sw)
+            kind = m.loss if isinstance(m.loss, str) else getattr(m.loss, '__name__', str(m.loss))
+            ta.loss_kind = nat.LOSSES[str(kind).lower()]
+            h.keep += [yd, sw]
+        px.loss_scale = float(loss_scale)
+        for name, t, shape in (('d_pred_extra', d_pred_extra, (h.n_rows, h.T)), ('d_out_extra', d_out_extra, (h.M, h.T)),
+                               ('d_state_extra', d_state_extra, (h.N, h.S))):
+            if t is None: continue
+            t = t.to(dev, torch.float32).contiguous()
+            if tuple(t.shape) != shape: raise ValueError(f'{name} must be {shape}, got {tuple(t.shape)}')
+            setattr(px, name, nat.ptr(t)); h.keep.append(t)
+        h.d_nodes = h.d_arc_labels = None
+        if want_label_grads:
+            h.d_nodes = p.new(h.N, h.L)
+            px.d_nodes, px.ld_d_nodes = nat.ptr(h.d_nodes), h.L
+        if want_arc_label_grads:
+            h.d_arc_labels = p.zeros(h.E, h.A)
+            if h.E > 0 and h.A > 0:
+                px.d_arc_labels = nat.ptr(h.d_arc_labels)
+                px.arcnode_by_source = nat.make_csr(_by_source(h.arcnode, dev))
+        nat.check(nat.lib().gnn_train_step_ex(C.byref(ta), C.byref(px)))
+        for g_ in h.gs: g_.touched = h.k > 0
+        h.go.touched = h.M > 0
+        return h
 
     def train_step(self, x_list, y, sample_weight, state0=None, seed=None, apply=True):
         """Returns dict(loss=..., k=..., y_pred=tensor). Gradients stay in self.gs (list for composite models) / self.go;

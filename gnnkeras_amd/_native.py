@@ -37,6 +37,7 @@ EXPORTS = ['gnn_last_error', 'gnn_last_kernel_name', 'gnn_abi_version', 'gnn_str
            'gnn_colstats_workspace_bytes', 'gnn_colstats', 'gnn_first_layer_param_grads', 'gnn_bn_input_grad',
            'gnn_scatter_add_rows', 'gnn_axpby', 'gnn_loss_grad', 'gnn_dropout', 'gnn_adam_step', 'gnn_adam_multi', 'gnn_sgd_step',
            'gnn_converged_gated', 'gnn_aggregate_gated', 'gnn_train_workspace_bytes', 'gnn_train_step', 'gnn_train_groups_supported', 'gnn_ragged_copy',
+           'gnn_train_step_ex', 'gnn_train_phases_supported', 'gnn_gate_all',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_destroy', 'gnn_shard_loop']
 GNN_MAX_SEGMENTS = 6
 LOSSES = {'categorical_crossentropy': 0, 'cce': 0, 'binary_crossentropy': 1, 'bce': 1, 'mse': 2,
@@ -133,6 +134,21 @@ class TrainArgs(C.Structure):
                 ('forward_only', C.c_int32),
                 # ABI 10: training-mode convergence groups (forward_only): host tables [n_groups + 1] of nodes / rows of out_index, k per group
                 ('group_node_begin', C.c_void_p), ('n_groups', C.c_int32), ('group_out_begin', C.c_void_p), ('k_groups', C.c_void_p)]
+
+
+# gnn_train_step_ex (additive, ABI 10): the step in two phases, upstream gradients in, label gradients out (include/gnnloop.h)
+TRAIN_PHASE_FORWARD, TRAIN_PHASE_BACKWARD = 1, 2
+LOSS_NONE = -1
+
+
+class TrainPhaseState(C.Structure):     # gnn_train_phase_state_t: written by phase 1, read by phase 2
+    _fields_ = [('magic', C.c_int32), ('k', C.c_int32), ('general_head', C.c_int32), ('reserved', C.c_int32)]
+
+
+class TrainPhaseArgs(C.Structure):      # gnn_train_phase_args_t: all-zero = gnn_train_step
+    _fields_ = [('phase', C.c_int32), ('loss_scale', C.c_float), ('phase_state', C.POINTER(TrainPhaseState)), ('node_out', C.c_void_p),
+                ('d_pred_extra', C.c_void_p), ('d_out_extra', C.c_void_p), ('d_state_extra', C.c_void_p),
+                ('d_nodes', C.c_void_p), ('ld_d_nodes', C.c_int32), ('d_arc_labels', C.c_void_p), ('arcnode_by_source', CSR)]
 
 
 # gnn_train_groups_supported(): 0 covered, -1 shape not covered, -2 malformed group arrays, g + 1 > 0: group g has too many nodes
@@ -280,6 +296,9 @@ def lib():
             'gnn_train_workspace_bytes': (sz, [C.POINTER(TrainArgs)]),
             'gnn_train_step': (C.c_int, [C.POINTER(TrainArgs)]),
             'gnn_train_groups_supported': (C.c_int, [C.POINTER(TrainArgs)]),
+            'gnn_train_step_ex': (C.c_int, [C.POINTER(TrainArgs), C.POINTER(TrainPhaseArgs)]),
+            'gnn_train_phases_supported': (C.c_int, [C.POINTER(TrainArgs)]),
+            'gnn_gate_all': (C.c_int, [vp, i32, vp, vp]),
             'gnn_loop_xc_applies': (C.c_int, [C.POINTER(LoopArgs)]),
             'gnn_loop_group_max_nodes': (C.c_int, [C.POINTER(LoopArgs)]),
             'gnn_train_xc_applies': (C.c_int, [C.POINTER(TrainArgs)]),
@@ -299,7 +318,8 @@ def lib():
         if (l.gnn_struct_size(0), l.gnn_struct_size(1), l.gnn_struct_size(2), l.gnn_struct_size(3)) != \
                 (C.sizeof(CSR), C.sizeof(MLP), C.sizeof(LoopArgs), LoopArgs.flags.offset) or \
                 (l.gnn_struct_size(4), l.gnn_struct_size(5), l.gnn_struct_size(6), l.gnn_struct_size(7)) != \
-                (C.sizeof(TrainArgs), TrainArgs.tape.offset, C.sizeof(RaggedDesc), C.sizeof(ShardLoopArgs)):
+                (C.sizeof(TrainArgs), TrainArgs.tape.offset, C.sizeof(RaggedDesc), C.sizeof(ShardLoopArgs)) or \
+                (l.gnn_struct_size(8), l.gnn_struct_size(9)) != (C.sizeof(TrainPhaseArgs), C.sizeof(TrainPhaseState)):
             raise NativeError('ctypes struct layout does not match libgnnloop.so: rebuild it')
         _lib = l
     return _lib

@@ -1345,6 +1345,8 @@ size_t gnn_struct_size(int which) {
         case 5: return offsetof(gnn_train_args_t, tape);
         case 6: return sizeof(gnn_ragged_desc_t);
         case 7: return sizeof(gnn_shard_loop_args_t);
+        case 8: return sizeof(gnn_train_phase_args_t);
+        case 9: return sizeof(gnn_train_phase_state_t);
         default: return 0;
     }
 }

@@ -541,9 +541,13 @@ struct TrainSmallBwd {
     float inv_n;                 // 1 / N
     float *err;                  // [1] = 2 when a barrier timed out
     unsigned long long wait_ticks;   // bound of a barrier wait (buffer_ops.hpp: wait_until)
+    // label gradients (gnn_train_step_ex; read by the LAB instantiations only; NULL: not wanted - uniform over the grid).  Rows of S floats, homogeneous models.
+    float *dz_out;               // [N][S] sum over the executed iterations of dZ_t (kernels_train_labels.hpp turns it into the constants' gradients)
+    float *g0_out;               // [N][S] d loss / d state_0 (state_dim == 0: state_0 = nodes)
 };
 
-template <int SQ, bool HAS_W, bool LOCAL>
+// LAB: the instantiation that also stores sum_t dZ_t / d loss / d state_0 (label gradients); LAB = false is the kernel without them
+template <int SQ, bool HAS_W, bool LOCAL, bool LAB = false>
 __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(TrainSmallBwd a, TileTab tt, TypeTab yt, TypeConsts yc) {
     using Csr = TileCsr<SQ, HAS_W, LOCAL>;
     constexpr int S = 16 * SQ, LPR = S / 4, NPP = Csr::NPP, NPASS = Csr::NPASS;
@@ -802,6 +806,21 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(TrainSmallBwd a, T
         TS_STAMP(7);
     }
     TS_WRITE(1);
+    // ---- label gradients wanted: sum_t dZ_t and d loss / d state_0 of the tile's rows, whole 16-byte row pieces ------------------------------------
+    if (LAB && a.dz_out) {
+#pragma unroll
+        for (int u = 0; u < NCH; ++u) {
+            const int rr = (tid + u * TS_NT) / LPR;
+            if (rr < nt) *reinterpret_cast<f32x4 *>(a.dz_out + (size_t)(n0 + rr) * S + 4 * ch) = dzsum[u];
+        }
+    }
+    if (LAB && a.g0_out) {
+#pragma unroll
+        for (int u = 0; u < NCH; ++u) {
+            const int rr = (tid + u * TS_NT) / LPR;
+            if (rr < nt) *reinterpret_cast<f32x4 *>(a.g0_out + (size_t)(n0 + rr) * S + 4 * ch) = *reinterpret_cast<const f32x4 *>(Gs + rr * LDZ + 4 * ch);
+        }
+    }
     // ---- the shares of this workgroup (heterogeneous models: the type's own arrays, one slot per tile of the type) ------------------------------
     float *pw = yt.n > 0 ? yt.partW[ty] + (size_t)(blockIdx.x - wg_lo) * ((size_t)in_s * a.Sw + a.Sw) : a.partW + (size_t)blockIdx.x * ((size_t)in_s * a.Sw + a.Sw);
     float *pb = !bn ? nullptr : yt.n > 0 ? yt.partBN[ty] + (size_t)(blockIdx.x - wg_lo) * 2 * in_s : a.partBN + (size_t)blockIdx.x * 2 * in_s;

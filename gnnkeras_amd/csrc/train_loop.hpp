@@ -11,6 +11,7 @@
 #include "kernels_train.hpp"
 #include "kernels_train_big.hpp"
 #include "kernels_train_small.hpp"
+#include "kernels_train_labels.hpp"
 
 namespace {
 
@@ -98,6 +99,9 @@ struct TrainPlan {
     bool small, tiled; int n_wg;
     int SPs, ldS;                // small path: the padded state width the persistent kernels run (16 / 32 / 64) and the tape's row stride
     float *sm_cc, *sm_part, *sm_partW, *sm_partBN; unsigned long long *sm_bar;
+    // label gradients (gnn_train_step_ex, not on the row-streaming path): sum_t dZ_t of the first state layer [N][ld_dz], d loss / d state_0
+    // [N][SPs] (persistent kernels), the gradients of the own / aggregated label columns [N][L] and of the aggregated arc labels [N][A]
+    float *dz_sum, *g0, *lab_own, *lab_agg, *arc_agg; int ld_dz;
     size_t bytes;
 };
 
@@ -243,6 +247,12 @@ int make_train_plan(const gnn_train_args_t &ta, void *ws, TrainPlan &p) {
     p.sm_partW = c.take<float>(p.small ? (size_t)p.n_wg * (p.in_s + 1) * p.S : 0);
     p.sm_partBN = c.take<float>(p.small ? (size_t)p.n_wg * 2 * p.in_s : 0);
     p.sm_bar = c.take<unsigned long long>(p.small ? 4 : 0);
+    p.ld_dz = p.small ? p.SPs : p.H1s;
+    p.dz_sum = c.take<float>(p.big ? 0 : (size_t)p.N * p.ld_dz);
+    p.g0 = c.take<float>(p.small ? (size_t)p.N * p.SPs : 0);
+    p.lab_own = c.take<float>(p.big ? 0 : (size_t)p.N * std::max(p.L, 1));
+    p.lab_agg = c.take<float>(p.big ? 0 : (size_t)p.N * std::max(p.L, 1));
+    p.arc_agg = c.take<float>(p.big ? 0 : (size_t)p.N * std::max(p.A, 1));
     p.cs.m = &ns; p.cs.g = &ta.grad_state; p.co.m = &no; p.co.g = &ta.grad_output;
     p.bytes = (c.off + 255) & ~(size_t)255;
     return 0;
@@ -363,7 +373,8 @@ int act_grad_inplace(float *G, int ldg, const float *Y, int ldy, int M, int H, i
 // `first_col`: the block starts at that input column instead of 0 (composite models: the state segment sits behind the type's labels).
 // `drop`: the Dropout layers of this call (their forward copies in drop->buf[]; the masks are regenerated from the call's keys).
 int net_backward(NetCtx &x, const gnn::Seg *segs, int nseg, float *const *hs, float *G, int ldg, int M, const float *stats, bool accumulate,
-                 float *dx_all, int kdx, float *part, hipStream_t st, int second_row = -1, int first_col = 0, const DropRun *drop = nullptr) {
+                 float *dx_all, int kdx, float *part, hipStream_t st, int second_row = -1, int first_col = 0, const DropRun *drop = nullptr,
+                 float *dz_acc = nullptr) {
     const gnn_mlp_t &m = *x.m;
     int n_chunks;
     const int rpc = rows_per_chunk_for(std::max(M, 1), &n_chunks);
@@ -387,6 +398,11 @@ int net_backward(NetCtx &x, const gnn::Seg *segs, int nseg, float *const *hs, fl
     for (int s = 0; s < nseg; ++s) Kv += segs[s].width;
     const bool allk = Kv == K && K <= 192 && H <= 64 && n_chunks >= 256;
     TRY(act_grad_inplace(G, ldg, hs[0], H, M, H, m.activation[0], st));
+    if (dz_acc && M > 0) {            // label gradients: sum over the iterations of the first layer's dZ ([M x H], kernels_train_labels.hpp)
+        if (ldg != H) return fail("net_backward: dZ of the first layer is not contiguous");
+        gnn::k_axpby<<<std::min(cdiv((long)M * H, 256), 1024), 256, 0, st>>>(1.0f, G, 1.0f, dz_acc, dz_acc, (size_t)M * H);
+        LAUNCH_OK();
+    }
     {
         gnn::GradSegs gs;
         memset(&gs, 0, sizeof(gs));
@@ -741,6 +757,12 @@ int launch_train_small_bwd_sq(const gnn::TrainSmallBwd &ba, const gnn::TileTab &
     memset(&nonec, 0, sizeof(nonec));
     const gnn::TypeTab &y = yt ? *yt : none;
     const gnn::TypeConsts &c = yc ? *yc : nonec;
+    if (ba.dz_out || ba.g0_out) {      // label gradients wanted (homogeneous models): the instantiations with the two extra stores
+        if (local) return has_w ? launch_persistent(&gnn::k_train_small_bwd<SQ, true, true, true>, ba, tt, n_wg, lds, st, y, c)
+                                : launch_persistent(&gnn::k_train_small_bwd<SQ, false, true, true>, ba, tt, n_wg, lds, st, y, c);
+        return has_w ? launch_persistent(&gnn::k_train_small_bwd<SQ, true, false, true>, ba, tt, n_wg, lds, st, y, c)
+                     : launch_persistent(&gnn::k_train_small_bwd<SQ, false, false, true>, ba, tt, n_wg, lds, st, y, c);
+    }
     if (local) return has_w ? launch_persistent(&gnn::k_train_small_bwd<SQ, true, true>, ba, tt, n_wg, lds, st, y, c)
                             : launch_persistent(&gnn::k_train_small_bwd<SQ, false, true>, ba, tt, n_wg, lds, st, y, c);
     return has_w ? launch_persistent(&gnn::k_train_small_bwd<SQ, true, false>, ba, tt, n_wg, lds, st, y, c)
@@ -829,11 +851,33 @@ int gnn_train_xc_applies(const gnn_train_args_t *args) {
     return p.big && p.Kc > 0 ? 1 : 0;
 }
 
-static int train_step_impl(const gnn_train_args_t &ta);
+static int train_step_impl(const gnn_train_args_t &ta, const gnn_train_phase_args_t &px);
 
-int gnn_train_step(const gnn_train_args_t *args) {
+int gnn_train_step(const gnn_train_args_t *args) { return gnn_train_step_ex(args, nullptr); }
+
+int gnn_train_phases_supported(const gnn_train_args_t *args) {
+    if (!args || args->loop.composite || args->n_groups != 0 || args->forward_only) return -1;
+    TrainPlan p;
+    if (make_train_plan(*args, nullptr, p)) return -1;
+    return (p.big || p.H1s > gnn::LG_MAX_H) ? -1 : 0;
+}
+
+int gnn_gate_all(const int32_t *const *words, int32_t n, int32_t *gate, void *stream) {
+    if (!words || !gate || n < 1 || n > gnn::GATE_MAX_WORDS) return fail("gnn_gate_all: 1 .. %d words and a gate", gnn::GATE_MAX_WORDS);
+    gnn::GateWords g;
+    memset(&g, 0, sizeof(g));
+    g.n = n;
+    for (int i = 0; i < n; ++i) { if (!words[i]) return fail("gnn_gate_all: word %d is NULL", i); g.w[i] = words[i]; }
+    gnn::k_gate_all<<<1, 1, 0, (hipStream_t)stream>>>(g, gate);
+    LAUNCH_OK();
+    return 0;
+}
+
+int gnn_train_step_ex(const gnn_train_args_t *args, const gnn_train_phase_args_t *px) {
     if (!args) return fail("args is NULL");
-    const int rc = train_step_impl(*args);
+    gnn_train_phase_args_t none;
+    memset(&none, 0, sizeof(none));
+    const int rc = train_step_impl(*args, px ? *px : none);
     // A call that fails behind its first launches has already fetched the previous step's validity word into *prev_grads_ok_host and reset
     // the word on the tape: the copy must have LANDED when the caller looks at it (the caller's own view of the word is stale by then).  A call
     // that fails in front of them leaves *prev_grads_ok_host as the caller initialised it (a sentinel) and the word on the tape untouched.
@@ -845,15 +889,45 @@ int gnn_train_step(const gnn_train_args_t *args) {
     return rc;
 }
 
-static int train_step_impl(const gnn_train_args_t &ta) {
+constexpr int32_t PHASE_MAGIC = 0x50483130;
+
+// the second argument block of gnn_train_step_ex against the plan: everything that refuses a call, before its first launch
+static int check_phase_args(const gnn_train_args_t &ta, const gnn_train_phase_args_t &px, const TrainPlan &p) {
+    if (px.phase == 0 && ta.loss_kind == GNN_LOSS_NONE) return fail("GNN_LOSS_NONE is valid in phase %d only (a whole step needs a loss of its own)", GNN_TRAIN_PHASE_BACKWARD);
+    if (px.phase == GNN_TRAIN_PHASE_FORWARD && ta.loss_kind == GNN_LOSS_NONE) { /* (the same args as the phase-2 call: the loss is not looked at) */ }
+    const bool used = px.phase != 0 || px.loss_scale != 0.0f || px.phase_state || px.node_out || px.d_pred_extra || px.d_out_extra || px.d_state_extra ||
+                      px.d_nodes || px.d_arc_labels;
+    if (!used) return 0;
+    if (p.big) return fail("gnn_train_step_ex: the row-streaming path (>= GNN_TRAIN_BIG_MIN_NODES nodes) has no phases / upstream gradients / label gradients: such steps train through the building blocks");
+    if (p.H1s > gnn::LG_MAX_H) return fail("gnn_train_step_ex: first state layer of %d units (at most %d)", p.H1s, gnn::LG_MAX_H);
+    if (px.phase != 0 && !px.phase_state) return fail("gnn_train_step_ex: phase %d needs phase_state", px.phase);
+    if (px.phase == GNN_TRAIN_PHASE_BACKWARD && px.phase_state->magic != PHASE_MAGIC) return fail("gnn_train_step_ex: phase_state was not filled by a phase-1 call");
+    if (px.phase == GNN_TRAIN_PHASE_BACKWARD && (px.phase_state->k < 0 || px.phase_state->k > p.K)) return fail("gnn_train_step_ex: phase_state holds k = %d", px.phase_state->k);
+    if (px.d_nodes && px.ld_d_nodes != 0 && px.ld_d_nodes < p.L) return fail("gnn_train_step_ex: ld_d_nodes %d < dim_node_label %d", px.ld_d_nodes, p.L);
+    if (px.d_arc_labels && p.A > 0 && p.E > 0) {
+        if (!px.arcnode_by_source.rowptr) return fail("gnn_train_step_ex: d_arc_labels needs arcnode_by_source");
+        TRY(check_csr(px.arcnode_by_source, "arcnode_by_source", p.E, p.N));
+    }
+    return 0;
+}
+
+static int train_step_impl(const gnn_train_args_t &ta, const gnn_train_phase_args_t &px) {
     const gnn_loop_args_t &a = ta.loop;
     TrainPlan p;
     if (!ta.tape || ((uintptr_t)ta.tape & 255) != 0) return fail("tape must be a 256-byte aligned device buffer");
     const bool fwd_only = ta.forward_only != 0;                   // ABI 9: the training-mode forward alone (no loss, no gradients)
+    const int phase = px.phase;
+    if (phase < 0 || phase > GNN_TRAIN_PHASE_BACKWARD) return fail("gnn_train_step_ex: unknown phase %d", phase);
+    if ((phase != 0 || px.loss_scale != 0.0f || px.d_pred_extra || px.d_out_extra || px.d_state_extra || px.d_nodes || px.d_arc_labels || px.node_out) &&
+        (ta.n_groups != 0 || a.composite || fwd_only))
+        return fail("gnn_train_step_ex: phases, upstream gradients and label gradients cover whole steps of homogeneous models only (gnn_train_phases_supported)");
+    const bool do_fwd = phase != GNN_TRAIN_PHASE_BACKWARD;        // phase 0 / 1: setup, loop, output network
+    const bool no_loss = ta.loss_kind == GNN_LOSS_NONE && phase != 0;
     if (ta.n_groups != 0) return train_forward_groups(ta);         // ABI 10: independent convergence groups (train_group.hpp)
     if (a.composite) return train_step_composite(ta);             // one state network per node type (train_composite.hpp); honours forward_only
     if (fwd_only && ta.prev_grads_ok_host) return fail("gnn_train_step(forward_only): prev_grads_ok_host must be NULL");
     TRY(make_train_plan(ta, ta.tape, p));
+    TRY(check_phase_args(ta, px, p));
     if (ta.tape_bytes < p.bytes) return fail("tape too small: %zu < %zu bytes", ta.tape_bytes, p.bytes);
     if (p.big && p.Kc > 0) TRY(check_xc_args(a));
     TRY(check_csr(a.adjacency, "adjacency", p.N, p.N));
@@ -868,10 +942,11 @@ static int train_step_impl(const gnn_train_args_t &ta) {
         TRY(check_csr(a.nodegraph, "nodegraph", p.G, p.M));
         if (!fwd_only) TRY(check_csr(ta.nodegraph_by_source, "nodegraph_by_source", p.M, p.G));
     }
-    if (p.R < 1 || (!fwd_only && !ta.targets)) return fail("gnn_train_step needs at least one target row");
-    if (!fwd_only && (ta.loss_kind < 0 || ta.loss_kind > 3)) return fail("unknown loss kind %d", ta.loss_kind);
-    if (!ta.y_pred || (!fwd_only && !ta.loss) || !ta.k_host || !ta.state) return fail("y_pred / loss / k_host / state is NULL");
-    if (!fwd_only) {
+    const bool own_loss = !fwd_only && phase != GNN_TRAIN_PHASE_FORWARD && !no_loss;      // (phase 1 stops in front of the loss)
+    if (p.R < 1 || (own_loss && !ta.targets)) return fail("gnn_train_step needs at least one target row");
+    if (own_loss && (ta.loss_kind < 0 || ta.loss_kind > 3)) return fail("unknown loss kind %d", ta.loss_kind);
+    if (!ta.y_pred || (own_loss && !ta.loss) || !ta.k_host || !ta.state) return fail("y_pred / loss / k_host / state is NULL");
+    if (!fwd_only && phase != GNN_TRAIN_PHASE_FORWARD) {
         TRY(check_grads(a.net_state[0], ta.grad_state, "grad_state"));
         TRY(check_grads(a.net_output, ta.grad_output, "grad_output"));
     }
@@ -885,10 +960,16 @@ static int train_step_impl(const gnn_train_args_t &ta) {
     // ---- setup: transposes, aggregates of the constants, state_0, iteration-invariant statistics -----------------------------------
     // the validity word the previous call on this tape left (stream-ordered behind that call's launches; on the host at this call's one
     // synchronisation), then this call's: 0 until the last launch of the step has been issued
+    gnn::Seg segs[GNN_MAX_SEGS];
+    gnn::TileTab tiles;
+    TRY(tile_table(ta, p, tiles));
+    if (!fwd_only && ta.grads_ok_dev) *ta.grads_ok_dev = p.grads_ok;
+    int k = 0;
+    if (!do_fwd) { k = px.phase_state->k; p.head_fast = false; }      // phase 2: what phase 1 learned at its synchronisation
+    if (do_fwd) {
     if (ta.prev_grads_ok_host) HIP_OK(hipMemcpyAsync(ta.prev_grads_ok_host, p.grads_ok, sizeof(int), hipMemcpyDeviceToHost, st));
     if (!fwd_only) {               // (a forward leaves the word of the last STEP on this tape as it is)
         HIP_OK(hipMemsetAsync(p.grads_ok, 0, sizeof(int) * 4, st));
-        if (ta.grads_ok_dev) *ta.grads_ok_dev = p.grads_ok;
         TRY(transposes(p.cs, st));
         TRY(transposes(p.co, st));
     }
@@ -904,7 +985,6 @@ static int train_step_impl(const gnn_train_args_t &ta) {
     if (a.state_dim > 0 && p.ldS == p.S) HIP_OK(hipMemcpyAsync(p.states, a.state0, sizeof(float) * NS, hipMemcpyDeviceToDevice, st));
     else if (a.state_dim > 0) TRY(launch_copy2d(nullptr, a.state0, p.S, p.states, p.ldS, p.N, p.S, p.ldS, st));
     else TRY(launch_copy2d(nullptr, a.nodes, a.ld_nodes, p.states, p.ldS, p.N, p.S, p.ldS, st));
-    gnn::Seg segs[GNN_MAX_SEGS];
     if (bn_s && p.K > 0) {
         const int n = state_segs(a, p, 0, segs);
         gnn::Seg cst[GNN_MAX_SEGS]; int nc = 0;
@@ -978,8 +1058,6 @@ static int train_step_impl(const gnn_train_args_t &ta) {
             LAUNCH_OK();
         }
     }
-    gnn::TileTab tiles;
-    TRY(tile_table(ta, p, tiles));
     if (p.small) {
         // Small graphs (kernels_train_small.hpp): all K gated iterations in one persistent launch, one workgroup per 64-node tile
         const gnn::ConstSegs cs = const_segs_of(a, p);
@@ -1035,15 +1113,19 @@ static int train_step_impl(const gnn_train_args_t &ta) {
     float k_f2[3] = {0.0f, 0.0f, 0.0f};
     HIP_OK(hipMemcpyAsync(k_f2, p.k_dev, 3 * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));                                  // the one host synchronisation of the step
-    const int k = (int)k_f2[0];
+    k = (int)k_f2[0];
     *ta.k_host = k;
     if (k_f2[1] == 1.0f) return fail("tile_node_begin: an arc of `adjacency` leaves its tile");
     if (k_f2[1] != 0.0f) return fail("a workgroup of the persistent training kernel never arrived at a grid barrier (not resident?)");
     if (k < 0 || k > p.K) return fail("iteration count %d out of range", k);
     if (k_f2[2] != 0.0f) p.head_fast = false;      // a permuted / repeated out_index of length n_nodes: the general head (gathers, scatter-add)
+    if (phase == GNN_TRAIN_PHASE_FORWARD) { px.phase_state->magic = PHASE_MAGIC; px.phase_state->k = k; px.phase_state->general_head = p.head_fast ? 0 : 1; px.phase_state->reserved = 0; }
+    }      // do_fwd
     const float *state_k = p.states + (size_t)k * NS;
-    if (p.ldS == p.S) HIP_OK(hipMemcpyAsync(ta.state, state_k, sizeof(float) * NS, hipMemcpyDeviceToDevice, st));
-    else TRY(launch_copy2d(nullptr, state_k, p.ldS, ta.state, p.S, p.N, p.S, p.S, st));
+    if (do_fwd) {
+        if (p.ldS == p.S) HIP_OK(hipMemcpyAsync(ta.state, state_k, sizeof(float) * NS, hipMemcpyDeviceToDevice, st));
+        else TRY(launch_copy2d(nullptr, state_k, p.ldS, ta.state, p.S, p.N, p.S, p.S, st));
+    }
     // The moving averages of BatchNormalization (one update per executed call).  On the persistent small-graph path they wait until the
     // backward launch has passed its grid barriers and are gated by the step's validity word: a step whose backward failed changes nothing.
     auto moving_state = [&](const int *gate) -> int {
@@ -1054,8 +1136,8 @@ static int train_step_impl(const gnn_train_args_t &ta) {
         }
         return 0;
     };
-    bool moving_output_pending = false;
-    if (!p.small) TRY(moving_state(nullptr));
+    bool moving_output_pending = p.small && bn_o && p.M > 0;      // (the output network's waits for the validity word on that path too)
+    if (!p.small && do_fwd) TRY(moving_state(nullptr));
 
     // ---- output network, training mode ---------------------------------------------------------------------------------------------
     gnn::Seg osegs[GNN_MAX_SEGS];
@@ -1065,8 +1147,10 @@ static int train_step_impl(const gnn_train_args_t &ta) {
     int n_state_segs = 0;
     if (p.M > 0) {
         if (a.focus == GNN_FOCUS_ARC) {
-            k_arc_endpoints<<<cdiv(p.M, 256), 256, 0, st>>>(a.out_index, a.arc_src, a.arc_dst, p.M, p.isrc, p.idst);
-            LAUNCH_OK();
+            if (do_fwd) {
+                k_arc_endpoints<<<cdiv(p.M, 256), 256, 0, st>>>(a.out_index, a.arc_src, a.arc_dst, p.M, p.isrc, p.idst);
+                LAUNCH_OK();
+            }
             const int *ends[2] = {p.isrc, p.idst};
             for (int e = 0; e < 2; ++e) {
                 bn_req_off[n_state_segs] = ocol; bn_req_idx[n_state_segs++] = ends[e];
@@ -1087,7 +1171,7 @@ static int train_step_impl(const gnn_train_args_t &ta) {
     float *ohs[GNN_MAX_LAYERS];
     for (int l = 0; l < no.n_layers; ++l) ohs[l] = (l == no.n_layers - 1 && !p.pooled && !drop_o_last) ? ta.y_pred : p.co.hid[l];
     float *out_nodes = drop_o_last ? dro.buf[no.n_layers] : ohs[no.n_layers - 1];
-    if (p.M > 0) {
+    if (p.M > 0 && do_fwd) {
         const float *W0 = no.kernel[0], *b0 = no.bias[0];
         if (bn_o) {
             if (p.head_fast && bn_s && k >= 1) {
@@ -1105,8 +1189,7 @@ static int train_step_impl(const gnn_train_args_t &ta) {
             } else
             TRY(colstats_segs(nullptr, osegs, nos, p.M, p.stats_o, p.stats_o + p.in_o, p.part, st));
             TRY(fold_with_stats(no, p.stats_o, p.Wf_o, p.bf_o, st, true));      // (centred: the first layer subtracts the means on load)
-            if (p.small) moving_output_pending = true;
-            else {
+            if (!p.small) {
                 gnn::k_bn_moving_multi<<<cdiv(p.in_o, 256), 256, 0, st>>>(p.stats_o, 2 * p.in_o, 1, p.in_o, const_cast<float *>(no.bn_mean),
                                                                         const_cast<float *>(no.bn_var), ta.bn_momentum);
                 LAUNCH_OK();
@@ -1115,7 +1198,9 @@ static int train_step_impl(const gnn_train_args_t &ta) {
         }
         TRY(forward_layers(no, osegs, nos, p.M, W0, b0, ohs, nullptr, st, nullptr, nullptr, bn_o ? p.stats_o : nullptr, &dro));
     }
-    if (p.pooled) TRY(launch_aggregate(nullptr, a.nodegraph, out_nodes, p.T, p.T, ta.y_pred, p.T, st));
+    if (p.pooled && do_fwd) TRY(launch_aggregate(nullptr, a.nodegraph, out_nodes, p.T, p.T, ta.y_pred, p.T, st));
+    if (px.node_out && do_fwd && p.M > 0) HIP_OK(hipMemcpyAsync(px.node_out, out_nodes, sizeof(float) * (size_t)p.M * p.T, hipMemcpyDeviceToDevice, st));
+    if (phase == GNN_TRAIN_PHASE_FORWARD) return 0;      // the tape is kept: phase 2 goes on from here
     if (fwd_only) {
         // the forward alone: the moving averages the persistent small-graph path keeps back for the step's validity word are due now
         if (p.small) TRY(moving_state(nullptr));
@@ -1127,6 +1212,13 @@ static int train_step_impl(const gnn_train_args_t &ta) {
         return 0;
     }
     // ---- loss and its gradient ----------------------------------------------------------------------------------------------------
+    auto add_into = [&](float *dst, const float *src, size_t n) -> int {      // dst += src
+        gnn::k_axpby<<<std::min(cdiv((long)n, 256), 1024), 256, 0, st>>>(1.0f, dst, 1.0f, src, dst, n);
+        LAUNCH_OK();
+        return 0;
+    };
+    if (no_loss) HIP_OK(hipMemsetAsync(p.dpred, 0, sizeof(float) * (size_t)p.R * p.T, st));      // no loss of its own: upstream gradients only
+    else {
     gnn::k_loss_grad<<<cdiv(p.R, 256), 256, 0, st>>>(ta.loss_kind, ta.targets, ta.y_pred, ta.sample_weight, p.R, p.T, p.dpred, p.loss_rows);
     LAUNCH_OK();
     if (p.R > 65536) {             // (one block summing a million rows took 0.9 ms)
@@ -1135,8 +1227,21 @@ static int train_step_impl(const gnn_train_args_t &ta) {
         gnn::k_sum_scale<<<1, 256, 0, st>>>(p.loss_part, 256, 1.0f / (float)p.R, ta.loss);
     } else gnn::k_sum_scale<<<1, 256, 0, st>>>(p.loss_rows, p.R, 1.0f / (float)p.R, ta.loss);
     LAUNCH_OK();
+    if (px.loss_scale != 0.0f && px.loss_scale != 1.0f) {
+        gnn::k_axpby<<<std::min(cdiv((long)p.R * p.T, 256), 1024), 256, 0, st>>>(px.loss_scale, p.dpred, 0.0f, nullptr, p.dpred, (size_t)p.R * p.T);
+        LAUNCH_OK();
+    }
+    }
+    if (px.d_pred_extra) TRY(add_into(p.dpred, px.d_pred_extra, (size_t)p.R * p.T));
     float *G_out = p.dpred;
     if (p.pooled) { TRY(launch_aggregate(nullptr, ta.nodegraph_by_source, p.dpred, p.T, p.T, p.G_out, p.T, st)); G_out = p.G_out; }
+    if (px.d_out_extra && p.M > 0) TRY(add_into(G_out, px.d_out_extra, (size_t)p.M * p.T));
+    // label gradients (kernels_train_labels.hpp): what the caller wants of d loss / d nodes, d loss / d arc labels
+    const bool want_nodes = px.d_nodes != nullptr, want_arcs = px.d_arc_labels != nullptr && p.A > 0 && p.E > 0;
+    const bool want_lab = (want_nodes && p.with_labels) || want_arcs;       // something of the constant segments' gradient is wanted (sum of dZ)
+    const bool want_g0 = want_nodes && !p.with_labels;             // state_0 = nodes: iteration 0's input gradient IS consumed
+    const int node_part = p.with_labels ? p.S + p.L : p.S;         // columns of one endpoint / node in the output network's input
+    if (want_lab) HIP_OK(hipMemsetAsync(p.dz_sum, 0, sizeof(float) * (size_t)p.N * p.ld_dz, st));
 
     // ---- backward: output network, then the k iterations -----------------------------------------------------------------------------------
     // Large graphs (round 5): G_{t-1} leaves the transposed aggregate as dZ_{t-1} = G_{t-1} (.) act'(state_t) (k_aggregate_dz), so that the two
@@ -1159,9 +1264,19 @@ static int train_step_impl(const gnn_train_args_t &ta) {
                                                                                                    p.M, p.S, p.G_state, p.S);
             LAUNCH_OK();
         }
+        if (want_lab) {       // the label / arc-label segments of the head's input gradient (scattered into the outputs at the end of the step)
+            gnn::BnGradReq lr[3]; int nl = 0;
+            if (want_nodes && p.with_labels)
+                for (int i = 0; i < n_state_segs; ++i)
+                    lr[nl++] = gnn::BnGradReq{p.dx_o_all + bn_req_off[i] + p.S, p.in_o, a.nodes, a.ld_nodes, bn_req_idx[i], p.L, bn_req_off[i] + p.S};
+            if (want_arcs && a.focus == GNN_FOCUS_ARC)
+                lr[nl++] = gnn::BnGradReq{p.dx_o_all + 2 * node_part, p.in_o, a.arc_labels, a.ld_arcs, a.out_index, p.A, 2 * node_part};
+            TRY(bn_input_grads(no, p.co, p.stats_o, lr, nl, p.M, st));
+        }
     } else {
         TRY(zero_grads(no, ta.grad_output, st));
     }
+    if (px.d_state_extra) TRY(add_into(p.G_state, px.d_state_extra, (size_t)p.N * p.S));
     if (k == 0) TRY(zero_grads(ns, ta.grad_state, st));
     if (p.small && k > 0) {
         // the k iterations of back-propagation in one persistent launch; every workgroup leaves its share of the kernel gradient
@@ -1178,6 +1293,7 @@ static int train_step_impl(const gnn_train_args_t &ta) {
         ba.G0 = p.G_state; ba.dxa = p.dx_s_all; ba.bar = p.sm_bar + 2; ba.part = p.sm_part; ba.partW = p.sm_partW;
         ba.partBN = p.sm_partBN;
         ba.inv_n = 1.0f / (float)p.N; ba.err = p.k_dev; ba.wait_ticks = gnn::wait_ticks();
+        ba.dz_out = want_lab ? p.dz_sum : nullptr; ba.g0_out = want_g0 ? p.g0 : nullptr;
         if (const char *e = getenv("GNN_DEBUG_FAIL_BWD")) { if (e[0] == '1') ba.wait_ticks = 0; }      // (test hook: every barrier wait of THIS launch expires at once)
         switch (p.SPs) {
             case 16: TRY(launch_train_small_bwd_sq<1>(ba, tiles, p.n_wg, ba.w_s != nullptr, st)); break;
@@ -1252,8 +1368,10 @@ static int train_step_impl(const gnn_train_args_t &ta) {
             if (t == 0) break;                                       // nothing consumes d loss / d state_0: no input gradient, no transposed aggregate
             if (!dx_done) TRY(launch_train_bwd_dx(ba, p.S, st));
         } else {
-            TRY(net_backward(p.cs, segs, n, hs, p.G_state, p.S, p.N, stats, t != k - 1, t > 0 ? p.dx_s_all : nullptr, t > 0 ? p.kdx_s : 0, p.part, st, p.off_agg, 0, &drs));
-            if (t == 0) break;                                       // (as above)
+            const bool dx_t = t > 0 || want_g0;                      // (label gradients with state_0 = nodes: iteration 0's input gradient too)
+            TRY(net_backward(p.cs, segs, n, hs, p.G_state, p.S, p.N, stats, t != k - 1, dx_t ? p.dx_s_all : nullptr, dx_t ? p.kdx_s : 0, p.part, st, p.off_agg, 0, &drs,
+                             want_lab ? p.dz_sum : nullptr));
+            if (!dx_t) break;                                        // (as above)
             gnn::BnGradReq rq[2] = {gnn::BnGradReq{p.dx_s_all, p.kdx_s, s_t, p.S, nullptr, p.S, 0},
                                     gnn::BnGradReq{p.dx_s_all + p.S, p.kdx_s, agg_t, p.S, nullptr, p.S, p.off_agg}};
             TRY(bn_input_grads(ns, p.cs, stats, rq, 2, p.N, st));
@@ -1291,6 +1409,56 @@ static int train_step_impl(const gnn_train_args_t &ta) {
                                                                  p.dx_s_all, p.kdx_s, p.G_state, p.S)
                 switch (G) { case 4: AGGA(4); break; case 8: AGGA(8); break; case 16: AGGA(16); break; case 32: AGGA(32); break; default: AGGA(64); break; }
 #undef AGGA
+                LAUNCH_OK();
+            }
+        }
+    }
+    if (want_lab || want_g0) {
+        // ---- label gradients: one row-parallel pass turns sum_t dZ_t into the gradients of the constant segments; the own-label columns plus
+        // the transposed aggregate of the aggregated-label columns are d loss / d nodes, the transposed ArcNode aggregate of the aggregated-arc
+        // columns d loss / d arc labels; the head's label segments are scatter-added on top
+        const int ldn = px.ld_d_nodes > 0 ? px.ld_d_nodes : p.L;
+        gnn::LabelGradArgs la;
+        memset(&la, 0, sizeof(la));
+        la.N = p.N; la.H = p.H1s; la.ldz = p.ld_dz; la.DZ = p.dz_sum; la.W = ns.kernel[0];
+        la.cs = const_segs_of(a, p);
+        if (p.with_labels) {
+            la.out[0] = want_nodes ? p.lab_own : nullptr; la.ldo[0] = p.L;
+            la.out[1] = want_nodes ? p.lab_agg : nullptr; la.ldo[1] = p.L;
+            la.out[2] = want_arcs ? p.arc_agg : nullptr; la.ldo[2] = p.A;
+        } else { la.out[0] = want_arcs ? p.arc_agg : nullptr; la.ldo[0] = p.A; }
+        if (bn_s) { la.gamma = ns.bn_gamma; la.mean = p.stats_tpl; la.var = p.stats_tpl + p.in_s; la.dgamma = ta.grad_state.dgamma; la.dbeta = ta.grad_state.dbeta; la.eps = ns.bn_eps; }
+        la.inv_n = 1.0f / (float)p.N;
+        if (want_lab && p.Kc > 0 && p.K > 0) {
+            gnn::k_label_grads<<<std::min(cdiv(p.N, gnn::LG_ROWS), 4096), 256, sizeof(float) * gnn::LG_ROWS * (p.H1s + 1), st>>>(la);
+            LAUNCH_OK();
+        }
+        if (want_nodes && p.with_labels) {
+            if (p.K > 0) {
+                const gnn_csr_t &c = ta.adjacency_by_source;
+                int G = 4;
+                while (G < p.L && G < 64) G <<= 1;
+                const int groups = 256 / G, grid = std::min(cdiv(p.N, groups), 256 * 16);
+#define AGGL(GG) gnn::k_aggregate_add<GG><<<grid, 256, 0, st>>>(c.n_dst, c.rowptr, c.src, c.w, c.row_scale, p.lab_agg, p.L, p.L, p.lab_own, p.L, px.d_nodes, ldn)
+                switch (G) { case 4: AGGL(4); break; case 8: AGGL(8); break; case 16: AGGL(16); break; case 32: AGGL(32); break; default: AGGL(64); break; }
+#undef AGGL
+                LAUNCH_OK();
+            } else HIP_OK(hipMemset2DAsync(px.d_nodes, sizeof(float) * ldn, 0, sizeof(float) * p.L, p.N, st));
+            for (int i = 0; i < n_state_segs && p.M > 0; ++i) {
+                gnn::k_scatter_add_rows<<<std::min(cdiv((long)p.M * p.L, 256), 256 * 16), 256, 0, st>>>(p.dx_o_all + bn_req_off[i] + p.S, p.in_o, bn_req_idx[i],
+                                                                                                       p.M, p.L, px.d_nodes, ldn);
+                LAUNCH_OK();
+            }
+        } else if (want_nodes) {       // state_0 = nodes: d loss / d nodes is d loss / d state_0
+            if (p.small && k > 0) TRY(launch_copy2d(nullptr, p.g0, p.SPs, px.d_nodes, ldn, p.N, p.L, p.L, st));
+            else TRY(launch_copy2d(nullptr, p.G_state, p.S, px.d_nodes, ldn, p.N, p.L, p.L, st));
+        }
+        if (want_arcs) {
+            if (p.K > 0) TRY(launch_aggregate(nullptr, px.arcnode_by_source, p.arc_agg, p.A, p.A, px.d_arc_labels, p.A, st));
+            else HIP_OK(hipMemsetAsync(px.d_arc_labels, 0, sizeof(float) * (size_t)p.E * p.A, st));
+            if (a.focus == GNN_FOCUS_ARC && p.M > 0) {
+                gnn::k_scatter_add_rows<<<std::min(cdiv((long)p.M * p.A, 256), 256 * 16), 256, 0, st>>>(p.dx_o_all + 2 * node_part, p.in_o, a.out_index, p.M, p.A,
+                                                                                                       px.d_arc_labels, p.A);
                 LAUNCH_OK();
             }
         }

@@ -504,7 +504,8 @@ int gnn_ragged_copy(const gnn_ragged_desc_t *desc, int32_t n_desc, const int32_t
  * focus, out_index, nodegraph, state0, max_iteration, state_threshold and stream exactly as for gnn_loop_forward; its
  * k_out / state_out / out / workspace fields are ignored.  Heterogeneous (composite) models are covered since ABI 6
  * (grad_state_types; gnnkeras_amd/csrc/train_composite.hpp), Dropout layers behind Dense layers since ABI 8 (gnn_dropout_spec_t);
- * Dropout in front of the first Dense and LGNN label gradients are not: the caller uses the building blocks for those.
+ * Dropout in front of the first Dense is not: the caller uses the building blocks for it.  LGNN label gradients, upstream gradients
+ * and the step in two phases: gnn_train_step_ex below (homogeneous models; composite ones use the building blocks for those).
  * The call synchronises the stream ONCE (to learn k, as the reference does when it divides by k). */
 /* ABI 8: the Dropout / AlphaDropout layers of one network (reference MLP.py:25-27, :60-66: `dropout_rate`, `dropout_pos`, `alphadropout`) in
  * a training step.  Layer i of the list sits at POSITION pos[i]: in front of Dense pos[i] (pos = n_layers: behind the last Dense).  The
@@ -624,6 +625,58 @@ int gnn_train_xc_applies(const gnn_train_args_t *args);
 #define GNN_TRAIN_GROUPS_MALFORMED (-2)
 #define GNN_TRAIN_GROUP_MAX_NODES 256
 int gnn_train_groups_supported(const gnn_train_args_t *args);
+
+/* ---- the step in two PHASES, with upstream gradients in and label gradients out (additive; GNN_ABI_VERSION stays 10) ----------
+ * A joint LGNN step (reference LGNN.py:252-287, training modes 'parallel' / 'residual') needs the forward of EVERY layer before the
+ * backward of ANY layer: layer i + 1's forward consumes layer i's state and output, layer i's backward the label gradient of layer
+ * i + 1.  gnn_train_step_ex(args, px) is gnn_train_step(args) with a second, optional argument block; px == NULL or an all-zero
+ * block is exactly gnn_train_step(args).  (The block is a struct of its own and not a tail of gnn_train_args_t: the layout of that
+ * struct is pinned as it is.)  Homogeneous models below GNN_TRAIN_BIG_MIN_NODES nodes: gnn_train_phases_supported.
+ *   phase 0                          the whole step
+ *   GNN_TRAIN_PHASE_FORWARD (1)      everything up to and including the output network and the pooling, the tape kept: writes y_pred,
+ *                                    state, k_host and - when given - node_out; performs the step's ONE synchronisation; fills
+ *                                    *phase_state with what it learned there
+ *   GNN_TRAIN_PHASE_BACKWARD (2)     everything from the loss on, read from the tape of a phase-1 call with the SAME args (same tape,
+ *                                    same y_pred) and the same phase_state; does not synchronise
+ * Phase 1 followed by phase 2 issues the launches of phase 0 in the same order, cut in front of the loss kernel; the moving
+ * statistics of the persistent small-graph path stay behind the backward launch, gated by the step's validity word (forward_only is
+ * the call that moves them at once).  Between the two calls the tape must not be used by another call.
+ * loss_kind == GNN_LOSS_NONE (phase 2 only): no loss of its own - targets / loss may be NULL, d loss / d prediction starts at zero.
+ * A call that is refused fails before its first launch and touches nothing.
+ * gnn_train_workspace_bytes of a homogeneous step below GNN_TRAIN_BIG_MIN_NODES nodes includes the label-gradient scratch
+ * (n_nodes x (first state layer's width + padded state width + 2 dim_node_label + dim_arc_label) floats) whether or not label
+ * gradients are requested: phase 1 and phase 2 share one layout. */
+#define GNN_TRAIN_PHASE_FORWARD 1
+#define GNN_TRAIN_PHASE_BACKWARD 2
+#define GNN_LOSS_NONE (-1)
+typedef struct gnn_train_phase_state {      /* opaque to the caller: written by phase 1, read by phase 2 */
+    int32_t magic;
+    int32_t k;                              /* iterations executed                                                             */
+    int32_t general_head;                   /* the thin-head decision read with k (always the general head when phases apply)   */
+    int32_t reserved;
+} gnn_train_phase_state_t;
+typedef struct gnn_train_phase_args {
+    int32_t phase;                          /* 0, GNN_TRAIN_PHASE_FORWARD, GNN_TRAIN_PHASE_BACKWARD                             */
+    float loss_scale;                       /* 0 means 1: d loss / d prediction is multiplied by it; *loss stays unscaled        */
+    gnn_train_phase_state_t *phase_state;   /* HOST struct; required in phases 1 and 2                                          */
+    float *node_out;                        /* phase 0 / 1, optional OUT [n_out, T]: the output rows before the pooling         */
+    /* upstream gradients (phase 0 / 2), each optional */
+    const float *d_pred_extra;              /* [n_rows, T] added to d loss / d prediction in front of the pooling backward      */
+    const float *d_out_extra;               /* [n_out, T] added behind the pooling backward                                     */
+    const float *d_state_extra;             /* [n_nodes, S] added to d loss / d state_k                                         */
+    /* label gradients (phase 0 / 2), optional OUT, overwritten */
+    float *d_nodes; int32_t ld_d_nodes;     /* [n_nodes, dim_node_label], row stride ld_d_nodes (0: dim_node_label)             */
+    float *d_arc_labels;                    /* [n_arcs, dim_arc_label]                                                          */
+    gnn_csr_t arcnode_by_source;            /* CSR of ArcNode itself (n_dst = n_arcs, n_src = n_nodes): needed with d_arc_labels */
+} gnn_train_phase_args_t;
+int gnn_train_step_ex(const gnn_train_args_t *args, const gnn_train_phase_args_t *px);
+/* 0 when the phases / upstream gradients / label gradients cover these arguments, else -1 (composite models, convergence groups,
+ * forward_only, the row-streaming path from GNN_TRAIN_BIG_MIN_NODES nodes on, a first state layer wider than 960 units: the caller
+ * keeps the building blocks).  Reads dims and network descriptions only. */
+int gnn_train_phases_supported(const gnn_train_args_t *args);
+/* *gate (device int32) = 1 when every one of the n validity words (HOST array of n <= 16 device pointers) holds 1, else 0: the optimizer
+ * gate of a joint step of n layers - all or nothing.  The moving statistics stay gated per layer, by the layer's own word. */
+int gnn_gate_all(const int32_t *const *words, int32_t n, int32_t *gate, void *stream);
 
 #ifdef __cplusplus
 }
