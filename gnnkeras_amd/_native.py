@@ -28,7 +28,7 @@ XC_FILL, XC_VALID = 0, 1                # enum gnn_xc_mode
 FLAG_FUSED_GEN2, FLAG_FUSED_GEN4, FLAG_FUSED_GEN5, FLAG_FUSED_GEN6, FLAG_FUSED_GEN7 = 2 << 4, 4 << 4, 5 << 4, 6 << 4, 7 << 4     # pin the fused-kernel generation (tests, tuning)
 
 EXPORTS = ['gnn_last_error', 'gnn_last_kernel_name', 'gnn_abi_version', 'gnn_struct_size', 'gnn_loop_workspace_bytes', 'gnn_loop_forward', 'gnn_loop_groups_supported', 'gnn_loop_group_max_nodes', 'gnn_aggregate',
-           'gnn_loop_xc_applies', 'gnn_train_xc_applies',
+           'gnn_loop_xc_applies', 'gnn_loop_route_name', 'gnn_train_xc_applies',
            'gnn_mlp_workspace_bytes', 'gnn_mlp_forward', 'gnn_converged', 'gnn_state_step', 'gnn_state_step_agg', 'gnn_state_ld', 'gnn_debug_occupy', 'gnn_debug_occupy_until', 'gnn_debug_expiry_beacon', 'gnn_debug_host_flag',
            'gnn_device_malloc', 'gnn_device_free', 'gnn_ipc_export', 'gnn_ipc_open', 'gnn_ipc_close', 'gnn_shard_iteration_peers', 'gnn_peer_wait', 'gnn_peer_publish', 'gnn_shard_iteration_split_rows',
            'gnn_shard_setup', 'gnn_shard_iteration', 'gnn_shard_output', 'gnn_gather_rows',
@@ -300,6 +300,7 @@ def lib():
             'gnn_train_phases_supported': (C.c_int, [C.POINTER(TrainArgs)]),
             'gnn_gate_all': (C.c_int, [vp, i32, vp, vp]),
             'gnn_loop_xc_applies': (C.c_int, [C.POINTER(LoopArgs)]),
+            'gnn_loop_route_name': (C.c_char_p, [C.POINTER(LoopArgs)]),
             'gnn_loop_group_max_nodes': (C.c_int, [C.POINTER(LoopArgs)]),
             'gnn_train_xc_applies': (C.c_int, [C.POINTER(TrainArgs)]),
             'gnn_ragged_copy': (C.c_int, [vp, i32, vp, i32, vp]),

@@ -76,6 +76,41 @@ int state_ld(int S) {
     return round_up(S, 4);
 }
 
+// --- the routing knobs, read in ONE place (what they route: loop_route.hpp) ------------------------------------------
+struct Knobs {
+    int pin;                 // the effective pin of the kernel generation: the flag bits, else GNN_FUSED_KERNEL, else 0 (automatic)
+    int flag_pin, env_pin;   // its two sources (the size-based 2 / 4 choice, the prefix form and the overlapped shard iteration read them apart)
+    int mid_max_nodes;       // GNN_MID_MAX_NODES: largest graph of the mid-size whole-loop kernel
+    bool prefix_fusion, xwide, rowdense;      // GNN_PREFIX_FUSION / GNN_XWIDE / GNN_ROWDENSE = 0 switch that kernel off
+    // GNN_XC=0 keeps the per-node constant C in the wave-specialised kernel at every size, GNN_XC_MIN_NODES moves the size from which
+    // the constant inputs are multiplied instead (tuning knobs; both forms are held to the same tests).  Measured, d = 64, 10 arcs per
+    // node, us per iteration with inputs / with C: 100 k nodes 61.1 / 59.1, 200 k 105.0 / 105.8, 400 k 192.2 / 199.7, 600 k 281.6 / 294.0,
+    // 1 M (C4) 458 / 480, 4 M 2 215 / 2 329; d = 32 at C4 size 263.2 / 263.7.
+    bool xc; int xc_min_nodes;
+};
+const Knobs &process_knobs() {      // read once per process: all five at the first use of any of them (a forward plan, or a dense launch's GNN_ROWDENSE)
+    static const Knobs once = [] {
+        Knobs k = {};
+        const char *e;
+        k.env_pin = (e = getenv("GNN_FUSED_KERNEL")) ? atoi(e) : 0;
+        k.mid_max_nodes = (e = getenv("GNN_MID_MAX_NODES")) ? atoi(e) : 36000;
+        k.prefix_fusion = !((e = getenv("GNN_PREFIX_FUSION")) && e[0] == '0');
+        k.xwide = !((e = getenv("GNN_XWIDE")) && atoi(e) == 0);
+        k.rowdense = !((e = getenv("GNN_ROWDENSE")) && e[0] == '0');
+        return k;
+    }();
+    return once;
+}
+Knobs knobs(int flags) {            // ... plus the call's pin and the two knobs read at every call (tests switch them inside one process)
+    Knobs k = process_knobs();
+    k.flag_pin = (flags & GNN_FLAG_FUSED_GEN_MASK) >> 4;
+    k.pin = k.flag_pin ? k.flag_pin : k.env_pin;
+    const char *e = getenv("GNN_XC"), *m = getenv("GNN_XC_MIN_NODES");
+    k.xc = !(e && atoi(e) == 0);
+    k.xc_min_nodes = m ? atoi(m) : 196608;
+    return k;
+}
+
 // --- workspace carving: same code computes the size (base == nullptr) and hands out the pointers --------------------
 struct Carver {
     char *base;
@@ -191,9 +226,7 @@ int device_cus();
 // One contiguous input matrix of 16 .. 64 columns at large M (the layers behind the first): rows straight into the matrix cores
 // (kernel_rowdense.hpp).  GNN_ROWDENSE=0 keeps k_segdense.
 bool rowdense_applies(const gnn::SegDenseArgs &a) {
-    static int off = -1;
-    if (off < 0) { const char *e = getenv("GNN_ROWDENSE"); off = (e && e[0] == '0') ? 1 : 0; }
-    if (off || a.M < 32768 || a.nseg != 1 || a.addend || a.out_rowidx || a.in_gamma || a.in_center || a.act == GNN_ACT_SOFTMAX) return false;
+    if (!process_knobs().rowdense || a.M < 32768 || a.nseg != 1 || a.addend || a.out_rowidx || a.in_gamma || a.in_center || a.act == GNN_ACT_SOFTMAX) return false;
     const gnn::Seg &s = a.seg[0];
     if (s.rowidx || s.wrow != 0 || s.width < 8 || s.width > 64 || s.width % 4 || a.H < 8 || a.H > 64 || a.H % 4) return false;
     if (s.ld % 4 || a.ldy % 4 || (a.pred_flag && a.ld_pred % 4)) return false;
@@ -234,9 +267,7 @@ int launch_rowdense(const gnn::SegDenseArgs &a, hipStream_t st) {
 // Wide layers over one or two contiguous matrices + a per-row addend at large M (the un-fused first layer of state widths above 128,
 // wide hidden layers): k_rowdense_wide, output columns in passes of 64.
 bool rowdense_wide_applies(const gnn::SegDenseArgs &a) {
-    static int off = -1;
-    if (off < 0) { const char *e = getenv("GNN_ROWDENSE"); off = (e && e[0] == '0') ? 1 : 0; }
-    if (off || a.M < 32768 || a.nseg < 1 || a.nseg > 2 || a.out_rowidx || a.add_rowidx || a.in_gamma || a.in_center || a.pred_flag || a.act == GNN_ACT_SOFTMAX) return false;
+    if (!process_knobs().rowdense || a.M < 32768 || a.nseg < 1 || a.nseg > 2 || a.out_rowidx || a.add_rowidx || a.in_gamma || a.in_center || a.pred_flag || a.act == GNN_ACT_SOFTMAX) return false;
     if (a.H <= 64 || a.H % 4 || a.ldy % 4 || (a.addend && a.ld_add % 4)) return false;
     int chunks = 0;
     uintptr_t bits = reinterpret_cast<uintptr_t>(a.Y) | reinterpret_cast<uintptr_t>(a.addend);
@@ -466,23 +497,6 @@ constexpr int GNN_SMALL_MAX_TILES = 512;   // upper bound of CUs a whole-loop la
 // then (128-byte aligned) the mid-size whole-loop kernel's barrier lines; all zeroed by the set-up launch
 constexpr int GNN_LOOP_WORDS = 16 + 32 + gnn::MID_BAR_WORDS;
 
-int fused_generation(int SP, int n_nodes, int flags);
-
-// GNN_XC=0 keeps the per-node constant C in the wave-specialised kernel at every size, GNN_XC_MIN_NODES moves the size from
-// which the constant inputs are multiplied instead (tuning knobs; both forms are held to the same tests).  Measured, d = 64,
-// 10 arcs per node, us per iteration with inputs / with C: 100 k nodes 61.1 / 59.1, 200 k 105.0 / 105.8, 400 k 192.2 / 199.7,
-// 600 k 281.6 / 294.0, 1 M (C4) 458 / 480, 4 M 2 215 / 2 329; d = 32 at C4 size 263.2 / 263.7.
-bool xc_disabled() {
-    int v = -1;      // (read at every call: tests switch it inside one process)
-    { const char *e = getenv("GNN_XC"); v = (e && atoi(e) == 0) ? 1 : 0; }
-    return v == 1;
-}
-int xc_min_nodes() {
-    int v = -1;      // (read at every call: tests switch it inside one process)
-    { const char *e = getenv("GNN_XC_MIN_NODES"); v = e ? atoi(e) : 196608; }
-    return v;
-}
-
 int state_width(const gnn_loop_args_t &a) { return a.state_dim > 0 ? a.state_dim : a.dim_node_label; }
 
 int make_plan(const gnn_loop_args_t &a, void *ws, Plan &p, bool validate_ptrs) {
@@ -535,12 +549,10 @@ int make_plan(const gnn_loop_args_t &a, void *ws, Plan &p, bool validate_ptrs) {
     for (int t = 0; t < p.T; ++t) {
         TRY(check_mlp(a.net_state[t], "net_state", validate_ptrs));
         const gnn_mlp_t &ns = a.net_state[t];
-        int expect;
         if (p.composite) {
             if (a.type_dim_label[t] < 0 || a.type_dim_label[t] > p.L) return fail("type_dim_label[%d]=%d out of [0,%d]", t, a.type_dim_label[t], p.L);
             sum_dt += a.type_dim_label[t];
         }
-        (void)expect;
         if (ns.units[ns.n_layers - 1] != p.S) return fail("net_state[%d] output width %d != state width %d", t, ns.units[ns.n_layers - 1], p.S);
         p.H1max = std::max(p.H1max, (int)ns.units[0]);
         p.Hmax_state = std::max(p.Hmax_state, max_units(ns));
@@ -612,7 +624,8 @@ int make_plan(const gnn_loop_args_t &a, void *ws, Plan &p, bool validate_ptrs) {
     p.C = c.take<float>((size_t)p.N * p.ldC);
     // at most 31 constant input columns per node type (one more carries the bias): the wave-specialised kernel may read the
     // inputs (128 B per node) and multiply them instead of reading C (4 H1 bytes per node)
-    p.xc_ok = p.SP <= 64 && !(a.flags & GNN_FLAG_UNFUSED) && !xc_disabled() && p.N >= xc_min_nodes();
+    const Knobs k = knobs(a.flags);
+    p.xc_ok = p.SP <= 64 && !(a.flags & GNN_FLAG_UNFUSED) && k.xc && p.N >= k.xc_min_nodes;
     for (int t = 0; t < p.T; ++t) {
         const int kc = p.composite ? a.type_dim_label[t] + sum_dt + p.A : (a.state_dim > 0 ? 2 * p.L : 0) + p.A;
         p.xc_ok = p.xc_ok && kc <= 31 && a.net_state[t].n_layers == 1;
@@ -671,6 +684,10 @@ int make_plan(const gnn_loop_args_t &a, void *ws, Plan &p, bool validate_ptrs) {
 
 // the operator the iterations walk: the light one when hub rows were split off
 inline const gnn_csr_t &iter_adjacency(const gnn_loop_args_t &a, const Plan &p) { return p.n_heavy > 0 ? a.adjacency_light : a.adjacency; }
+
+}  // namespace
+#include "loop_route.hpp"      // which kernel form runs: route_loop(), route_iteration()
+namespace {
 
 // hub pre-pass: virtual rows N .. N + n_heavy of the buffer the iteration is about to read
 int launch_heavy(const gnn_loop_args_t &a, const Plan &p, const int *gate, const float *src, hipStream_t st) {
@@ -799,7 +816,7 @@ int setup_constants(const gnn_loop_args_t &a, const Plan &p, hipStream_t st, boo
         d.Y = p.C; d.ldy = p.ldC; d.out_rowidx = tp.rows;
         TRY(launch_segdense(d, st));
     }
-    if (p.xc_ok && p.N > 0 && (fused_generation(p.SP, p.N, a.flags) == 4 || a.nodes_src)) {   // only the wave-specialised kernel reads them (shards: the
+    if (p.xc_ok && p.N > 0 && (size_generation(p, a.flags) == 4 || a.nodes_src)) {       // only the wave-specialised kernel reads them (shards: the
                                                                                        // overlapped iteration always runs it)
         for (int t = 0; t < p.T; ++t) {
             const TypePlan &tp = p.tp[t];
@@ -816,15 +833,6 @@ int setup_constants(const gnn_loop_args_t &a, const Plan &p, hipStream_t st, boo
         }
     }
     return 0;
-}
-
-// Small homogeneous graphs about to run the whole-loop kernel: BN folds, both constant aggregates, C, the predicate of
-// state_0 and the zeroing of the loop words in ONE launch (kernels_setup.hpp) instead of five.
-bool setup_small_applies(const gnn_loop_args_t &a, const Plan &p) {
-    if (p.composite || p.N == 0) return false;
-    const int L = a.state_dim > 0 ? p.L : 0, H = a.net_state[0].units[0];
-    if (H > 128) return false;
-    return gnn::setup_small_lds(H, 2 * L + p.A, std::max(a.net_state[0].in_dim, a.net_output.in_dim)) <= 64 * 1024;
 }
 
 int setup_small(const gnn_loop_args_t &a, const Plan &p, hipStream_t st) {
@@ -903,25 +911,6 @@ int output_stage(const gnn_loop_args_t &a, const Plan &p, hipStream_t st) {
     return 0;
 }
 
-// Which generation of the fused iteration kernel runs.  GNN_FUSED_KERNEL unset / 0 = automatic:
-//   4  wave-specialised (12 gather waves + 4 matrix waves per workgroup, 32 waves per CU)      <- d > 16 and >= 32768 nodes
-//   2  phase-alternating (every wave gathers, then every wave multiplies; 16 waves per CU)      <- d <= 16 or small graphs
-//      (measured crossover on ER graphs with 10 arcs / node, d = 64: 17.2 vs 16.4 us at 2e3 nodes, 28.3 vs 28.5 at 3e4,
-//       60 vs 74 at 1e5, 480 vs 542 at 1e6)
-// (a software-pipelined generation 3 lost to both at every size - profiles/r01_gather_sweep.txt - and was removed)
-// A tuning knob, never a correctness switch: both are held to the same parity tests.
-int fused_generation(int SP, int n_nodes, int flags) {
-    const int pinned = (flags & GNN_FLAG_FUSED_GEN_MASK) >> 4;
-    if (pinned == 2 || pinned == 4) return pinned;
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("GNN_FUSED_KERNEL");
-        v = e ? atoi(e) : 0;
-        if (v != 2 && v != 4) v = 0;
-    }
-    return v ? v : ((SP > 16 && n_nodes >= 32768) ? 4 : 2);
-}
-
 int device_cus() {
     static int n_cu = 0;
     if (n_cu == 0) {
@@ -933,31 +922,6 @@ int device_cus() {
     return n_cu;
 }
 
-// the fused kernel that runs ONE iteration: the size-based / pinned choice, except that two-layer state networks go to the
-// wave-specialised kernel at any size (the only per-iteration kernel that carries a second Dense) unless pinned elsewhere
-// the state network's LAST activation is a softmax (legal: reference MLP.py:12-78 takes any Keras activation): only the
-// wave-specialised kernel's row-major epilogue has whole rows in one lane group, so that kernel runs whatever is pinned
-bool state_softmax(const gnn_loop_args_t &a, const Plan &p) {
-    for (int t = 0; t < p.T; ++t) {
-        const gnn_mlp_t &m = a.net_state[t];
-        if (m.n_layers >= 1 && m.activation[m.n_layers - 1] == GNN_ACT_SOFTMAX) return true;
-    }
-    return false;
-}
-
-int iteration_generation(const gnn_loop_args_t &a, const Plan &p) {
-    if (state_softmax(a, p)) return 4;
-    const int gen = fused_generation(p.SP, p.N, a.flags);
-    bool two = false;
-    for (int t = 0; t < p.T; ++t) two |= a.net_state[t].n_layers == 2;
-    if (!two) return gen;
-    const int pinned = (a.flags & GNN_FLAG_FUSED_GEN_MASK) >> 4;
-    static int env = -1;
-    if (env < 0) { const char *e = getenv("GNN_FUSED_KERNEL"); env = e ? atoi(e) : 0; }
-    const int want = pinned ? pinned : env;
-    return (p.SP > 16 && (want == 0 || want >= 4)) ? 4 : gen;
-}
-
 // what a fused kernel needs to know about node type t (the second Dense of a two-layer state network included)
 gnn::FusedType fused_type(const gnn_loop_args_t &a, const Plan &p, int t) {
     const gnn_mlp_t &m = a.net_state[t];
@@ -967,41 +931,28 @@ gnn::FusedType fused_type(const gnn_loop_args_t &a, const Plan &p, int t) {
                           two ? m.kernel[1] : nullptr, two ? m.bias[1] : nullptr, two ? (int)m.activation[1] : 0, p.tp[t].Wc, 0};
 }
 
-// State networks with two or more hidden layers (reference MLP.py:83-139 `hidden_units=[h1, h2, ..]`): the first TWO Dense layers run
-// fused with the aggregate in the wave-specialised kernel's two-layer form, which then writes the second hidden layer's activations
-// (not a state) - the remaining layers are plain dense launches over that matrix, the last one carrying the predicate.  Homogeneous
-// models on one GPU, hidden widths within the padded state width.  Un-fused before: aggregate + one dense launch per layer.
-bool prefix_applies(const gnn_loop_args_t &a, const Plan &p) {
-    if (a.flags & GNN_FLAG_UNFUSED) return false;
-    static int off = -1;
-    if (off < 0) { const char *e = getenv("GNN_PREFIX_FUSION"); off = (e && e[0] == '0') ? 1 : 0; }
-    if (off || p.composite || p.T != 1 || p.tp[0].rows || a.nodes_src || p.n_groups > 0) return false;
-    const gnn_mlp_t &m = a.net_state[0];
-    if (m.n_layers < 3 || (p.SP != 32 && p.SP != 64)) return false;
-    if (m.units[0] > p.SP || m.units[1] > p.SP || m.activation[0] == GNN_ACT_SOFTMAX || m.activation[1] == GNN_ACT_SOFTMAX) return false;
-    const int pinned = (a.flags & GNN_FLAG_FUSED_GEN_MASK) >> 4;
-    if (pinned != 0 && pinned != 4) return false;
-    if ((size_t)(p.N + p.n_heavy) * p.SP * 4 >= ((size_t)1 << 32) || (size_t)p.N * p.ldC * 4 >= ((size_t)1 << 32)) return false;
-    if ((size_t)iter_adjacency(a, p).nnz * 4 >= ((size_t)1 << 32)) return false;
-    return true;
+// what every kernel that takes a Fused2Args is told alike (fa: zeroed): the operator, C, every non-empty node type, S, the threshold (not the error word: per-iteration callers only)
+void fill_fused_args(gnn::Fused2Args &fa, const gnn_loop_args_t &a, const Plan &p, const gnn_csr_t &adj) {
+    fa.rowptr = adj.rowptr; fa.src = adj.src; fa.w = adj.w; fa.row_scale = adj.row_scale;
+    fa.C = p.C; fa.ldC = p.ldC;
+    for (int t = 0; t < p.T; ++t)
+        if (p.tp[t].count > 0) fa.tp[fa.n_types++] = fused_type(a, p, t);
+    fa.S = p.S; fa.thr = a.state_threshold;
 }
 
+// The three-layer prefix form (loop_route.hpp: prefix_covers): the first two Dense layers fused with the aggregate, the rest as dense launches
 int iteration_prefix(const gnn_loop_args_t &a, const Plan &p, const int *gate, const float *src, float *dst, int *flag_next, float *k_out,
                      float k_val, hipStream_t st) {
     TRY(launch_heavy(a, p, gate, src, st));
-    const gnn_csr_t &adj = iter_adjacency(a, p);
     const gnn_mlp_t &m = a.net_state[0];
     gnn::Fused2Args fa;
     memset(&fa, 0, sizeof(fa));
+    fill_fused_args(fa, a, p, iter_adjacency(a, p));
     fa.gate = gate; fa.n_gate = gate ? 1 : 0; fa.gate_stride = 0;
-    fa.rowptr = adj.rowptr; fa.src = adj.src; fa.w = adj.w; fa.row_scale = adj.row_scale;
-    fa.state_in = src; fa.state_out = p.agg; fa.row_base = 0;          // p.agg: [N, SP], free on this path, receives the hidden activations
-    fa.C = p.C; fa.ldC = p.ldC;
-    fa.n_types = 1;
+    fa.state_in = src; fa.state_out = p.agg; fa.row_base = 0; fa.err = p.err;      // p.agg: [N, SP], free on this path, receives the hidden activations
+    fa.n_types = 1;                                                     // ... of the SECOND hidden layer (no predicate, no k: the tail below has them)
     fa.tp[0] = gnn::FusedType{nullptr, p.tp[0].count, p.tp[0].Wf, p.tp[0].wrow_state, p.tp[0].wrow_agg, (int)m.units[0], (int)m.activation[0],
                               m.kernel[1], m.bias[1], (int)m.activation[1], nullptr, (int)m.units[1]};
-    fa.S = p.S; fa.thr = a.state_threshold;
-    fa.flag_next = nullptr; fa.k_out = nullptr; fa.err = p.err;
     FUSED_OK(gnn::launch_fused4(fa, p.SP, device_cus(), st));
     GNN_SET_KERNEL_NAME("k_state_fused4<.., L2> (aggregate + two Dense layers) + k_segdense (remaining layers)");
     gnn_mlp_t tail;
@@ -1022,159 +973,76 @@ int iteration_prefix(const gnn_loop_args_t &a, const Plan &p, const int *gate, c
     return 0;
 }
 
-// one fused iteration over every node type (one launch per type)
-int iteration_fused(const gnn_loop_args_t &a, const Plan &p, const int *gate, int n_gate, int gate_stride,
+// one fused iteration over every node type (one launch per type) on `kernel`, the route's fused kernel (IterRoute::fused()); the
+// overlapped and the peer-store forms exist on the wave-specialised kernel alone (and on the wide kernel at padded width 128)
+int iteration_fused(const gnn_loop_args_t &a, const Plan &p, IterKernel kernel, const int *gate, int n_gate, int gate_stride,
                     const float *src, float *dst, int row_base, int *flag_next, float *k_out, float k_val,
                     hipStream_t st, const gnn_csr_t *adj_override = nullptr, const float *agg_init = nullptr,
                     const int *rows_override = nullptr, int count_override = 0, const gnn_peer_set_t *peers = nullptr) {
-    auto type_of = [&](int t) { return fused_type(a, p, t); };
     TRY(launch_heavy(a, p, n_gate == 1 ? gate : nullptr, src, st));
     const gnn_csr_t &adj = adj_override ? *adj_override : iter_adjacency(a, p);
     gnn::Fused2Args fa;
     memset(&fa, 0, sizeof(fa));
+    fill_fused_args(fa, a, p, adj);
     fa.gate = n_gate ? gate : nullptr; fa.n_gate = n_gate; fa.gate_stride = gate_stride;
-    fa.rowptr = adj.rowptr; fa.src = adj.src; fa.w = adj.w; fa.row_scale = adj.row_scale;
-    fa.state_in = src; fa.state_out = dst; fa.row_base = row_base;
-    fa.C = p.C; fa.ldC = p.ldC;
-    fa.n_types = 0;
-    for (int t = 0; t < p.T; ++t)
-        if (p.tp[t].count > 0) fa.tp[fa.n_types++] = type_of(t);
+    fa.state_in = src; fa.state_out = dst; fa.row_base = row_base; fa.err = p.err;
     if (rows_override && fa.n_types == 1) {      // a SUB-RANGE of a homogeneous shard's rows (the pipelined exchange): the row-list form
         fa.tp[0].rows = rows_override; fa.tp[0].count = count_override;
         if (count_override == 0) fa.n_types = 0;
     }
-    fa.S = p.S; fa.thr = a.state_threshold;
     fa.flag_next = flag_next;
     fa.k_out = k_out; fa.k_val = k_val;
-    fa.err = p.err;
     fa.agg_init = agg_init;
     if (peers) {
         if (peers->n_peers < 0 || peers->n_peers > GNN_MAX_PEERS) return fail("n_peers %d out of [0, %d]", peers->n_peers, GNN_MAX_PEERS);
         fa.n_peers = peers->n_peers;
         for (int i = 0; i < peers->n_peers; ++i) fa.peer_out[i] = peers->state_out_full[i];
     }
-    if (p.xc_ok && !adj.w && (agg_init || fused_generation(p.SP, p.N, a.flags) == 4)) fa.Xc = p.Xc;
+    if (p.xc_ok && !adj.w && (agg_init || size_generation(p, a.flags) == 4)) fa.Xc = p.Xc;
     if (fa.n_types == 0) {                      // no nodes at all: only the iteration counter moves
         if (k_out) TRY(launch_converge(fa.gate, src, src, 0, p.S, p.SP, p.SP, a.state_threshold, flag_next, k_out, k_val, st));
         return 0;
     }
     if (fa.n_peers > 0 && (p.SP == 128 || p.T != 1 || adj.w || a.net_state[0].n_layers != 1 || (p.SP != 32 && p.SP != 64) || p.n_heavy != 0))
         return fail("peer stores: homogeneous one-layer shards without per-arc weights or hub rows, state widths 17 .. 64");
-    if (p.SP == 128) { FUSED_OK(gnn::launch_wide(fa, device_cus(), st, 0)); return 0; }
-    const int gen = (agg_init || fa.n_peers > 0) ? 4 : iteration_generation(a, p);
-    if (gen == 4) FUSED_OK(gnn::launch_fused4(fa, p.SP, device_cus(), st));
+    if (kernel == IterKernel::wide) FUSED_OK(gnn::launch_wide(fa, device_cus(), st, 0));
+    else if (kernel == IterKernel::fused4 || agg_init || fa.n_peers > 0) FUSED_OK(gnn::launch_fused4(fa, p.SP, device_cus(), st));
     else FUSED_OK(gnn::launch_fused2(fa, p.SP, 8, device_cus(), st));
     return 0;
 }
 
-// The whole loop in ONE launch (kernel_state_small.hpp) for graphs of at most 64 nodes per CU.  `persistent_applies` is
-// the static part of the decision (hub rows, d <= 16, too many tiles, pinned to another kernel: one launch per iteration).
-bool persistent_applies(const gnn_loop_args_t &a, const Plan &p) {
-    const int pinned = (a.flags & GNN_FLAG_FUSED_GEN_MASK) >> 4;
-    if (pinned != 0 && pinned != 5) return false;
-    static int env = -1;
-    if (env < 0) { const char *e = getenv("GNN_FUSED_KERNEL"); env = e ? atoi(e) : 0; }
-    if (pinned == 0 && env != 0 && env != 5) return false;
-    if (p.n_heavy != 0 || a.max_iteration < 1 || (p.SP != 16 && p.SP != 32 && p.SP != 64)) return false;
-    int tiles = 0;
-    for (int t = 0; t < p.T; ++t) tiles += (p.tp[t].count + 63) / 64;
-    if (p.n_groups > 0) tiles = p.group_tiles;
-    return tiles > 0 && tiles <= std::min(device_cus(), GNN_SMALL_MAX_TILES);
-}
-
-// returns 2 when the kernel does not apply after all and the caller launches per iteration.  `pred0` (optional): the
-// predicate of state_0 as one word per tile; `state_final` (optional): the caller's compact result buffer.
-int loop_persistent(const gnn_loop_args_t &a, const Plan &p, const float *first, float *const B[2], const int *pred0,
-                    int n_pred0, float *state_final, hipStream_t st) {
-    if (!persistent_applies(a, p)) return 2;
+// The whole loop in ONE launch: the small kernel (kernel_state_small.hpp, one 64-node tile per CU; `mid` false) or the mid-size one
+// (kernel_state_mid.hpp, several tiles per workgroup).  Returns 2 when the kernel does not apply after all (persistent_fits, the tile
+// budget) and the caller goes on to the next form of its route.  Small kernel only - `pred0` (optional): the predicate of state_0 as
+// one word per tile; `state_final` (optional): the caller's compact result buffer.
+int loop_whole(const gnn_loop_args_t &a, const Plan &p, bool mid, const float *first, float *const B[2], const int *pred0,
+               int n_pred0, float *state_final, hipStream_t st) {
     gnn::SmallArgs sa;
     memset(&sa, 0, sizeof(sa));
     gnn::Fused2Args &fa = sa.f;
-    const gnn_csr_t &adj = iter_adjacency(a, p);
-    fa.rowptr = adj.rowptr; fa.src = adj.src; fa.w = adj.w; fa.row_scale = adj.row_scale;
-    fa.state_in = first; fa.row_base = 0;
-    fa.C = p.C; fa.ldC = p.ldC;
-    for (int t = 0; t < p.T; ++t)
-        if (p.tp[t].count > 0)
-            fa.tp[fa.n_types++] = fused_type(a, p, t);
+    fill_fused_args(fa, a, p, iter_adjacency(a, p));
     if (fa.n_types == 0) return 2;
-    fa.S = p.S; fa.thr = a.state_threshold; fa.k_out = a.k_out;
+    fa.state_in = first; fa.row_base = 0; fa.k_out = a.k_out;
     sa.buf[0] = B[0]; sa.buf[1] = B[1];
-    sa.max_iteration = a.max_iteration;
-    sa.no_exit = (a.flags & GNN_FLAG_NO_EARLY_EXIT) != 0;
+    sa.max_iteration = a.max_iteration; sa.no_exit = (a.flags & GNN_FLAG_NO_EARLY_EXIT) != 0;
     sa.flags = p.flags;
-    sa.pred0 = pred0; sa.n_pred0 = n_pred0;
-    sa.state_final = state_final; sa.ld_final = p.S;
-    sa.bar = reinterpret_cast<unsigned long long *>(p.flags + ((a.max_iteration + 3) & ~1));     // 8-byte aligned (flags is 256-B aligned)
-    if (p.n_groups > 0) {              // one pair of arrival counters per group: the (otherwise idle) mid-size kernel's lines
-        static_assert(4 * GNN_MAX_GROUPS <= gnn::MID_BAR_WORDS, "group counters must fit the zeroed barrier words");
-        sa.groups = p.gt;
+    int rc;
+    if (mid) {
         sa.bar = reinterpret_cast<unsigned long long *>(p.mid_bar);
+        rc = gnn::launch_mid(sa, p.SP, device_cus(), st);
+    } else {
+        sa.pred0 = pred0; sa.n_pred0 = n_pred0;
+        sa.state_final = state_final; sa.ld_final = p.S;
+        sa.bar = reinterpret_cast<unsigned long long *>(p.flags + ((a.max_iteration + 3) & ~1));     // 8-byte aligned (flags is 256-B aligned)
+        if (p.n_groups > 0) {              // one pair of arrival counters per group: the (otherwise idle) mid-size kernel's lines
+            static_assert(4 * GNN_MAX_GROUPS <= gnn::MID_BAR_WORDS, "group counters must fit the zeroed barrier words");
+            sa.groups = p.gt;
+            sa.bar = reinterpret_cast<unsigned long long *>(p.mid_bar);
+        }
+        rc = gnn::launch_small(sa, p.SP, device_cus(), st, p.n_groups > 0 ? p.group_tiles : 0);
     }
-    const int rc = gnn::launch_small(sa, p.SP, device_cus(), st, p.n_groups > 0 ? p.group_tiles : 0);
-    if (rc == 1) return fail("persistent loop kernel: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+    if (rc == 1) return fail("%s loop kernel: launch failed (%s)", mid ? "mid-size" : "persistent", hipGetErrorString(hipGetLastError()));
     return rc;
-}
-
-// Mid-size graphs: the whole loop in one launch with several tiles per workgroup (kernel_state_mid.hpp).  Between the
-// small whole-loop kernel's range (one tile per CU) and GNN_MID_MAX_NODES.  The default is where one launch per iteration
-// of the wave-specialised kernel catches up (profiles/r02_mid_sweep.txt, 10 arcs per node: d = 64 25.4 vs 28.5 us at
-// 30 000 nodes, 40.1 vs 35.7 at 45 000; d = 32 16.4 vs 17.6 at 30 000, 26.3 vs 26.1 at 60 000); pinned with
-// GNN_FLAG_FUSED_GEN6 at any size.
-int mid_max_nodes() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("GNN_MID_MAX_NODES"); v = e ? atoi(e) : 36000; }
-    return v;
-}
-
-bool mid_applies(const gnn_loop_args_t &a, const Plan &p) {
-    const int pinned = (a.flags & GNN_FLAG_FUSED_GEN_MASK) >> 4;
-    if (pinned != 0 && pinned != 6) return false;
-    static int env = -1;
-    if (env < 0) { const char *e = getenv("GNN_FUSED_KERNEL"); env = e ? atoi(e) : 0; }
-    if (pinned == 0 && env != 0 && env != 6) return false;
-    if (p.n_heavy != 0 || a.max_iteration < 1 || (p.SP != 32 && p.SP != 64) || p.N == 0) return false;
-    return pinned == 6 || env == 6 || p.N <= mid_max_nodes();
-}
-
-int loop_mid(const gnn_loop_args_t &a, const Plan &p, const float *first, float *const B[2], hipStream_t st) {
-    gnn::SmallArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    gnn::Fused2Args &fa = sa.f;
-    const gnn_csr_t &adj = iter_adjacency(a, p);
-    fa.rowptr = adj.rowptr; fa.src = adj.src; fa.w = adj.w; fa.row_scale = adj.row_scale;
-    fa.state_in = first; fa.row_base = 0;
-    fa.C = p.C; fa.ldC = p.ldC;
-    for (int t = 0; t < p.T; ++t)
-        if (p.tp[t].count > 0)
-            fa.tp[fa.n_types++] = fused_type(a, p, t);
-    if (fa.n_types == 0) return 2;
-    fa.S = p.S; fa.thr = a.state_threshold; fa.k_out = a.k_out;
-    sa.buf[0] = B[0]; sa.buf[1] = B[1];
-    sa.max_iteration = a.max_iteration;
-    sa.no_exit = (a.flags & GNN_FLAG_NO_EARLY_EXIT) != 0;
-    sa.flags = p.flags;
-    sa.bar = reinterpret_cast<unsigned long long *>(p.mid_bar);
-    const int rc = gnn::launch_mid(sa, p.SP, device_cus(), st);
-    if (rc == 1) return fail("mid-size loop kernel: launch failed (%s)", hipGetErrorString(hipGetLastError()));
-    return rc;
-}
-
-// Groups whose whole state fits the LDS of one CU: one workgroup per group, no grid barrier (kernel_state_lds.hpp, generation 7).
-// May this call take that form, by its pinned generation / GNN_FUSED_KERNEL?
-bool lds_generation_allowed(const gnn_loop_args_t &a) {
-    const int pinned = (a.flags & GNN_FLAG_FUSED_GEN_MASK) >> 4;
-    static int env = -1;
-    if (env < 0) { const char *e = getenv("GNN_FUSED_KERNEL"); env = e ? atoi(e) : 0; }
-    return !((pinned != 0 && pinned != 7) || (pinned == 0 && env != 0 && env != 7));
-}
-
-bool lds_applies(const gnn_loop_args_t &a, const Plan &p) {
-    if (!lds_generation_allowed(a)) return false;
-    if (p.n_groups < 1 || p.composite || p.n_heavy != 0 || a.max_iteration < 1 || (p.SP != 16 && p.SP != 32)) return false;
-    if (a.net_state[0].n_layers != 1 || a.net_state[0].activation[0] == GNN_ACT_SOFTMAX || (a.flags & GNN_FLAG_UNFUSED)) return false;
-    if (p.has_sets && p.n_groups > device_cus()) return false;      // groups that wait for each other must all be resident
-    return gnn::lds_group_fits(p.group_max_nodes, p.SP);
 }
 
 // what both one-CU-per-group kernels are told alike (la: zeroed); tile64_begin and the state network(s) are the caller's
@@ -1204,19 +1072,7 @@ int loop_lds(const gnn_loop_args_t &a, const Plan &p, hipStream_t st) {
     return rc;
 }
 
-// ... of a heterogeneous model (kernel_state_lds_types.hpp): every type's state network one Dense layer; the largest group must fit with
-// every (group, type) range padded to 16 rows - decided from the shapes alone (type_nodes is a device array): rows <= n_g + 15 n_types.
-bool lds_types_applies(const gnn_loop_args_t &a, const Plan &p) {
-    if (!lds_generation_allowed(a)) return false;
-    if (p.n_groups < 1 || !p.composite || p.T < 1 || p.T > GNN_MAX_TYPES || p.n_heavy != 0 || a.n_heavy_segments > 0 || a.nodes_src) return false;
-    if (a.max_iteration < 1 || (p.SP != 16 && p.SP != 32) || (a.flags & GNN_FLAG_UNFUSED)) return false;
-    for (int t = 0; t < p.T; ++t)
-        if (a.net_state[t].n_layers != 1 || a.net_state[t].activation[0] == GNN_ACT_SOFTMAX || (int)a.net_state[t].units[0] != p.S) return false;
-    if (p.has_sets && p.n_groups > device_cus()) return false;      // groups that wait for each other must all be resident
-    if ((size_t)(p.N + (size_t)15 * p.T * p.n_groups) * p.SP * 4 >= ((size_t)1 << 32)) return false;      // the staging rows: 32-bit byte offsets
-    return gnn::lds_types_group_fits(p.group_max_nodes, p.T, p.SP);
-}
-
+// ... of a heterogeneous model (kernel_state_lds_types.hpp)
 int loop_lds_types(const gnn_loop_args_t &a, const Plan &p, hipStream_t st) {
     gnn::LdsTypesArgs ta;
     memset(&ta, 0, sizeof(ta));
@@ -1228,46 +1084,6 @@ int loop_lds_types(const gnn_loop_args_t &a, const Plan &p, hipStream_t st) {
     const int rc = gnn::launch_lds_types(ta, p.SP, p.group_max_nodes, st);
     if (rc == 1) return fail("LDS-resident loop kernel (types): launch failed (%s)", hipGetErrorString(hipGetLastError()));
     return rc;
-}
-
-// 0: un-fused kernels; 1: any fused kernel; 2: two-layer state networks - only the wave-specialised kernel and the
-// persistent whole-loop kernel carry the second Dense; 3: state width 65 .. 128 - the wide kernel, whatever generation is pinned.
-int fusable(const gnn_loop_args_t &a, const Plan &p) {
-    if (a.flags & GNN_FLAG_UNFUSED) return 0;
-    if (p.SP > 128) return 0;      // W1 = [2SP x SP] floats must fit the CU's LDS: 128 KB at SP = 128 (kernel_state_wide.hpp)
-    // the fused kernel addresses state rows and C with 32-bit byte offsets off a scalar base
-    if ((size_t)(std::max(a.adjacency.n_src, p.N) + p.n_heavy) * p.SP * 4 >= ((size_t)1 << 32) || (size_t)p.N * p.ldC * 4 >= ((size_t)1 << 32)) return 0;
-    // ... and the CSR arrays through 4 GiB buffer windows
-    if ((size_t)iter_adjacency(a, p).nnz * 4 >= ((size_t)1 << 32) || ((size_t)p.N + 1) * 4 >= ((size_t)1 << 32)) return 0;
-    // One Dense layer everywhere, or two with at most SP hidden units (the matrix waves have the time, and LDS holds a
-    // second weight matrix in place of two ring slots).
-    bool two = false;
-    for (int t = 0; t < p.T; ++t) {
-        const gnn_mlp_t &m = a.net_state[t];
-        if (m.n_layers < 1 || m.n_layers > 2) return 0;
-        if (m.activation[m.n_layers - 1] == GNN_ACT_SOFTMAX && p.SP > 64) return 0;   // a softmax state: the wave-specialised kernel only (widths up to 64)
-        if (m.n_layers == 2 && (m.activation[0] == GNN_ACT_SOFTMAX || m.units[0] > p.SP)) return 0;
-        if (t > 0 && (m.n_layers == 2) != two) return 0;                // every node type the same depth
-        two = m.n_layers == 2;
-    }
-    if (p.SP == 128) return two ? 0 : 3;     // state widths 65 .. 128: one-layer state networks on the wide kernel
-    return two ? 2 : 1;
-}
-
-// State widths 129 .. 256 (kernel_state_xwide.hpp): homogeneous graphs, one Dense layer, no hub split (make_plan keeps hub rows
-// off these widths), every array within the 32-bit byte offsets of a buffer window.  GNN_XWIDE=0 keeps the un-fused path.
-bool xwide_applies(const gnn_loop_args_t &a, const Plan &p) {
-    static int env = -1;
-    if (env < 0) { const char *e = getenv("GNN_XWIDE"); env = (e && atoi(e) == 0) ? 0 : 1; }
-    if (!env || (a.flags & GNN_FLAG_UNFUSED)) return false;
-    if (p.SP <= 128 || p.S > 256 || p.composite || p.T != 1 || p.tp[0].rows || p.n_heavy != 0 || p.N < 1 || !p.Wx) return false;
-    if (a.n_heavy_segments > 0) return false;      // hub rows (the caller's split says so): one gather wave would walk a hub two rows at a time
-
-    const gnn_mlp_t &m = a.net_state[0];
-    if (m.n_layers != 1 || m.activation[0] == GNN_ACT_SOFTMAX || (int)m.units[0] != p.S) return false;
-    if ((size_t)std::max(a.adjacency.n_src, p.N) * p.SP * 4 >= ((size_t)1 << 32) || (size_t)p.N * p.ldC * 4 >= ((size_t)1 << 32)) return false;
-    if ((size_t)a.adjacency.nnz * 4 >= ((size_t)1 << 32) || ((size_t)p.N + 1) * 4 >= ((size_t)1 << 32)) return false;
-    return true;
 }
 
 #ifdef XB_EXPERIMENT
@@ -1296,12 +1112,6 @@ int iteration_xwide(const gnn_loop_args_t &a, const Plan &p, const int *gate, co
 #endif
     FUSED_OK(gnn::launch_xwide_b3(xa, device_cus(), xwide_matrix_waves(), st));
     return 0;
-}
-
-// may ONE ITERATION of this model run in a fused launch? (the per-iteration entry points and the loop's fallback)
-bool can_fuse(const gnn_loop_args_t &a, const Plan &p) {
-    const int f = fusable(a, p);
-    return f == 1 || f == 3 || (f == 2 && iteration_generation(a, p) == 4);
 }
 
 }  // namespace
@@ -1351,21 +1161,20 @@ size_t gnn_struct_size(int which) {
     }
 }
 
-// every iteration on the XC form of the wave-specialised kernel (large homogeneous / composite graphs): C is never read
-bool xc_loop_applies(const gnn_loop_args_t &a, const Plan &p, int fz, bool soft, bool whole_loop) {
-    return p.xc_ok && !whole_loop && fz == 1 && (soft || !mid_applies(a, p)) && p.SP != 128 && !iter_adjacency(a, p).w &&
-           iteration_generation(a, p) == 4 && fused_generation(p.SP, p.N, a.flags) == 4;
-}
-
 int gnn_loop_xc_applies(const gnn_loop_args_t *args) {
     if (!args) return 0;
     Plan p;
     if (make_plan(*args, nullptr, p, false)) return 0;
     if (p.composite || p.N == 0 || p.n_groups > 0) return 0;
-    const int fz = fusable(*args, p);
-    const bool soft = state_softmax(*args, p);
-    const bool whole_loop = fz != 0 && !soft && persistent_applies(*args, p);
-    return xc_loop_applies(*args, p, fz, soft, whole_loop) ? 1 : 0;
+    return route_loop(*args, p).xc_loop ? 1 : 0;
+}
+
+const char *gnn_loop_route_name(const gnn_loop_args_t *args) {
+    static thread_local char name[640];
+    name[0] = 0;
+    Plan p;
+    if (args && !make_plan(*args, args->workspace, p, false)) route_name(route_loop(*args, p), name, sizeof(name));
+    return name;
 }
 
 size_t gnn_loop_workspace_bytes(const gnn_loop_args_t *args) {
@@ -1419,9 +1228,11 @@ int gnn_loop_forward(const gnn_loop_args_t *args) {
 
     // Graphs the whole-loop kernel covers: one set-up launch, the loop, the output stage.  Everything else: the general
     // set-up (one launch per constant) and one launch per iteration.
-    const int fz = fusable(a, p);
+    const LoopRoute route = route_loop(a, p);
+    if (route.refused) return fail("%s", route.refused);
+    switch (route.whole) {
     // Groups that fit the LDS of one CU: set-up launch, one workgroup per group, output stage.
-    if (p.n_groups > 0 && fz == 1 && lds_applies(a, p) && setup_small_applies(a, p)) {
+    case WholeLoop::lds: {
         TRY(upload_group_tabs(a, p, st));
         Plan q = p;
         q.gt.n = 0;                                 // the set-up kernel reads the device tables
@@ -1433,10 +1244,8 @@ int gnn_loop_forward(const gnn_loop_args_t *args) {
         return output_stage(a, p, st);
     }
     // ... of a heterogeneous model: the general set-up (constants per type), the type-begin table and state_0's predicate per group, then
-    // one workgroup per group on the typed kernel.  Nothing else runs composite groups: what is not covered fails here, before any launch.
-    if (p.n_groups > 0 && p.composite) {
-        if (fz != 1 || !lds_types_applies(a, p))
-            return fail("convergence groups of a composite graph need the one-CU-per-group kernel (gnn_loop_groups_supported() != 2 for these args)");
+    // one workgroup per group on the typed kernel.  Nothing else runs composite groups: what is not covered was refused above, before any launch.
+    case WholeLoop::lds_types: {
         TRY(upload_group_tabs(a, p, st));
         TRY(setup_constants(a, p, st, /*zero_loop_words=*/true));
         HIP_OK(hipMemsetAsync(a.k_out, 0, sizeof(float) * (size_t)p.n_groups, st));
@@ -1453,15 +1262,10 @@ int gnn_loop_forward(const gnn_loop_args_t *args) {
         if (a.ev_loop_end) HIP_OK(hipEventRecord((hipEvent_t)a.ev_loop_end, st));
         return output_stage(a, p, st);
     }
-    if (p.has_sets) return fail("convergence group sets need the one-CU-per-group form (gnn_loop_groups_supported() != 2 for these args)");
-    if (p.n_groups > GNN_MAX_GROUPS) return fail("more than %d convergence groups need every group to fit one CU's LDS (gnn_loop_groups_supported() != 2)", GNN_MAX_GROUPS);
-    const bool soft = state_softmax(a, p);          // (one launch per iteration on the wave-specialised kernel)
-    const bool whole_loop = fz != 0 && !soft && persistent_applies(a, p);
-    const bool small_setup = whole_loop && setup_small_applies(a, p);
-    if (p.n_groups > 0 && !small_setup) return fail("convergence groups need the whole-loop kernel (gnn_loop_groups_supported() == 0 for these args)");
-    const bool xc_loop = xc_loop_applies(a, p, fz, soft, whole_loop);
-    // ... of a homogeneous graph: the line is filled in place, into the caller's buffer if there is one, or adopted from it (gnn_loop_args_t::xc)
-    const bool xc_line = xc_loop && !p.composite && p.N > 0;
+    default: break;      // the small / mid-size whole-loop kernel, one launch per iteration: below
+    }
+    const bool small_setup = route.small_setup, xc_loop = route.xc_loop, xc_line = route.xc_line;
+    // xc_line: the line is filled in place, into the caller's buffer if there is one, or adopted from it (gnn_loop_args_t::xc)
     if (xc_line && a.xc) { TRY(check_xc_args(a)); p.Xc = a.xc; }
     if (small_setup) TRY(setup_small(a, p, st));
     else             TRY(setup_constants(a, p, st, /*zero_loop_words=*/true, /*skip_c=*/xc_loop, nullptr, xc_line,
@@ -1477,10 +1281,8 @@ int gnn_loop_forward(const gnn_loop_args_t *args) {
     if (p.SP != p.S) HIP_OK(hipMemsetAsync(p.buf[1], 0, sizeof(float) * (size_t)p.N * p.SP, st));
     if (!small_setup) TRY(launch_converge(nullptr, first, nullptr, p.N, p.S, p.SP, 0, a.state_threshold, p.flags, nullptr, 0.f, st));
 
-    const bool fused = can_fuse(a, p);
-    const bool prefix = !fused && prefix_applies(a, p);
-    const bool xwide = !fused && !prefix && xwide_applies(a, p);
-    if (xwide) TRY(setup_xwide(a, p, st));
+    const IterKernel kernel = route.iter.kernel;
+    if (kernel == IterKernel::xwide) TRY(setup_xwide(a, p, st));
     const bool no_exit = (a.flags & GNN_FLAG_NO_EARLY_EXIT) != 0;
     // Ping-pong buffers.  When the caller's state_out has the padded layout too, it stands in for the buffer the LAST
     // iteration writes (B[max_iteration & 1]): a loop that runs to max_iteration leaves the result where the caller
@@ -1490,14 +1292,14 @@ int gnn_loop_forward(const gnn_loop_args_t *args) {
         B[a.max_iteration & 1] = a.state_out;
     if (a.ev_loop_begin) HIP_OK(hipEventRecord((hipEvent_t)a.ev_loop_begin, st));
     int persistent = 2;
-    if (whole_loop) {                              // (two-layer state networks too); the kernel also writes state_out
-        persistent = loop_persistent(a, p, first, B, small_setup ? p.pred0 : nullptr, small_setup ? p.group_tiles : 0, a.state_out, st);
+    if (route.whole == WholeLoop::small) {         // (two-layer state networks too); the kernel also writes state_out
+        persistent = loop_whole(a, p, /*mid=*/false, first, B, small_setup ? p.pred0 : nullptr, small_setup ? p.group_tiles : 0, a.state_out, st);
         if (persistent == 1) return 1;
         if (persistent == 2 && small_setup) return fail("whole-loop kernel refused a graph its set-up kernel accepted");
     }
     bool loop_done = persistent == 0;
-    if (!loop_done && fz == 1 && !soft && mid_applies(a, p)) {
-        const int rc = loop_mid(a, p, first, B, st);
+    if (!loop_done && route.try_mid) {
+        const int rc = loop_whole(a, p, /*mid=*/true, first, B, nullptr, 0, nullptr, st);
         if (rc == 1) return 1;
         loop_done = rc == 0;
     }
@@ -1505,10 +1307,10 @@ int gnn_loop_forward(const gnn_loop_args_t *args) {
         const int *gate = no_exit ? nullptr : p.flags + it;
         const float *src = it == 0 ? first : B[it & 1];
         float *dst = B[(it + 1) & 1];
-        if (fused)       TRY(iteration_fused(a, p, gate, gate ? 1 : 0, 0, src, dst, 0, p.flags + it + 1, a.k_out, (float)(it + 1), st));
-        else if (prefix) TRY(iteration_prefix(a, p, gate, src, dst, p.flags + it + 1, a.k_out, (float)(it + 1), st));
-        else if (xwide)  TRY(iteration_xwide(a, p, gate, src, dst, p.flags + it + 1, a.k_out, (float)(it + 1), st));
-        else             TRY(iteration_unfused(a, p, gate, src, dst, 0, p.flags + it + 1, a.k_out, (float)(it + 1), st));
+        if (route.iter.fused())                  TRY(iteration_fused(a, p, kernel, gate, gate ? 1 : 0, 0, src, dst, 0, p.flags + it + 1, a.k_out, (float)(it + 1), st));
+        else if (kernel == IterKernel::prefix)   TRY(iteration_prefix(a, p, gate, src, dst, p.flags + it + 1, a.k_out, (float)(it + 1), st));
+        else if (kernel == IterKernel::xwide)    TRY(iteration_xwide(a, p, gate, src, dst, p.flags + it + 1, a.k_out, (float)(it + 1), st));
+        else                                     TRY(iteration_unfused(a, p, gate, src, dst, 0, p.flags + it + 1, a.k_out, (float)(it + 1), st));
     }
 
     if (a.ev_loop_end) HIP_OK(hipEventRecord((hipEvent_t)a.ev_loop_end, st));
@@ -1522,7 +1324,7 @@ int gnn_loop_forward(const gnn_loop_args_t *args) {
         }
     }
     TRY(output_stage(a, p, st));
-    if (!loop_done && (fused || xwide) && a.max_iteration > 0) TRY(launch_fold_error(p, a.k_out, st));
+    if (!loop_done && (route.iter.fused() || kernel == IterKernel::xwide) && a.max_iteration > 0) TRY(launch_fold_error(p, a.k_out, st));
     return 0;
 }
 
@@ -1530,11 +1332,10 @@ int gnn_loop_groups_supported(const gnn_loop_args_t *args) {
     if (!args || args->n_groups < 1) return 0;
     Plan p;
     if (make_plan(*args, nullptr, p, false)) return 0;
-    const int fz = fusable(*args, p);
-    if (p.composite) return fz == 1 && lds_types_applies(*args, p) ? 2 : 0;      // (the spread form: homogeneous models only)
-    if (fz == 1 && lds_applies(*args, p) && setup_small_applies(*args, p)) return 2;
-    if (args->n_groups > GNN_MAX_GROUPS) return 0;
-    return fz != 0 && !state_softmax(*args, p) && persistent_applies(*args, p) && setup_small_applies(*args, p) ? 1 : 0;
+    const LoopRoute route = route_loop(*args, p);
+    if (route.whole == WholeLoop::lds || route.whole == WholeLoop::lds_types) return 2;
+    if (p.composite || args->n_groups > GNN_MAX_GROUPS) return 0;                   // (the spread form: homogeneous models only)
+    return route.whole == WholeLoop::small && route.small_setup ? 1 : 0;           // (group SETS: only the answer 2 runs them - gnn_loop_args_t)
 }
 
 int gnn_loop_group_max_nodes(const gnn_loop_args_t *args) {
@@ -1626,9 +1427,10 @@ static int state_step_impl(const gnn_loop_args_t *args, const float *state_in, c
     TRY(launch_copy2d(nullptr, state_in, p.S, p.buf[0], p.SP, p.N, p.S, p.SP, st));
     if (p.SP != p.S) HIP_OK(hipMemsetAsync(p.buf[1], 0, sizeof(float) * (size_t)p.N * p.SP, st));
     if (flag_out) HIP_OK(hipMemsetAsync(flag_out, 0, sizeof(int32_t), st));
-    if (can_fuse(a, p))
-        TRY(iteration_fused(a, p, nullptr, 0, 0, p.buf[0], p.buf[1], 0, flag_out, nullptr, 0.f, st));
-    else if (xwide_applies(a, p)) {
+    const IterRoute it = route_iteration(a, p, knobs(a.flags));
+    if (it.fused())
+        TRY(iteration_fused(a, p, it.kernel, nullptr, 0, 0, p.buf[0], p.buf[1], 0, flag_out, nullptr, 0.f, st));
+    else if (it.kernel == IterKernel::xwide) {
         TRY(setup_xwide(a, p, st));
         TRY(iteration_xwide(a, p, nullptr, p.buf[0], p.buf[1], flag_out, nullptr, 0.f, st));
     } else
@@ -1756,28 +1558,53 @@ int gnn_shard_setup(const gnn_loop_args_t *args) {
     return setup_constants(a, p, st);
 }
 
+// What every gnn_shard_iteration* entry point opens with: the checks of the caller's buffers, iteration number and gate list ...
+static int check_shard_iteration(const gnn_loop_args_t &a, const float *state_in_full, const float *state_out_full, const int32_t *flag_out,
+                                 int32_t iteration, const int32_t *gate, int32_t n_gate) {
+    if (!state_in_full || !state_out_full || !flag_out) return fail("state buffers / flag_out are NULL");
+    if (iteration < 0 || iteration >= a.max_iteration) return fail("iteration %d out of [0, max_iteration)", iteration);
+    if (n_gate < 0 || (n_gate > 0 && !gate)) return fail("bad gate list");
+    return 0;
+}
+// ... and, behind its own checks, the OR of the peers' gate words into this iteration's gate word (*g; NULL = run unconditionally) and
+// flag_out back to zero.  `first`: the gate word is evaluated once and read by every chunk's launch; later chunks OR into flag_out.
+static int shard_gate(const gnn_loop_args_t &a, const Plan &p, const int32_t *gate, int32_t n_gate, int32_t gate_stride, int32_t iteration,
+                      int32_t *flag_out, const int **g, bool first = true) {
+    hipStream_t st = (hipStream_t)a.stream;
+    *g = nullptr;
+    if (n_gate > 0 && !(a.flags & GNN_FLAG_NO_EARLY_EXIT)) {
+        if (first) {
+            k_or_flags<<<1, 64, 0, st>>>(gate, n_gate, gate_stride, p.flags + iteration);
+            LAUNCH_OK();
+        }
+        *g = p.flags + iteration;
+    }
+    if (first) HIP_OK(hipMemsetAsync(flag_out, 0, sizeof(int32_t), st));
+    return 0;
+}
+
+// one iteration of a shard on the route's per-iteration kernel; `peers` (optional): the rows are also stored into the peers' buffers
+static int shard_iteration(const gnn_loop_args_t &a, const float *state_in_full, float *state_out_full, int32_t row_base, const int32_t *gate,
+                           int32_t n_gate, int32_t gate_stride, int32_t *flag_out, int32_t iteration, const gnn_peer_set_t *peers) {
+    TRY(check_shard_iteration(a, state_in_full, state_out_full, flag_out, iteration, gate, n_gate));
+    Plan p;
+    TRY(make_plan(a, a.workspace, p, false));
+    if (row_base < 0 || row_base + p.N > a.adjacency.n_src) return fail("row_base out of the full buffer");
+    const IterRoute it = route_iteration(a, p, knobs(a.flags));
+    if (peers && !it.fused()) return fail("peer stores need the fused iteration kernel");
+    hipStream_t st = (hipStream_t)a.stream;
+    const int *g;
+    TRY(shard_gate(a, p, gate, n_gate, gate_stride, iteration, flag_out, &g));
+    if (!it.fused()) return iteration_unfused(a, p, g, state_in_full, state_out_full, row_base, flag_out, a.k_out, (float)(iteration + 1), st);
+    return iteration_fused(a, p, it.kernel, g, g ? 1 : 0, 0, state_in_full, state_out_full, row_base, flag_out, a.k_out, (float)(iteration + 1), st,
+                           nullptr, nullptr, nullptr, 0, peers);
+}
+
 int gnn_shard_iteration(const gnn_loop_args_t *args, const float *state_in_full, float *state_out_full,
                         int32_t row_base, const int32_t *gate, int32_t n_gate, int32_t gate_stride, int32_t *flag_out,
                         int32_t iteration) {
     if (!args) return fail("args is NULL");
-    const gnn_loop_args_t &a = *args;
-    if (!state_in_full || !state_out_full || !flag_out) return fail("state buffers / flag_out are NULL");
-    if (iteration < 0 || iteration >= a.max_iteration) return fail("iteration %d out of [0, max_iteration)", iteration);
-    if (n_gate < 0 || (n_gate > 0 && !gate)) return fail("bad gate list");
-    Plan p;
-    TRY(make_plan(a, a.workspace, p, false));
-    if (row_base < 0 || row_base + p.N > a.adjacency.n_src) return fail("row_base out of the full buffer");
-    hipStream_t st = (hipStream_t)a.stream;
-    const int *g = nullptr;
-    if (n_gate > 0 && !(a.flags & GNN_FLAG_NO_EARLY_EXIT)) {
-        k_or_flags<<<1, 64, 0, st>>>(gate, n_gate, gate_stride, p.flags + iteration);
-        LAUNCH_OK();
-        g = p.flags + iteration;
-    }
-    HIP_OK(hipMemsetAsync(flag_out, 0, sizeof(int32_t), st));
-    if (can_fuse(a, p))
-        return iteration_fused(a, p, g, g ? 1 : 0, 0, state_in_full, state_out_full, row_base, flag_out, a.k_out, (float)(iteration + 1), st);
-    return iteration_unfused(a, p, g, state_in_full, state_out_full, row_base, flag_out, a.k_out, (float)(iteration + 1), st);
+    return shard_iteration(*args, state_in_full, state_out_full, row_base, gate, n_gate, gate_stride, flag_out, iteration, nullptr);
 }
 
 // ---- the exchange inside the iteration kernel (include/gnnloop.h: gnn_shard_iteration_peers, gnn_peer_wait / _publish, gnn_ipc_*) --------
@@ -1785,24 +1612,7 @@ int gnn_shard_iteration_peers(const gnn_loop_args_t *args, const float *state_in
                               const int32_t *gate, int32_t n_gate, int32_t gate_stride, int32_t *flag_out, int32_t iteration,
                               const gnn_peer_set_t *peers) {
     if (!args || !peers) return fail("args / peers is NULL");
-    const gnn_loop_args_t &a = *args;
-    if (!state_in_full || !state_out_full || !flag_out) return fail("state buffers / flag_out are NULL");
-    if (iteration < 0 || iteration >= a.max_iteration) return fail("iteration %d out of [0, max_iteration)", iteration);
-    if (n_gate < 0 || (n_gate > 0 && !gate)) return fail("bad gate list");
-    Plan p;
-    TRY(make_plan(a, a.workspace, p, false));
-    if (row_base < 0 || row_base + p.N > a.adjacency.n_src) return fail("row_base out of the full buffer");
-    if (!can_fuse(a, p)) return fail("peer stores need the fused iteration kernel");
-    hipStream_t st = (hipStream_t)a.stream;
-    const int *g = nullptr;
-    if (n_gate > 0 && !(a.flags & GNN_FLAG_NO_EARLY_EXIT)) {
-        k_or_flags<<<1, 64, 0, st>>>(gate, n_gate, gate_stride, p.flags + iteration);
-        LAUNCH_OK();
-        g = p.flags + iteration;
-    }
-    HIP_OK(hipMemsetAsync(flag_out, 0, sizeof(int32_t), st));
-    return iteration_fused(a, p, g, g ? 1 : 0, 0, state_in_full, state_out_full, row_base, flag_out, a.k_out, (float)(iteration + 1), st,
-                           nullptr, nullptr, nullptr, 0, peers);
+    return shard_iteration(*args, state_in_full, state_out_full, row_base, gate, n_gate, gate_stride, flag_out, iteration, peers);
 }
 
 // buffers whose BASE pointer a host can export (a framework's caching allocator hands out interior pointers of larger segments)
@@ -1882,12 +1692,7 @@ int gnn_shard_can_split(const gnn_loop_args_t *args) {
     if (!args) return 0;
     Plan p;
     if (make_plan(*args, args->workspace, p, false)) return 0;
-    const int f = fusable(*args, p);
-    if (p.n_heavy != 0) return 0;
-    if (f == 3) return 1;                                          // state widths 65 .. 128: the wide kernel, whatever is pinned
-    if (f != 1 || p.SP <= 16) return 0;                            // one-layer state nets on the wave-specialised kernel
-    const int pinned = (args->flags & GNN_FLAG_FUSED_GEN_MASK) >> 4;
-    return pinned == 0 || pinned == 4;
+    return route_iteration(*args, p, knobs(args->flags)).split_ok ? 1 : 0;
 }
 
 int gnn_shard_partial(const gnn_loop_args_t *args, const gnn_csr_t *adjacency_own, const float *state_in_full,
@@ -1908,24 +1713,16 @@ int gnn_shard_iteration_split(const gnn_loop_args_t *args, const gnn_csr_t *adja
                               int32_t n_gate, int32_t gate_stride, int32_t *flag_out, int32_t iteration) {
     if (!args || !adjacency_halo || !agg_partial) return fail("args / adjacency_halo / agg_partial is NULL");
     const gnn_loop_args_t &a = *args;
-    if (!state_in_full || !state_out_full || !flag_out) return fail("state buffers / flag_out are NULL");
-    if (iteration < 0 || iteration >= a.max_iteration) return fail("iteration %d out of [0, max_iteration)", iteration);
-    if (n_gate < 0 || (n_gate > 0 && !gate)) return fail("bad gate list");
+    TRY(check_shard_iteration(a, state_in_full, state_out_full, flag_out, iteration, gate, n_gate));
     if (!gnn_shard_can_split(args)) return fail("gnn_shard_iteration_split: this model / shard does not run on the wave-specialised kernel");
     Plan p;
     TRY(make_plan(a, a.workspace, p, false));
     TRY(check_csr(*adjacency_halo, "adjacency_halo", p.N, a.adjacency.n_src));
     if (row_base < 0 || row_base + p.N > a.adjacency.n_src) return fail("row_base out of the full buffer");
-    hipStream_t st = (hipStream_t)a.stream;
-    const int *g = nullptr;
-    if (n_gate > 0 && !(a.flags & GNN_FLAG_NO_EARLY_EXIT)) {
-        k_or_flags<<<1, 64, 0, st>>>(gate, n_gate, gate_stride, p.flags + iteration);
-        LAUNCH_OK();
-        g = p.flags + iteration;
-    }
-    HIP_OK(hipMemsetAsync(flag_out, 0, sizeof(int32_t), st));
-    return iteration_fused(a, p, g, g ? 1 : 0, 0, state_in_full, state_out_full, row_base, flag_out, a.k_out,
-                           (float)(iteration + 1), st, adjacency_halo, agg_partial);
+    const int *g;
+    TRY(shard_gate(a, p, gate, n_gate, gate_stride, iteration, flag_out, &g));
+    return iteration_fused(a, p, route_iteration(a, p, knobs(a.flags)).kernel, g, g ? 1 : 0, 0, state_in_full, state_out_full, row_base, flag_out, a.k_out,
+                           (float)(iteration + 1), (hipStream_t)a.stream, adjacency_halo, agg_partial);
 }
 
 int gnn_shard_iteration_split_rows(const gnn_loop_args_t *args, const gnn_csr_t *adjacency_halo, const float *agg_partial,
@@ -1934,9 +1731,7 @@ int gnn_shard_iteration_split_rows(const gnn_loop_args_t *args, const gnn_csr_t 
                                    const int32_t *node_ids, int32_t n_ids, int32_t first_chunk) {
     if (!args || !adjacency_halo || !agg_partial) return fail("args / adjacency_halo / agg_partial is NULL");
     const gnn_loop_args_t &a = *args;
-    if (!state_in_full || !state_out_full || !flag_out) return fail("state buffers / flag_out are NULL");
-    if (iteration < 0 || iteration >= a.max_iteration) return fail("iteration %d out of [0, max_iteration)", iteration);
-    if (n_gate < 0 || (n_gate > 0 && !gate)) return fail("bad gate list");
+    TRY(check_shard_iteration(a, state_in_full, state_out_full, flag_out, iteration, gate, n_gate));
     if (n_ids < 0 || n_ids > a.n_nodes || (n_ids > 0 && !node_ids)) return fail("bad node_ids / n_ids");
     if (a.composite) return fail("gnn_shard_iteration_split_rows: homogeneous models");
     if (!gnn_shard_can_split(args)) return fail("gnn_shard_iteration_split_rows: this model / shard does not run on the wave-specialised kernel");
@@ -1945,19 +1740,11 @@ int gnn_shard_iteration_split_rows(const gnn_loop_args_t *args, const gnn_csr_t 
     if (p.SP > 64) return fail("gnn_shard_iteration_split_rows: state widths up to 64");
     TRY(check_csr(*adjacency_halo, "adjacency_halo", p.N, a.adjacency.n_src));
     if (row_base < 0 || row_base + p.N > a.adjacency.n_src) return fail("row_base out of the full buffer");
-    hipStream_t st = (hipStream_t)a.stream;
-    const int *g = nullptr;
-    if (n_gate > 0 && !(a.flags & GNN_FLAG_NO_EARLY_EXIT)) {
-        if (first_chunk) {          // the gate word of this iteration: evaluated once, read by every chunk's launch
-            k_or_flags<<<1, 64, 0, st>>>(gate, n_gate, gate_stride, p.flags + iteration);
-            LAUNCH_OK();
-        }
-        g = p.flags + iteration;
-    }
-    if (first_chunk) HIP_OK(hipMemsetAsync(flag_out, 0, sizeof(int32_t), st));      // (later chunks OR into it)
+    const int *g;
+    TRY(shard_gate(a, p, gate, n_gate, gate_stride, iteration, flag_out, &g, first_chunk != 0));
     if (n_ids == 0) return 0;
-    return iteration_fused(a, p, g, g ? 1 : 0, 0, state_in_full, state_out_full, row_base, flag_out, a.k_out,
-                           (float)(iteration + 1), st, adjacency_halo, agg_partial, node_ids, n_ids);
+    return iteration_fused(a, p, route_iteration(a, p, knobs(a.flags)).kernel, g, g ? 1 : 0, 0, state_in_full, state_out_full, row_base, flag_out, a.k_out,
+                           (float)(iteration + 1), (hipStream_t)a.stream, adjacency_halo, agg_partial, node_ids, n_ids);
 }
 
 int gnn_shard_output(const gnn_loop_args_t *args, const float *buf0_full, const float *buf1_full, int32_t row_base) {
@@ -1975,7 +1762,7 @@ int gnn_shard_output(const gnn_loop_args_t *args, const float *buf0_full, const 
         LAUNCH_OK();
     }
     TRY(output_stage(a, p, st));
-    return can_fuse(a, p) ? launch_fold_error(p, a.k_out, st) : 0;
+    return route_iteration(a, p, knobs(a.flags)).fused() ? launch_fold_error(p, a.k_out, st) : 0;
 }
 
 }  // extern "C"

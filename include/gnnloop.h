@@ -211,6 +211,19 @@ int gnn_loop_forward(const gnn_loop_args_t *args);
 /* 1 when gnn_loop_forward would read / fill args->xc for these arguments, else 0.  Reads dims, network shapes, flags, the
  * GNN_XC / GNN_XC_MIN_NODES environment, n_heavy_segments and WHETHER adjacency.w / adjacency_light.w are NULL; no device memory. */
 int gnn_loop_xc_applies(const gnn_loop_args_t *args);
+/* Which kernels gnn_loop_forward would run for these arguments, without launching anything (additive; reads what the two queries
+ * around it read).  A thread-local string, valid until this thread's next call:
+ *   "k_state_lds" / "k_state_lds_types"        convergence groups, one workgroup per group;
+ *   "k_state_small(setup_small)"               the small whole-loop kernel behind its one-launch set-up;
+ *   "[k_state_small > ][k_state_mid > ]<k>"    the kernels in the order they are tried: a whole-loop launcher may still decline at
+ *                                              launch (residency, tile budget), <k> is the per-iteration kernel - k_state_fused2,
+ *                                              k_state_fused4, k_state_wide, "k_state_fused4<.., L2>" (three-layer prefix form),
+ *                                              k_state_xwide_b3 or k_aggregate_vec (un-fused) - with "+xc" when every iteration
+ *                                              reads the constants line (gnn_loop_xc_applies);
+ *   "refused: <gnn_last_error text>"           gnn_loop_forward fails with that text before its first launch;
+ *   ""                                         args is NULL or malformed (gnn_loop_workspace_bytes answers 0).
+ * The stems are those of gnn_last_kernel_name().  The rule itself: gnnkeras_amd/csrc/loop_route.hpp. */
+const char *gnn_loop_route_name(const gnn_loop_args_t *args);
 /* Non-zero when gnn_loop_forward accepts these args with n_groups > 0, else 0 (the caller then runs one call per batch).
  *   2: every group's state fits the LDS of one CU (nodes_g * padded width * 4 <= 156 KB, width <= 32, one-layer state network):
  *      one workgroup per group, any number of groups up to GNN_MAX_GROUPS_RESIDENT - the more the better, 256 run at once.

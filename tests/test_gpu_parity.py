@@ -1291,3 +1291,94 @@ def test_constant_inputs_variant_at_every_size(mutag_graphs, monkeypatch):
     test_hub_rows_use_the_segment_prepass('average', False, 64)
     test_hub_rows_use_the_segment_prepass('average', False, 32)
     assert ',true>' in c3_case('average').replace(' ', ''), 'C3 did not run the XC form'
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# every route of the forward loop (csrc/loop_route.hpp) at the smallest shape that crosses a tile boundary: what
+# gnn_loop_route_name announces is what runs, and it computes what the un-fused kernels compute
+# ----------------------------------------------------------------------------------------------------------------------
+def _route_name(model, n, e, L, A, flags, groups=None, type_counts=None, type_dims=None):
+    """gnn_loop_route_name for the shapes of a call (dims, network shapes, flags, group table; `average`: no per-arc weights)."""
+    a = nat.LoopArgs()
+    a.abi_version, a.n_nodes, a.n_arcs, a.dim_arc_label = nat.GNN_ABI_VERSION, n, e, A
+    a.state_dim, a.max_iteration, a.state_threshold, a.flags = model.state_vect_dim, model.max_iteration, float(model.state_threshold), flags
+    a.adjacency, a.arcnode = nat.CSR(n, n, e, None, None, None, None), nat.CSR(n, e, e, None, None, None, None)
+    if type_dims is None:
+        a.n_types, a.dim_node_label = 1, L
+        a.net_state[0] = model.net_state.to('cuda').native()
+    else:
+        a.composite, a.n_types, a.dim_node_label = 1, len(type_dims), max(type_dims)
+        for t, net in enumerate(model.net_state):
+            a.net_state[t], a.type_dim_label[t], a.type_offsets[t + 1] = net.to('cuda').native(), type_dims[t], sum(type_counts[:t + 1])
+    a.net_output = model.net_output.to('cuda').native()
+    a.focus, a.n_out = nat.FOCUS['n'], n
+    if groups is not None:
+        nb = (C.c_int32 * len(groups))(*groups)
+        a.group_node_begin, a.n_groups = C.cast(nb, C.c_void_p), len(groups) - 1
+    return nat.lib().gnn_loop_route_name(C.byref(a)).decode()
+
+
+ROUTE_CASES = {        # route: (state width, flags, hidden layers of the state network, GNN_XC_MIN_NODES, the name)
+    'small': (32, 0, None, None, 'k_state_small(setup_small)'),
+    'mid': (32, nat.FLAG_FUSED_GEN6, None, None, 'k_state_mid > k_state_fused2'),
+    'fused2': (32, nat.FLAG_FUSED_GEN2, None, None, 'k_state_fused2'),
+    'fused4': (32, nat.FLAG_FUSED_GEN4, None, None, 'k_state_fused4'),
+    'fused4+xc': (32, nat.FLAG_FUSED_GEN4, None, '0', 'k_state_fused4+xc'),
+    'wide': (128, 0, None, None, 'k_state_wide'),
+    'xwide': (200, 0, None, None, 'k_state_xwide_b3'),
+    'prefix': (32, 0, [24, 24], None, 'k_state_fused4<.., L2>'),
+    'unfused': (300, 0, None, None, 'k_aggregate_vec'),
+    'lds groups': (16, 0, None, None, 'k_state_lds'),
+    'typed lds groups': (16, 0, None, None, 'k_state_lds_types'),
+}
+
+
+@pytest.mark.parametrize('route', list(ROUTE_CASES))
+def test_every_route_runs_what_its_name_says_and_equals_the_unfused_kernels(route, monkeypatch):
+    """130 nodes (64 + 64 + 2), about 4 arcs per node, 5 iterations (threshold 0: k = 5); groups of 20, 40 and 70 nodes."""
+    d, flags, hidden, xc_min, want_name = ROUTE_CASES[route]
+    if xc_min is not None: monkeypatch.setenv('GNN_XC_MIN_NODES', xc_min)
+    rng = np.random.default_rng(130)
+    L, A, K = 5, 2, 5
+    grouped, typed = 'groups' in route, route.startswith('typed')
+    sizes = (20, 40, 70) if grouped else (130,)
+    if typed:
+        dims = (3, 2)
+        gl = [er_composite_graph(n, 4 * n, dim_node_label=dims, aggregation_mode='average', seed=60 + i) for i, n in enumerate(sizes)]
+        seq = CompositeMultiGraphSequencer(gl, 'n', 'average', 1, shuffle=False)
+        ns, no = composite_nets(dims, gl[0].arcs.shape[1] - 2, d, 2, 'n')
+        model = CompositeGNNnodeBased(ns, no, d, K, 0.0)
+        A = gl[0].arcs.shape[1] - 2
+        kw = dict(type_dims=dims, type_counts=[int(sum(g.type_mask[:, t].sum() for g in gl)) for t in range(len(dims))])
+    else:
+        gl = [_random_graph(rng, n, 4 * n, L, A) for n in sizes]
+        seq = MultiGraphSequencer(gl, 'n', 'average', 1, shuffle=False)
+        ns, no = starter_nets('n', d, L=L, A=A, scale=0.3, hidden_state=hidden, act='tanh' if hidden else 'selu')
+        model = GNNnodeBased(ns, no, d, K, 0.0)
+        kw = {}
+    s0s = [rng.normal(0, 0.1, (n, d)).astype(np.float32) for n in sizes]
+    # the un-fused kernels, batch by batch (they run no convergence groups)
+    model.native_flags = nat.FLAG_UNFUSED
+    ref = [model.Loop(*model.process_inputs(seq[i][0]), state0=dev(s0s[i])) for i in range(len(sizes))]
+    k_ref = [float(r[0]) for r in ref]
+    st_ref, o_ref = torch.cat([r[1] for r in ref]).cpu().numpy(), torch.cat([r[2] for r in ref]).cpu().numpy()
+    assert k_ref == [float(K)] * len(sizes)
+    if grouped: x, begin = seq.merged_batches(0, len(sizes))
+    else: x, begin = seq[0][0], None
+    n, e = x[0].shape[0], x[1].shape[0]
+    name = _route_name(model, n, e, L, A, flags, groups=begin, **kw)
+    print(route, '->', name)
+    assert name == want_name
+    model.native_flags = flags
+    k, st, o = model.Loop(*model.process_inputs(x), state0=dev(np.concatenate(s0s)), **(dict(groups=begin) if grouped else {}))
+    torch.cuda.synchronize()
+    last = _last_kernel()
+    print(route, 'ran', last)
+    stem = name.split(' > ')[0].replace('(setup_small)', '').replace('+xc', '')
+    assert last.startswith(stem), (name, last)
+    if stem == 'k_state_fused4':          # the XC template argument (the 7th) is the name's "+xc"
+        assert last[last.index('<') + 1:last.index('>')].split(',')[6] == ('true' if name.endswith('+xc') else 'false'), (name, last)
+    assert [float(v) for v in k.reshape(-1).cpu()] == k_ref
+    e_st, e_o = rel_err(st.cpu().numpy(), st_ref), rel_err(o.cpu().numpy(), o_ref)
+    print(route, 'state / output against the un-fused kernels:', e_st, e_o)
+    assert e_st <= TOL and e_o <= TOL, (route, e_st, e_o)
