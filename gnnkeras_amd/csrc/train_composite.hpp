@@ -5,12 +5,11 @@
 // executed iteration and network, the output network on the converged state alone (CompositeGNN.py:237-239), Keras loss, and
 // back-propagation through the k executed iterations.
 //
-// Round 3 trained such models from Python on the device building blocks (Models/training.py): ~25 launches per node type and
-// iteration pair with the interpreter between them - 15.6 ms per step on batches of 32 small typed graphs (d = 32, 20 iterations)
-// against 1.1 ms for a homogeneous batch of that size.  This is the same arithmetic with the orchestration inside the library
-// (the general kernels of train_loop.hpp with per-type row lists: k_segdense / k_dense_grad_* / k_colstats_* take a row index per
-// segment), one host synchronisation per step (to learn k).  Node, graph and arc focus (CompositeGNN.py:315-327: the output network over
-// [state_src | state_dst | arc label] of the masked arcs); LGNN label gradients keep the building-block path.
+// The same arithmetic as the building blocks driven from Python (Models/training.py) with the orchestration inside the library (the general
+// kernels of train_loop.hpp with per-type row lists: k_segdense / k_dense_grad_* / k_colstats_* take a row index per segment), one host
+// synchronisation per step (to learn k).  Node, graph and arc focus (CompositeGNN.py:315-327: the output network over [state_src | state_dst
+// | arc label] of the masked arcs); LGNN label gradients keep the building-block path.  The phases the step shares with the homogeneous one
+// (argument checks, read_k, output head, loss, head backward, finish_step, ..) are train_loop.hpp's.
 #pragma once
 // (included by gnnloop.hip behind train_loop.hpp: shares its anonymous-namespace helpers)
 #include "train_composite_big.hpp"      // large graphs: the row-streaming kernels on per-type position ranges
@@ -28,25 +27,16 @@ struct CType {                       // one node type
     float *Gc, *dx;                  // [count, S] gathered gradient rows, [count, 2 S] d loss / d [state | agg] rows
 };
 
-struct CPlan {
-    int N, E, S, L, A, M, R, T, K, G, n_types, sum_d, W_comp;
-    bool pooled, agg_taped;
-    int *grads_ok;               // first word of the tape (gnn_train_args_t::grads_ok_dev)
-    int *flags; float *k_dev;
-    float *states, *agg, *agg_comp;
-    float *stats_o, *Wf_o, *bf_o, *dx_o_all, *dx_full, *G_state, *G_out, *dpred, *loss_rows, *loss_part, *part;
-    size_t part_floats;
-    NetCtx co;
+struct CPlan : StepPlan {            // (train_loop.hpp: what the two kinds' plans share)
+    int n_types, sum_d, W_comp;
+    float *agg_comp, *dx_full;
     CType ty[GNN_MAX_TYPES];
     // small graphs: the K forward / k backward iterations as ONE persistent launch each (kernels_train_small.hpp), the nodes walked in type
     // order in tiles of <= 64 nodes of one type: the tape's rows are POSITIONS (position i = node type_nodes[i]), `inv` maps back
-    bool small; int SPs, ldS, n_wg, wg_begin[GNN_MAX_TYPES + 1];
-    int *inv; float *sm_cc, *sm_part, *sm_dxa, *sm_partW[GNN_MAX_TYPES], *sm_partBN[GNN_MAX_TYPES]; unsigned long long *sm_bar;
-    int *isrc, *idst;            // arc focus: the end nodes of the masked arcs
+    int wg_begin[GNN_MAX_TYPES + 1];
+    int *inv; float *sm_dxa, *sm_partW[GNN_MAX_TYPES], *sm_partBN[GNN_MAX_TYPES];
     // large graphs (train_composite_big.hpp): the tape's rows are POSITIONS too, every type a contiguous range of them
-    bool big; CBig B;
-    bool head_fast; float *part_h;       // large graphs: a thin output head over EVERY node on the row-streaming head kernels (k_head_wgrad / k_head_dx)
-    size_t bytes;
+    CBig B;
 };
 
 // inv[perm[i]] = i
@@ -80,7 +70,27 @@ int gather_rows(const float *src, int ld_src, const int *idx, int M, int width, 
     return 0;
 }
 
-int make_cplan(const gnn_train_args_t &ta, void *ws, CPlan &p) {
+// Which path a composite step takes (dims, SPs, n_wg of `p` are set; the sibling of homogeneous_train_path, train_loop.hpp).  The
+// persistent kernels: every state network one Dense layer of the state's width, every non-empty type with or every one without
+// BatchNormalization - the tiles meet at the same grid barriers -, 1 .. 256 tiles, all resident at once.  The row-streaming kernels on type
+// ranges: composite_big_applies (train_composite_big.hpp).  Else one launch per layer, type and iteration.
+TrainPath composite_train_path(const gnn_train_args_t &ta, CPlan &p, bool drop_s) {
+    const gnn_loop_args_t &a = ta.loop;
+    bool uniform = true;
+    int bn_seen = -1;
+    for (int t = 0; t < p.n_types; ++t) {
+        const gnn_mlp_t &m = a.net_state[t];
+        if (!one_dense_of_state_width(m, p.S)) uniform = false;
+        if (a.type_offsets[t + 1] - a.type_offsets[t] <= 0) continue;
+        if (bn_seen < 0) bn_seen = m.has_bn ? 1 : 0;
+        else if (bn_seen != (m.has_bn ? 1 : 0)) uniform = false;
+    }
+    if (uniform && train_small_fits(p, drop_s) && p.n_wg >= 1 && p.n_wg <= 256) return TrainPath::small;
+    return !drop_s && composite_big_applies(ta, p.N, p.S, p.W_comp, &p.B.XT) ? TrainPath::big : TrainPath::general;
+}
+
+// the first half of make_cplan: the dims checked against the networks, the tiles, the path
+int cplan_dims_and_path(const gnn_train_args_t &ta, void *ws, CPlan &p) {
     const gnn_loop_args_t &a = ta.loop;
     memset(&p, 0, sizeof(p));
     if (a.abi_version != GNN_ABI_VERSION) return fail("abi_version %d != %d", a.abi_version, GNN_ABI_VERSION);
@@ -113,26 +123,23 @@ int make_cplan(const gnn_train_args_t &ta, void *ws, CPlan &p) {
     p.G = p.pooled ? a.nodegraph.n_dst : 0;
     p.R = p.pooled ? p.G : p.M;
 
-    // ---- which path: the persistent small-graph kernels (one-layer state networks of the state's width, every non-empty type with or every
-    // one without BatchNormalization - the tiles meet at the same grid barriers -, all tiles resident at once) or one launch per layer, type
-    // and iteration
     p.SPs = p.S <= 16 ? 16 : p.S <= 32 ? 32 : 64;
     p.n_wg = 0; p.wg_begin[0] = 0;
-    bool uniform = p.S <= 64 && train_small_enabled() && p.N < train_big_min_nodes() && !drop_s;
-    int bn_seen = -1;
-    for (int t = 0; t < p.n_types; ++t) {
-        const gnn_mlp_t &m = a.net_state[t];
-        const int cnt = a.type_offsets[t + 1] - a.type_offsets[t];
-        p.n_wg += cdiv(std::max(cnt, 0), 64);
+    for (int t = 0; t < p.n_types; ++t) {          // tiles of <= 64 nodes of ONE type
+        p.n_wg += cdiv(std::max(a.type_offsets[t + 1] - a.type_offsets[t], 0), 64);
         p.wg_begin[t + 1] = p.n_wg;
-        if (m.n_layers != 1 || m.units[0] != p.S || m.activation[0] == GNN_ACT_SOFTMAX) uniform = false;
-        if (cnt > 0) { if (bn_seen < 0) bn_seen = m.has_bn ? 1 : 0; else if (bn_seen != (m.has_bn ? 1 : 0)) uniform = false; }
     }
-    p.small = uniform && p.n_wg >= 1 && p.n_wg <= std::min(device_cus(), 256) && (size_t)p.K * p.N * p.SPs * sizeof(float) <= agg_tape_budget();
-    p.ldS = p.small ? p.SPs : p.S;
-    p.big = !p.small && !drop_s && composite_big_applies(ta, p.N, p.S, p.W_comp, &p.B.XT);
+    p.path = composite_train_path(ta, p, drop_s);
+    p.ldS = p.path == TrainPath::small ? p.SPs : p.S;
     p.B.XW = 32 * p.B.XT;
+    return 0;
+}
 
+int make_cplan(const gnn_train_args_t &ta, void *ws, CPlan &p) {
+    TRY(cplan_dims_and_path(ta, ws, p));
+    const gnn_loop_args_t &a = ta.loop;
+    const gnn_mlp_t &no = a.net_output;
+    const bool arc = a.focus == GNN_FOCUS_ARC, small = p.path == TrainPath::small, big = p.path == TrainPath::big;
     Carver c(ws);
     p.grads_ok = c.take<int>(4);
     p.flags = c.take<int>(p.K + 8);
@@ -155,7 +162,6 @@ int make_cplan(const gnn_train_args_t &ta, void *ws, CPlan &p) {
     for (int t = 0; t < p.n_types; ++t) {
         CType &y = p.ty[t];
         y.m = &a.net_state[t];
-        TRY(check_mlp(*y.m, "net_state", ws != nullptr));
         y.g = ta.grad_state_types[t];
         y.count = a.type_offsets[t + 1] - a.type_offsets[t];
         if (y.count < 0) return fail("type_offsets must ascend");
@@ -165,25 +171,25 @@ int make_cplan(const gnn_train_args_t &ta, void *ws, CPlan &p) {
         if (y.m->in_dim != y.in_dim) return fail("net_state[%d].in_dim %d != %d expected from the graph dims", t, y.m->in_dim, y.in_dim);
         if (y.m->units[y.m->n_layers - 1] != p.S) return fail("net_state[%d] output width %d != state width %d", t, y.m->units[y.m->n_layers - 1], p.S);
         y.off_state = y.d_t; y.off_agg = y.d_t + p.S; y.off_comp = y.d_t + 2 * p.S;
-        carve_net(c, y.nc, *y.m, p.big ? 0 : y.count, p.part_floats, &ta.drop_state[t]);      // (large graphs: no per-layer row buffers - the kernels stream the tape)
+        carve_net(c, y.nc, *y.m, big ? 0 : y.count, p.part_floats, &ta.drop_state[t]);      // (large graphs: no per-layer row buffers - the kernels stream the tape)
         y.nc.m = y.m; y.nc.g = &y.g;
         y.stats = c.take<float>((size_t)p.K * 2 * y.in_dim);
         y.stats_tpl = c.take<float>(2 * (size_t)y.in_dim);
         y.Wf = c.take<float>((size_t)p.K * y.in_dim * y.m->units[0]);
         y.bf = c.take<float>((size_t)p.K * y.m->units[0]);
-        y.Gc = c.take<float>(p.big ? 0 : (size_t)std::max(y.count, 1) * p.S);
-        y.dx = c.take<float>(p.big ? 0 : (size_t)std::max(y.count, 1) * 2 * p.S);
+        y.Gc = c.take<float>(big ? 0 : (size_t)std::max(y.count, 1) * p.S);
+        y.dx = c.take<float>(big ? 0 : (size_t)std::max(y.count, 1) * 2 * p.S);
         int nc_; rows_per_chunk_for(std::max(y.count, 1), &nc_);
         p.part_floats = std::max(p.part_floats, (size_t)(nc_ + 1) * y.in_dim);
         const int tiles_t = p.wg_begin[t + 1] - p.wg_begin[t];
-        p.sm_partW[t] = c.take<float>(p.small ? (size_t)tiles_t * ((size_t)y.in_dim * p.S + p.S) : 0);
-        p.sm_partBN[t] = c.take<float>(p.small ? (size_t)tiles_t * 2 * y.in_dim : 0);
+        p.sm_partW[t] = c.take<float>(small ? (size_t)tiles_t * ((size_t)y.in_dim * p.S + p.S) : 0);
+        p.sm_partBN[t] = c.take<float>(small ? (size_t)tiles_t * 2 * y.in_dim : 0);
     }
     // every node is an output row (out_index the identity: checked on the device, read with k), one thin Dense over the state alone
-    p.head_fast = p.big && !arc && no.n_layers == 1 && no.units[0] <= 4 && p.M == p.N && p.S % 4 == 0 && p.S / 4 <= 32 && ta.drop_output.n == 0;
+    p.head_fast = big && !arc && no.n_layers == 1 && no.units[0] <= 4 && p.M == p.N && p.S % 4 == 0 && p.S / 4 <= 32 && ta.drop_output.n == 0;
     p.part_h = c.take<float>(p.head_fast ? (size_t)BIG_HEAD_BLOCKS * ((size_t)no.in_dim * no.units[0] + no.units[0]) : 0);
-    p.inv = c.take<int>((p.small || p.big) ? p.N : 0);
-    if (p.big) {
+    p.inv = c.take<int>((small || big) ? p.N : 0);
+    if (big) {
         CBig &B = p.B;
         const gnn_csr_t &ad = a.adjacency, &as = ta.adjacency_by_source;
         B.scan_tmp = c.take<int>((size_t)cdiv(p.N, SCAN_CHUNK) + 2);
@@ -224,10 +230,10 @@ int make_cplan(const gnn_train_args_t &ta, void *ws, CPlan &p) {
             B.Kc[t] = y.d_t + p.W_comp;
         }
     }
-    p.sm_cc = c.take<float>(p.small ? (size_t)p.N * p.SPs : 0);
-    p.sm_part = c.take<float>(p.small ? (size_t)2 * p.n_wg * 8 * p.SPs : 0);
-    p.sm_dxa = c.take<float>(p.small ? (size_t)p.N * p.SPs : 0);
-    p.sm_bar = c.take<unsigned long long>(p.small ? 4 : 0);
+    p.sm_cc = c.take<float>(small ? (size_t)p.N * p.SPs : 0);
+    p.sm_part = c.take<float>(small ? (size_t)2 * p.n_wg * 8 * p.SPs : 0);
+    p.sm_dxa = c.take<float>(small ? (size_t)p.N * p.SPs : 0);
+    p.sm_bar = c.take<unsigned long long>(small ? 4 : 0);
     carve_net(c, p.co, no, p.M, p.part_floats, &ta.drop_output);
     p.co.m = &no; p.co.g = &ta.grad_output;
     {
@@ -275,18 +281,9 @@ int composite_big_setup(const gnn_train_args_t &ta, CPlan &p, hipStream_t st) {
         const CType &y = p.ty[q];
         if (y.count == 0) continue;
         const int off = a.type_offsets[q];
-        gnn::PackSegs ps;
-        memset(&ps, 0, sizeof(ps));
-        gnn::ConstSegs cs;
-        memset(&cs, 0, sizeof(cs));
-        if (y.d_t > 0) {
-            ps.ptr[ps.n] = a.nodes; ps.ld[ps.n] = a.ld_nodes; ps.width[ps.n] = y.d_t; ps.wrow[ps.n] = 0; ++ps.n;
-            cs.ptr[cs.n] = a.nodes; cs.ld[cs.n] = a.ld_nodes; cs.width[cs.n] = y.d_t; cs.wrow[cs.n] = 0; ++cs.n;
-        }
-        if (p.W_comp > 0) {
-            ps.ptr[ps.n] = p.agg_comp; ps.ld[ps.n] = p.W_comp; ps.width[ps.n] = p.W_comp; ps.wrow[ps.n] = y.off_comp; ++ps.n;
-            cs.ptr[cs.n] = p.agg_comp; cs.ld[cs.n] = p.W_comp; cs.width[cs.n] = p.W_comp; cs.wrow[cs.n] = y.off_comp; ++cs.n;
-        }
+        gnn::PackSegs ps{};
+        if (y.d_t > 0) { ps.ptr[ps.n] = a.nodes; ps.ld[ps.n] = a.ld_nodes; ps.width[ps.n] = y.d_t; ps.wrow[ps.n] = 0; ++ps.n; }
+        if (p.W_comp > 0) { ps.ptr[ps.n] = p.agg_comp; ps.ld[ps.n] = p.W_comp; ps.width[ps.n] = p.W_comp; ps.wrow[ps.n] = y.off_comp; ++ps.n; }
         float *line = B.xc + (size_t)off * B.XW;
         const int grid = (int)std::min<long>(cdiv((long)y.count * B.XW, 256), 256 * 16);
         if (B.XT == 2) k_pack_xc_pos<64><<<grid, 256, 0, st>>>(y.count, y.rows, ps, line);
@@ -296,22 +293,13 @@ int composite_big_setup(const gnn_train_args_t &ta, CPlan &p, hipStream_t st) {
             // the batch statistics of the constant columns (the same in every iteration): one pass over the packed line, moments around its
             // row 0; each segment's columns land at its BatchNorm columns of the template, which every iteration's slot starts from
             HIP_OK(hipMemsetAsync(y.stats_tpl, 0, sizeof(float) * 2 * y.in_dim, st));
-            int sgrid = 0;
-            TRY(rows_stats(nullptr, line, B.XW, B.XW, y.count, B.part_y[q], st, &sgrid));
-            int c0 = 0;
-            for (int sg = 0; sg < ps.n; ++sg) {
-                gnn::k_stats_finish<<<ps.width[sg], 256, 0, st>>>(nullptr, B.part_y[q] + c0, sgrid, B.XW, 1.0f / (float)y.count, y.stats_tpl + ps.wrow[sg],
-                                                                 y.stats_tpl + y.in_dim + ps.wrow[sg], line + c0);
-                LAUNCH_OK();
-                c0 += ps.width[sg];
-            }
+            TRY(line_stats(line, B.XW, y.count, B.part_y[q], ps.width, ps.wrow, ps.n, y.stats_tpl, y.in_dim, st));
             gnn::k_replicate<<<std::min(cdiv((long)2 * y.in_dim * p.K, 256), 1024), 256, 0, st>>>(y.stats_tpl, 2 * y.in_dim, p.K, y.stats);
             LAUNCH_OK();
         }
         // Cc = b + sum over the constant columns of (a (x - mean) + beta) W: the first layer over the line's segments alone, BatchNormalization
         // applied as the columns are staged (the mean leaves the value first)
-        gnn::SegDenseArgs sa;
-        memset(&sa, 0, sizeof(sa));
+        gnn::SegDenseArgs sa{};
         sa.M = y.count; sa.H = p.S;
         int c0 = 0;
         for (int sg = 0; sg < ps.n; ++sg) { sa.seg[sa.nseg++] = gnn::Seg{line + c0, nullptr, B.XW, ps.width[sg], ps.wrow[sg]}; c0 += ps.width[sg]; }
@@ -336,8 +324,7 @@ int composite_big_forward(const gnn_train_args_t &ta, CPlan &p, hipStream_t st) 
         const float *s_t = p.states + (size_t)t * NS;
         float *s_n = p.states + (size_t)(t + 1) * NS;
         float *agg_t = p.agg + (p.agg_taped ? (size_t)t * NS : 0);
-        gnn::StatsFinishJobs fin;
-        memset(&fin, 0, sizeof(fin));
+        gnn::StatsFinishJobs fin{};
         int n_fin = 0;
         for (int q = 0; q < p.n_types; ++q) {
             CType &y = p.ty[q];
@@ -362,10 +349,8 @@ int composite_big_forward(const gnn_train_args_t &ta, CPlan &p, hipStream_t st) 
         // the state / agg rows of every type's first layer with this iteration's statistics folded in; the bias the kernel adds is the shift of
         // THOSE columns alone (sum beta W over them) - b and the constant columns' share sit in Cc
         FoldList fl;
-        gnn::TypeLaunch<gnn::TrainFwdArgs> fw;
-        memset(&fw, 0, sizeof(fw));
-        gnn::StatsFinishJobs nxt;
-        memset(&nxt, 0, sizeof(nxt));
+        gnn::TypeLaunch<gnn::TrainFwdArgs> fw{};
+        gnn::StatsFinishJobs nxt{};
         int n_nxt = 0;
         fw.n = p.n_types;
         for (int q = 0; q < p.n_types; ++q) {
@@ -427,8 +412,7 @@ int composite_big_backward(const gnn_train_args_t &ta, CPlan &p, int k, hipStrea
     const size_t NS = (size_t)p.N * p.S;
     if (k == 0) return 0;
     {   // the first dZ: G by position, times act'(state_k) of the row's own type
-        ActRanges ar;
-        memset(&ar, 0, sizeof(ar));
+        ActRanges ar{};
         ar.n = p.n_types;
         for (int q = 0; q < p.n_types; ++q) { ar.begin[q] = a.type_offsets[q]; ar.act[q] = p.ty[q].m->activation[0]; }
         ar.begin[p.n_types] = p.N;
@@ -502,8 +486,7 @@ int composite_big_backward(const gnn_train_args_t &ta, CPlan &p, int k, hipStrea
             const int off = a.type_offsets[q];
             const size_t ro = (size_t)off * p.S;
             const gnn_csr_t cs = big_sub_csr(B.s, p.N, off, y.count, !unit_w);
-            gnn::AggDzArgs z;
-            memset(&z, 0, sizeof(z));
+            gnn::AggDzArgs z{};
             z.Y = s_t + ro; z.ldy = p.S; z.wrow_state = y.off_state;
             if (ns.has_bn) {
                 const float *stats = y.stats + (size_t)t * 2 * y.in_dim;
@@ -523,42 +506,29 @@ size_t composite_train_workspace_bytes(const gnn_train_args_t &ta) {
     return p.bytes;
 }
 
-int train_step_composite(const gnn_train_args_t &ta) {
-    const gnn_loop_args_t &a = ta.loop;
-    CPlan p;
-    const bool fwd_only = ta.forward_only != 0;         // the training-mode forward alone: no loss, no gradients, the validity word untouched
-    if (fwd_only && ta.prev_grads_ok_host) return fail("gnn_train_step(forward_only): prev_grads_ok_host must be NULL");
-    TRY(make_cplan(ta, ta.tape, p));
-    if (!ta.tape || ta.tape_bytes < p.bytes) return fail("tape too small: %zu < %zu bytes", ta.tape_bytes, p.bytes);
-    TRY(check_csr(a.adjacency, "adjacency", p.N, p.N));
-    TRY(check_csr(a.arcnode, "arcnode", p.N, p.E));
-    if (!fwd_only) TRY(check_csr(ta.adjacency_by_source, "adjacency_by_source", p.N, p.N));
-    for (int t = 0; t < p.n_types; ++t) {
-        TRY(check_csr(a.composite_adjacency[t], "composite_adjacency", p.N, p.N));
-        if (!fwd_only) TRY(check_grads(*p.ty[t].m, p.ty[t].g, "grad_state_types"));
-    }
-    if (!a.nodes || !a.type_nodes) return fail("nodes / type_nodes is NULL");
-    if (a.state_dim > 0 && !a.state0) return fail("state0 is required when state_dim > 0");
-    if (p.M > 0 && !a.out_index) return fail("out_index is NULL");
-    if (p.E > 0 && p.A > 0 && !a.arc_labels) return fail("arc_labels is NULL");
-    if (a.focus == GNN_FOCUS_ARC && p.E > 0 && (!a.arc_src || !a.arc_dst)) return fail("arc focus needs arc_src / arc_dst");
-    if (p.pooled) {
-        if (a.nodegraph.n_src != p.M) return fail("graph focus: NodeGraph has %d rows but %d nodes pass the mask", a.nodegraph.n_src, p.M);
-        TRY(check_csr(a.nodegraph, "nodegraph", p.G, p.M));
-        if (!fwd_only) TRY(check_csr(ta.nodegraph_by_source, "nodegraph_by_source", p.M, p.G));
-    }
-    if (!fwd_only && p.R > 0 && !ta.targets) return fail("targets is NULL");
-    if (!fwd_only && (ta.loss_kind < 0 || ta.loss_kind > 3)) return fail("unknown loss kind %d", ta.loss_kind);
-    if ((p.R > 0 && !ta.y_pred) || (!fwd_only && !ta.loss) || !ta.k_host || !ta.state) return fail("y_pred / loss / k_host / state is NULL");
-    if (!fwd_only) TRY(check_grads(a.net_output, ta.grad_output, "grad_output"));
-    const gnn_mlp_t &no = a.net_output;
-    const bool bn_o = no.has_bn != 0;
-    hipStream_t st = (hipStream_t)a.stream;
-    const size_t NS = (size_t)p.N * p.ldS;             // one state matrix of the tape
+// ==== the composite step's own phases, in the order train_step_composite() below calls them ==============================================
 
-    // ---- setup: transposes, aggregated_component (CompositeGNN.py:251-253), state_0, the constant columns' statistics ------------
+// the constant inputs of type y's first layer: [labels[:, :d_t] | aggregated_component]
+gnn::ConstSegs ctype_const_segs(const gnn_loop_args_t &a, const CPlan &p, const CType &y) {
+    gnn::ConstSegs cs{};
+    if (y.d_t > 0) { cs.ptr[cs.n] = a.nodes; cs.ld[cs.n] = a.ld_nodes; cs.width[cs.n] = y.d_t; cs.wrow[cs.n] = 0; ++cs.n; }
+    if (p.W_comp > 0) { cs.ptr[cs.n] = p.agg_comp; cs.ld[cs.n] = p.W_comp; cs.width[cs.n] = p.W_comp; cs.wrow[cs.n] = y.off_comp; ++cs.n; }
+    return cs;
+}
+
+int moving_state(const gnn_train_args_t &ta, const CPlan &p, int k, const int *gate, hipStream_t st) {
+    for (int q = 0; q < p.n_types; ++q)
+        if (p.ty[q].count > 0) TRY(bn_moving(*p.ty[q].m, p.ty[q].stats, k, ta.bn_momentum, gate, st));
+    return 0;
+}
+
+// ---- setup: the previous step's validity word, transposes, aggregated_component (CompositeGNN.py:251-253), state_0 (by position on the two
+// fast paths: position i = node type_nodes[i]), the constant columns' statistics
+int composite_setup(const gnn_train_args_t &ta, CPlan &p, hipStream_t st) {
+    const gnn_loop_args_t &a = ta.loop;
+    const bool small = p.path == TrainPath::small, big = p.path == TrainPath::big;
     if (ta.prev_grads_ok_host) HIP_OK(hipMemcpyAsync(ta.prev_grads_ok_host, p.grads_ok, sizeof(int), hipMemcpyDeviceToHost, st));
-    if (!fwd_only) {               // (a forward leaves the word of the last STEP on this tape as it is)
+    if (!ta.forward_only) {               // (a forward leaves the word of the last STEP on this tape as it is)
         HIP_OK(hipMemsetAsync(p.grads_ok, 0, sizeof(int) * 4, st));
         if (ta.grads_ok_dev) *ta.grads_ok_dev = p.grads_ok;
         for (int t = 0; t < p.n_types; ++t) TRY(transposes(p.ty[t].nc, st));
@@ -566,26 +536,25 @@ int train_step_composite(const gnn_train_args_t &ta) {
     }
     HIP_OK(hipMemsetAsync(p.flags, 0, sizeof(int) * (p.K + 8), st));
     HIP_OK(hipMemsetAsync(p.k_dev, 0, sizeof(float) * 4, st));
-    {
-        int col = 0;
-        for (int t = 0; t < p.n_types; ++t) {
-            const int dt = a.type_dim_label[t];
-            if (dt > 0) TRY(launch_aggregate(nullptr, a.composite_adjacency[t], a.nodes, a.ld_nodes, dt, p.agg_comp + col, p.W_comp, st));
-            col += dt;
-        }
-        if (p.A > 0) TRY(launch_aggregate(nullptr, a.arcnode, a.arc_labels, a.ld_arcs, p.A, p.agg_comp + col, p.W_comp, st));
+    int col = 0;
+    for (int t = 0; t < p.n_types; ++t) {
+        const int dt = a.type_dim_label[t];
+        if (dt > 0) TRY(launch_aggregate(nullptr, a.composite_adjacency[t], a.nodes, a.ld_nodes, dt, p.agg_comp + col, p.W_comp, st));
+        col += dt;
     }
-    if (p.small) {          // the tape's rows are positions in type order (position i = node type_nodes[i]), ldS floats each, pad columns zero
-        if (p.ldS != p.S) HIP_OK(hipMemsetAsync(p.states, 0, sizeof(float) * NS, st));
+    if (p.A > 0) TRY(launch_aggregate(nullptr, a.arcnode, a.arc_labels, a.ld_arcs, p.A, p.agg_comp + col, p.W_comp, st));
+    if (small) {            // rows of ldS floats, pad columns zero
+        if (p.ldS != p.S) HIP_OK(hipMemsetAsync(p.states, 0, sizeof(float) * p.N * p.ldS, st));
         if (a.state_dim > 0) TRY(gather_rows(a.state0, p.S, a.type_nodes, p.N, p.S, p.states, p.ldS, st));
         else TRY(gather_rows(a.nodes, a.ld_nodes, a.type_nodes, p.N, p.S, p.states, p.ldS, st));
         k_invert_perm<<<std::min(cdiv(p.N, 256), 1024), 256, 0, st>>>(a.type_nodes, p.N, p.inv);
         LAUNCH_OK();
-    } else if (p.big) {     // (composite_big_setup below: state_0 by position)
-    } else if (a.state_dim > 0) HIP_OK(hipMemcpyAsync(p.states, a.state0, sizeof(float) * NS, hipMemcpyDeviceToDevice, st));
-    else TRY(launch_copy2d(nullptr, a.nodes, a.ld_nodes, p.states, p.S, p.N, p.S, p.S, st));
+    } else if (!big) {      // (large graphs: composite_big_setup below)
+        if (a.state_dim > 0) HIP_OK(hipMemcpyAsync(p.states, a.state0, sizeof(float) * p.N * p.ldS, hipMemcpyDeviceToDevice, st));
+        else TRY(launch_copy2d(nullptr, a.nodes, a.ld_nodes, p.states, p.S, p.N, p.S, p.S, st));
+    }
     gnn::Seg segs[GNN_MAX_SEGS];
-    for (int t = 0; t < p.n_types && !p.big; ++t) {      // (large graphs: composite_big_setup takes them from the packed constants line, one pass)
+    for (int t = 0; t < p.n_types && !big; ++t) {      // (large graphs: composite_big_setup takes them from the packed constants line, one pass)
         CType &y = p.ty[t];
         if (!y.m->has_bn || y.count == 0) continue;
         int is_, ia_;
@@ -597,260 +566,107 @@ int train_step_composite(const gnn_train_args_t &ta) {
         gnn::k_replicate<<<std::min(cdiv((long)2 * y.in_dim * p.K, 256), 1024), 256, 0, st>>>(y.stats_tpl, 2 * y.in_dim, p.K, y.stats);
         LAUNCH_OK();
     }
-
     // (gnn_last_kernel_name(): which orchestration took the step - tests and bench.py read it)
-    if (p.big) GNN_SET_KERNEL_NAME("train_step composite: row-streaming kernels on type ranges (fwd_b6<ADD>, wgrad_b6<XT=%d>)", p.B.XT);
-    else if (p.small) GNN_SET_KERNEL_NAME("train_step composite: persistent small-graph kernels");
+    if (big) GNN_SET_KERNEL_NAME("train_step composite: row-streaming kernels on type ranges (fwd_b6<ADD>, wgrad_b6<XT=%d>)", p.B.XT);
+    else if (small) GNN_SET_KERNEL_NAME("train_step composite: persistent small-graph kernels");
     else GNN_SET_KERNEL_NAME("train_step composite: general kernels (one launch per layer, type and iteration)");
-    if (p.big) TRY(composite_big_setup(ta, p, st));
-    if (p.head_fast) {     // the thin-head kernels treat output row m as node m: out_index must BE the identity (checked on the device, read with k)
-        gnn::k_not_identity<<<std::min(cdiv(p.M, 256), 1024), 256, 0, st>>>(a.out_index, p.M, p.k_dev + 2);
+    if (big) TRY(composite_big_setup(ta, p, st));
+    return finish_setup(ta, p, st);
+}
+
+// ---- training-mode forward: K gated iterations; tape = states, neighbour sums, per-type statistics (large graphs: composite_big_forward) ----
+// Small graphs: one persistent launch over tiles of <= 64 consecutive positions of ONE type (`tiles`); per type the network, its statistics
+// tape and where its shares go (`yt`) - the backward launch takes the same tables
+int composite_forward_small(const gnn_train_args_t &ta, CPlan &p, gnn::TileTab &tiles, gnn::TypeTab &yt, hipStream_t st) {
+    const gnn_loop_args_t &a = ta.loop;
+    int b = 0;
+    for (int q = 0; q < p.n_types; ++q) {
+        const CType &y = p.ty[q];
+        const int pos0 = a.type_offsets[q];
+        for (int r0 = 0; r0 < y.count; r0 += 64) tiles.begin[b++] = pos0 + r0;
+        yt.wg_begin[q] = p.wg_begin[q]; yt.count[q] = y.count;
+        yt.W[q] = y.m->kernel[0]; yt.gamma[q] = y.m->has_bn ? y.m->bn_gamma : nullptr; yt.beta[q] = y.m->bn_beta; yt.stats[q] = y.stats;
+        yt.in_s[q] = y.in_dim; yt.off_state[q] = y.off_state; yt.off_agg[q] = y.off_agg; yt.act[q] = y.m->activation[0];
+        yt.partW[q] = p.sm_partW[q]; yt.partBN[q] = p.sm_partBN[q];
+    }
+    tiles.begin[b] = p.N; tiles.n = b;
+    yt.n = p.n_types; yt.wg_begin[p.n_types] = p.n_wg; yt.perm = a.type_nodes; yt.inv = p.inv;
+    if (b != p.n_wg) return fail("composite tiles: %d != %d", b, p.n_wg);
+    // the constant part of every node's first layer (its type's network over its labels and the aggregated component), in position order
+    for (int q = 0; q < p.n_types; ++q) {
+        const CType &y = p.ty[q];
+        if (y.count == 0) continue;
+        gnn::k_train_small_const<<<cdiv(y.count * p.SPs, 256), 256, 0, st>>>(y.count, p.SPs, p.S, ctype_const_segs(a, p, y), y.m->kernel[0], y.m->bias[0],
+                                                                         y.m->has_bn ? y.m->bn_gamma : nullptr, y.m->bn_beta, y.stats_tpl, y.stats_tpl + y.in_dim,
+                                                                         y.m->bn_eps, p.sm_cc + (size_t)a.type_offsets[q] * p.SPs, y.rows);
         LAUNCH_OK();
     }
+    HIP_OK(hipMemsetAsync(p.sm_bar, 0, sizeof(unsigned long long) * 4, st));
+    gnn::TrainSmallFwd fa{};
+    fa.eps = p.ty[0].m->bn_eps;
+    return launch_train_small_fwd(fa, ta, p, tiles, &yt, st);
+}
 
-    // ---- training-mode forward: gated iterations; tape = states, neighbour sums, per-type statistics ---------------------------------
-    TRY(launch_converge(nullptr, p.states, nullptr, p.N, p.S, p.ldS, 0, a.state_threshold, p.flags, nullptr, 0.f, st));
-    if (p.big) TRY(composite_big_forward(ta, p, st));
-    gnn::TileTab tiles;
-    gnn::TypeTab yt;
-    memset(&tiles, 0, sizeof(tiles)); memset(&yt, 0, sizeof(yt));
-    if (p.small) {
-        // tiles of <= 64 consecutive positions of ONE type; per type the network, its statistics tape and where its shares go
-        int b = 0;
-        for (int q = 0; q < p.n_types; ++q) {
-            const CType &y = p.ty[q];
-            const int pos0 = a.type_offsets[q];
-            for (int r0 = 0; r0 < y.count; r0 += 64) tiles.begin[b++] = pos0 + r0;
-            yt.wg_begin[q] = p.wg_begin[q]; yt.count[q] = y.count;
-            yt.W[q] = y.m->kernel[0]; yt.gamma[q] = y.m->has_bn ? y.m->bn_gamma : nullptr; yt.beta[q] = y.m->bn_beta; yt.stats[q] = y.stats;
-            yt.in_s[q] = y.in_dim; yt.off_state[q] = y.off_state; yt.off_agg[q] = y.off_agg; yt.act[q] = y.m->activation[0];
-            yt.partW[q] = p.sm_partW[q]; yt.partBN[q] = p.sm_partBN[q];
-        }
-        tiles.begin[b] = p.N; tiles.n = b;
-        yt.n = p.n_types; yt.wg_begin[p.n_types] = p.n_wg; yt.perm = a.type_nodes; yt.inv = p.inv;
-        if (b != p.n_wg) return fail("composite tiles: %d != %d", b, p.n_wg);
-        // the constant part of every node's first layer (its type's network over its labels and the aggregated component), in position order
-        for (int q = 0; q < p.n_types; ++q) {
-            const CType &y = p.ty[q];
-            if (y.count == 0) continue;
-            gnn::ConstSegs cs;
-            memset(&cs, 0, sizeof(cs));
-            if (y.d_t > 0) { cs.ptr[cs.n] = a.nodes; cs.ld[cs.n] = a.ld_nodes; cs.width[cs.n] = y.d_t; cs.wrow[cs.n] = 0; ++cs.n; }
-            if (p.W_comp > 0) { cs.ptr[cs.n] = p.agg_comp; cs.ld[cs.n] = p.W_comp; cs.width[cs.n] = p.W_comp; cs.wrow[cs.n] = y.off_comp; ++cs.n; }
-            gnn::k_train_small_const<<<cdiv(y.count * p.SPs, 256), 256, 0, st>>>(y.count, p.SPs, p.S, cs, y.m->kernel[0], y.m->bias[0], y.m->has_bn ? y.m->bn_gamma : nullptr,
-                                                                             y.m->bn_beta, y.stats_tpl, y.stats_tpl + y.in_dim, y.m->bn_eps,
-                                                                             p.sm_cc + (size_t)a.type_offsets[q] * p.SPs, y.rows);
-            LAUNCH_OK();
-        }
-        HIP_OK(hipMemsetAsync(p.sm_bar, 0, sizeof(unsigned long long) * 4, st));
-        gnn::TrainSmallFwd fa;
-        memset(&fa, 0, sizeof(fa));
-        fa.N = p.N; fa.S = p.SPs; fa.Sw = p.S; fa.K = p.K;
-        fa.rowptr = a.adjacency.rowptr; fa.src = a.adjacency.src; fa.w = a.adjacency.w; fa.row_scale = a.adjacency.row_scale;
-        fa.states = p.states; fa.agg = p.agg; fa.eps = p.ty[0].m->bn_eps;
-        fa.Cc = p.sm_cc; fa.thr = a.state_threshold; fa.flag0 = p.flags;
-        fa.bar = p.sm_bar; fa.part = p.sm_part; fa.k_out = p.k_dev; fa.wait_ticks = gnn::wait_ticks();
-        if (const char *e = getenv("GNN_DEBUG_FAIL_FWD")) { if (e[0] == '1') fa.wait_ticks = 0; }      // (test hook: every barrier wait of THIS forward launch expires at once)
-        switch (p.SPs) {
-            case 16: TRY(launch_train_small_fwd_sq<1>(fa, tiles, p.n_wg, a.adjacency.w != nullptr, st, &yt)); break;
-            case 32: TRY(launch_train_small_fwd_sq<2>(fa, tiles, p.n_wg, a.adjacency.w != nullptr, st, &yt)); break;
-            default: TRY(launch_train_small_fwd_sq<4>(fa, tiles, p.n_wg, a.adjacency.w != nullptr, st, &yt)); break;
-        }
-    }
-    for (int t = 0; t < p.K && !p.small && !p.big; ++t) {
+// the general path: one launch per layer, type and iteration, every type's rows through its row list
+int composite_forward_general(const gnn_train_args_t &ta, CPlan &p, hipStream_t st) {
+    const gnn_loop_args_t &a = ta.loop;
+    gnn::Seg segs[GNN_MAX_SEGS];
+    for (int t = 0; t < p.K; ++t) {
         const int *gate = p.flags + t;
-        const float *s_t = p.states + (size_t)t * NS;
-        float *s_n = p.states + (size_t)(t + 1) * NS;
-        float *agg_t = p.agg + (p.agg_taped ? (size_t)t * NS : 0);
-        TRY(launch_aggregate(gate, a.adjacency, s_t, p.S, p.S, agg_t, p.S, st));
+        const float *s_t = state_at(p, t);
+        float *s_n = state_at(p, t + 1);
+        TRY(launch_aggregate(gate, a.adjacency, s_t, p.S, p.S, agg_at(p, t), p.S, st));
         for (int q = 0; q < p.n_types; ++q) {
             CType &y = p.ty[q];
             if (y.count == 0) continue;
             const gnn_mlp_t &ns = *y.m;
             int is_, ia_;
             const int n = ctype_segs(a, p, y, t, segs, &is_, &ia_);
-            const float *W0 = ns.kernel[0], *b0 = ns.bias[0], *bn_on_load = nullptr, *centre = nullptr;
-            if (ns.has_bn) {
-                float *stats = y.stats + (size_t)t * 2 * y.in_dim;
-                gnn::Seg dyn[2] = {segs[is_], segs[ia_]};
-                TRY(colstats_segs(gate, dyn, 2, y.count, stats, stats + y.in_dim, p.part, st));
-                if (ns.units[0] <= 4) {               // thin first layer: the thin-dense kernel wants folded weights (centred: it subtracts the means on load)
-                    float *Wf = y.Wf + (size_t)t * y.in_dim * ns.units[0], *bf = y.bf + (size_t)t * ns.units[0];
-                    TRY(fold_with_stats(ns, stats, Wf, bf, st, true));
-                    W0 = Wf; b0 = bf; centre = stats;
-                } else bn_on_load = stats;
-            }
-            float *hs[GNN_MAX_LAYERS];
-            for (int l = 0; l < ns.n_layers; ++l) hs[l] = y.nc.hid[l];
-            DropRun drs{&ta.drop_state[q], ta.drop_seed, t, {}};      // (ABI 8: the type's Dropout layers, fresh masks every iteration)
-            for (int qq = 0; qq <= ns.n_layers; ++qq) drs.buf[qq] = y.nc.dropbuf[qq];
-            TRY(forward_layers(ns, segs, n, y.count, W0, b0, hs, gate, st, nullptr, bn_on_load, centre, &drs));
+            const gnn::Seg dyn[2] = {segs[is_], segs[ia_]};
+            FirstLayer f;
+            TRY(first_layer_of(ns, gate, dyn, y.count, y.stats + (size_t)t * 2 * y.in_dim, y.Wf + (size_t)t * y.in_dim * ns.units[0], y.bf + (size_t)t * ns.units[0],
+                               p.part, f, st));
+            const DropRun drs = drop_run(&ta.drop_state[q], ta.drop_seed, t, y.nc);      // (ABI 8: the type's Dropout layers, fresh masks every iteration)
+            TRY(forward_layers(ns, segs, n, y.count, f.W0, f.b0, y.nc.hid, gate, st, nullptr, f.bn_on_load, f.centre, &drs));
             // the type's rows of the new state (CompositeGNN.py:229-231: scatter_nd + reduce_sum over the one-hot types).  A closed gate
-            // leaves hs stale and the scatter harmless: state t + 1 is never read then.
-            TRY(scatter_rows(drop_at(&drs, ns.n_layers) ? drs.buf[ns.n_layers] : hs[ns.n_layers - 1], p.S, y.rows, y.count, p.S, s_n, p.S, st));
+            // leaves the layer buffers stale and the scatter harmless: state t + 1 is never read then.
+            TRY(scatter_rows(drop_at(&drs, ns.n_layers) ? drs.buf[ns.n_layers] : y.nc.hid[ns.n_layers - 1], p.S, y.rows, y.count, p.S, s_n, p.S, st));
         }
         TRY(launch_converge(gate, s_n, s_t, p.N, p.S, p.S, p.S, a.state_threshold, p.flags + t + 1, p.k_dev, (float)(t + 1), st));
     }
-    float k_f2[3] = {0.0f, 0.0f, 0.0f};
-    HIP_OK(hipMemcpyAsync(k_f2, p.k_dev, 3 * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));                                  // the one host synchronisation of the step
-    const int k = (int)k_f2[0];
-    *ta.k_host = k;
-    if (k_f2[2] != 0.0f) p.head_fast = false;      // a permuted / repeated out_index of length n_nodes: the general head (gathers, scatter-add)
-    if (k_f2[1] != 0.0f) return fail("a workgroup of the persistent training kernel never arrived at a grid barrier (not resident?)");
-    if (k < 0 || k > p.K) return fail("iteration count %d out of range", k);
-    if (p.small || p.big) TRY(scatter_rows(p.states + (size_t)k * NS, p.ldS, a.type_nodes, p.N, p.S, ta.state, p.S, st));      // positions -> the caller's node order
-    else HIP_OK(hipMemcpyAsync(ta.state, p.states + (size_t)k * NS, sizeof(float) * NS, hipMemcpyDeviceToDevice, st));
-    const float *state_k = ta.state;                                   // [N, S] in the caller's node order
-    // The moving averages of BatchNormalization (one update per executed call).  On the persistent path they wait until the backward
-    // launch has passed its grid barriers and are gated by the step's validity word (train_loop.hpp: a failed backward changes nothing).
-    auto moving_state = [&](const int *gate) -> int {
-        for (int q = 0; q < p.n_types && k > 0; ++q) {
-            const CType &y = p.ty[q];
-            if (!y.m->has_bn || y.count == 0) continue;
-            gnn::k_bn_moving_multi<<<cdiv(y.in_dim, 256), 256, 0, st>>>(y.stats, 2 * y.in_dim, k, y.in_dim, const_cast<float *>(y.m->bn_mean),
-                                                                       const_cast<float *>(y.m->bn_var), ta.bn_momentum, gate);
-            LAUNCH_OK();
-        }
-        return 0;
-    };
-    if (!p.small) TRY(moving_state(nullptr));
+    return 0;
+}
 
-    // ---- output network on the converged state of the masked nodes (CompositeGNN.py:237-239, :270), training mode --------------------
-    gnn::Seg osegs[3];
-    int nos = 0, n_state_segs = 0;
-    int bn_req_off[2] = {0, 0};                 // column offsets of the state segments inside the output net's input
-    const int *bn_req_idx[2] = {nullptr, nullptr};
-    if (a.focus == GNN_FOCUS_ARC && p.M > 0) {
-        k_arc_endpoints<<<cdiv(p.M, 256), 256, 0, st>>>(a.out_index, a.arc_src, a.arc_dst, p.M, p.isrc, p.idst);
+// ---- backward through the k executed iterations; p.G_state = d loss / d state_k in the caller's node order (large graphs:
+// composite_big_backward).  Small graphs: one persistent launch, then every tile's [kernel | bias] (and [d gamma | d beta]) share of ITS
+// type's gradients summed in tile order
+int composite_backward_small(const gnn_train_args_t &ta, CPlan &p, const gnn::TileTab &tiles, const gnn::TypeTab &yt, int k, hipStream_t st) {
+    gnn::TypeConsts yc{};
+    for (int q = 0; q < p.n_types; ++q) yc.cs[q] = ctype_const_segs(ta.loop, p, p.ty[q]);
+    gnn::TrainSmallBwd ba{};
+    ba.eps = p.ty[0].m->bn_eps; ba.dxa = p.sm_dxa;
+    TRY(launch_train_small_bwd(ba, ta, p, k, tiles, &yt, &yc, st));
+    for (int q = 0; q < p.n_types; ++q) {
+        const CType &y = p.ty[q];
+        const int tiles_q = p.wg_begin[q + 1] - p.wg_begin[q];
+        if (tiles_q == 0) continue;
+        const int n = (y.in_dim + 1) * p.S;
+        gnn::k_reduce_partials<<<cdiv(n, 64), 256, 0, st>>>(p.sm_partW[q], tiles_q, n, y.g.dkernel[0], 0, 1.0f, y.in_dim * p.S, y.g.dbias[0]);
         LAUNCH_OK();
-        const int *ends[2] = {p.isrc, p.idst};
-        for (int e = 0; e < 2; ++e) {
-            bn_req_off[n_state_segs] = e * p.S; bn_req_idx[n_state_segs++] = ends[e];
-            osegs[nos++] = gnn::Seg{state_k, ends[e], p.S, p.S, e * p.S};
+        if (y.m->has_bn) {
+            gnn::k_reduce_partials<<<cdiv(2 * y.in_dim, 64), 256, 0, st>>>(p.sm_partBN[q], tiles_q, 2 * y.in_dim, y.g.dgamma, 0, 1.0f, y.in_dim, y.g.dbeta);
+            LAUNCH_OK();
         }
-        if (p.A > 0) osegs[nos++] = gnn::Seg{a.arc_labels, a.out_index, a.ld_arcs, p.A, 2 * p.S};
-    } else {
-        bn_req_off[0] = 0; bn_req_idx[0] = a.out_index; n_state_segs = 1;
-        osegs[nos++] = gnn::Seg{state_k, a.out_index, p.S, p.S, 0};
     }
-    DropRun dro{&ta.drop_output, ta.drop_seed, 0, {}};
-    for (int qq = 0; qq <= no.n_layers; ++qq) dro.buf[qq] = p.co.dropbuf[qq];
-    const bool drop_o_last = drop_at(&dro, no.n_layers);          // (a Dropout layer behind the last Dense: the network's output is its dropped-out copy)
-    if (drop_o_last && !p.pooled) dro.buf[no.n_layers] = ta.y_pred;
-    float *ohs[GNN_MAX_LAYERS];
-    for (int l = 0; l < no.n_layers; ++l) ohs[l] = (l == no.n_layers - 1 && !p.pooled && !drop_o_last) ? ta.y_pred : p.co.hid[l];
-    float *out_nodes = drop_o_last ? dro.buf[no.n_layers] : ohs[no.n_layers - 1];
-    if (p.M > 0) {
-        const float *W0 = no.kernel[0], *b0 = no.bias[0];
-        if (bn_o) {
-            if (p.head_fast) {          // every node a row, in order: one pass over the state (moments around its row 0)
-                int grid = 0;
-                TRY(rows_stats(nullptr, state_k, p.S, p.S, p.N, p.B.part_y[0], st, &grid));
-                gnn::k_stats_finish<<<p.S, 256, 0, st>>>(nullptr, p.B.part_y[0], grid, p.S, 1.0f / (float)p.N, p.stats_o, p.stats_o + no.in_dim, state_k);
-                LAUNCH_OK();
-            } else
-            TRY(colstats_segs(nullptr, osegs, nos, p.M, p.stats_o, p.stats_o + no.in_dim, p.part, st));
-            TRY(fold_with_stats(no, p.stats_o, p.Wf_o, p.bf_o, st, true));
-            if (!p.small) {
-                gnn::k_bn_moving_multi<<<cdiv(no.in_dim, 256), 256, 0, st>>>(p.stats_o, 2 * no.in_dim, 1, no.in_dim, const_cast<float *>(no.bn_mean),
-                                                                            const_cast<float *>(no.bn_var), ta.bn_momentum);
-                LAUNCH_OK();
-            }
-            W0 = p.Wf_o; b0 = p.bf_o;
-        }
-        TRY(forward_layers(no, osegs, nos, p.M, W0, b0, ohs, nullptr, st, nullptr, nullptr, bn_o ? p.stats_o : nullptr, &dro));
-    }
-    if (p.pooled) TRY(launch_aggregate(nullptr, a.nodegraph, out_nodes, p.T, p.T, ta.y_pred, p.T, st));
-    if (fwd_only) {
-        // the forward alone: the moving averages the persistent small-graph path keeps back for the step's validity word are due now
-        if (p.small) {
-            TRY(moving_state(nullptr));
-            if (bn_o && p.M > 0) {
-                gnn::k_bn_moving_multi<<<cdiv(no.in_dim, 256), 256, 0, st>>>(p.stats_o, 2 * no.in_dim, 1, no.in_dim, const_cast<float *>(no.bn_mean),
-                                                                            const_cast<float *>(no.bn_var), ta.bn_momentum);
-                LAUNCH_OK();
-            }
-        }
-        return 0;
-    }
-    gnn::k_loss_grad<<<cdiv(std::max(p.R, 1), 256), 256, 0, st>>>(ta.loss_kind, ta.targets, ta.y_pred, ta.sample_weight, p.R, p.T, p.dpred, p.loss_rows);
-    LAUNCH_OK();
-    if (p.R > 65536) {
-        gnn::k_sum_partials<<<256, 256, 0, st>>>(p.loss_rows, p.R, p.loss_part);
-        LAUNCH_OK();
-        gnn::k_sum_scale<<<1, 256, 0, st>>>(p.loss_part, 256, 1.0f / (float)std::max(p.R, 1), ta.loss);
-    } else gnn::k_sum_scale<<<1, 256, 0, st>>>(p.loss_rows, p.R, 1.0f / (float)std::max(p.R, 1), ta.loss);
-    LAUNCH_OK();
-    float *G_out = p.dpred;
-    if (p.pooled) { TRY(launch_aggregate(nullptr, ta.nodegraph_by_source, p.dpred, p.T, p.T, p.G_out, p.T, st)); G_out = p.G_out; }
+    return 0;
+}
 
-    // ---- backward: output network, then the k iterations ------------------------------------------------------------------------------
-    if (p.head_fast) {          // the head's parameter gradients, d loss / d state_k written straight into the state gradient (every row is an output row)
-        TrainPlan hp;
-        memset(&hp, 0, sizeof(hp));
-        hp.M = p.M; hp.N = p.N; hp.S = p.S; hp.ldS = p.S; hp.T = p.T; hp.with_labels = false; hp.L = 0;
-        hp.part_h = p.part_h; hp.co = p.co; hp.G_state = p.G_state;
-        TRY(head_backward(hp, a, state_k, out_nodes, G_out, bn_o ? p.stats_o : nullptr, st, -1));
-    } else {
-    HIP_OK(hipMemsetAsync(p.G_state, 0, sizeof(float) * (size_t)p.N * p.S, st));
-    if (p.M > 0) {
-        TRY(net_backward(p.co, osegs, nos, ohs, G_out, p.T, p.M, bn_o ? p.stats_o : nullptr, false, p.dx_o_all, no.in_dim, p.part, st, -1, 0, &dro));
-        gnn::BnGradReq rq[2];
-        for (int i = 0; i < n_state_segs; ++i) rq[i] = gnn::BnGradReq{p.dx_o_all + bn_req_off[i], no.in_dim, state_k, p.S, bn_req_idx[i], p.S, bn_req_off[i]};
-        TRY(bn_input_grads(no, p.co, p.stats_o, rq, n_state_segs, p.M, st));
-        for (int i = 0; i < n_state_segs; ++i) {     // (an arc's two end nodes, one after the other: the additions to a node's row stay ordered)
-            gnn::k_scatter_add_rows<<<std::min(cdiv((long)p.M * p.S, 256), 256 * 16), 256, 0, st>>>(p.dx_o_all + bn_req_off[i], no.in_dim, bn_req_idx[i], p.M, p.S, p.G_state, p.S);
-            LAUNCH_OK();
-        }
-    } else TRY(zero_grads(no, ta.grad_output, st));
-    }
-    for (int q = 0; q < p.n_types; ++q)
-        if (k == 0 || p.ty[q].count == 0) TRY(zero_grads(*p.ty[q].m, p.ty[q].g, st));
-    if (p.small && k > 0) {
-        // the k iterations of back-propagation in one persistent launch; every tile leaves its share of ITS type's gradients
-        gnn::TypeConsts yc;
-        memset(&yc, 0, sizeof(yc));
-        for (int q = 0; q < p.n_types; ++q) {
-            const CType &y = p.ty[q];
-            gnn::ConstSegs &cs = yc.cs[q];
-            if (y.d_t > 0) { cs.ptr[cs.n] = a.nodes; cs.ld[cs.n] = a.ld_nodes; cs.width[cs.n] = y.d_t; cs.wrow[cs.n] = 0; ++cs.n; }
-            if (p.W_comp > 0) { cs.ptr[cs.n] = p.agg_comp; cs.ld[cs.n] = p.W_comp; cs.width[cs.n] = p.W_comp; cs.wrow[cs.n] = y.off_comp; ++cs.n; }
-        }
-        gnn::TrainSmallBwd ba;
-        memset(&ba, 0, sizeof(ba));
-        const gnn_csr_t &cs_ = ta.adjacency_by_source;
-        const bool unit_w = !a.adjacency.w;       // entries depend on the destination only: scale the agg-half once per row, walk unit weights
-        ba.N = p.N; ba.S = p.SPs; ba.Sw = p.S; ba.k = k;
-        ba.rowptr_s = cs_.rowptr; ba.src_s = cs_.src; ba.w_s = unit_w ? nullptr : cs_.w; ba.row_scale_s = unit_w ? nullptr : cs_.row_scale;
-        ba.row_scale = unit_w ? a.adjacency.row_scale : nullptr;
-        ba.states = p.states; ba.agg = p.agg; ba.eps = p.ty[0].m->bn_eps;
-        ba.G0 = p.G_state; ba.dxa = p.sm_dxa; ba.bar = p.sm_bar + 2; ba.part = p.sm_part;
-        ba.inv_n = 1.0f / (float)p.N; ba.err = p.k_dev; ba.wait_ticks = gnn::wait_ticks();
-        if (const char *e = getenv("GNN_DEBUG_FAIL_BWD")) { if (e[0] == '1') ba.wait_ticks = 0; }
-        switch (p.SPs) {
-            case 16: TRY(launch_train_small_bwd_sq<1>(ba, tiles, p.n_wg, ba.w_s != nullptr, st, &yt, &yc)); break;
-            case 32: TRY(launch_train_small_bwd_sq<2>(ba, tiles, p.n_wg, ba.w_s != nullptr, st, &yt, &yc)); break;
-            default: TRY(launch_train_small_bwd_sq<4>(ba, tiles, p.n_wg, ba.w_s != nullptr, st, &yt, &yc)); break;
-        }
-        for (int q = 0; q < p.n_types; ++q) {          // every tile's [kernel | bias] (and [d gamma | d beta]) share, summed in tile order
-            const CType &y = p.ty[q];
-            const int tiles_q = p.wg_begin[q + 1] - p.wg_begin[q];
-            if (tiles_q == 0) continue;
-            const int n = (y.in_dim + 1) * p.S;
-            gnn::k_reduce_partials<<<cdiv(n, 64), 256, 0, st>>>(p.sm_partW[q], tiles_q, n, y.g.dkernel[0], 0, 1.0f, y.in_dim * p.S, y.g.dbias[0]);
-            LAUNCH_OK();
-            if (y.m->has_bn) {
-                gnn::k_reduce_partials<<<cdiv(2 * y.in_dim, 64), 256, 0, st>>>(p.sm_partBN[q], tiles_q, 2 * y.in_dim, y.g.dgamma, 0, 1.0f, y.in_dim, y.g.dbeta);
-                LAUNCH_OK();
-            }
-        }
-    }
-    if (p.big) TRY(composite_big_backward(ta, p, k, st));
-    for (int t = k - 1; t >= 0 && !p.small && !p.big; --t) {
-        const float *s_t = p.states + (size_t)t * NS;
-        const float *s_n = p.states + (size_t)(t + 1) * NS;
-        float *agg_t = p.agg + (p.agg_taped ? (size_t)t * NS : 0);
+// the general path: net_backward per type and iteration on the type's gathered rows, then the transposed aggregate over all nodes
+int composite_backward_general(const gnn_train_args_t &ta, CPlan &p, int k, hipStream_t st) {
+    const gnn_loop_args_t &a = ta.loop;
+    gnn::Seg segs[GNN_MAX_SEGS];
+    for (int t = k - 1; t >= 0; --t) {
+        const float *s_t = state_at(p, t), *s_n = state_at(p, t + 1), *agg_t = agg_at(p, t);
         if (!p.agg_taped) TRY(launch_aggregate(nullptr, a.adjacency, s_t, p.S, p.S, p.agg, p.S, st));
         for (int q = 0; q < p.n_types; ++q) {
             CType &y = p.ty[q];
@@ -859,17 +675,10 @@ int train_step_composite(const gnn_train_args_t &ta) {
             int is_, ia_;
             const int n = ctype_segs(a, p, y, t, segs, &is_, &ia_);
             const float *stats = ns.has_bn ? y.stats + (size_t)t * 2 * y.in_dim : nullptr;
-            float *hs[GNN_MAX_LAYERS];
-            for (int l = 0; l < ns.n_layers; ++l) hs[l] = y.nc.hid[l];
-            DropRun drs{&ta.drop_state[q], ta.drop_seed, t, {}};      // (iteration t's masks again: the same keys)
-            for (int qq = 0; qq <= ns.n_layers; ++qq) drs.buf[qq] = y.nc.dropbuf[qq];
+            float *const *hs = y.nc.hid;
+            const DropRun drs = drop_run(&ta.drop_state[q], ta.drop_seed, t, y.nc);      // (iteration t's masks again: the same keys)
             const bool drop_any = ta.drop_state[q].n > 0;
-            if (ns.n_layers > 1 || drop_any) {     // hidden activations are not on the tape: recompute them (with Dropout layers: the last layer's too)
-                const bool folded = ns.has_bn && ns.units[0] <= 4;
-                const float *W0 = folded ? y.Wf + (size_t)t * y.in_dim * ns.units[0] : ns.kernel[0], *b0 = folded ? y.bf + (size_t)t * ns.units[0] : ns.bias[0];
-                gnn_mlp_t head = ns; head.n_layers = drop_any ? ns.n_layers : ns.n_layers - 1;
-                TRY(forward_layers(head, segs, n, y.count, W0, b0, hs, nullptr, st, nullptr, (ns.has_bn && !folded) ? stats : nullptr, folded ? stats : nullptr, &drs, true));
-            }
+            TRY(recompute_hidden(ns, segs, n, y.count, stats, y.Wf + (size_t)t * y.in_dim * ns.units[0], y.bf + (size_t)t * ns.units[0], hs, drs, drop_any, st));
             if (!drop_any) TRY(gather_rows(s_n, p.S, y.rows, y.count, p.S, hs[ns.n_layers - 1], p.S, st));      // the last layer's output: the type's rows of state t + 1
             TRY(gather_rows(p.G_state, p.S, y.rows, y.count, p.S, y.Gc, p.S, st));
             TRY(net_backward(y.nc, segs, n, hs, y.Gc, p.S, y.count, stats, t != k - 1, y.dx, 2 * p.S, p.part, st, -1, y.off_state, &drs));
@@ -878,31 +687,64 @@ int train_step_composite(const gnn_train_args_t &ta) {
             TRY(bn_input_grads(ns, y.nc, stats, rq, 2, y.count, st));
             TRY(scatter_rows(y.dx, 2 * p.S, y.rows, y.count, 2 * p.S, p.dx_full, 2 * p.S, st));
         }
-        {   // G_state = d state (own) + Adj . d agg   (arcs walked by source)
-            const gnn_csr_t &c = ta.adjacency_by_source;
-            int G = 4;
-            while (G < p.S && G < 64) G <<= 1;
-            const int groups = 256 / G, grid = std::min(cdiv(p.N, groups), 256 * 16);
-#define AGGA(GG) gnn::k_aggregate_add<GG><<<grid, 256, 0, st>>>(c.n_dst, c.rowptr, c.src, c.w, c.row_scale, p.dx_full + p.S, 2 * p.S, p.S, \
-                                                                 p.dx_full, 2 * p.S, p.G_state, p.S)
-            switch (G) { case 4: AGGA(4); break; case 8: AGGA(8); break; case 16: AGGA(16); break; case 32: AGGA(32); break; default: AGGA(64); break; }
-#undef AGGA
-            LAUNCH_OK();
-        }
-    }
-    if (ta.average_st_grads && k > 0)
-        for (int q = 0; q < p.n_types; ++q) TRY(scale_grads(*p.ty[q].m, p.ty[q].g, 1.0f / (float)k, st));
-    gnn::k_grads_ok<<<1, 1, 0, st>>>(p.small ? p.k_dev : nullptr, p.grads_ok);      // (only the persistent backward launch can fail)
-    LAUNCH_OK();
-    if (p.small) {
-        TRY(moving_state(p.grads_ok));
-        if (bn_o && p.M > 0) {
-            gnn::k_bn_moving_multi<<<cdiv(no.in_dim, 256), 256, 0, st>>>(p.stats_o, 2 * no.in_dim, 1, no.in_dim, const_cast<float *>(no.bn_mean),
-                                                                        const_cast<float *>(no.bn_var), ta.bn_momentum, p.grads_ok);
-            LAUNCH_OK();
-        }
+        // G_state = d state (own) + Adj . d agg   (arcs walked by source)
+        TRY(launch_aggregate_add(ta.adjacency_by_source, p.dx_full + p.S, 2 * p.S, p.S, p.dx_full, 2 * p.S, p.G_state, p.S, st));
     }
     return 0;
+}
+
+// The step as its phases (no phase cut here: gnn_train_step_ex covers homogeneous models)
+int train_step_composite(const gnn_train_args_t &ta) {
+    const gnn_loop_args_t &a = ta.loop;
+    CPlan p;
+    const bool fwd_only = ta.forward_only != 0;         // the training-mode forward alone: no loss, no gradients, the validity word untouched
+    if (fwd_only && ta.prev_grads_ok_host) return fail("gnn_train_step(forward_only): prev_grads_ok_host must be NULL");
+    TRY(make_cplan(ta, ta.tape, p));
+    if (!ta.tape || ta.tape_bytes < p.bytes) return fail("tape too small: %zu < %zu bytes", ta.tape_bytes, p.bytes);
+    TRY(check_step_args(ta, p, !fwd_only, !fwd_only));
+    const bool small = p.path == TrainPath::small, big = p.path == TrainPath::big;
+    const gnn_mlp_t &no = a.net_output;
+    hipStream_t st = (hipStream_t)a.stream;
+
+    // ---- forward: setup, the K gated iterations on the plan's path, k (the step's one synchronisation), the converged state -----------------
+    gnn::TileTab tiles;
+    gnn::TypeTab yt;
+    memset(&tiles, 0, sizeof(tiles)); memset(&yt, 0, sizeof(yt));
+    int k = 0;
+    TRY(composite_setup(ta, p, st));
+    TRY(big ? composite_big_forward(ta, p, st) : small ? composite_forward_small(ta, p, tiles, yt, st) : composite_forward_general(ta, p, st));
+    TRY(read_k(ta, p, &k, st));
+    if (small || big) TRY(scatter_rows(state_at(p, k), p.ldS, a.type_nodes, p.N, p.S, ta.state, p.S, st));      // positions -> the caller's node order
+    else HIP_OK(hipMemcpyAsync(ta.state, state_at(p, k), sizeof(float) * p.N * p.ldS, hipMemcpyDeviceToDevice, st));
+    const float *state_k = ta.state;                                   // [N, S] in the caller's node order
+    if (!small) TRY(moving_state(ta, p, k, nullptr, st));              // (the persistent path: moving_deferred)
+
+    // ---- output network on the converged state of the masked nodes (CompositeGNN.py:237-239, :270), training mode ----------------------------
+    HeadRun h;
+    TRY(head_segments(ta, p, state_k, p.S, 0, true, h, st));
+    const bool stats_one_pass = p.M > 0 && no.has_bn && p.head_fast;
+    if (stats_one_pass) {          // every node a row, in order: one pass over the state (moments around its row 0)
+        int grid = 0;
+        TRY(rows_stats(nullptr, state_k, p.S, p.S, p.N, p.B.part_y[0], st, &grid));
+        gnn::k_stats_finish<<<p.S, 256, 0, st>>>(nullptr, p.B.part_y[0], grid, p.S, 1.0f / (float)p.N, p.stats_o, p.stats_o + no.in_dim, state_k);
+        LAUNCH_OK();
+    }
+    TRY(head_forward(ta, p, h, stats_one_pass, st));
+    if (fwd_only) return moving_deferred(ta, p, k, nullptr, st);       // the forward alone: what the persistent path keeps back for the validity word is due now
+
+    // ---- loss, then backward: output network, the k iterations on the plan's path --------------------------------------------------------------
+    float *G_out = nullptr;
+    TRY(loss_gradient(ta, p, true, 0.0f, nullptr, &G_out, st));
+    // (the thin head: its parameter gradients, d loss / d state_k written straight into the state gradient - every row is an output row)
+    if (p.head_fast) TRY(head_backward(p, a, nullptr, 0, state_k, p.S, h.out_nodes, G_out, no.has_bn ? p.stats_o : nullptr, st, -1));
+    else TRY(head_backward_general(ta, p, h, G_out, st));
+    for (int q = 0; q < p.n_types; ++q)
+        if (k == 0 || p.ty[q].count == 0) TRY(zero_grads(*p.ty[q].m, p.ty[q].g, st));
+    if (big) TRY(composite_big_backward(ta, p, k, st));
+    else if (small && k > 0) TRY(composite_backward_small(ta, p, tiles, yt, k, st));
+    else if (!small) TRY(composite_backward_general(ta, p, k, st));
+    for (int q = 0; q < p.n_types && ta.average_st_grads && k > 0; ++q) TRY(scale_grads(*p.ty[q].m, p.ty[q].g, 1.0f / (float)k, st));
+    return finish_step(ta, p, k, st);
 }
 
 }  // namespace
