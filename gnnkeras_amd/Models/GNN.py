@@ -619,7 +619,8 @@ class GNNnodeBased(_LoopModel):
         self.state_vect_dim = int(state_vect_dim)
         self.max_iteration = int(max_iteration)
         self.state_threshold = state_threshold
-        self.native_flags = 0          # OR of _native.FLAG_* (tests use FLAG_UNFUSED)
+        self.native_flags = 0          # OR of _native.FLAG_* (tests use FLAG_UNFUSED); FLAG_TRAIN_HIDDEN_SMALL (opt-in, the only bit a training step
+                                       # reads): a state network Dense(H) - Dense(state width) trains on the persistent small-graph kernels
         self.loop_events = None        # optional (begin, end) torch.cuda.Event pair recorded around the iterations
         self._engine_init()
 

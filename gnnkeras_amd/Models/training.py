@@ -291,6 +291,12 @@ def _mix32(*values):
     return h
 
 
+def _train_flags(model):
+    """What a training step takes of `model.native_flags`: the opt-in bit of the hidden-layer persistent kernels alone (the other bits
+    steer the inference loop and keep having no effect on a step)."""
+    return int(getattr(model, 'native_flags', 0)) & nat.FLAG_TRAIN_HIDDEN_SMALL
+
+
 class LoopTrainer:
     """One instance per model; owns gradient buffers and scratch. Homogeneous node / arc / graph focus."""
 
@@ -975,6 +981,7 @@ class LoopTrainer:
             a.net_state[0] = m.net_state.native()
         a.net_output = m.net_output.native()
         a.state_dim, a.max_iteration, a.state_threshold = d, m.max_iteration, float(m.state_threshold)
+        a.flags = _train_flags(m)
         if d > 0:
             if state0 is None:
                 gen = None
@@ -1160,6 +1167,7 @@ class LoopTrainer:
         a.abi_version, a.n_types = nat.GNN_ABI_VERSION, 1
         a.n_nodes, a.n_arcs, a.dim_node_label, a.dim_arc_label = int(n_nodes), int(n_arcs), int(dim_node_label), int(dim_arc_label)
         a.state_dim, a.max_iteration, a.state_threshold = m.state_vect_dim, m.max_iteration, float(m.state_threshold)
+        a.flags = _train_flags(m)
         for dst, net in ((a.net_state[0], m.net_state), (a.net_output, m.net_output)):
             units = [int(u) for u in net.units]
             dst.in_dim, dst.n_layers = int(net.input_dim), len(units)

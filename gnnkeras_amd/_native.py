@@ -24,6 +24,7 @@ FOCUS = {'n': 0, 'a': 1, 'g': 2}
 FLAG_UNFUSED = 1
 FLAG_NO_EARLY_EXIT = 2
 FLAG_FUSED_GEN_MASK = 7 << 4
+FLAG_TRAIN_HIDDEN_SMALL = 1 << 8        # training steps only, opt-in: a state network Dense(H) - Dense(state width) on the persistent small-graph kernels (include/gnnloop.h)
 XC_FILL, XC_VALID = 0, 1                # enum gnn_xc_mode
 FLAG_FUSED_GEN2, FLAG_FUSED_GEN4, FLAG_FUSED_GEN5, FLAG_FUSED_GEN6, FLAG_FUSED_GEN7 = 2 << 4, 4 << 4, 5 << 4, 6 << 4, 7 << 4     # pin the fused-kernel generation (tests, tuning)
 

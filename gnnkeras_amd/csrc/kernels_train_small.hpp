@@ -26,8 +26,30 @@
 //             statistics of iteration t), one per backward iteration with BatchNormalization, none without.
 // Every workgroup must be resident (grid <= CUs, one workgroup per CU); polls sleep and are bounded: an expired wait poisons k / the
 // gradients.
+//
+// Hidden-layer form (template parameter HID; opt-in through GNN_FLAG_TRAIN_HIDDEN_SMALL, homogeneous models; the rule is
+// hidden_dense_of_state_width() in train_loop.hpp): the state network is Dense(H) - Dense(S), 1 <= H <= the padded width.
+// BatchNormalization sits in front of the FIRST Dense only (reference MLP.py:66-70), so the second Dense, its activation and their
+// gradients are local to a tile - no new barrier, no new exchange, no new slot that crosses a barrier:
+//   forward    h = act1(BN([state | agg]) . W1 + Cc) is the one-layer product H wide.  Its accumulators ARE the B operands of the second
+//              product - lane (c, g) holds columns 16 q + 4 g + e of row c, what k-step (q, e) takes from it - so state' = act2(h . W2 + b2)
+//              follows without a trip through LDS; W2 ([S][S + 4] floats) and b2 live in LDS behind the one-layer layout.
+//   backward   in front of the one-layer code: dZ2 = G (.) act2'(states[t + 1]) in place over G (dead until step D), q2 += colsum(dZ2) and
+//              P2 += h^T dZ2 (this workgroup's share of d W2 / d b2, in registers over all iterations like accP), dH = dZ2 . W2^T and dZ1 =
+//              dH (.) act1'(h) of every wave's own 16 rows -> Zs; then q, dy = dZ1 . W1^T, the BatchNorm partials, Phat, dx and the gather
+//              run unchanged on dZ1 (dzsum accumulates dZ1: the constants' products and k_label_grads are linear in it).  The hidden rows
+//              share the LDS tile of Da (they are dead before step D writes it); the shares of d W2 / d b2 leave through partW2.
+// h_t is KEPT ON THE TAPE ([K][N][S] floats, written by the forward launch) rather than recomputed: recomputing needs the first product
+// again in the backward sweep (2 S x S matrix-core steps per tile and iteration, the constant part Cc read once more, the activation
+// evaluated twice) to save K x N x S floats that stay in L2 at these sizes (d = 32 x 50 iterations x 1 k nodes: 6.4 MB), and the taped
+// rows are bit for bit what the forward used.  They count in the tape budget beside the neighbour sums (train_small_fits).
+// The hidden form is instantiated for the padded widths 16 and 32.  At 64 the backward kernel's extra accumulators (P2: 16 registers, dH:
+// 16, the hidden row pieces) do not fit beside the one-layer kernel's (it is at 256 + 213 .. 256 registers already): the LOCAL form spilled
+// 400 .. 620 bytes per lane to scratch, so the rule refuses that width.  The one-layer instantiations (HID = false) are the kernels they
+// were: the hidden form's arguments travel in derived structs (TrainSmallFwdH / TrainSmallBwdH), read under `if constexpr`.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "kernels_general.hpp"
 #include "kernel_state_fused4.hpp"      // activate4
 #include "kernel_state_lds.hpp"         // row16_sum_to_lane15
@@ -307,9 +329,23 @@ struct TrainSmallFwd {
     float *k_out;                // [0] = iterations executed (-1e9: a barrier timed out), [1] = 1 when an arc leaves its tile (LOCAL)
     unsigned long long wait_ticks;   // bound of a barrier wait (buffer_ops.hpp: wait_until)
 };
+// ... of the hidden-layer form (the HID instantiations; homogeneous models): W is [in_s][Hw], Cc has Hw real columns, `act` is the hidden activation
+struct TrainSmallFwdH : TrainSmallFwd {
+    int Hw;                      // hidden width, 1 .. 16 SQ
+    const float *W2, *b2;        // second Dense: [Hw][Sw], [Sw]
+    int act2;                    // its activation (the state's)
+    float *hid;                  // [K][N][S] the hidden rows h_t of every iteration, kept for the backward pass (pad columns zero)
+};
+// what the one-layer and the hidden-layer instantiations read from their own argument blocks
+template <bool HID, typename A> __device__ __forceinline__ int first_layer_width(const A &a) { if constexpr (HID) return a.Hw; else return a.Sw; }
+template <bool HID, typename A> __device__ __forceinline__ int state_activation(const A &a, int act) { if constexpr (HID) return a.act2; else return act; }
 
-template <int SQ, bool HAS_W, bool LOCAL>
-__global__ void __launch_bounds__(TS_NT, 1) k_train_small_fwd(TrainSmallFwd a, TileTab tt, TypeTab yt) {
+template <int SQ, bool HID = false>
+constexpr int train_small_fwd_floats() { return 64 * (2 * 16 * SQ + 4) + (2 * 16 * SQ) * (16 * SQ + 4) + 3 * 2 * 16 * SQ + 512 + (HID ? 16 * SQ * (16 * SQ + 4) + 16 * SQ : 0); }
+
+// HID: the state network has a hidden layer (see the header comment); HID = false is the one-layer kernel, unchanged
+template <int SQ, bool HAS_W, bool LOCAL, bool HID = false>
+__global__ void __launch_bounds__(TS_NT, 1) k_train_small_fwd(std::conditional_t<HID, TrainSmallFwdH, TrainSmallFwd> a, TileTab tt, TypeTab yt) {
     using Csr = TileCsr<SQ, HAS_W, LOCAL>;
     constexpr int S = 16 * SQ, NPP = Csr::NPP, NPASS = Csr::NPASS;
     constexpr int LDX = 2 * S + 4;        // row stride of the [own | agg] tile: == 4 (mod 32) dwords, 16-B chunks conflict-free
@@ -319,6 +355,8 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_fwd(TrainSmallFwd a, T
     float *W0 = Xs + 64 * LDX;            // [2 S][LDW] kernel rows of the state / agg columns
     float *st_a = W0 + 2 * S * LDW;       // [2 S] a_k, [2 S] beta_k, [2 S] column means of this iteration, reduction scratch [512]
     float *st_c = st_a + 2 * S, *piv = st_c + 2 * S, *red = piv + 2 * S;
+    float *W2s = ts_smem + train_small_fwd_floats<SQ>();      // HID: [S][LDW] rows of the second kernel (rows >= Hw, columns >= Sw zero), [S] its bias
+    float *b2s = W2s + S * LDW;
     __shared__ int cont;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -326,6 +364,7 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_fwd(TrainSmallFwd a, T
     const bool tab = LOCAL || tt.n > 0;
     const int n0 = tab ? tt.begin[blockIdx.x] : (int)blockIdx.x * 64;
     const int nt = tab ? tt.begin[blockIdx.x + 1] - n0 : min(64, a.N - n0);
+    const int Hw = first_layer_width<HID>(a);     // width of the first layer's output (= the kernel's row length)
     // heterogeneous models: this tile's node type selects the network (TypeTab); the statistics span the tiles [wg_lo, wg_hi) of the type
     int ty = 0;
     if (yt.n > 0) { while (ty + 1 < yt.n && (int)blockIdx.x >= yt.wg_begin[ty + 1]) ++ty; }
@@ -342,7 +381,14 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_fwd(TrainSmallFwd a, T
     for (int i = tid; i < 2 * S * S; i += TS_NT) {
         const int k = i / S, h = i % S;
         const int kk = k < S ? k : k - S;
-        W0[k * LDW + h] = (kk < a.Sw && h < a.Sw) ? Wk[(size_t)((k < S ? off_state : off_agg) + kk) * a.Sw + h] : 0.0f;
+        W0[k * LDW + h] = (kk < a.Sw && h < Hw) ? Wk[(size_t)((k < S ? off_state : off_agg) + kk) * Hw + h] : 0.0f;
+    }
+    if constexpr (HID) {
+        for (int i = tid; i < S * S; i += TS_NT) {
+            const int k = i / S, h = i % S;
+            W2s[k * LDW + h] = (k < Hw && h < a.Sw) ? a.W2[(size_t)k * a.Sw + h] : 0.0f;
+        }
+        if (tid < S) b2s[tid] = tid < a.Sw ? a.b2[tid] : 0.0f;
     }
     if (tid < 2 * S) { piv[tid] = 0.0f; st_a[tid] = 1.0f; st_c[tid] = 0.0f; }
     Csr csr;
@@ -477,12 +523,36 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_fwd(TrainSmallFwd a, T
             }
         }
         asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");          // (MFMA results consumed behind a branch: see kernels_train_big.hpp)
+        if constexpr (HID) {
+            // ---- C2. h = act1(..) of this lane's chunks -> the tape; state' = act2(h . W2 + b2): lane (c, g) holds columns 16 qq + 4 g + e of
+            // row c of ITS wave - exactly the B operand of k-step (qq, e), so h goes from the accumulators into the second product as it is
+            f32x4 hv[SQ];
+#pragma unroll
+            for (int ct = 0; ct < SQ; ++ct) {
+                hv[ct] = acc[ct];
+                activate4(act, hv[ct]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) hv[ct][e] = 16 * ct + 4 * g + e < Hw ? hv[ct][e] : 0.0f;
+                if (oin) *reinterpret_cast<f32x4 *>(a.hid + (size_t)it * NS + (size_t)orow * S + 16 * ct + 4 * g) = hv[ct];
+                acc[ct] = *reinterpret_cast<const f32x4 *>(b2s + 16 * ct + 4 * g);
+            }
+#pragma unroll
+            for (int qq = 0; qq < SQ; ++qq)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float *wr = W2s + (16 * qq + 4 * g + e) * LDW + c;
+#pragma unroll
+                    for (int ct = 0; ct < SQ; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[16 * ct], hv[qq][e], acc[ct], 0, 0, 0);
+                }
+            asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
+        }
+        const int act_out = state_activation<HID>(a, act);
         float d2 = 0.0f, n2 = 0.0f;
         float *orow_lds = Xs + (16 * wave + c) * LDX + 4 * g;
 #pragma unroll
         for (int ct = 0; ct < SQ; ++ct) {
             f32x4 v = acc[ct];
-            activate4(act, v);
+            activate4(act_out, v);
             const f32x4 o = *reinterpret_cast<const f32x4 *>(orow_lds + 16 * ct);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { v[e] = (oin && 16 * ct + 4 * g + e < a.Sw) ? v[e] : 0.0f; const float d = v[e] - o[e]; d2 = fmaf(d, d, d2); n2 = fmaf(o[e], o[e], n2); }
@@ -506,11 +576,8 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_fwd(TrainSmallFwd a, T
     if (tid == 0 && gb.timed_out) a.k_out[1] = 2.0f;
 }
 
-template <int SQ>
-inline size_t train_small_fwd_lds() {
-    constexpr int S = 16 * SQ;
-    return sizeof(float) * (64 * (2 * S + 4) + (2 * S) * (S + 4) + 3 * 2 * S + 512);
-}
+template <int SQ, bool HID = false>
+inline size_t train_small_fwd_lds() { return sizeof(float) * train_small_fwd_floats<SQ, HID>(); }
 
 // ---- backward ----------------------------------------------------------------------------------------------------------------------------------
 // BatchNormalization in terms of xhat = (x - mean) rstd (what the tile keeps in LDS):  with  Phat = xhat^T dZ,  q = colsum(dZ),
@@ -545,10 +612,25 @@ struct TrainSmallBwd {
     float *dz_out;               // [N][S] sum over the executed iterations of dZ_t (kernels_train_labels.hpp turns it into the constants' gradients)
     float *g0_out;               // [N][S] d loss / d state_0 (state_dim == 0: state_0 = nodes)
 };
+// ... of the hidden-layer form (the HID instantiations; homogeneous models): W is [in_s][Hw], partW [n_wg][in_s * Hw + Hw], dz_out has Hw real
+// columns, `act` is the hidden activation
+struct TrainSmallBwdH : TrainSmallBwd {
+    int Hw;                      // hidden width, 1 .. 16 SQ
+    const float *W2;             // second Dense kernel [Hw][Sw]
+    int act2;                    // its activation (the state's)
+    const float *hid;            // [k][N][S] the forward tape's hidden rows
+    float *partW2;               // [n_wg][Hw * Sw + Sw] every workgroup's share of the second layer's kernel and bias gradients
+};
+
+template <int SQ>
+constexpr int train_small_bwd_floats(bool da) {       // `da`: the [64][S + 4] tile behind Gs (LOCAL: d loss / d agg; HID: the hidden rows, shared with it)
+    return 64 * (2 * 16 * SQ + 4) + (da ? 3 : 2) * 64 * (16 * SQ + 4) + 2 * 16 * SQ * (16 * SQ + 4) + (16 * SQ + 16 * 16 * SQ) + 4 * 16 * SQ + 16 * 16 * SQ + 512;
+}
 
 // LAB: the instantiation that also stores sum_t dZ_t / d loss / d state_0 (label gradients); LAB = false is the kernel without them
-template <int SQ, bool HAS_W, bool LOCAL, bool LAB = false>
-__global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(TrainSmallBwd a, TileTab tt, TypeTab yt, TypeConsts yc) {
+// HID: the state network has a hidden layer (see the header comment); HID = false is the one-layer kernel, unchanged
+template <int SQ, bool HAS_W, bool LOCAL, bool LAB = false, bool HID = false>
+__global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(std::conditional_t<HID, TrainSmallBwdH, TrainSmallBwd> a, TileTab tt, TypeTab yt, TypeConsts yc) {
     using Csr = TileCsr<SQ, HAS_W, LOCAL>;
     constexpr int S = 16 * SQ, LPR = S / 4, NPP = Csr::NPP, NPASS = Csr::NPASS;
     constexpr int LDX = 2 * S + 4;        // == 4 (mod 32)
@@ -562,7 +644,10 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(TrainSmallBwd a, T
     float *Zs = Xs + 64 * LDX;            // [64][LDZ]  dZ
     float *Gs = Zs + 64 * LDZ;            // [64][LDZ]  G (d loss / d state of the tile)
     float *Da = Gs + 64 * LDZ;            // [64][LDZ]  d loss / d agg rows of the tile (LOCAL)
-    float *Wr = Da + (LOCAL ? 64 * LDZ : 0);       // [2 S][LDW] kernel rows of the state / agg columns
+    float *Hs = Da;                       // HID: [64][LDZ] the hidden rows h_t - dead before step D writes Da, whose storage they share
+    float *Wr = Da + ((LOCAL || HID) ? 64 * LDZ : 0);       // [2 S][LDW] kernel rows of the state / agg columns
+    float *W2s = ts_smem + train_small_bwd_floats<SQ>(LOCAL || HID);      // HID: [S][LDW] rows of the second kernel (rows >= Hw, columns >= Sw zero)
+    constexpr int NT_2 = SQ * SQ, TP2 = (NT_2 + 3) / 4;      // HID: 16 x 16 tiles of P2 = h^T dZ2 (kt, ht), ... per wave
     float *vec = Wr + 2 * S * LDW;
     float *ql_s = vec, *S1_s = ql_s + S, *S2_s = S1_s + 2 * S, *cfA = S2_s + 2 * S, *cfC = cfA + 2 * S, *cfB = cfC + 2 * S,
           *rs_s = cfB + 2 * S, *sh_s = rs_s + 2 * S, *red = sh_s + 2 * S;      // red: [4][2 S] / [4][S] scratch
@@ -591,9 +676,16 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(TrainSmallBwd a, T
     auto wrow_dyn = [&](int j) { return j < S ? off_state + j : off_agg + (j - S); };      // weight row / BatchNorm column of tile column j (valid j only)
     auto valid_dyn = [&](int j) { return (j < S ? j : j - S) < a.Sw; };           // pad columns of the padded state width carry zeros
 
+    const int Hw = first_layer_width<HID>(a);     // width of the first layer's output (= the kernel's row length)
     for (int i = tid; i < 2 * S * S; i += TS_NT) {
         const int j = i / S, h = i % S;
-        Wr[j * LDW + h] = (valid_dyn(j) && h < a.Sw) ? Wk[(size_t)wrow_dyn(j) * a.Sw + h] : 0.0f;
+        Wr[j * LDW + h] = (valid_dyn(j) && h < Hw) ? Wk[(size_t)wrow_dyn(j) * Hw + h] : 0.0f;
+    }
+    if constexpr (HID) {
+        for (int i = tid; i < S * S; i += TS_NT) {
+            const int k = i / S, h = i % S;
+            W2s[k * LDW + h] = (k < Hw && h < a.Sw) ? a.W2[(size_t)k * a.Sw + h] : 0.0f;
+        }
     }
     for (int i = tid; i < 64 * S; i += TS_NT) {          // (G0 is in the caller's node order)
         const int rr = i / S, h = i % S;
@@ -636,8 +728,24 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(TrainSmallBwd a, T
             }
         }
     };
+    // HID: this workgroup's share of the second layer's gradients over all iterations (P2 = h^T dZ2 in tiles, q2 = colsum(dZ2) by thread
+    // h < S), and the hidden rows of iteration t as row pieces
+    f32x4 accP2[HID ? TP2 : 1];
+#pragma unroll
+    for (int i = 0; i < (HID ? TP2 : 1); ++i) accP2[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    float q2sum = 0.0f;
+    f32x4 hp[HID ? NCH : 1];
+    auto fetch_h = [&](int t, f32x4 (&fh)[HID ? NCH : 1]) {
+#pragma unroll
+        for (int u = 0; u < (HID ? NCH : 0); ++u) {
+            const int rr = (tid + u * TS_NT) / LPR;
+            fh[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if constexpr (HID) { if (rr < nt && t >= 0) fh[u] = *reinterpret_cast<const f32x4 *>(a.hid + (size_t)t * NS + (size_t)(n0 + rr) * S + 4 * ch); }
+        }
+    };
     if (a.k > 0) {
         fetch(a.k - 1, xs, xa);
+        if (HID) fetch_h(a.k - 1, hp);
 #pragma unroll
         for (int u = 0; u < NCH; ++u) {
             const int rr = (tid + u * TS_NT) / LPR;
@@ -652,6 +760,8 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(TrainSmallBwd a, T
         // ---- A. xhat and dZ = G (.) act'(output) of the tile into LDS; the rows of iteration t - 1 are requested now -----------------------------
         f32x4 xs_n[NCH], xa_n[NCH];
         fetch(t - 1, xs_n, xa_n);
+        f32x4 hp_n[HID ? NCH : 1];
+        if (HID) fetch_h(t - 1, hp_n);
         {
             f32x4 qp = {0.f, 0.f, 0.f, 0.f};
             const f32x4 r0 = *reinterpret_cast<const f32x4 *>(rs_s + 4 * ch), s0 = *reinterpret_cast<const f32x4 *>(sh_s + 4 * ch);
@@ -664,12 +774,18 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(TrainSmallBwd a, T
                 for (int e = 0; e < 4; ++e) {
                     hs[e] = rr < nt ? (xs[u][e] - s0[e]) * r0[e] : 0.0f;
                     ha[e] = rr < nt ? (xa[u][e] - s1[e]) * r1[e] : 0.0f;
-                    gz[e] *= activate_grad_from_output(act, y[u][e]);
+                    gz[e] *= activate_grad_from_output(state_activation<HID>(a, act), y[u][e]);
                 }
                 *reinterpret_cast<f32x4 *>(Xs + rr * LDX + 4 * ch) = hs;
                 *reinterpret_cast<f32x4 *>(Xs + rr * LDX + S + 4 * ch) = ha;
-                *reinterpret_cast<f32x4 *>(Zs + rr * LDZ + 4 * ch) = gz;
-                dzsum[u] += gz; qp += gz;
+                if (HID) {      // gz = dZ2 of the SECOND layer: in place over G (dead until step D), the hidden rows beside it
+                    *reinterpret_cast<f32x4 *>(Gs + rr * LDZ + 4 * ch) = gz;
+                    *reinterpret_cast<f32x4 *>(Hs + rr * LDZ + 4 * ch) = hp[HID ? u : 0];
+                } else {
+                    *reinterpret_cast<f32x4 *>(Zs + rr * LDZ + 4 * ch) = gz;
+                    dzsum[u] += gz;
+                }
+                qp += gz;
             }
             // q of the tile: this thread's rows, then the lanes with the same chunk (stride LPR), then the four waves (in order)
 #pragma unroll
@@ -679,6 +795,57 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(TrainSmallBwd a, T
             if (lane < LPR) *reinterpret_cast<f32x4 *>(red + wave * S + 4 * ch) = qp;
         }
         __syncthreads();
+        if (HID) {
+            // ---- A2. the second layer, local to the tile: q2 += colsum(dZ2), P2 += h^T dZ2 (all rows of the tile, tiles dealt to the waves),
+            // dH = dZ2 . W2^T and dZ1 = dH (.) act1'(h) of the wave's own 16 rows -> Zs; from there on the one-layer code runs on dZ1
+            if (tid < S) q2sum += ((red[tid] + red[S + tid]) + red[2 * S + tid]) + red[3 * S + tid];
+#pragma unroll
+            for (int i = 0; i < (HID ? TP2 : 0); ++i) {
+                const int ti = wave + 4 * i;
+                if (ti < NT_2) {
+                    const int kt = ti / SQ, ht = ti % SQ;
+                    const float *xp = Hs + g * LDZ + 16 * kt + c, *zp = Gs + g * LDZ + 16 * ht + c;
+#pragma unroll 4
+                    for (int ms = 0; ms < 16; ++ms)
+                        accP2[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(xp[4 * ms * LDZ], zp[4 * ms * LDZ], accP2[i], 0, 0, 0);
+                }
+            }
+            f32x4 dh[SQ];
+#pragma unroll
+            for (int u = 0; u < SQ; ++u) dh[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            const float *z2row = Gs + (16 * wave + c) * LDZ + 4 * g;
+#pragma unroll 2
+            for (int qq = 0; qq < S / 16; ++qq) {
+                const f32x4 zv = *reinterpret_cast<const f32x4 *>(z2row + 16 * qq);
+#pragma unroll
+                for (int u = 0; u < SQ; ++u) {
+                    const f32x4 wv = *reinterpret_cast<const f32x4 *>(W2s + (16 * u + c) * LDW + 16 * qq + 4 * g);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dh[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[e], zv[e], dh[u], 0, 0, 0);
+                }
+            }
+            asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
+#pragma unroll
+            for (int u = 0; u < SQ; ++u) {
+                const f32x4 hv = *reinterpret_cast<const f32x4 *>(Hs + (16 * wave + c) * LDZ + 16 * u + 4 * g);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) dh[u][e] *= activate_grad_from_output(act, hv[e]);
+                *reinterpret_cast<f32x4 *>(Zs + (16 * wave + c) * LDZ + 16 * u + 4 * g) = dh[u];
+            }
+            __syncthreads();
+            f32x4 qp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int u = 0; u < NCH; ++u) {
+                const f32x4 gz = *reinterpret_cast<const f32x4 *>(Zs + ((tid + u * TS_NT) / LPR) * LDZ + 4 * ch);
+                dzsum[u] += gz; qp += gz;
+            }
+#pragma unroll
+            for (int off = LPR; off < 64; off <<= 1)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) qp[e] += __shfl_xor(qp[e], off, 64);
+            if (lane < LPR) *reinterpret_cast<f32x4 *>(red + wave * S + 4 * ch) = qp;
+            __syncthreads();
+        }
         TS_STAMP(0);
         if (tid < S) { const float t3 = ((red[tid] + red[S + tid]) + red[2 * S + tid]) + red[3 * S + tid]; ql_s[tid] = t3; qsum += t3; }
         // ---- B. dy = dZ . W^T on the matrix cores (operands swapped: lane (c, g) holds columns j0 .. j0 + 3 of row c of its wave) ------------
@@ -802,6 +969,10 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(TrainSmallBwd a, T
         if (t > 0) coefficients(t - 1);
 #pragma unroll
         for (int u = 0; u < NCH; ++u) { y[u] = xs[u]; xs[u] = xs_n[u]; xa[u] = xa_n[u]; }       // states[t] is the output of iteration t - 1
+        if (HID) {
+#pragma unroll
+            for (int u = 0; u < NCH; ++u) hp[HID ? u : 0] = hp_n[HID ? u : 0];
+        }
         __syncthreads();
         TS_STAMP(7);
     }
@@ -822,9 +993,25 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(TrainSmallBwd a, T
         }
     }
     // ---- the shares of this workgroup (heterogeneous models: the type's own arrays, one slot per tile of the type) ------------------------------
-    float *pw = yt.n > 0 ? yt.partW[ty] + (size_t)(blockIdx.x - wg_lo) * ((size_t)in_s * a.Sw + a.Sw) : a.partW + (size_t)blockIdx.x * ((size_t)in_s * a.Sw + a.Sw);
+    float *pw = yt.n > 0 ? yt.partW[ty] + (size_t)(blockIdx.x - wg_lo) * ((size_t)in_s * Hw + Hw) : a.partW + (size_t)blockIdx.x * ((size_t)in_s * Hw + Hw);
     float *pb = !bn ? nullptr : yt.n > 0 ? yt.partBN[ty] + (size_t)(blockIdx.x - wg_lo) * 2 * in_s : a.partBN + (size_t)blockIdx.x * 2 * in_s;
-    if (tid < S) { if (tid < a.Sw) pw[(size_t)in_s * a.Sw + tid] = qsum; ql_s[tid] = qsum; }
+    if (tid < S) { if (tid < Hw) pw[(size_t)in_s * Hw + tid] = qsum; ql_s[tid] = qsum; }
+    if constexpr (HID) {      // the second layer's share: P2 rows h < Hw, columns < Sw, then q2
+        float *pw2 = a.partW2 + (size_t)blockIdx.x * ((size_t)Hw * a.Sw + a.Sw);
+        if (tid < a.Sw) pw2[(size_t)Hw * a.Sw + tid] = q2sum;
+#pragma unroll
+        for (int i = 0; i < (HID ? TP2 : 0); ++i) {
+            const int ti = wave + 4 * i;
+            if (ti < NT_2) {
+                const int kt = ti / SQ, ht = ti % SQ;
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const int j = 16 * kt + 4 * g + reg, h = 16 * ht + c;
+                    if (j < Hw && h < a.Sw) pw2[(size_t)j * a.Sw + h] = accP2[i][reg];
+                }
+            }
+        }
+    }
     __syncthreads();
     // kernel rows of the state / agg columns: gamma_k sum_t Phat + beta_k sum_t q
 #pragma unroll
@@ -835,10 +1022,10 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(TrainSmallBwd a, T
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
                 const int j = 16 * kt + 4 * g + reg, k = wrow_dyn(j), h = 16 * ht + c;
-                if (!valid_dyn(j) || h >= a.Sw) continue;
+                if (!valid_dyn(j) || h >= Hw) continue;
                 float v = accP[i][reg];
                 if (bn) v = fmaf(gamma_[k], v, beta_[k] * ql_s[h]);
-                pw[(size_t)k * a.Sw + h] = v;
+                pw[(size_t)k * Hw + h] = v;
             }
         }
     }
@@ -888,13 +1075,13 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(TrainSmallBwd a, T
 #pragma unroll
                 for (int reg = 0; reg < 4; ++reg) {
                     const int jj = 16 * kt + 4 * g + reg, k = cb + jj < Kc ? wrow_c[jj] : -1;
-                    const bool hv = 16 * ht + c < a.Sw;
-                    const float w = (k >= 0 && hv) ? Wk[(size_t)k * a.Sw + 16 * ht + c] : 0.0f;
+                    const bool hv = 16 * ht + c < Hw;
+                    const float w = (k >= 0 && hv) ? Wk[(size_t)k * Hw + 16 * ht + c] : 0.0f;
                     float s2 = w * Pc[reg], s1 = w * ql_s[16 * ht + c];
 #pragma unroll
                     for (int off = 1; off < 16; off <<= 1) { s2 += __shfl_xor(s2, off, 64); s1 += __shfl_xor(s1, off, 64); }
                     if (k >= 0) {
-                        if (hv) pw[(size_t)k * a.Sw + 16 * ht + c] = bn ? fmaf(gamma_[k], Pc[reg], beta_[k] * ql_s[16 * ht + c]) : Pc[reg];
+                        if (hv) pw[(size_t)k * Hw + 16 * ht + c] = bn ? fmaf(gamma_[k], Pc[reg], beta_[k] * ql_s[16 * ht + c]) : Pc[reg];
                         if (bn && c == 0) { red[64 + ht * 32 + jj] = s2; red[64 + 4 * 32 + ht * 32 + jj] = s1; }
                     }
                 }
@@ -913,9 +1100,9 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(TrainSmallBwd a, T
 }
 
 template <int SQ>
-inline size_t train_small_bwd_lds(bool local) {
+inline size_t train_small_bwd_lds(bool local, bool hid = false) {
     constexpr int S = 16 * SQ;
-    return sizeof(float) * (64 * (2 * S + 4) + (local ? 3 : 2) * 64 * (S + 4) + 2 * S * (S + 4) + (S + 16 * S) + 4 * S + 16 * S + 512);
+    return sizeof(float) * (train_small_bwd_floats<SQ>(local || hid) + (hid ? S * (S + 4) : 0));
 }
 
 }  // namespace gnn

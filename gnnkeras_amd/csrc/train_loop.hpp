@@ -92,6 +92,8 @@ struct StepPlan {
     int *flags; float *k_dev, *states, *agg;
     int SPs, ldS, n_wg;          // small path: the padded state width the persistent kernels run (16 / 32 / 64), the tape's row stride, the tiles
     float *sm_cc, *sm_part; unsigned long long *sm_bar;
+    bool hid_small;              // small path, hidden-layer form (GNN_FLAG_TRAIN_HIDDEN_SMALL; homogeneous models): the state network is two Dense layers
+    float *sm_hid, *sm_partW2;   // ... its hidden rows on the tape [K][N][ldS], every workgroup's share of the second layer's gradients
     float *stats_o, *Wf_o, *bf_o, *dx_o_all, *G_state, *G_out, *dpred, *loss_rows, *loss_part;
     int *isrc, *idst;            // arc focus: the end nodes of the masked arcs
     float *part, *part_h; size_t part_floats;
@@ -129,9 +131,16 @@ inline bool train_small_enabled() { const char *e = getenv("GNN_TRAIN_SMALL"); r
 inline bool one_dense_of_state_width(const gnn_mlp_t &m, int S) { return m.n_layers == 1 && m.units[0] == S && m.activation[0] != GNN_ACT_SOFTMAX; }
 // the persistent kernels: switched on, below the large-graph threshold, no Dropout in a state network, the padded width at most 64, every
 // tile resident at once (the workgroups meet at grid barriers), every iteration's neighbour sum within the aggregate-tape budget
-inline bool train_small_fits(const StepPlan &p, bool drop_s) {
+// (`taped` matrices of N x SPs floats per iteration: the neighbour sums, and the hidden rows of the hidden-layer form)
+inline bool train_small_fits(const StepPlan &p, bool drop_s, int taped = 1) {
     return train_small_enabled() && p.N < train_big_min_nodes() && !drop_s && p.S <= 64 && p.n_wg <= device_cus() &&
-           (size_t)std::max(p.K, 1) * p.N * p.SPs * sizeof(float) <= agg_tape_budget();
+           (size_t)taped * std::max(p.K, 1) * p.N * p.SPs * sizeof(float) <= agg_tape_budget();
+}
+// the hidden-layer form of the persistent kernels (opt-in: GNN_FLAG_TRAIN_HIDDEN_SMALL): Dense(H) - Dense(S), 1 <= H <= the padded state
+// width `SPs` the kernels run, neither activation softmax (BatchNormalization sits in front of the first Dense only: the second is local to a tile).
+// Padded widths 16 and 32 only: at 64 the backward kernel's second set of accumulators does not fit the register file (it would spill to scratch).
+inline bool hidden_dense_of_state_width(const gnn_mlp_t &m, int S, int SPs) {
+    return SPs <= 32 && m.n_layers == 2 && m.units[1] == S && m.units[0] >= 1 && m.units[0] <= SPs && m.activation[0] != GNN_ACT_SOFTMAX && m.activation[1] != GNN_ACT_SOFTMAX;
 }
 
 size_t grad_part_floats(int K, int H, int M) { int nc; rows_per_chunk_for(std::max(M, 1), &nc); return (size_t)nc * ((size_t)K * H + H); }
@@ -157,8 +166,14 @@ void carve_net(Carver &c, NetCtx &x, const gnn_mlp_t &m, int rows, size_t &part_
 // Which path a homogeneous step takes (dims, Kc, SPs and n_wg of `p` are set).  Both fast paths want one Dense layer without Dropout, at least one
 // iteration and at most 32 constant input columns (one line per node); the row-streaming kernels exist for state widths 16 / 32 / 64 and address the
 // state through 4 GiB windows; the persistent kernels pad the width to 16 / 32 / 64 inside the tape (the starter configuration's 14 label columns).
-TrainPath homogeneous_train_path(const gnn_train_args_t &ta, const TrainPlan &p) {
+// `hidden` (out): the persistent kernels in their hidden-layer form - asked for by GNN_FLAG_TRAIN_HIDDEN_SMALL, a network
+// hidden_dense_of_state_width() accepts, and every condition of the persistent path with the hidden rows counted on the tape beside the
+// neighbour sums; with the flag set every other shape is routed exactly as without it.
+TrainPath homogeneous_train_path(const gnn_train_args_t &ta, const TrainPlan &p, bool &hidden) {
     const bool drop_s = ta.drop_state[0].n > 0;
+    hidden = (ta.loop.flags & GNN_FLAG_TRAIN_HIDDEN_SMALL) != 0 && hidden_dense_of_state_width(ta.loop.net_state[0], p.S, p.SPs) && !drop_s && p.K >= 1 &&
+             p.Kc <= 32 && train_small_fits(p, drop_s, 2);
+    if (hidden) return TrainPath::small;
     if (!one_dense_of_state_width(ta.loop.net_state[0], p.S) || drop_s || p.K <= 0 || p.Kc > 32) return TrainPath::general;
     if (p.N >= train_big_min_nodes())
         return ((p.S == 16 || p.S == 32 || p.S == 64) && (size_t)p.N * p.S * 4 < ((size_t)1 << 32)) ? TrainPath::big : TrainPath::general;
@@ -200,7 +215,7 @@ int make_train_plan(const gnn_train_args_t &ta, void *ws, TrainPlan &p) {
     p.tiled = ta.n_tiles > 0 && ta.tile_node_begin != nullptr;
     p.n_wg = p.tiled ? ta.n_tiles : cdiv(p.N, 64);
     if (p.tiled && p.n_wg > 256) { p.tiled = false; p.n_wg = cdiv(p.N, 64); }
-    p.path = homogeneous_train_path(ta, p);
+    p.path = homogeneous_train_path(ta, p, p.hid_small);
     const bool big = p.path == TrainPath::big, small = p.path == TrainPath::small;
     // every node is an output row (out_index ascending and n_out == n_nodes: the identity), one thin Dense: kernels_train_big.hpp
     p.head_fast = big && no.n_layers == 1 && no.units[0] <= 4 && a.focus != GNN_FOCUS_ARC && p.M == p.N && p.S % 4 == 0 &&
@@ -262,9 +277,11 @@ int make_train_plan(const gnn_train_args_t &ta, void *ws, TrainPlan &p) {
     p.part_h = c.take<float>(p.head_fast ? (size_t)BIG_HEAD_BLOCKS * ((size_t)p.in_o * p.H1o + p.H1o) : 0);             // k_head_wgrad: one partial per workgroup
     p.sm_cc = c.take<float>(small ? (size_t)p.N * p.SPs : 0);
     p.sm_part = c.take<float>(small ? (size_t)2 * p.n_wg * 8 * p.SPs : 0);
-    p.sm_partW = c.take<float>(small ? (size_t)p.n_wg * (p.in_s + 1) * p.S : 0);
+    p.sm_partW = c.take<float>(small ? (size_t)p.n_wg * (p.in_s + 1) * p.H1s : 0);
     p.sm_partBN = c.take<float>(small ? (size_t)p.n_wg * 2 * p.in_s : 0);
     p.sm_bar = c.take<unsigned long long>(small ? 4 : 0);
+    p.sm_hid = c.take<float>(p.hid_small ? (size_t)p.K * p.N * p.ldS : 0);
+    p.sm_partW2 = c.take<float>(p.hid_small ? (size_t)p.n_wg * (p.H1s + 1) * p.S : 0);
     p.ld_dz = small ? p.SPs : p.H1s;
     p.dz_sum = c.take<float>(big ? 0 : (size_t)p.N * p.ld_dz);
     p.g0 = c.take<float>(small ? (size_t)p.N * p.SPs : 0);
@@ -808,6 +825,35 @@ int launch_train_small_bwd_sq(const gnn::TrainSmallBwd &ba, const gnn::TileTab &
                  : launch_persistent(&gnn::k_train_small_bwd<SQ, false, false>, ba, tt, n_wg, lds, st, y, c);
 }
 
+// the hidden-layer form of both launches (homogeneous models; fa.W2 / ba.W2 set): LOCAL with a tile table, both HAS_W forms, LAB as above
+template <int SQ>
+int launch_train_small_fwd_hid_sq(const gnn::TrainSmallFwdH &fa, const gnn::TileTab &tt, int n_wg, bool has_w, hipStream_t st) {
+    const size_t lds = gnn::train_small_fwd_lds<SQ, true>();
+    static const gnn::TypeTab y{};
+    if (tt.n > 0) return has_w ? launch_persistent(&gnn::k_train_small_fwd<SQ, true, true, true>, fa, tt, n_wg, lds, st, y)
+                               : launch_persistent(&gnn::k_train_small_fwd<SQ, false, true, true>, fa, tt, n_wg, lds, st, y);
+    return has_w ? launch_persistent(&gnn::k_train_small_fwd<SQ, true, false, true>, fa, tt, n_wg, lds, st, y)
+                 : launch_persistent(&gnn::k_train_small_fwd<SQ, false, false, true>, fa, tt, n_wg, lds, st, y);
+}
+
+template <int SQ>
+int launch_train_small_bwd_hid_sq(const gnn::TrainSmallBwdH &ba, const gnn::TileTab &tt, int n_wg, bool has_w, hipStream_t st) {
+    const bool local = tt.n > 0;
+    const size_t lds = gnn::train_small_bwd_lds<SQ>(local, true);
+    static const gnn::TypeTab y{};
+    static const gnn::TypeConsts c{};
+    if (ba.dz_out || ba.g0_out) {
+        if (local) return has_w ? launch_persistent(&gnn::k_train_small_bwd<SQ, true, true, true, true>, ba, tt, n_wg, lds, st, y, c)
+                                : launch_persistent(&gnn::k_train_small_bwd<SQ, false, true, true, true>, ba, tt, n_wg, lds, st, y, c);
+        return has_w ? launch_persistent(&gnn::k_train_small_bwd<SQ, true, false, true, true>, ba, tt, n_wg, lds, st, y, c)
+                     : launch_persistent(&gnn::k_train_small_bwd<SQ, false, false, true, true>, ba, tt, n_wg, lds, st, y, c);
+    }
+    if (local) return has_w ? launch_persistent(&gnn::k_train_small_bwd<SQ, true, true, false, true>, ba, tt, n_wg, lds, st, y, c)
+                            : launch_persistent(&gnn::k_train_small_bwd<SQ, false, true, false, true>, ba, tt, n_wg, lds, st, y, c);
+    return has_w ? launch_persistent(&gnn::k_train_small_bwd<SQ, true, false, false, true>, ba, tt, n_wg, lds, st, y, c)
+                 : launch_persistent(&gnn::k_train_small_bwd<SQ, false, false, false, true>, ba, tt, n_wg, lds, st, y, c);
+}
+
 // the per-workgroup partials [grid][K H + H] of a first layer's P = X^T dZ | q summed into x.P / x.q, then its parameter gradients (and the
 // BatchNorm input-gradient moments m1 / m2) over M rows; `centred`: the rows arrived centred (P is P - mean q^T)
 int first_layer_grads(const NetCtx &x, const float *part, int grid, int M, const float *stats, bool accumulate, bool centred, hipStream_t st) {
@@ -904,7 +950,8 @@ int check_step_args(const gnn_train_args_t &ta, const StepPlan &p, bool own_loss
     return 0;
 }
 
-// the common fields of the persistent forward launch and the instance for the padded width (`fa`: zeroed, the caller's own fields set)
+// the common fields of the persistent forward launch and the instance for the padded width (`fa`: zeroed, the caller's own fields set;
+// p.hid_small: `fa` / `ba` below ARE the hidden-layer blocks TrainSmallFwdH / TrainSmallBwdH - forward_small / backward_small make them)
 int launch_train_small_fwd(gnn::TrainSmallFwd &fa, const gnn_train_args_t &ta, const StepPlan &p, const gnn::TileTab &tiles, const gnn::TypeTab *yt, hipStream_t st) {
     const gnn_csr_t &ad = ta.loop.adjacency;
     fa.N = p.N; fa.S = p.SPs; fa.Sw = p.S; fa.K = p.K;
@@ -913,6 +960,10 @@ int launch_train_small_fwd(gnn::TrainSmallFwd &fa, const gnn_train_args_t &ta, c
     fa.Cc = p.sm_cc; fa.thr = ta.loop.state_threshold; fa.flag0 = p.flags;
     fa.bar = p.sm_bar; fa.part = p.sm_part; fa.k_out = p.k_dev; fa.wait_ticks = gnn::wait_ticks();
     if (const char *e = getenv("GNN_DEBUG_FAIL_FWD")) { if (e[0] == '1') fa.wait_ticks = 0; }      // (test hook: every barrier wait of THIS forward launch expires at once)
+    if (p.hid_small) {
+        const auto hid = p.SPs == 16 ? launch_train_small_fwd_hid_sq<1> : launch_train_small_fwd_hid_sq<2>;      // (the rule: padded widths 16 / 32)
+        return hid(static_cast<const gnn::TrainSmallFwdH &>(fa), tiles, p.n_wg, ad.w != nullptr, st);
+    }
     const auto launch = p.SPs == 16 ? launch_train_small_fwd_sq<1> : p.SPs == 32 ? launch_train_small_fwd_sq<2> : launch_train_small_fwd_sq<4>;
     return launch(fa, tiles, p.n_wg, ad.w != nullptr, st, yt);
 }
@@ -929,6 +980,10 @@ int launch_train_small_bwd(gnn::TrainSmallBwd &ba, const gnn_train_args_t &ta, c
     ba.G0 = p.G_state; ba.bar = p.sm_bar + 2; ba.part = p.sm_part;
     ba.inv_n = 1.0f / (float)p.N; ba.err = p.k_dev; ba.wait_ticks = gnn::wait_ticks();
     if (const char *e = getenv("GNN_DEBUG_FAIL_BWD")) { if (e[0] == '1') ba.wait_ticks = 0; }      // (test hook: every barrier wait of THIS launch expires at once)
+    if (p.hid_small) {
+        const auto hid = p.SPs == 16 ? launch_train_small_bwd_hid_sq<1> : launch_train_small_bwd_hid_sq<2>;
+        return hid(static_cast<const gnn::TrainSmallBwdH &>(ba), tiles, p.n_wg, ba.w_s != nullptr, st);
+    }
     const auto launch = p.SPs == 16 ? launch_train_small_bwd_sq<1> : p.SPs == 32 ? launch_train_small_bwd_sq<2> : launch_train_small_bwd_sq<4>;
     return launch(ba, tiles, p.n_wg, ba.w_s != nullptr, st, yt, yc);
 }
@@ -1213,13 +1268,14 @@ int forward_small(const gnn_train_args_t &ta, TrainPlan &p, const gnn::TileTab &
     const gnn_loop_args_t &a = ta.loop;
     const gnn_mlp_t &ns = a.net_state[0];
     const float *gamma = ns.has_bn ? ns.bn_gamma : nullptr;
-    gnn::k_train_small_const<<<cdiv(p.N * p.SPs, 256), 256, 0, st>>>(p.N, p.SPs, p.S, const_segs_of(a, p), ns.kernel[0], ns.bias[0], gamma, ns.bn_beta, p.stats_tpl,
+    gnn::k_train_small_const<<<cdiv(p.N * p.SPs, 256), 256, 0, st>>>(p.N, p.SPs, p.H1s, const_segs_of(a, p), ns.kernel[0], ns.bias[0], gamma, ns.bn_beta, p.stats_tpl,
                                                                    p.stats_tpl + p.in_s, ns.bn_eps, p.sm_cc);
     LAUNCH_OK();
     HIP_OK(hipMemsetAsync(p.sm_bar, 0, sizeof(unsigned long long) * 4, st));
-    gnn::TrainSmallFwd fa{};
+    gnn::TrainSmallFwdH fa{};      // (the one-layer launch takes its base part)
     fa.stats = p.stats_s; fa.in_s = p.in_s; fa.off_agg = p.off_agg;
     fa.W = ns.kernel[0]; fa.gamma = gamma; fa.beta = ns.bn_beta; fa.eps = ns.bn_eps; fa.act = ns.activation[0];
+    if (p.hid_small) { fa.Hw = p.H1s; fa.W2 = ns.kernel[1]; fa.b2 = ns.bias[1]; fa.act2 = ns.activation[1]; fa.hid = p.sm_hid; }
     return launch_train_small_fwd(fa, ta, p, tiles, nullptr, st);
 }
 
@@ -1290,16 +1346,22 @@ int head_label_bn_grads(const gnn_train_args_t &ta, const TrainPlan &p, const He
 // Small graphs: one persistent launch, then every workgroup's [kernel | bias] (and [d gamma | d beta]) share summed in workgroup order
 int backward_small(const gnn_train_args_t &ta, TrainPlan &p, const gnn::TileTab &tiles, int k, const LabelWants &w, hipStream_t st) {
     const gnn_mlp_t &ns = ta.loop.net_state[0];
-    gnn::TrainSmallBwd ba{};
+    gnn::TrainSmallBwdH ba{};      // (the one-layer launch takes its base part)
     ba.stats = p.stats_s; ba.in_s = p.in_s; ba.off_agg = p.off_agg;
     ba.cs = const_segs_of(ta.loop, p);
     ba.W = ns.kernel[0]; ba.gamma = ns.has_bn ? ns.bn_gamma : nullptr; ba.beta = ns.bn_beta; ba.eps = ns.bn_eps; ba.act = ns.activation[0];
     ba.dxa = p.dx_s_all; ba.partW = p.sm_partW; ba.partBN = p.sm_partBN;
     ba.dz_out = w.lab ? p.dz_sum : nullptr; ba.g0_out = w.g0 ? p.g0 : nullptr;
+    if (p.hid_small) { ba.Hw = p.H1s; ba.W2 = ns.kernel[1]; ba.act2 = ns.activation[1]; ba.hid = p.sm_hid; ba.partW2 = p.sm_partW2; }
     TRY(launch_train_small_bwd(ba, ta, p, k, tiles, nullptr, nullptr, st));
-    const int n = (p.in_s + 1) * p.S;
-    gnn::k_reduce_partials<<<cdiv(n, 64), 256, 0, st>>>(p.sm_partW, p.n_wg, n, ta.grad_state.dkernel[0], 0, 1.0f, p.in_s * p.S, ta.grad_state.dbias[0]);
+    const int n = (p.in_s + 1) * p.H1s;
+    gnn::k_reduce_partials<<<cdiv(n, 64), 256, 0, st>>>(p.sm_partW, p.n_wg, n, ta.grad_state.dkernel[0], 0, 1.0f, p.in_s * p.H1s, ta.grad_state.dbias[0]);
     LAUNCH_OK();
+    if (p.hid_small) {          // the second layer's shares, in workgroup order like the first's
+        const int n2 = (p.H1s + 1) * p.S;
+        gnn::k_reduce_partials<<<cdiv(n2, 64), 256, 0, st>>>(p.sm_partW2, p.n_wg, n2, ta.grad_state.dkernel[1], 0, 1.0f, p.H1s * p.S, ta.grad_state.dbias[1]);
+        LAUNCH_OK();
+    }
     if (ns.has_bn) {
         gnn::k_reduce_partials<<<cdiv(2 * p.in_s, 64), 256, 0, st>>>(p.sm_partBN, p.n_wg, 2 * p.in_s, ta.grad_state.dgamma, 0, 1.0f, p.in_s, ta.grad_state.dbeta);
         LAUNCH_OK();
@@ -1565,7 +1627,7 @@ static int train_step_impl(const gnn_train_args_t &ta, const gnn_train_phase_arg
     TRY(check_step_args(ta, p, !fwd_only && phase != GNN_TRAIN_PHASE_FORWARD && !no_loss, !fwd_only && phase != GNN_TRAIN_PHASE_FORWARD));
     const gnn_mlp_t &ns = a.net_state[0], &no = a.net_output;
     hipStream_t st = (hipStream_t)a.stream;
-    GNN_SET_KERNEL_NAME(big ? "train_step: row-streaming kernels (kernels_train_big.hpp)" : small ? "train_step: persistent small-graph kernels" : "train_step: general kernels");
+    GNN_SET_KERNEL_NAME(big ? "train_step: row-streaming kernels (kernels_train_big.hpp)" : p.hid_small ? "train_step: persistent small-graph kernels (hidden layer)" : small ? "train_step: persistent small-graph kernels" : "train_step: general kernels");
     gnn::TileTab tiles;
     TRY(tile_table(ta, p, tiles));
     if (!fwd_only && ta.grads_ok_dev) *ta.grads_ok_dev = p.grads_ok;

@@ -46,7 +46,16 @@ enum gnn_flags {
      * the size-based choice when it does not apply).  Results are the same within float32
      * summation order; the GNN_FUSED_KERNEL environment variable has the same effect process-wide. */
     GNN_FLAG_FUSED_GEN2 = 2 << 4, GNN_FLAG_FUSED_GEN4 = 4 << 4,
-    GNN_FLAG_FUSED_GEN5 = 5 << 4, GNN_FLAG_FUSED_GEN6 = 6 << 4, GNN_FLAG_FUSED_GEN7 = 7 << 4, GNN_FLAG_FUSED_GEN_MASK = 7 << 4
+    GNN_FLAG_FUSED_GEN5 = 5 << 4, GNN_FLAG_FUSED_GEN6 = 6 << 4, GNN_FLAG_FUSED_GEN7 = 7 << 4, GNN_FLAG_FUSED_GEN_MASK = 7 << 4,
+    /* Training steps only (read from gnn_train_args_t::loop.flags by gnn_train_step / gnn_train_step_ex and the functions that plan
+     * for them; the forward loop ignores it).  Opt-in: a homogeneous model whose state network is Dense(H) - Dense(state width) runs
+     * the persistent small-graph training kernels in their hidden-layer form - all iterations of a sweep in one launch - when
+     * 1 <= H <= the padded state width (16 / 32 / 64), neither activation is softmax and every condition of the one-layer persistent
+     * path holds (no Dropout in the state network, max_iteration >= 1, at most 32 constant input columns, fewer nodes than the
+     * row-streaming threshold, every tile resident, neighbour sums AND hidden rows within the tape budget).  Every other shape plans,
+     * routes and computes as without the flag; gnn_last_kernel_name() then says "train_step: persistent small-graph kernels (hidden
+     * layer)".  Without the flag such a network trains on the general kernels (one launch per layer and iteration). */
+    GNN_FLAG_TRAIN_HIDDEN_SMALL = 1 << 8
 };
 
 /* A sparse operator A (n_src x n_dst, COO in the reference: tf.SparseTensor) stored as the CSR of its transpose:
