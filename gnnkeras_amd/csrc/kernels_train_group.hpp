@@ -20,6 +20,9 @@
 //   k_bn_moving_groups    the ordered part: moving <- 0.99 moving + 0.01 batch, group after group, iteration after iteration - the literal
 //                         recurrence, one thread per column
 // A forward keeps no tape: the workspace is O(N S) (Cc, parked neighbour sums) plus the statistics slots [G][K][2 in_s].
+//
+// The body of k_train_group_fwd is written as tg_* pieces (LDS carve, prologue, tile statistics, normalisation, dense update, epilogue)
+// that k_train_group_fwd_types (kernels_train_group_types.hpp: one state network per node type) is made of as well.
 #pragma once
 #include "kernels_train_small.hpp"
 
@@ -96,20 +99,32 @@ k_train_group_const(const int *__restrict__ gbeg, int S, int Sw, ConstSegs cs, c
 }
 
 // ---- the loop -------------------------------------------------------------------------------------------------------------------------------
-struct TrainGroupFwd {
+// What k_train_group_fwd and k_train_group_fwd_types (kernels_train_group_types.hpp) are both made of: the tg_* pieces below.  The two kernels
+// differ in which rows a tile holds (a contiguous range of the group, or a type's row list), in which network is current, and in the
+// compile-time FORM of each side:
+//     WREG               the weight block sits in registers (SQ <= 2) - otherwise every product re-reads it from LDS
+//     NORM_WITHOUT_BN    a network without BatchNormalization still runs the normalisation, with a = 1, c = 0, mean = 0 - otherwise it is skipped
+//     DIVIDE_BY_ROWS     mean = S1 / rows - otherwise S1 * (1 / rows)
+// Each kernel keeps the form it has always had: the results are the same bits as before the pieces were shared.
+struct TrainGroupFormRange { static constexpr bool NORM_WITHOUT_BN = false, DIVIDE_BY_ROWS = false; template <int SQ> static constexpr bool WREG = SQ <= 2; };
+struct TrainGroupFormTypes { static constexpr bool NORM_WITHOUT_BN = true, DIVIDE_BY_ROWS = true; template <int SQ> static constexpr bool WREG = false; };
+
+struct TrainGroupCommon {        // the fields both argument structs share
     int S, Sw, K;                // S = padded width (16 SQ), Sw the state's real width
     const int *rowptr, *src; const float *w, *row_scale;       // adjacency by destination (merged graph)
     const int *gbeg;             // DEVICE [G + 1]
     const float *state0; int ld0;// [N][ld0]: state_0 in the first Sw columns
     float *state_out;            // [N][Sw]
-    float *agg;                  // [N][S] parked neighbour sums (groups of more than one tile); written and read by the owning workgroup only
+    float *agg;                  // [N][S] parked neighbour sums; written and read by the owning workgroup only
+    const float *Cc;             // [N][S]
+    float thr;
+    float *k_groups;             // [G]: iterations executed; -1: an arc leaves the group (every result of the group is invalid)
+};
+struct TrainGroupFwd : TrainGroupCommon {
     float *stats;                // [G][K][2 in_s]
     int in_s, off_agg;
     const float *W, *gamma, *beta; float eps;
     int act;
-    const float *Cc;             // [N][S]
-    float thr;
-    float *k_groups;             // [G]: iterations executed; -1: an arc leaves the group (every result of the group is invalid)
 };
 
 template <int SQ>
@@ -118,37 +133,34 @@ inline size_t train_group_fwd_lds(int rows) {          // rows = the largest gro
     return sizeof(float) * (64 * (2 * S + 4) + (2 * S) * (S + 4) + 3 * 2 * S + 512 + 4 * S + (size_t)rows * (S + 4));
 }
 
-template <int SQ, bool HAS_W>
-__global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd(TrainGroupFwd a) {
-    using Csr = TileCsr<SQ, HAS_W, true>;
-    constexpr int S = 16 * SQ, LPR = S / 4, NPP = Csr::NPP, NPASS = Csr::NPASS;
-    constexpr int LDX = 2 * S + 4, LDW = S + 4, LDS_ST = S + 4;
-    extern __shared__ __attribute__((aligned(16))) float tg_smem[];
-    float *Xs = tg_smem;                  // [64][LDX]  [own | agg] of the current tile
-    float *W0 = Xs + 64 * LDX;            // [2 S][LDW]
-    float *st_a = W0 + 2 * S * LDW;       // [2 S] a_k | beta_k | column means | reduction scratch [512] | tile sums [4 S]
-    float *st_c = st_a + 2 * S, *piv = st_c + 2 * S, *red = piv + 2 * S, *fin = red + 512;
-    float *St = fin + 4 * S;              // [ng][LDS_ST] the group's state
+// the LDS of a workgroup in the order of train_group_fwd_lds: everything but the state, which follows at rest()
+template <int SQ>
+struct TrainGroupLds {
+    static constexpr int S = 16 * SQ, LDX = 2 * S + 4, LDW = S + 4, LDS_ST = S + 4;
+    float *Xs;                   // [64][LDX]  [own | agg] of the current tile
+    float *W0;                   // [2 S][LDW] the current network's state / agg weight rows
+    float *st_a, *st_c, *piv;    // [2 S] each: a_k | beta_k | column means
+    float *red, *fin;            // reduction scratch [512] | tile sums [4 S]
+    __device__ __forceinline__ explicit TrainGroupLds(float *smem)
+        : Xs(smem), W0(Xs + 64 * LDX), st_a(W0 + 2 * S * LDW), st_c(st_a + 2 * S), piv(st_c + 2 * S), red(piv + 2 * S), fin(red + 512) {}
+    __device__ __forceinline__ float *rest() const { return fin + 4 * S; }
+};
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int c = lane & 15, g = lane >> 4;
-    const int gi = blockIdx.x;
-    const int n0 = a.gbeg[gi], ng = a.gbeg[gi + 1] - n0;
-    if (ng < 1 || ng > GROUP_CAP) {       // (the host never launches such a table)
-        if (tid == 0) a.k_groups[gi] = -2.0f;
-        return;
-    }
-    const int ntiles = (ng + 63) / 64;
-    const bool single = ntiles == 1;
-    const bool bn = a.gamma != nullptr;
-    const double inv_rows = 1.0 / (double)ng;
-
+// the [2 S][LDW] weight block of one network: its state rows, then its neighbour-sum rows
+template <int SQ>
+__device__ __forceinline__ void tg_load_weights(float *W0, const float *W, int off_state, int off_agg, int Sw, int tid) {
+    constexpr int S = 16 * SQ, LDW = S + 4;
     for (int i = tid; i < 2 * S * S; i += TS_NT) {
         const int k = i / S, h = i % S;
         const int kk = k < S ? k : k - S;
-        W0[k * LDW + h] = (kk < a.Sw && h < a.Sw) ? a.W[(size_t)((k < S ? 0 : a.off_agg) + kk) * a.Sw + h] : 0.0f;
+        W0[k * LDW + h] = (kk < Sw && h < Sw) ? W[(size_t)((k < S ? off_state : off_agg) + kk) * Sw + h] : 0.0f;
     }
-    if (tid < 2 * S) { piv[tid] = 0.0f; st_a[tid] = 1.0f; st_c[tid] = 0.0f; }
+}
+
+// state_0 of the group into LDS; whether the loop runs at all
+template <int SQ>
+__device__ __forceinline__ bool tg_prologue(const TrainGroupCommon &a, float *St, int n0, int ng, int tid) {
+    constexpr int LDS_ST = 16 * SQ + 4;
     for (int i = tid; i < ng * LDS_ST; i += TS_NT) {
         const int r = i / LDS_ST, h = i % LDS_ST;
         St[i] = h < a.Sw ? a.state0[(size_t)(n0 + r) * a.ld0 + h] : 0.0f;
@@ -161,9 +173,153 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd(TrainGroupFwd a) {
         for (int h = 0; h < a.Sw; ++h) { const float d = St[r * LDS_ST + h] - 1.0f; d2 = fmaf(d, d, d2); }
         if (sqrtf(d2) > a.thr * sqrtf((float)a.Sw)) any0 = 1;
     }
-    const bool run = __syncthreads_or(any0) != 0;
+    return __syncthreads_or(any0) != 0;
+}
 
-    constexpr bool WREG = SQ <= 2;
+// the tile in Xs (nr rows) adds its share to the column sums S1 / S2 of thread tid < 2 S: float32 sums around the tile's first row, moved
+// to the origin and added in double (merge_tile_stats)
+template <int SQ>
+__device__ __forceinline__ void tg_tile_stats(const TrainGroupLds<SQ> &L, int nr, int tid, double &S1, double &S2) {
+    constexpr int S = 16 * SQ, LDX = 2 * S + 4;
+    const int col = tid & (2 * S - 1), part_i = tid / (2 * S);
+    constexpr int NG = TS_NT / (2 * S), RPG = 64 / NG;
+    float s1 = 0.0f, s2 = 0.0f;
+    const float pv = L.Xs[col];
+    float xr[RPG];
+#pragma unroll
+    for (int u = 0; u < RPG; ++u) xr[u] = L.Xs[(part_i * RPG + u) * LDX + col];
+#pragma unroll
+    for (int u = 0; u < RPG; ++u) {
+        const float x = part_i * RPG + u < nr ? xr[u] - pv : 0.0f;
+        s1 += x; s2 = fmaf(x, x, s2);
+    }
+    L.red[part_i * 4 * S + col] = s1; L.red[part_i * 4 * S + 2 * S + col] = s2;
+    __syncthreads();
+    if (tid < 4 * S) {
+        float tt = 0.0f;
+#pragma unroll
+        for (int gq = 0; gq < NG; ++gq) tt += L.red[gq * 4 * S + tid];
+        L.fin[tid] = tt;
+    }
+    __syncthreads();
+    if (tid < 2 * S) {
+        const double nj = (double)nr, p_ = (double)L.Xs[tid], a1 = (double)L.fin[tid];
+        S1 += a1 + nj * p_;
+        S2 += (double)L.fin[2 * S + tid] + p_ * (2.0 * a1 + nj * p_);
+    }
+}
+
+// S1 / S2 over `rows` rows -> the normalisation st_a (x - piv) + st_c of the current network, and the iteration's statistics slot `sl`
+// [2 in_dim].  Column tid < S is weight row off_state + tid, column S + kk weight row off_agg + kk.
+template <int SQ, class Form>
+__device__ __forceinline__ void tg_set_norm(const TrainGroupLds<SQ> &L, bool bn, double S1, double S2, int rows, int Sw, int off_state, int off_agg,
+                                            const float *gamma, const float *beta, float eps, float *sl, int in_dim, int tid) {
+    constexpr int S = 16 * SQ;
+    if (!Form::NORM_WITHOUT_BN && !bn) return;
+    if (tid < 2 * S) {
+        const int kk = tid < S ? tid : tid - S;
+        float ak = bn ? 0.0f : 1.0f, ck = 0.0f, mu = 0.0f;
+        if (bn && kk < Sw) {
+            const int k = (tid < S ? off_state : off_agg) + kk;
+            const double inv_rows = 1.0 / (double)rows;
+            const double mean = Form::DIVIDE_BY_ROWS ? S1 / (double)rows : S1 * inv_rows;
+            mu = (float)mean;
+            const float va = (float)fmax((Form::DIVIDE_BY_ROWS ? S2 / (double)rows : S2 * inv_rows) - mean * mean, 0.0);
+            ak = gamma[k] / sqrtf(va + eps); ck = beta[k];
+            sl[k] = mu; sl[in_dim + k] = va;
+        }
+        L.st_a[tid] = ak; L.st_c[tid] = ck; L.piv[tid] = mu;
+    }
+}
+
+// The dense update of the tile in Xs: (a (x - mean) + beta) . W + Cc on v_mfma_f32_16x16x4_f32 (operand layout of k_train_small_fwd),
+// activation, predicate; this lane's row (row 16 wave + c of the tile, `oin`: it is a row) goes back into the LDS state at row lrow of the
+// group - in place: it depends on the same row of the old state only.
+template <int SQ, class Form>
+__device__ __forceinline__ void tg_dense_tile(const TrainGroupLds<SQ> &L, float *St, const float (&wreg)[Form::template WREG<SQ> ? 2 * SQ : 1][4][SQ],
+                                              const TrainGroupCommon &a, int n0, int lrow, bool oin, bool bn, int act, int wave, int c, int g, int &any) {
+    constexpr int S = 16 * SQ, LDX = 2 * S + 4, LDW = S + 4, LDS_ST = S + 4;
+    constexpr bool WREG = Form::template WREG<SQ>;
+    f32x4 acc[SQ];
+#pragma unroll
+    for (int ct = 0; ct < SQ; ++ct)
+        acc[ct] = oin ? *reinterpret_cast<const f32x4 *>(a.Cc + (size_t)(n0 + lrow) * S + 16 * ct + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    const float *xrow = L.Xs + (16 * wave + c) * LDX + 4 * g;
+#pragma unroll
+    for (int qq = 0; qq < 2 * S / 16; ++qq) {
+        f32x4 xv = *reinterpret_cast<const f32x4 *>(xrow + 16 * qq);
+        if (Form::NORM_WITHOUT_BN || bn) {
+            const f32x4 av = *reinterpret_cast<const f32x4 *>(L.st_a + 16 * qq + 4 * g), cv = *reinterpret_cast<const f32x4 *>(L.st_c + 16 * qq + 4 * g);
+            const f32x4 mv = *reinterpret_cast<const f32x4 *>(L.piv + 16 * qq + 4 * g);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) xv[e] = fmaf(xv[e] - mv[e], av[e], cv[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float *wr = L.W0 + (16 * qq + 4 * g + e) * LDW + c;
+#pragma unroll
+            for (int ct = 0; ct < SQ; ++ct)
+                acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(WREG ? wreg[WREG ? qq : 0][e][ct] : wr[16 * ct], xv[e], acc[ct], 0, 0, 0);
+        }
+    }
+    asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");          // (MFMA results consumed behind a branch: see kernels_train_big.hpp)
+    float d2 = 0.0f, n2 = 0.0f;
+    const float *old_lds = L.Xs + (16 * wave + c) * LDX + 4 * g;
+    float *new_lds = St + lrow * LDS_ST + 4 * g;
+#pragma unroll
+    for (int ct = 0; ct < SQ; ++ct) {
+        f32x4 v = acc[ct];
+        activate4(act, v);
+        const f32x4 o = *reinterpret_cast<const f32x4 *>(old_lds + 16 * ct);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { v[e] = (oin && 16 * ct + 4 * g + e < a.Sw) ? v[e] : 0.0f; const float d = v[e] - o[e]; d2 = fmaf(d, d, d2); n2 = fmaf(o[e], o[e], n2); }
+        if (oin) *reinterpret_cast<f32x4 *>(new_lds + 16 * ct) = v;
+    }
+    d2 += __shfl_xor(d2, 16, 64); d2 += __shfl_xor(d2, 32, 64);
+    n2 += __shfl_xor(n2, 16, 64); n2 += __shfl_xor(n2, 32, 64);
+    if (oin && sqrtf(d2) > a.thr * sqrtf(n2)) any = 1;
+}
+
+// the group's state and its k go out; `csr_bad`: this thread met an arc that leaves the group
+template <int SQ>
+__device__ __forceinline__ void tg_epilogue(const TrainGroupCommon &a, const float *St, int csr_bad, int k_done, int gi, int n0, int ng, int tid) {
+    constexpr int LDS_ST = 16 * SQ + 4;
+    const int bad = __syncthreads_or(csr_bad);
+    for (int i = tid; i < ng * a.Sw; i += TS_NT) {
+        const int r = i / a.Sw, h = i % a.Sw;
+        a.state_out[(size_t)(n0 + r) * a.Sw + h] = St[r * LDS_ST + h];
+    }
+    if (tid == 0) a.k_groups[gi] = bad ? -1.0f : (float)k_done;
+}
+
+template <int SQ, bool HAS_W>
+__global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd(TrainGroupFwd a) {
+    using Csr = TileCsr<SQ, HAS_W, true>;
+    using Form = TrainGroupFormRange;
+    constexpr int S = 16 * SQ, LPR = S / 4, NPP = Csr::NPP, NPASS = Csr::NPASS;
+    constexpr int LDX = 2 * S + 4, LDW = S + 4, LDS_ST = S + 4;
+    extern __shared__ __attribute__((aligned(16))) float tg_smem[];
+    const TrainGroupLds<SQ> L(tg_smem);
+    float *Xs = L.Xs, *W0 = L.W0;
+    float *St = L.rest();                 // [ng][LDS_ST] the group's state
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = lane & 15, g = lane >> 4;
+    const int gi = blockIdx.x;
+    const int n0 = a.gbeg[gi], ng = a.gbeg[gi + 1] - n0;
+    if (ng < 1 || ng > GROUP_CAP) {       // (the host never launches such a table)
+        if (tid == 0) a.k_groups[gi] = -2.0f;
+        return;
+    }
+    const int ntiles = (ng + 63) / 64;
+    const bool single = ntiles == 1;
+    const bool bn = a.gamma != nullptr;
+
+    tg_load_weights<SQ>(W0, a.W, 0, a.off_agg, a.Sw, tid);
+    if (tid < 2 * S) { L.piv[tid] = 0.0f; L.st_a[tid] = 1.0f; L.st_c[tid] = 0.0f; }
+    const bool run = tg_prologue<SQ>(a, St, n0, ng, tid);
+
+    constexpr bool WREG = Form::WREG<SQ>;
     float wreg[WREG ? 2 * S / 16 : 1][4][SQ];
     if (WREG) {
 #pragma unroll
@@ -199,51 +355,9 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd(TrainGroupFwd a) {
                 if (!single && rr < nr) *reinterpret_cast<f32x4 *>(a.agg + (size_t)(n0 + r0 + rr) * S + 4 * l4) = acc[p];
             }
             __syncthreads();
-            if (bn) {
-                const int col = tid & (2 * S - 1), part_i = tid / (2 * S);
-                constexpr int NG = TS_NT / (2 * S), RPG = 64 / NG;
-                float s1 = 0.0f, s2 = 0.0f;
-                const float pv = Xs[col];
-                float xr[RPG];
-#pragma unroll
-                for (int u = 0; u < RPG; ++u) xr[u] = Xs[(part_i * RPG + u) * LDX + col];
-#pragma unroll
-                for (int u = 0; u < RPG; ++u) {
-                    const float x = part_i * RPG + u < nr ? xr[u] - pv : 0.0f;
-                    s1 += x; s2 = fmaf(x, x, s2);
-                }
-                red[part_i * 4 * S + col] = s1; red[part_i * 4 * S + 2 * S + col] = s2;
-                __syncthreads();
-                if (tid < 4 * S) {
-                    float tt = 0.0f;
-#pragma unroll
-                    for (int gq = 0; gq < NG; ++gq) tt += red[gq * 4 * S + tid];
-                    fin[tid] = tt;
-                }
-                __syncthreads();
-                if (tid < 2 * S) {        // the tile's share moved to the origin and added in double (merge_tile_stats)
-                    const double nj = (double)nr, p_ = (double)Xs[tid], a1 = (double)fin[tid];
-                    S1 += a1 + nj * p_;
-                    S2 += (double)fin[2 * S + tid] + p_ * (2.0 * a1 + nj * p_);
-                }
-            }
+            if (bn) tg_tile_stats<SQ>(L, nr, tid, S1, S2);
         }
-        if (bn) {
-            if (tid < 2 * S) {
-                const int kk = tid < S ? tid : tid - S;
-                float ak = 0.0f, ck = 0.0f, mu = 0.0f;
-                if (kk < a.Sw) {
-                    const int k = (tid < S ? 0 : a.off_agg) + kk;
-                    const double mean = S1 * inv_rows;
-                    mu = (float)mean;
-                    const float va = (float)fmax(S2 * inv_rows - mean * mean, 0.0);
-                    ak = a.gamma[k] / sqrtf(va + a.eps); ck = a.beta[k];
-                    float *sl = a.stats + ((size_t)gi * a.K + it) * 2 * a.in_s;
-                    sl[k] = mu; sl[a.in_s + k] = va;
-                }
-                st_a[tid] = ak; st_c[tid] = ck; piv[tid] = mu;
-            }
-        }
+        tg_set_norm<SQ, Form>(L, bn, S1, S2, ng, a.Sw, 0, a.off_agg, a.gamma, a.beta, a.eps, a.stats + ((size_t)gi * a.K + it) * 2 * a.in_s, a.in_s, tid);
         __syncthreads();
         // ---- pass 2: (a (x - mean) + beta) . W + Cc, activation, predicate; the new rows replace the old ones in the LDS state -----------------
         int any = 0;
@@ -265,56 +379,12 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd(TrainGroupFwd a) {
                 }
                 __syncthreads();
             }
-            const bool oin = 16 * wave + c < nr;
-            const int orow = n0 + r0 + 16 * wave + c;
-            f32x4 acc[SQ];
-#pragma unroll
-            for (int ct = 0; ct < SQ; ++ct)
-                acc[ct] = oin ? *reinterpret_cast<const f32x4 *>(a.Cc + (size_t)orow * S + 16 * ct + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
-            const float *xrow = Xs + (16 * wave + c) * LDX + 4 * g;
-#pragma unroll
-            for (int qq = 0; qq < 2 * S / 16; ++qq) {
-                f32x4 xv = *reinterpret_cast<const f32x4 *>(xrow + 16 * qq);
-                if (bn) {
-                    const f32x4 av = *reinterpret_cast<const f32x4 *>(st_a + 16 * qq + 4 * g), cv = *reinterpret_cast<const f32x4 *>(st_c + 16 * qq + 4 * g);
-                    const f32x4 mv = *reinterpret_cast<const f32x4 *>(piv + 16 * qq + 4 * g);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) xv[e] = fmaf(xv[e] - mv[e], av[e], cv[e]);
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float *wr = W0 + (16 * qq + 4 * g + e) * LDW + c;
-#pragma unroll
-                    for (int ct = 0; ct < SQ; ++ct)
-                        acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(WREG ? wreg[WREG ? qq : 0][e][ct] : wr[16 * ct], xv[e], acc[ct], 0, 0, 0);
-                }
-            }
-            asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");          // (MFMA results consumed behind a branch: see kernels_train_big.hpp)
-            float d2 = 0.0f, n2 = 0.0f;
-            const float *old_lds = Xs + (16 * wave + c) * LDX + 4 * g;
-            float *new_lds = St + (r0 + 16 * wave + c) * LDS_ST + 4 * g;
-#pragma unroll
-            for (int ct = 0; ct < SQ; ++ct) {
-                f32x4 v = acc[ct];
-                activate4(a.act, v);
-                const f32x4 o = *reinterpret_cast<const f32x4 *>(old_lds + 16 * ct);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { v[e] = (oin && 16 * ct + 4 * g + e < a.Sw) ? v[e] : 0.0f; const float d = v[e] - o[e]; d2 = fmaf(d, d, d2); n2 = fmaf(o[e], o[e], n2); }
-                if (oin) *reinterpret_cast<f32x4 *>(new_lds + 16 * ct) = v;
-            }
-            d2 += __shfl_xor(d2, 16, 64); d2 += __shfl_xor(d2, 32, 64);
-            n2 += __shfl_xor(n2, 16, 64); n2 += __shfl_xor(n2, 32, 64);
-            if (oin && sqrtf(d2) > a.thr * sqrtf(n2)) any = 1;
+            tg_dense_tile<SQ, Form>(L, St, wreg, a, n0, r0 + 16 * wave + c, 16 * wave + c < nr, bn, a.act, wave, c, g, any);
         }
         k_done = it + 1;
         if (!__syncthreads_or(any)) break;        // (also: the new state is complete before the next gather)
     }
-    const int bad = __syncthreads_or(csr.bad);
-    for (int i = tid; i < ng * a.Sw; i += TS_NT) {
-        const int r = i / a.Sw, h = i % a.Sw;
-        a.state_out[(size_t)(n0 + r) * a.Sw + h] = St[r * LDS_ST + h];
-    }
-    if (tid == 0) a.k_groups[gi] = bad ? -1.0f : (float)k_done;
+    tg_epilogue<SQ>(a, St, csr.bad, k_done, gi, n0, ng, tid);
 }
 
 // ---- output head ----------------------------------------------------------------------------------------------------------------------------

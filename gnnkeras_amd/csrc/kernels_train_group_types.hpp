@@ -16,6 +16,8 @@
 //                               sums of pass 1: no gather ever sees a new row of the running iteration.
 // The weight block [2 S][S + 4] of the CURRENT type is (re)loaded from L2 when the walk moves to another type with rows in the group: one block
 // fits next to a 256-row state at width 64 (138 KB), eight do not.  A group whose rows are all of one type loads it once.
+// The tile body - statistics, normalisation, dense update - and the prologue / epilogue are the tg_* pieces of kernels_train_group.hpp in
+// this kernel's form (TrainGroupFormTypes); what is written here is the walk: which rows a tile holds and which network is current.
 #pragma once
 #include "kernels_train_group.hpp"
 #include "kernel_state_lds_types.hpp"
@@ -98,18 +100,10 @@ __global__ void __launch_bounds__(256) k_train_group_const_types(TrainGroupConst
 }
 
 // ---- the loop -------------------------------------------------------------------------------------------------------------------------------
-struct TrainGroupFwdTypes {
-    int S, Sw, K, n_types, G;    // S = padded width (16 SQ), Sw the state's real width
-    const int *rowptr, *src; const float *w, *row_scale;       // adjacency by destination (merged graph)
-    const int *gbeg;             // DEVICE [G + 1]
+struct TrainGroupFwdTypes : TrainGroupCommon {
+    int n_types, G;
     const int *tbeg;             // DEVICE [n_types][G + 1] positions in type_nodes
     const int *type_nodes;       // DEVICE node ids per type, ascending
-    const float *state0; int ld0;
-    float *state_out;            // [N][Sw]
-    float *agg;                  // [N][S] parked neighbour sums; written and read by the owning workgroup only
-    const float *Cc;             // [N][S]
-    float thr;
-    float *k_groups;             // [G]
     GroupTypeNet net[GNN_MAX_TYPES];
 };
 
@@ -119,15 +113,14 @@ inline size_t train_group_fwd_types_lds(int rows) { return train_group_fwd_lds<S
 template <int SQ, bool HAS_W>
 __global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd_types(TrainGroupFwdTypes a) {
     using Csr = TileCsr<SQ, HAS_W, true>;
+    using Form = TrainGroupFormTypes;
     constexpr int S = 16 * SQ, LPR = S / 4, NPP = Csr::NPP, NPASS = Csr::NPASS;
-    constexpr int LDX = 2 * S + 4, LDW = S + 4, LDS_ST = S + 4;
+    constexpr int LDX = 2 * S + 4, LDS_ST = S + 4;
     extern __shared__ __attribute__((aligned(16))) float tgt_smem[];
-    float *Xs = tgt_smem;                 // [64][LDX]  [own | agg] of the current tile (rows of ONE type)
-    float *W0 = Xs + 64 * LDX;            // [2 S][LDW] the current type's state / agg weight rows
-    float *st_a = W0 + 2 * S * LDW;       // [2 S] a_k | beta_k | column means | reduction scratch [512] | tile sums [4 S]
-    float *st_c = st_a + 2 * S, *piv = st_c + 2 * S, *red = piv + 2 * S, *fin = red + 512;
-    int *rid = reinterpret_cast<int *>(fin + 4 * S);      // [64] the tile's rows inside the group
-    float *St = fin + 4 * S + 64;         // [ng][LDS_ST] the group's state, by node
+    const TrainGroupLds<SQ> L(tgt_smem);  // (Xs: rows of ONE type; W0: the current type's weight rows)
+    float *Xs = L.Xs;
+    int *rid = reinterpret_cast<int *>(L.rest());         // [64] the tile's rows inside the group
+    float *St = L.rest() + 64;            // [ng][LDS_ST] the group's state, by node
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, g = lane >> 4;
@@ -140,20 +133,9 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd_types(TrainGroupFw
     const int ntiles = (ng + 63) / 64;
     const bool single = ntiles == 1;
 
-    for (int i = tid; i < ng * LDS_ST; i += TS_NT) {
-        const int r = i / LDS_ST, h = i % LDS_ST;
-        St[i] = h < a.Sw ? a.state0[(size_t)(n0 + r) * a.ld0 + h] : 0.0f;
-    }
-    __syncthreads();
-    // the predicate of state_0 against a state of ones (reference GNN.py:256: state_old = ones_like(state))
-    int any0 = 0;
-    for (int r = tid; r < ng; r += TS_NT) {
-        float d2 = 0.0f;
-        for (int h = 0; h < a.Sw; ++h) { const float d = St[r * LDS_ST + h] - 1.0f; d2 = fmaf(d, d, d2); }
-        if (sqrtf(d2) > a.thr * sqrtf((float)a.Sw)) any0 = 1;
-    }
-    const bool run = __syncthreads_or(any0) != 0;
+    const bool run = tg_prologue<SQ>(a, St, n0, ng, tid);
 
+    const float no_wreg[1][4][SQ] = {};   // (Form: the weights are re-read from LDS)
     Csr csr;
     csr.bad = 0;
     if (single) csr.load_rows(n0, ng, n0, ng, a.rowptr, a.src, a.w, a.row_scale);
@@ -186,11 +168,7 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd_types(TrainGroupFw
             // which is all one workgroup's own stores and loads need (one CU, one vector L1); it also retires the previous type's Xs / W0 reads
             __syncthreads();
             if (loaded != ty) {
-                for (int i = tid; i < 2 * S * S; i += TS_NT) {
-                    const int k = i / S, h = i % S;
-                    const int kk = k < S ? k : k - S;
-                    W0[k * LDW + h] = (kk < a.Sw && h < a.Sw) ? net.W[(size_t)((k < S ? net.off_state : net.off_agg) + kk) * a.Sw + h] : 0.0f;
-                }
+                tg_load_weights<SQ>(L.W0, net.W, net.off_state, net.off_agg, a.Sw, tid);
                 loaded = ty;
             }
             auto load_tile = [&](int r0, int nr) {
@@ -214,52 +192,10 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd_types(TrainGroupFw
                 if (t > 0) __syncthreads();                 // (the previous tile's pivots have been read)
                 load_tile(r0, nr);
                 __syncthreads();
-                if (bn) {
-                    const int col = tid & (2 * S - 1), part_i = tid / (2 * S);
-                    constexpr int NG = TS_NT / (2 * S), RPG = 64 / NG;
-                    float s1 = 0.0f, s2 = 0.0f;
-                    const float pv = Xs[col];
-                    float xr[RPG];
-#pragma unroll
-                    for (int u = 0; u < RPG; ++u) xr[u] = Xs[(part_i * RPG + u) * LDX + col];
-#pragma unroll
-                    for (int u = 0; u < RPG; ++u) {
-                        const float x = part_i * RPG + u < nr ? xr[u] - pv : 0.0f;
-                        s1 += x; s2 = fmaf(x, x, s2);
-                    }
-                    red[part_i * 4 * S + col] = s1; red[part_i * 4 * S + 2 * S + col] = s2;
-                    __syncthreads();
-                    if (tid < 4 * S) {
-                        float tt = 0.0f;
-#pragma unroll
-                        for (int gq = 0; gq < NG; ++gq) tt += red[gq * 4 * S + tid];
-                        fin[tid] = tt;
-                    }
-                    __syncthreads();
-                    if (tid < 2 * S) {        // the tile's share moved to the origin and added in double (merge_tile_stats)
-                        const double nj = (double)nr, p_ = (double)Xs[tid], a1 = (double)fin[tid];
-                        S1 += a1 + nj * p_;
-                        S2 += (double)fin[2 * S + tid] + p_ * (2.0 * a1 + nj * p_);
-                    }
-                }
+                if (bn) tg_tile_stats<SQ>(L, nr, tid, S1, S2);
             }
-            if (tid < 2 * S) {
-                const int kk = tid < S ? tid : tid - S;
-                float ak = 1.0f, ck = 0.0f, mu = 0.0f;
-                if (bn) {
-                    ak = 0.0f;
-                    if (kk < a.Sw) {
-                        const int k = (tid < S ? net.off_state : net.off_agg) + kk;
-                        const double mean = S1 / (double)nt;
-                        mu = (float)mean;
-                        const float va = (float)fmax(S2 / (double)nt - mean * mean, 0.0);
-                        ak = net.gamma[k] / sqrtf(va + net.eps); ck = net.beta[k];
-                        float *sl = net.stats + ((size_t)gi * a.K + it) * 2 * net.in_dim;
-                        sl[k] = mu; sl[net.in_dim + k] = va;
-                    }
-                }
-                st_a[tid] = ak; st_c[tid] = ck; piv[tid] = mu;
-            }
+            tg_set_norm<SQ, Form>(L, bn, S1, S2, nt, a.Sw, net.off_state, net.off_agg, net.gamma, net.beta, net.eps,
+                                  net.stats + ((size_t)gi * a.K + it) * 2 * net.in_dim, net.in_dim, tid);
             __syncthreads();
             for (int t = 0; t < ntl; ++t) {
                 const int r0 = 64 * t, nr = min(64, nt - r0);
@@ -268,54 +204,13 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd_types(TrainGroupFw
                     load_tile(r0, nr);
                     __syncthreads();
                 }
-                const bool oin = 16 * wave + c < nr;
-                const int lrow = rid[16 * wave + c];
-                f32x4 acc[SQ];
-#pragma unroll
-                for (int ct = 0; ct < SQ; ++ct)
-                    acc[ct] = oin ? *reinterpret_cast<const f32x4 *>(a.Cc + (size_t)(n0 + lrow) * S + 16 * ct + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
-                const float *xrow = Xs + (16 * wave + c) * LDX + 4 * g;
-#pragma unroll
-                for (int qq = 0; qq < 2 * S / 16; ++qq) {
-                    f32x4 xv = *reinterpret_cast<const f32x4 *>(xrow + 16 * qq);
-                    const f32x4 av = *reinterpret_cast<const f32x4 *>(st_a + 16 * qq + 4 * g), cv = *reinterpret_cast<const f32x4 *>(st_c + 16 * qq + 4 * g);
-                    const f32x4 mv = *reinterpret_cast<const f32x4 *>(piv + 16 * qq + 4 * g);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) xv[e] = fmaf(xv[e] - mv[e], av[e], cv[e]);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float *wr = W0 + (16 * qq + 4 * g + e) * LDW + c;
-#pragma unroll
-                        for (int ct = 0; ct < SQ; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[16 * ct], xv[e], acc[ct], 0, 0, 0);
-                    }
-                }
-                asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");          // (MFMA results consumed behind a branch: see kernels_train_big.hpp)
-                float d2 = 0.0f, n2 = 0.0f;
-                const float *old_lds = Xs + (16 * wave + c) * LDX + 4 * g;
-                float *new_lds = St + lrow * LDS_ST + 4 * g;
-#pragma unroll
-                for (int ct = 0; ct < SQ; ++ct) {
-                    f32x4 v = acc[ct];
-                    activate4(net.act, v);
-                    const f32x4 o = *reinterpret_cast<const f32x4 *>(old_lds + 16 * ct);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { v[e] = (oin && 16 * ct + 4 * g + e < a.Sw) ? v[e] : 0.0f; const float d = v[e] - o[e]; d2 = fmaf(d, d, d2); n2 = fmaf(o[e], o[e], n2); }
-                    if (oin) *reinterpret_cast<f32x4 *>(new_lds + 16 * ct) = v;
-                }
-                d2 += __shfl_xor(d2, 16, 64); d2 += __shfl_xor(d2, 32, 64);
-                n2 += __shfl_xor(n2, 16, 64); n2 += __shfl_xor(n2, 32, 64);
-                if (oin && sqrtf(d2) > a.thr * sqrtf(n2)) any = 1;
+                tg_dense_tile<SQ, Form>(L, St, no_wreg, a, n0, rid[16 * wave + c], 16 * wave + c < nr, bn, net.act, wave, c, g, any);
             }
         }
         k_done = it + 1;
         if (!__syncthreads_or(any)) break;        // (also: the new state is complete before the next gather)
     }
-    const int bad = __syncthreads_or(csr.bad);
-    for (int i = tid; i < ng * a.Sw; i += TS_NT) {
-        const int r = i / a.Sw, h = i % a.Sw;
-        a.state_out[(size_t)(n0 + r) * a.Sw + h] = St[r * LDS_ST + h];
-    }
-    if (tid == 0) a.k_groups[gi] = bad ? -1.0f : (float)k_done;
+    tg_epilogue<SQ>(a, St, csr.bad, k_done, gi, n0, ng, tid);
 }
 
 }  // namespace gnn

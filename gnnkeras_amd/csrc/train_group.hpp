@@ -1,6 +1,8 @@
 // Host side of the grouped training-mode forward (C ABI 10; kernels_train_group.hpp): coverage, group tables, workspace, launches.
 // Included behind train_loop.hpp and train_composite.hpp in gnnloop.hip (shares their plans and helpers).  Heterogeneous models (one state
-// network per node type) take the *_types kernels of kernels_train_group_types.hpp: the second half of this file.
+// network per node type) take the *_types kernels of kernels_train_group_types.hpp.  Each kind has its own plan (workspace carve), coverage
+// rule, constants kernel and argument struct; what the two forwards share exists once, in the first half of this file: the group tables and
+// their upload, the refusals (train_group_checks), the launcher of the forward kernel, the shared argument fields and the output head.
 #pragma once
 #include "kernels_train_group.hpp"
 #include "kernels_train_group_types.hpp"
@@ -9,6 +11,190 @@ namespace {
 
 static_assert(GNN_TRAIN_GROUP_MAX_NODES == gnn::GROUP_CAP, "include/gnnloop.h and kernels_train_group.hpp disagree on the group size");
 
+// ---- both kinds ------------------------------------------------------------------------------------------------------------------------------
+// the host tables: 0 fine, -2 malformed (message set when `say`), g + 1: group g is too large
+int train_group_tables(const gnn_train_args_t &ta, int N, int M, bool say, int *max_nodes) {
+    const int G = ta.n_groups;
+    if (max_nodes) *max_nodes = 0;
+    if (!ta.group_node_begin || !ta.group_out_begin) { if (say) fail("group_node_begin / group_out_begin is NULL"); return GNN_TRAIN_GROUPS_MALFORMED; }
+    if (ta.group_node_begin[0] != 0 || ta.group_node_begin[G] != N) { if (say) fail("group_node_begin must span [0, n_nodes]"); return GNN_TRAIN_GROUPS_MALFORMED; }
+    if (ta.group_out_begin[0] != 0 || ta.group_out_begin[G] != M) { if (say) fail("group_out_begin must span [0, n_out]"); return GNN_TRAIN_GROUPS_MALFORMED; }
+    int too_large = 0, mx = 0;
+    for (int g = 0; g < G; ++g) {
+        const int n = ta.group_node_begin[g + 1] - ta.group_node_begin[g];
+        if (n <= 0) { if (say) fail("group %d is empty or group_node_begin is not ascending", g); return GNN_TRAIN_GROUPS_MALFORMED; }
+        if (ta.group_out_begin[g + 1] < ta.group_out_begin[g]) { if (say) fail("group_out_begin is not ascending at group %d", g); return GNN_TRAIN_GROUPS_MALFORMED; }
+        if (n > gnn::GROUP_CAP && !too_large) too_large = g + 1;
+        mx = std::max(mx, n);
+    }
+    if (max_nodes) *max_nodes = mx;
+    return too_large;
+}
+
+// gnn_train_groups_supported for one kind: its plan from dims alone, its coverage rule, the tables
+template <class Plan, class Make, class Covered>
+int train_groups_supported(const gnn_train_args_t &ta, Make make, Covered covered) {
+    Plan p;
+    if (make(ta, nullptr, p) || !covered(ta, p)) return GNN_TRAIN_GROUPS_UNCOVERED;
+    return train_group_tables(ta, p.N, p.M, false, nullptr);
+}
+
+// Everything a grouped forward refuses before its first launch, in this order.  GP is the kind's group plan (GroupPlan / GroupTypesPlan:
+// p with N, M, E, A; max_nodes; bytes), `make` carves it from ta.tape, `covered` is the kind's coverage rule and `inputs` the kind's own
+// checks of its input arrays (between the arcnode CSR and state0).
+template <class GP, class Make, class Covered, class Inputs>
+int train_group_checks(const gnn_train_args_t &ta, GP &gp, Make make, Covered covered, Inputs inputs) {
+    const gnn_loop_args_t &a = ta.loop;
+    if (!ta.forward_only) return fail("gnn_train_step: convergence groups need forward_only (a grouped training step is not implemented)");
+    if (ta.prev_grads_ok_host) return fail("gnn_train_step(forward_only): prev_grads_ok_host must be NULL");
+    if (ta.n_groups < 0) return fail("n_groups < 0");
+    TRY(make(ta, ta.tape, gp));
+    const auto &p = gp.p;
+    if (!covered(ta, p)) return fail("gnn_train_step: convergence groups do not cover this shape (gnn_train_groups_supported() == %d)", GNN_TRAIN_GROUPS_UNCOVERED);
+    const int tab = train_group_tables(ta, p.N, p.M, true, &gp.max_nodes);
+    if (tab < 0) return 1;
+    if (tab > 0) return fail("group %d has %d nodes (at most %d per convergence group: gnn_train_groups_supported())", tab - 1,
+                             ta.group_node_begin[tab] - ta.group_node_begin[tab - 1], gnn::GROUP_CAP);
+    if (ta.tape_bytes < gp.bytes) return fail("tape too small: %zu < %zu bytes", ta.tape_bytes, gp.bytes);
+    TRY(check_csr(a.adjacency, "adjacency", p.N, p.N));
+    TRY(check_csr(a.arcnode, "arcnode", p.N, p.E));
+    TRY(inputs());
+    if (a.state_dim > 0 && !a.state0) return fail("state0 is required when state_dim > 0");
+    if (p.M > 0 && !a.out_index) return fail("out_index is NULL");
+    if (a.focus == GNN_FOCUS_ARC && p.E > 0 && (!a.arc_src || !a.arc_dst)) return fail("arc focus needs arc_src / arc_dst");
+    if ((p.M > 0 && !ta.y_pred) || !ta.state || !ta.k_groups) return fail("y_pred / state / k_groups is NULL");
+    return 0;
+}
+
+// the group tables go to the device through a pinned staging buffer of this thread; its event says when the previous call's copy has left it
+int upload_group_tables(const gnn_train_args_t &ta, int *gbeg, int *obeg, hipStream_t st) {
+    static thread_local struct { int *buf; size_t cap; hipEvent_t ev; } stage = {nullptr, 0, nullptr};
+    const int G = ta.n_groups;
+    const size_t n_tab = 2 * ((size_t)G + 1);
+    if (stage.ev) HIP_OK(hipEventSynchronize(stage.ev));
+    else HIP_OK(hipEventCreateWithFlags(&stage.ev, hipEventDisableTiming));
+    if (stage.cap < n_tab) {
+        if (stage.buf) HIP_OK(hipHostFree(stage.buf));
+        stage.buf = nullptr; stage.cap = 0;
+        HIP_OK(hipHostMalloc((void **)&stage.buf, std::max<size_t>(n_tab, 4096) * sizeof(int), hipHostMallocDefault));
+        stage.cap = std::max<size_t>(n_tab, 4096);
+    }
+    memcpy(stage.buf, ta.group_node_begin, ((size_t)G + 1) * sizeof(int));
+    memcpy(stage.buf + G + 1, ta.group_out_begin, ((size_t)G + 1) * sizeof(int));
+    HIP_OK(hipMemcpyAsync(gbeg, stage.buf, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(obeg, stage.buf + G + 1, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_OK(hipEventRecord(stage.ev, st));
+    return 0;
+}
+
+// the argument fields both forward kernels read (S = the padded width, Sw the real one)
+void fill_train_group_common(gnn::TrainGroupCommon &fa, const gnn_train_args_t &ta, int S, int Sw, int K, const int *gbeg, float *agg, const float *cc) {
+    const gnn_loop_args_t &a = ta.loop;
+    fa.S = S; fa.Sw = Sw; fa.K = K;
+    fa.rowptr = a.adjacency.rowptr; fa.src = a.adjacency.src; fa.w = a.adjacency.w; fa.row_scale = a.adjacency.row_scale;
+    fa.gbeg = gbeg;
+    fa.state0 = a.state_dim > 0 ? a.state0 : a.nodes; fa.ld0 = a.state_dim > 0 ? Sw : a.ld_nodes;
+    fa.state_out = ta.state; fa.agg = agg; fa.Cc = cc; fa.thr = a.state_threshold; fa.k_groups = ta.k_groups;
+}
+
+// One launcher for both forward kernels.  A kernel family F names its argument struct, its instantiations and their LDS:
+//     using Args; template <int SQ, bool HAS_W> static constexpr void (*fn)(Args); template <int SQ> static size_t lds(int rows)
+struct TrainGroupKernel {
+    using Args = gnn::TrainGroupFwd;
+    template <int SQ, bool HAS_W> static constexpr void (*fn)(Args) = gnn::k_train_group_fwd<SQ, HAS_W>;
+    template <int SQ> static size_t lds(int rows) { return gnn::train_group_fwd_lds<SQ>(rows); }
+};
+struct TrainGroupTypesKernel {
+    using Args = gnn::TrainGroupFwdTypes;
+    template <int SQ, bool HAS_W> static constexpr void (*fn)(Args) = gnn::k_train_group_fwd_types<SQ, HAS_W>;
+    template <int SQ> static size_t lds(int rows) { return gnn::train_group_fwd_types_lds<SQ>(rows); }
+};
+
+template <class F, int SQ, bool HAS_W>
+int launch_train_group_fwd_one(const typename F::Args &fa, int G, int max_nodes, hipStream_t st) {
+    constexpr auto kern = F::template fn<SQ, HAS_W>;
+    // (the limit is raised to what the largest group allowed needs, once per kernel)
+    static std::mutex m;
+    static bool raised = false;
+    {
+        std::lock_guard<std::mutex> lock(m);
+        if (!raised) {
+            HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)F::template lds<SQ>(gnn::GROUP_CAP)));
+            raised = true;
+        }
+    }
+    kern<<<G, gnn::TS_NT, F::template lds<SQ>(max_nodes), st>>>(fa);
+    LAUNCH_OK();
+    return 0;
+}
+
+template <class F>
+int launch_train_group_fwd(const typename F::Args &fa, int G, int max_nodes, hipStream_t st) {
+    const bool has_w = fa.w != nullptr;
+    switch (fa.S) {
+        case 16: return has_w ? launch_train_group_fwd_one<F, 1, true>(fa, G, max_nodes, st) : launch_train_group_fwd_one<F, 1, false>(fa, G, max_nodes, st);
+        case 32: return has_w ? launch_train_group_fwd_one<F, 2, true>(fa, G, max_nodes, st) : launch_train_group_fwd_one<F, 2, false>(fa, G, max_nodes, st);
+        default: return has_w ? launch_train_group_fwd_one<F, 4, true>(fa, G, max_nodes, st) : launch_train_group_fwd_one<F, 4, false>(fa, G, max_nodes, st);
+    }
+}
+
+int launch_train_group_head(const gnn::TrainGroupHead &h, int G, hipStream_t st) {
+    const size_t lds = gnn::train_group_head_lds(h.in_o, h.T);
+    static std::mutex m;
+    static bool raised = false;
+    {
+        std::lock_guard<std::mutex> lock(m);
+        if (!raised) {
+            HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&gnn::k_train_group_head), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)gnn::train_group_head_lds(gnn::GROUP_HEAD_MAX_IN, gnn::GROUP_HEAD_MAX_UNITS)));
+            raised = true;
+        }
+    }
+    gnn::k_train_group_head<<<G, 256, lds, st>>>(h);
+    LAUNCH_OK();
+    return 0;
+}
+
+// The output network on every group's output rows, then its moving statistics in group order.  Input row: [state] (node focus),
+// [state_src | state_dst | arc label] (arc focus); `with_labels`: every state is followed by the node's L label columns (homogeneous models
+// with a state of its own - composite models filter on the state alone).
+int train_group_output(const gnn_train_args_t &ta, int G, int S, int L, int A, int M, int T, bool with_labels, const int *obeg, int *isrc, int *idst,
+                       float *stats_o, hipStream_t st) {
+    const gnn_loop_args_t &a = ta.loop;
+    const gnn_mlp_t &no = a.net_output;
+    const bool bn_o = no.has_bn != 0;
+    if (M < 1) return 0;
+    gnn::TrainGroupHead h;
+    memset(&h, 0, sizeof(h));
+    int n = 0;
+    auto seg = [&](const float *ptr, const int *idx, int ld, int width) { h.sg.ptr[n] = ptr; h.sg.idx[n] = idx; h.sg.ld[n] = ld; h.sg.width[n] = width; ++n; };
+    if (a.focus == GNN_FOCUS_ARC) {
+        k_arc_endpoints<<<cdiv(M, 256), 256, 0, st>>>(a.out_index, a.arc_src, a.arc_dst, M, isrc, idst);
+        LAUNCH_OK();
+        const int *ends[2] = {isrc, idst};
+        for (int e = 0; e < 2; ++e) {
+            seg(ta.state, ends[e], S, S);
+            if (with_labels) seg(a.nodes, ends[e], a.ld_nodes, L);
+        }
+        if (A > 0) seg(a.arc_labels, a.out_index, a.ld_arcs, A);
+    } else {
+        seg(ta.state, a.out_index, S, S);
+        if (with_labels) seg(a.nodes, a.out_index, a.ld_nodes, L);
+    }
+    h.sg.n = n;
+    h.obeg = obeg; h.in_o = no.in_dim; h.T = T; h.act = no.activation[0];
+    h.W = no.kernel[0]; h.b = no.bias[0]; h.gamma = bn_o ? no.bn_gamma : nullptr; h.beta = no.bn_beta; h.eps = no.bn_eps;
+    h.stats_o = stats_o; h.out = ta.y_pred;
+    TRY(launch_train_group_head(h, G, st));
+    if (bn_o) {
+        gnn::k_bn_moving_groups<<<cdiv(no.in_dim, 64), 64, 0, st>>>(stats_o, 1, no.in_dim, ta.k_groups, obeg, G, const_cast<float *>(no.bn_mean),
+                                                                  const_cast<float *>(no.bn_var), ta.bn_momentum, 0);
+        LAUNCH_OK();
+    }
+    return 0;
+}
+
+// ---- homogeneous models ----------------------------------------------------------------------------------------------------------------------
 struct GroupPlan {
     TrainPlan p;                 // dims only (planned without a workspace)
     int G, max_nodes;
@@ -28,25 +214,6 @@ bool train_groups_covered(const gnn_train_args_t &ta, const TrainPlan &p) {
     if (ns.n_layers != 1 || ns.units[0] != p.S || p.S > 64 || p.Kc > 32 || ns.activation[0] == GNN_ACT_SOFTMAX || p.K < 1) return false;
     if (no.n_layers != 1 || no.units[0] > gnn::GROUP_HEAD_MAX_UNITS || no.in_dim > gnn::GROUP_HEAD_MAX_IN) return false;
     return true;
-}
-
-// the host tables: 0 fine, -2 malformed (message set when `say`), g + 1: group g is too large
-int train_group_tables(const gnn_train_args_t &ta, int N, int M, bool say, int *max_nodes) {
-    const int G = ta.n_groups;
-    if (max_nodes) *max_nodes = 0;
-    if (!ta.group_node_begin || !ta.group_out_begin) { if (say) fail("group_node_begin / group_out_begin is NULL"); return GNN_TRAIN_GROUPS_MALFORMED; }
-    if (ta.group_node_begin[0] != 0 || ta.group_node_begin[G] != N) { if (say) fail("group_node_begin must span [0, n_nodes]"); return GNN_TRAIN_GROUPS_MALFORMED; }
-    if (ta.group_out_begin[0] != 0 || ta.group_out_begin[G] != M) { if (say) fail("group_out_begin must span [0, n_out]"); return GNN_TRAIN_GROUPS_MALFORMED; }
-    int too_large = 0, mx = 0;
-    for (int g = 0; g < G; ++g) {
-        const int n = ta.group_node_begin[g + 1] - ta.group_node_begin[g];
-        if (n <= 0) { if (say) fail("group %d is empty or group_node_begin is not ascending", g); return GNN_TRAIN_GROUPS_MALFORMED; }
-        if (ta.group_out_begin[g + 1] < ta.group_out_begin[g]) { if (say) fail("group_out_begin is not ascending at group %d", g); return GNN_TRAIN_GROUPS_MALFORMED; }
-        if (n > gnn::GROUP_CAP && !too_large) too_large = g + 1;
-        mx = std::max(mx, n);
-    }
-    if (max_nodes) *max_nodes = mx;
-    return too_large;
 }
 
 int make_group_plan(const gnn_train_args_t &ta, void *ws, GroupPlan &gp) {
@@ -76,94 +243,26 @@ size_t group_train_workspace_bytes(const gnn_train_args_t &ta) {
     return gp.bytes;
 }
 
-template <int SQ>
-int launch_train_group_fwd_sq(const gnn::TrainGroupFwd &fa, int G, int max_nodes, bool has_w, hipStream_t st) {
-    const size_t lds = gnn::train_group_fwd_lds<SQ>(max_nodes);
-    auto go = [&](auto kern) -> int {
-        // (the limit is raised to what the largest group allowed needs, once per kernel)
-        static std::mutex m;
-        static bool raised = false;
-        {
-            std::lock_guard<std::mutex> lock(m);
-            if (!raised) {
-                HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gnn::train_group_fwd_lds<SQ>(gnn::GROUP_CAP)));
-                raised = true;
-            }
-        }
-        kern<<<G, gnn::TS_NT, lds, st>>>(fa);
-        LAUNCH_OK();
-        return 0;
-    };
-    return has_w ? go(&gnn::k_train_group_fwd<SQ, true>) : go(&gnn::k_train_group_fwd<SQ, false>);
-}
-
 int train_forward_groups_types(const gnn_train_args_t &ta);
-
-int launch_train_group_head(const gnn::TrainGroupHead &h, int G, hipStream_t st) {
-    const size_t lds = gnn::train_group_head_lds(h.in_o, h.T);
-    static std::mutex m;
-    static bool raised = false;
-    {
-        std::lock_guard<std::mutex> lock(m);
-        if (!raised) {
-            HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&gnn::k_train_group_head), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)gnn::train_group_head_lds(gnn::GROUP_HEAD_MAX_IN, gnn::GROUP_HEAD_MAX_UNITS)));
-            raised = true;
-        }
-    }
-    gnn::k_train_group_head<<<G, 256, lds, st>>>(h);
-    LAUNCH_OK();
-    return 0;
-}
 
 int train_forward_groups(const gnn_train_args_t &ta) {
     const gnn_loop_args_t &a = ta.loop;
     if (a.composite) return train_forward_groups_types(ta);
-    if (!ta.forward_only) return fail("gnn_train_step: convergence groups need forward_only (a grouped training step is not implemented)");
-    if (ta.prev_grads_ok_host) return fail("gnn_train_step(forward_only): prev_grads_ok_host must be NULL");
-    if (ta.n_groups < 0) return fail("n_groups < 0");
     GroupPlan gp;
-    TRY(make_group_plan(ta, ta.tape, gp));
+    TRY(train_group_checks(ta, gp, make_group_plan, train_groups_covered, [&]() -> int {
+        if (!a.nodes || (gp.p.E > 0 && gp.p.A > 0 && !a.arc_labels)) return fail("nodes / arc_labels is NULL");
+        return 0;
+    }));
     const TrainPlan &p = gp.p;
-    if (!train_groups_covered(ta, p)) return fail("gnn_train_step: convergence groups do not cover this shape (gnn_train_groups_supported() == %d)", GNN_TRAIN_GROUPS_UNCOVERED);
-    const int tab = train_group_tables(ta, p.N, p.M, true, &gp.max_nodes);
-    if (tab < 0) return 1;
-    if (tab > 0) return fail("group %d has %d nodes (at most %d per convergence group: gnn_train_groups_supported())", tab - 1,
-                             ta.group_node_begin[tab] - ta.group_node_begin[tab - 1], gnn::GROUP_CAP);
-    if (ta.tape_bytes < gp.bytes) return fail("tape too small: %zu < %zu bytes", ta.tape_bytes, gp.bytes);
-    TRY(check_csr(a.adjacency, "adjacency", p.N, p.N));
-    TRY(check_csr(a.arcnode, "arcnode", p.N, p.E));
-    if (!a.nodes || (p.E > 0 && p.A > 0 && !a.arc_labels)) return fail("nodes / arc_labels is NULL");
-    if (a.state_dim > 0 && !a.state0) return fail("state0 is required when state_dim > 0");
-    if (p.M > 0 && !a.out_index) return fail("out_index is NULL");
-    if (a.focus == GNN_FOCUS_ARC && p.E > 0 && (!a.arc_src || !a.arc_dst)) return fail("arc focus needs arc_src / arc_dst");
-    if ((p.M > 0 && !ta.y_pred) || !ta.state || !ta.k_groups) return fail("y_pred / state / k_groups is NULL");
-    const gnn_mlp_t &ns = a.net_state[0], &no = a.net_output;
+    const gnn_mlp_t &ns = a.net_state[0];
     TRY(check_mlp(ns, "net_state", true));
-    TRY(check_mlp(no, "net_output", true));
-    const bool bn_s = ns.has_bn != 0, bn_o = no.has_bn != 0;
+    TRY(check_mlp(a.net_output, "net_output", true));
+    const bool bn_s = ns.has_bn != 0;
     hipStream_t st = (hipStream_t)a.stream;
     const int G = gp.G;
     GNN_SET_KERNEL_NAME("train_step: grouped forward kernels");
 
-    // the group tables go to the device through a pinned staging buffer of this thread; its event says when the previous call's copy has left it
-    {
-        static thread_local struct { int *buf; size_t cap; hipEvent_t ev; } stage = {nullptr, 0, nullptr};
-        const size_t n_tab = 2 * ((size_t)G + 1);
-        if (stage.ev) HIP_OK(hipEventSynchronize(stage.ev));
-        else HIP_OK(hipEventCreateWithFlags(&stage.ev, hipEventDisableTiming));
-        if (stage.cap < n_tab) {
-            if (stage.buf) HIP_OK(hipHostFree(stage.buf));
-            stage.buf = nullptr; stage.cap = 0;
-            HIP_OK(hipHostMalloc((void **)&stage.buf, std::max<size_t>(n_tab, 4096) * sizeof(int), hipHostMallocDefault));
-            stage.cap = std::max<size_t>(n_tab, 4096);
-        }
-        memcpy(stage.buf, ta.group_node_begin, ((size_t)G + 1) * sizeof(int));
-        memcpy(stage.buf + G + 1, ta.group_out_begin, ((size_t)G + 1) * sizeof(int));
-        HIP_OK(hipMemcpyAsync(gp.gbeg, stage.buf, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(gp.obeg, stage.buf + G + 1, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-        HIP_OK(hipEventRecord(stage.ev, st));
-    }
+    TRY(upload_group_tables(ta, gp.gbeg, gp.obeg, st));
     // aggregates of the constants over the merged graph (block-diagonal: a row sees its own group only)
     if (p.A > 0) TRY(launch_aggregate(nullptr, a.arcnode, a.arc_labels, a.ld_arcs, p.A, gp.agg_arcs, p.A, st));
     if (p.with_labels) TRY(launch_aggregate(nullptr, a.adjacency, a.nodes, a.ld_nodes, p.L, gp.agg_nodes, p.L, st));
@@ -181,53 +280,16 @@ int train_forward_groups(const gnn_train_args_t &ta) {
     LAUNCH_OK();
     gnn::TrainGroupFwd fa;
     memset(&fa, 0, sizeof(fa));
-    fa.S = p.SPs; fa.Sw = p.S; fa.K = p.K;
-    fa.rowptr = a.adjacency.rowptr; fa.src = a.adjacency.src; fa.w = a.adjacency.w; fa.row_scale = a.adjacency.row_scale;
-    fa.gbeg = gp.gbeg;
-    fa.state0 = a.state_dim > 0 ? a.state0 : a.nodes; fa.ld0 = a.state_dim > 0 ? p.S : a.ld_nodes;
-    fa.state_out = ta.state; fa.agg = gp.agg; fa.stats = gp.stats_s; fa.in_s = p.in_s; fa.off_agg = p.off_agg;
+    fill_train_group_common(fa, ta, p.SPs, p.S, p.K, gp.gbeg, gp.agg, gp.cc);
+    fa.stats = gp.stats_s; fa.in_s = p.in_s; fa.off_agg = p.off_agg;
     fa.W = ns.kernel[0]; fa.gamma = bn_s ? ns.bn_gamma : nullptr; fa.beta = ns.bn_beta; fa.eps = ns.bn_eps; fa.act = ns.activation[0];
-    fa.Cc = gp.cc; fa.thr = a.state_threshold; fa.k_groups = ta.k_groups;
-    switch (p.SPs) {
-        case 16: TRY(launch_train_group_fwd_sq<1>(fa, G, gp.max_nodes, a.adjacency.w != nullptr, st)); break;
-        case 32: TRY(launch_train_group_fwd_sq<2>(fa, G, gp.max_nodes, a.adjacency.w != nullptr, st)); break;
-        default: TRY(launch_train_group_fwd_sq<4>(fa, G, gp.max_nodes, a.adjacency.w != nullptr, st)); break;
-    }
+    TRY(launch_train_group_fwd<TrainGroupKernel>(fa, G, gp.max_nodes, st));
     if (bn_s) {
         gnn::k_bn_moving_groups<<<cdiv(p.in_s, 64), 64, 0, st>>>(gp.stats_s, p.K, p.in_s, ta.k_groups, nullptr, G, const_cast<float *>(ns.bn_mean),
                                                                 const_cast<float *>(ns.bn_var), ta.bn_momentum);
         LAUNCH_OK();
     }
-    if (p.M > 0) {
-        gnn::TrainGroupHead h;
-        memset(&h, 0, sizeof(h));
-        int n = 0;
-        auto seg = [&](const float *ptr, const int *idx, int ld, int width) { h.sg.ptr[n] = ptr; h.sg.idx[n] = idx; h.sg.ld[n] = ld; h.sg.width[n] = width; ++n; };
-        if (a.focus == GNN_FOCUS_ARC) {
-            k_arc_endpoints<<<cdiv(p.M, 256), 256, 0, st>>>(a.out_index, a.arc_src, a.arc_dst, p.M, gp.isrc, gp.idst);
-            LAUNCH_OK();
-            const int *ends[2] = {gp.isrc, gp.idst};
-            for (int e = 0; e < 2; ++e) {
-                seg(ta.state, ends[e], p.S, p.S);
-                if (p.with_labels) seg(a.nodes, ends[e], a.ld_nodes, p.L);
-            }
-            if (p.A > 0) seg(a.arc_labels, a.out_index, a.ld_arcs, p.A);
-        } else {
-            seg(ta.state, a.out_index, p.S, p.S);
-            if (p.with_labels) seg(a.nodes, a.out_index, a.ld_nodes, p.L);
-        }
-        h.sg.n = n;
-        h.obeg = gp.obeg; h.in_o = p.in_o; h.T = p.T; h.act = no.activation[0];
-        h.W = no.kernel[0]; h.b = no.bias[0]; h.gamma = bn_o ? no.bn_gamma : nullptr; h.beta = no.bn_beta; h.eps = no.bn_eps;
-        h.stats_o = gp.stats_o; h.out = ta.y_pred;
-        TRY(launch_train_group_head(h, G, st));
-        if (bn_o) {
-            gnn::k_bn_moving_groups<<<cdiv(p.in_o, 64), 64, 0, st>>>(gp.stats_o, 1, p.in_o, ta.k_groups, gp.obeg, G, const_cast<float *>(no.bn_mean),
-                                                                    const_cast<float *>(no.bn_var), ta.bn_momentum);
-            LAUNCH_OK();
-        }
-    }
-    return 0;
+    return train_group_output(ta, G, p.S, p.L, p.A, p.M, p.T, p.with_labels, gp.obeg, gp.isrc, gp.idst, gp.stats_o, st);
 }
 
 
@@ -283,78 +345,25 @@ size_t group_types_workspace_bytes(const gnn_train_args_t &ta) {
     return gp.bytes;
 }
 
-template <int SQ>
-int launch_train_group_fwd_types_sq(const gnn::TrainGroupFwdTypes &fa, int G, int max_nodes, bool has_w, hipStream_t st) {
-    const size_t lds = gnn::train_group_fwd_types_lds<SQ>(max_nodes);
-    auto go = [&](auto kern) -> int {
-        // (the limit is raised to what the largest group allowed needs, once per kernel)
-        static std::mutex m;
-        static bool raised = false;
-        {
-            std::lock_guard<std::mutex> lock(m);
-            if (!raised) {
-                HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gnn::train_group_fwd_types_lds<SQ>(gnn::GROUP_CAP)));
-                raised = true;
-            }
-        }
-        kern<<<G, gnn::TS_NT, lds, st>>>(fa);
-        LAUNCH_OK();
-        return 0;
-    };
-    return has_w ? go(&gnn::k_train_group_fwd_types<SQ, true>) : go(&gnn::k_train_group_fwd_types<SQ, false>);
-}
-
 int train_forward_groups_types(const gnn_train_args_t &ta) {
     const gnn_loop_args_t &a = ta.loop;
-    if (!ta.forward_only) return fail("gnn_train_step: convergence groups need forward_only (a grouped training step is not implemented)");
-    if (ta.prev_grads_ok_host) return fail("gnn_train_step(forward_only): prev_grads_ok_host must be NULL");
-    if (ta.n_groups < 0) return fail("n_groups < 0");
     GroupTypesPlan gp;
-    TRY(make_group_types_plan(ta, ta.tape, gp));
+    TRY(train_group_checks(ta, gp, make_group_types_plan, train_groups_types_covered, [&]() -> int {
+        for (int t = 0; t < gp.p.n_types; ++t) {
+            TRY(check_csr(a.composite_adjacency[t], "composite_adjacency", gp.p.N, gp.p.N));
+            TRY(check_mlp(a.net_state[t], "net_state", true));
+        }
+        if (!a.nodes || !a.type_nodes) return fail("nodes / type_nodes is NULL");
+        if (gp.p.E > 0 && gp.p.A > 0 && !a.arc_labels) return fail("arc_labels is NULL");
+        return 0;
+    }));
     const CPlan &p = gp.p;
-    if (!train_groups_types_covered(ta, p)) return fail("gnn_train_step: convergence groups do not cover this shape (gnn_train_groups_supported() == %d)", GNN_TRAIN_GROUPS_UNCOVERED);
-    const int tab = train_group_tables(ta, p.N, p.M, true, &gp.max_nodes);
-    if (tab < 0) return 1;
-    if (tab > 0) return fail("group %d has %d nodes (at most %d per convergence group: gnn_train_groups_supported())", tab - 1,
-                             ta.group_node_begin[tab] - ta.group_node_begin[tab - 1], gnn::GROUP_CAP);
-    if (ta.tape_bytes < gp.bytes) return fail("tape too small: %zu < %zu bytes", ta.tape_bytes, gp.bytes);
-    TRY(check_csr(a.adjacency, "adjacency", p.N, p.N));
-    TRY(check_csr(a.arcnode, "arcnode", p.N, p.E));
-    for (int t = 0; t < p.n_types; ++t) {
-        TRY(check_csr(a.composite_adjacency[t], "composite_adjacency", p.N, p.N));
-        TRY(check_mlp(a.net_state[t], "net_state", true));
-    }
-    if (!a.nodes || !a.type_nodes) return fail("nodes / type_nodes is NULL");
-    if (p.E > 0 && p.A > 0 && !a.arc_labels) return fail("arc_labels is NULL");
-    if (a.state_dim > 0 && !a.state0) return fail("state0 is required when state_dim > 0");
-    if (p.M > 0 && !a.out_index) return fail("out_index is NULL");
-    if (a.focus == GNN_FOCUS_ARC && p.E > 0 && (!a.arc_src || !a.arc_dst)) return fail("arc focus needs arc_src / arc_dst");
-    if ((p.M > 0 && !ta.y_pred) || !ta.state || !ta.k_groups) return fail("y_pred / state / k_groups is NULL");
-    const gnn_mlp_t &no = a.net_output;
-    TRY(check_mlp(no, "net_output", true));
-    const bool bn_o = no.has_bn != 0;
+    TRY(check_mlp(a.net_output, "net_output", true));
     hipStream_t st = (hipStream_t)a.stream;
     const int G = gp.G, SPs = gp.SPs;
     GNN_SET_KERNEL_NAME("train_step: grouped forward kernels (types)");
 
-    // the group tables go to the device through a pinned staging buffer of this thread; its event says when the previous call's copy has left it
-    {
-        static thread_local struct { int *buf; size_t cap; hipEvent_t ev; } stage = {nullptr, 0, nullptr};
-        const size_t n_tab = 2 * ((size_t)G + 1);
-        if (stage.ev) HIP_OK(hipEventSynchronize(stage.ev));
-        else HIP_OK(hipEventCreateWithFlags(&stage.ev, hipEventDisableTiming));
-        if (stage.cap < n_tab) {
-            if (stage.buf) HIP_OK(hipHostFree(stage.buf));
-            stage.buf = nullptr; stage.cap = 0;
-            HIP_OK(hipHostMalloc((void **)&stage.buf, std::max<size_t>(n_tab, 4096) * sizeof(int), hipHostMallocDefault));
-            stage.cap = std::max<size_t>(n_tab, 4096);
-        }
-        memcpy(stage.buf, ta.group_node_begin, ((size_t)G + 1) * sizeof(int));
-        memcpy(stage.buf + G + 1, ta.group_out_begin, ((size_t)G + 1) * sizeof(int));
-        HIP_OK(hipMemcpyAsync(gp.gbeg, stage.buf, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(gp.obeg, stage.buf + G + 1, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-        HIP_OK(hipEventRecord(stage.ev, st));
-    }
+    TRY(upload_group_tables(ta, gp.gbeg, gp.obeg, st));
     // the rows of every type per group: groups are contiguous node ranges, a type's row list ascends
     {
         gnn::TypeOffsets to;
@@ -388,16 +397,9 @@ int train_forward_groups_types(const gnn_train_args_t &ta) {
     ca.tbeg = gp.tbeg; ca.type_nodes = a.type_nodes; ca.nodes = a.nodes; ca.ld_nodes = a.ld_nodes; ca.agg_comp = gp.agg_comp; ca.Cc = gp.cc;
     gnn::k_train_group_const_types<<<G, 256, 0, st>>>(ca);
     LAUNCH_OK();
-    fa.S = SPs; fa.Sw = p.S; fa.K = p.K; fa.n_types = p.n_types; fa.G = G;
-    fa.rowptr = a.adjacency.rowptr; fa.src = a.adjacency.src; fa.w = a.adjacency.w; fa.row_scale = a.adjacency.row_scale;
-    fa.gbeg = gp.gbeg; fa.tbeg = gp.tbeg; fa.type_nodes = a.type_nodes;
-    fa.state0 = a.state_dim > 0 ? a.state0 : a.nodes; fa.ld0 = a.state_dim > 0 ? p.S : a.ld_nodes;
-    fa.state_out = ta.state; fa.agg = gp.agg; fa.Cc = gp.cc; fa.thr = a.state_threshold; fa.k_groups = ta.k_groups;
-    switch (SPs) {
-        case 16: TRY(launch_train_group_fwd_types_sq<1>(fa, G, gp.max_nodes, a.adjacency.w != nullptr, st)); break;
-        case 32: TRY(launch_train_group_fwd_types_sq<2>(fa, G, gp.max_nodes, a.adjacency.w != nullptr, st)); break;
-        default: TRY(launch_train_group_fwd_types_sq<4>(fa, G, gp.max_nodes, a.adjacency.w != nullptr, st)); break;
-    }
+    fill_train_group_common(fa, ta, SPs, p.S, p.K, gp.gbeg, gp.agg, gp.cc);
+    fa.n_types = p.n_types; fa.G = G; fa.tbeg = gp.tbeg; fa.type_nodes = a.type_nodes;
+    TRY(launch_train_group_fwd<TrainGroupTypesKernel>(fa, G, gp.max_nodes, st));
     // the moving statistics of network t: k_g steps for every group with rows of type t, group after group
     for (int t = 0; t < p.n_types; ++t) {
         const gnn_mlp_t &ns = a.net_state[t];
@@ -407,45 +409,13 @@ int train_forward_groups_types(const gnn_train_args_t &ta) {
                                                               const_cast<float *>(ns.bn_var), ta.bn_momentum, 1);
         LAUNCH_OK();
     }
-    if (p.M > 0) {
-        // composite models filter on the state alone: [state] (node focus), [state_src | state_dst | arc label] (arc focus)
-        gnn::TrainGroupHead h;
-        memset(&h, 0, sizeof(h));
-        int n = 0;
-        auto seg = [&](const float *ptr, const int *idx, int ld, int width) { h.sg.ptr[n] = ptr; h.sg.idx[n] = idx; h.sg.ld[n] = ld; h.sg.width[n] = width; ++n; };
-        if (a.focus == GNN_FOCUS_ARC) {
-            k_arc_endpoints<<<cdiv(p.M, 256), 256, 0, st>>>(a.out_index, a.arc_src, a.arc_dst, p.M, gp.isrc, gp.idst);
-            LAUNCH_OK();
-            seg(ta.state, gp.isrc, p.S, p.S);
-            seg(ta.state, gp.idst, p.S, p.S);
-            if (p.A > 0) seg(a.arc_labels, a.out_index, a.ld_arcs, p.A);
-        } else seg(ta.state, a.out_index, p.S, p.S);
-        h.sg.n = n;
-        h.obeg = gp.obeg; h.in_o = no.in_dim; h.T = p.T; h.act = no.activation[0];
-        h.W = no.kernel[0]; h.b = no.bias[0]; h.gamma = bn_o ? no.bn_gamma : nullptr; h.beta = no.bn_beta; h.eps = no.bn_eps;
-        h.stats_o = gp.stats_o; h.out = ta.y_pred;
-        TRY(launch_train_group_head(h, G, st));
-        if (bn_o) {
-            gnn::k_bn_moving_groups<<<cdiv(no.in_dim, 64), 64, 0, st>>>(gp.stats_o, 1, no.in_dim, ta.k_groups, gp.obeg, G, const_cast<float *>(no.bn_mean),
-                                                                      const_cast<float *>(no.bn_var), ta.bn_momentum, 0);
-            LAUNCH_OK();
-        }
-    }
-    return 0;
+    return train_group_output(ta, G, p.S, 0, p.A, p.M, p.T, false, gp.obeg, gp.isrc, gp.idst, gp.stats_o, st);
 }
 
 }  // namespace
 
 extern "C" int gnn_train_groups_supported(const gnn_train_args_t *args) {
     if (!args || args->n_groups < 1 || !args->forward_only) return GNN_TRAIN_GROUPS_UNCOVERED;
-    if (args->loop.composite) {
-        CPlan cp;
-        if (make_cplan(*args, nullptr, cp)) return GNN_TRAIN_GROUPS_UNCOVERED;
-        if (!train_groups_types_covered(*args, cp)) return GNN_TRAIN_GROUPS_UNCOVERED;
-        return train_group_tables(*args, cp.N, cp.M, false, nullptr);
-    }
-    TrainPlan p;
-    if (make_train_plan(*args, nullptr, p)) return GNN_TRAIN_GROUPS_UNCOVERED;
-    if (!train_groups_covered(*args, p)) return GNN_TRAIN_GROUPS_UNCOVERED;
-    return train_group_tables(*args, p.N, p.M, false, nullptr);
+    if (args->loop.composite) return train_groups_supported<CPlan>(*args, make_cplan, train_groups_types_covered);
+    return train_groups_supported<TrainPlan>(*args, make_train_plan, train_groups_covered);
 }
