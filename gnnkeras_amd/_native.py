@@ -31,6 +31,7 @@ FLAG_FUSED_GEN2, FLAG_FUSED_GEN4, FLAG_FUSED_GEN5, FLAG_FUSED_GEN6, FLAG_FUSED_G
 EXPORTS = ['gnn_last_error', 'gnn_last_kernel_name', 'gnn_abi_version', 'gnn_struct_size', 'gnn_loop_workspace_bytes', 'gnn_loop_forward', 'gnn_loop_groups_supported', 'gnn_loop_group_max_nodes', 'gnn_aggregate',
            'gnn_loop_xc_applies', 'gnn_loop_route_name', 'gnn_train_xc_applies',
            'gnn_mlp_workspace_bytes', 'gnn_mlp_forward', 'gnn_converged', 'gnn_state_step', 'gnn_state_step_agg', 'gnn_state_ld', 'gnn_debug_occupy', 'gnn_debug_occupy_until', 'gnn_debug_expiry_beacon', 'gnn_debug_host_flag',
+           'gnn_debug_f4_tile_plan', 'gnn_debug_f4_tile_queue_const', 'gnn_debug_f4_last_tickets',
            'gnn_device_malloc', 'gnn_device_free', 'gnn_ipc_export', 'gnn_ipc_open', 'gnn_ipc_close', 'gnn_shard_iteration_peers', 'gnn_peer_wait', 'gnn_peer_publish', 'gnn_shard_iteration_split_rows',
            'gnn_shard_setup', 'gnn_shard_iteration', 'gnn_shard_output', 'gnn_gather_rows',
            'gnn_shard_can_split', 'gnn_shard_partial', 'gnn_shard_iteration_split',
@@ -256,6 +257,12 @@ def lib():
         l.gnn_peer_publish.argtypes = [C.POINTER(PeerSet), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         l.gnn_debug_host_flag.restype = C.c_int
         l.gnn_debug_host_flag.argtypes = [C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_void_p)]
+        l.gnn_debug_f4_tile_plan.restype = None
+        l.gnn_debug_f4_tile_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+        l.gnn_debug_f4_tile_queue_const.restype = C.c_int32
+        l.gnn_debug_f4_tile_queue_const.argtypes = [C.c_int32, C.c_int32]
+        l.gnn_debug_f4_last_tickets.restype = C.c_longlong
+        l.gnn_debug_f4_last_tickets.argtypes = []
         l.gnn_debug_expiry_beacon.restype = C.c_int
         l.gnn_debug_expiry_beacon.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]
         l.gnn_state_step_agg.restype = C.c_int

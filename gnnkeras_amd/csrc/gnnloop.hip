@@ -87,6 +87,7 @@ struct Knobs {
     // node, us per iteration with inputs / with C: 100 k nodes 61.1 / 59.1, 200 k 105.0 / 105.8, 400 k 192.2 / 199.7, 600 k 281.6 / 294.0,
     // 1 M (C4) 458 / 480, 4 M 2 215 / 2 329; d = 32 at C4 size 263.2 / 263.7.
     bool xc; int xc_min_nodes;
+    bool tile_queue;         // GNN_F4_TILE_QUEUE=0: the wave-specialised kernel deals every tile statically (read at every call)
 };
 const Knobs &process_knobs() {      // read once per process: all five at the first use of any of them (a forward plan, or a dense launch's GNN_ROWDENSE)
     static const Knobs once = [] {
@@ -108,6 +109,8 @@ Knobs knobs(int flags) {            // ... plus the call's pin and the two knobs
     const char *e = getenv("GNN_XC"), *m = getenv("GNN_XC_MIN_NODES");
     k.xc = !(e && atoi(e) == 0);
     k.xc_min_nodes = m ? atoi(m) : 196608;
+    const char *q = getenv("GNN_F4_TILE_QUEUE");
+    k.tile_queue = !(q && atoi(q) == 0);
     return k;
 }
 
@@ -477,6 +480,7 @@ struct Plan {
     int *pred0;                      // state_0's predicate, one word per 64-node tile (written by k_setup_small, read by k_state_small);
                                      // composite groups: one word per group (k_pred0_groups)
     int *tbeg;                       // composite groups: rows of every type per group, positions in type_nodes [n_types][n_groups + 1]
+    int *tq;                         // tile-queue counters of the wave-specialised kernel: 8 per iteration (one per XCD), behind the loop words, zeroed with them
     int *err;                        // sticky "an in-launch wait expired" word of the fused kernels, folded into k at the end
     float *agg_arcs, *agg_nodes; int ld_agg_nodes;
     float *C; int ldC;
@@ -496,6 +500,8 @@ constexpr int GNN_SMALL_MAX_TILES = 512;   // upper bound of CUs a whole-loop la
 // words behind flags[max_iteration]: [1] last flag, [3..7) barrier counters of the small whole-loop kernel, [12] error word,
 // then (128-byte aligned) the mid-size whole-loop kernel's barrier lines; all zeroed by the set-up launch
 constexpr int GNN_LOOP_WORDS = 16 + 32 + gnn::MID_BAR_WORDS;
+constexpr int GNN_TQ_WORDS = 8;            // ... and behind those, per iteration: the tile-queue counters of that iteration's launch (one per XCD)
+inline size_t tq_words(const gnn_loop_args_t &a) { return (size_t)GNN_TQ_WORDS * (size_t)a.max_iteration; }
 
 int state_width(const gnn_loop_args_t &a) { return a.state_dim > 0 ? a.state_dim : a.dim_node_label; }
 
@@ -605,8 +611,9 @@ int make_plan(const gnn_loop_args_t &a, void *ws, Plan &p, bool validate_ptrs) {
 
     // ---- carve ----
     Carver c(ws);
-    p.flags = c.take<int>(a.max_iteration + GNN_LOOP_WORDS);   // behind the flags: the persistent kernel's two 64-bit barrier counters, the error word
+    p.flags = c.take<int>(a.max_iteration + GNN_LOOP_WORDS + tq_words(a));   // behind the flags: the persistent kernel's two 64-bit barrier counters, the error word
     p.err = p.flags ? p.flags + a.max_iteration + 12 : nullptr;
+    p.tq = p.flags ? p.flags + a.max_iteration + GNN_LOOP_WORDS : nullptr;
     p.mid_bar = p.flags ? p.flags + ((a.max_iteration + 16 + 31) & ~31) : nullptr;
     p.pred0 = c.take<int>(std::max(GNN_SMALL_MAX_TILES, p.group_tiles));
     p.d_group_tabs = c.take<int>(a.n_groups > 0 ? 4 * ((size_t)a.n_groups + 1) : 0);
@@ -770,7 +777,7 @@ int setup_constants(const gnn_loop_args_t &a, const Plan &p, hipStream_t st, boo
     FoldList fl;
     for (int t = 0; t < p.T; ++t) fl.add(a.net_state[t], p.tp[t].Wf, p.tp[t].bf);
     if (a.net_output.kernel[0]) fl.add(a.net_output, p.Wf_out, p.bf_out);      // absent for the standalone state step
-    if (zero_loop_words) { fl.fa.zero_a = p.flags; fl.fa.n_a = a.max_iteration + GNN_LOOP_WORDS; fl.fa.zero_b = a.k_out; fl.fa.n_b = 1; }
+    if (zero_loop_words) { fl.fa.zero_a = p.flags; fl.fa.n_a = a.max_iteration + GNN_LOOP_WORDS + (int)tq_words(a); fl.fa.zero_b = a.k_out; fl.fa.n_b = 1; }
     TRY(launch_fold_list(fl, st));
     if (xc_line) {      // nothing but the line is read on this path: no aggregate arrays, no C
         const TypePlan &tp = p.tp[0];
@@ -865,13 +872,21 @@ int setup_small(const gnn_loop_args_t &a, const Plan &p, hipStream_t st) {
 
 // a bounded in-launch wait of a fused kernel expired somewhere in the loop: k < 0 tells the caller (same convention as the
 // persistent whole-loop kernel, kernel_state_small.hpp)
-__global__ void k_fold_error(const int *err, float *k_out) {
-    if (*err != 0) *k_out = -1.0e9f;
+// ... and the tile-queue draws of the forward that ends here, summed into a device word for gnn_debug_f4_last_tickets (0: no launch took the queue)
+__device__ long long g_f4_last_tickets;
+__global__ void k_fold_error(const int *err, float *k_out, const int *tq, int n_tq) {
+    long long s = 0;
+    for (int i = threadIdx.x; i < n_tq; i += 64) s += tq[i];
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (threadIdx.x == 0) {
+        g_f4_last_tickets = s;
+        if (*err != 0) *k_out = -1.0e9f;
+    }
 }
 
-int launch_fold_error(const Plan &p, float *k_out, hipStream_t st) {
+int launch_fold_error(const Plan &p, float *k_out, hipStream_t st, const int *tq = nullptr, int n_tq = 0) {
     if (!k_out || !p.err) return 0;
-    k_fold_error<<<1, 1, 0, st>>>(p.err, k_out);
+    k_fold_error<<<1, 64, 0, st>>>(p.err, k_out, tq, n_tq);
     LAUNCH_OK();
     return 0;
 }
@@ -978,7 +993,7 @@ int iteration_prefix(const gnn_loop_args_t &a, const Plan &p, const int *gate, c
 int iteration_fused(const gnn_loop_args_t &a, const Plan &p, IterKernel kernel, const int *gate, int n_gate, int gate_stride,
                     const float *src, float *dst, int row_base, int *flag_next, float *k_out, float k_val,
                     hipStream_t st, const gnn_csr_t *adj_override = nullptr, const float *agg_init = nullptr,
-                    const int *rows_override = nullptr, int count_override = 0, const gnn_peer_set_t *peers = nullptr) {
+                    const int *rows_override = nullptr, int count_override = 0, const gnn_peer_set_t *peers = nullptr, int *tile_ctr = nullptr) {
     TRY(launch_heavy(a, p, n_gate == 1 ? gate : nullptr, src, st));
     const gnn_csr_t &adj = adj_override ? *adj_override : iter_adjacency(a, p);
     gnn::Fused2Args fa;
@@ -999,6 +1014,8 @@ int iteration_fused(const gnn_loop_args_t &a, const Plan &p, IterKernel kernel, 
         for (int i = 0; i < peers->n_peers; ++i) fa.peer_out[i] = peers->state_out_full[i];
     }
     if (p.xc_ok && !adj.w && (agg_init || size_generation(p, a.flags) == 4)) fa.Xc = p.Xc;
+    // the tile queue: single-type launches of the plain form only (the launcher still decides by the tiles per workgroup)
+    if (tile_ctr && kernel == IterKernel::fused4 && p.T == 1 && fa.n_types == 1 && !rows_override && !agg_init && !peers) fa.tq_ctr = tile_ctr;
     if (fa.n_types == 0) {                      // no nodes at all: only the iteration counter moves
         if (k_out) TRY(launch_converge(fa.gate, src, src, 0, p.S, p.SP, p.SP, a.state_threshold, flag_next, k_out, k_val, st));
         return 0;
@@ -1303,11 +1320,14 @@ int gnn_loop_forward(const gnn_loop_args_t *args) {
         if (rc == 1) return 1;
         loop_done = rc == 0;
     }
+    // launch `it` of the wave-specialised kernel hands out its last tiles through row `it` of the counters (zeroed by the set-up launch above)
+    int *const tq = (!small_setup && knobs(a.flags).tile_queue) ? p.tq : nullptr;
     for (int it = 0; !loop_done && it < a.max_iteration; ++it) {
         const int *gate = no_exit ? nullptr : p.flags + it;
         const float *src = it == 0 ? first : B[it & 1];
         float *dst = B[(it + 1) & 1];
-        if (route.iter.fused())                  TRY(iteration_fused(a, p, kernel, gate, gate ? 1 : 0, 0, src, dst, 0, p.flags + it + 1, a.k_out, (float)(it + 1), st));
+        if (route.iter.fused())                  TRY(iteration_fused(a, p, kernel, gate, gate ? 1 : 0, 0, src, dst, 0, p.flags + it + 1, a.k_out, (float)(it + 1), st,
+                                                                     nullptr, nullptr, nullptr, 0, nullptr, tq ? tq + (size_t)GNN_TQ_WORDS * it : nullptr));
         else if (kernel == IterKernel::prefix)   TRY(iteration_prefix(a, p, gate, src, dst, p.flags + it + 1, a.k_out, (float)(it + 1), st));
         else if (kernel == IterKernel::xwide)    TRY(iteration_xwide(a, p, gate, src, dst, p.flags + it + 1, a.k_out, (float)(it + 1), st));
         else                                     TRY(iteration_unfused(a, p, gate, src, dst, 0, p.flags + it + 1, a.k_out, (float)(it + 1), st));
@@ -1324,7 +1344,8 @@ int gnn_loop_forward(const gnn_loop_args_t *args) {
         }
     }
     TRY(output_stage(a, p, st));
-    if (!loop_done && (route.iter.fused() || kernel == IterKernel::xwide) && a.max_iteration > 0) TRY(launch_fold_error(p, a.k_out, st));
+    if (!loop_done && (route.iter.fused() || kernel == IterKernel::xwide) && a.max_iteration > 0)
+        TRY(launch_fold_error(p, a.k_out, st, tq, tq ? (int)tq_words(a) : 0));
     return 0;
 }
 
@@ -1469,6 +1490,29 @@ __global__ void __launch_bounds__(64) k_debug_occupy(unsigned long long ticks, i
         __builtin_amdgcn_s_sleep(64); ++polls;
     }
     if (threadIdx.x == 0 && polls < 0) { occ_smem[0] = polls; *sink = occ_smem[0]; }      // (keeps the LDS allocation alive; never taken)
+}
+
+void gnn_debug_f4_tile_plan(int32_t ntiles, int32_t n_workgroups, int32_t ahead, int32_t *out56) {
+    for (int xcd = 0; xcd < 8; ++xcd) {
+        const gnn::F4TilePlan q = gnn::f4_tile_plan(ntiles, n_workgroups, xcd, ahead);
+        int32_t *o = out56 + 7 * xcd;
+        o[0] = q.t_begin; o[1] = q.t_end; o[2] = q.blk; o[3] = q.T1; o[4] = q.pool_begin; o[5] = q.pool_end; o[6] = q.n_chunks;
+    }
+}
+int32_t gnn_debug_f4_tile_queue_const(int32_t which, int32_t padded_width) {
+    switch (which) {
+        case 0: return gnn::F4_TQ_CH;
+        case 1: return padded_width == 64 ? gnn::Fused4Cfg<64>::AHEAD : padded_width == 32 ? gnn::Fused4Cfg<32>::AHEAD : padded_width == 16 ? gnn::Fused4Cfg<16>::AHEAD : -1;
+        case 2: return gnn::F4_TQ_MIN_SHARE;
+        case 3: return gnn::F4_TQ_MAX_CHUNKS;
+        case 4: return gnn::F4_TQ_TAB;
+        default: return -1;
+    }
+}
+long long gnn_debug_f4_last_tickets(void) {
+    long long v = -1;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    return hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_f4_last_tickets), sizeof(v)) == hipSuccess ? v : -1;
 }
 
 int gnn_debug_occupy(int32_t n_workgroups, int32_t lds_bytes, int32_t milliseconds, void *stream) {

@@ -54,6 +54,8 @@ struct Fused2Args {
     int *flag_next;
     float *k_out; float k_val;
     int *err;                                      // sticky error word (workspace): a bounded in-launch wait expired
+    int *tq_ctr;                                   // k_state_fused4<.., TQ = true>: this launch's 8 tile-queue counters (one per XCD, zero at
+                                                   // the launch's start); nullptr = the static assignment
     // k_state_fused4<.., XC = true> (one node type): instead of the per-node constant C (4 H bytes per node and iteration) the
     // kernel reads the node's constant INPUTS Xc [n, 32] = [labels | agg labels | agg arcs | 1 | 0..] (128 bytes) and multiplies
     // them with the type's Wc [32, H] = folded first-layer rows of those inputs, then the folded bias, then zeros, on the matrix

@@ -31,7 +31,44 @@ namespace gnn {
 
 constexpr int XC_K = 32;                          // constant-input columns of the XC variant (padded; one of them is the bias' 1)
 
-template <int SP, int NC = 4, bool L2 = false, bool XC = false, int VPL = 1>
+// ---- the tile queue (TQ instantiations) -----------------------------------------------------------------------------
+// An XCD's tile range [t_begin, t_end) is dealt in two parts: every workgroup's first T1 tiles statically (t_first + L * blk, as in
+// the static form: a contiguous block at the front of the range), the rest - the pool - in chunks of F4_TQ_CH consecutive tiles
+// through one counter per XCD and launch.  A workgroup that runs fast draws more chunks: the exits of a launch level out without
+// a second generation of workgroups (and its ramp).  The last chunk may run past t_end: those tiles are pad tiles.
+// Measured at C4 (five alternating headline runs each, medians in ms per step; the static parent 22.86): CH 4 / T1 = 3/4 of the share
+// 22.65 (range 0.13), CH 2 / 3/4 (pool cut to the table's 960 chunks) 22.78, CH 2 / 7/8 22.61 (range 0.04) - shipped
+// (profiles/f4_tile_queue_ab.json).
+constexpr int F4_TQ_CH = 2;                      // tiles per chunk
+constexpr int F4_TQ_NUM = 7, F4_TQ_DEN = 8;      // T1 = 7/8 of a workgroup's equal share: the pool is the last eighth of every XCD's range
+constexpr int F4_TQ_TAB = 1024;                  // LDS table of a workgroup's chunks, one int each: sized for the whole pool of an XCD
+constexpr int F4_TQ_MAX_CHUNKS = 960;            // ... so a pool never has more chunks than this (+ the END marks behind them)
+constexpr int F4_TQ_MIN_SHARE = 16;              // tiles per workgroup below which a launch stays static (C3: 12, the 200 k-node shape: 24)
+constexpr int F4_TQ_END = -2;                    // tile_of(): no such tile, the loops end;  -1: a pad tile (all rows absent)
+struct F4TilePlan { int t_begin, t_end, blk, T1, pool_begin, pool_end, n_chunks; };
+// `ahead`: the smallest T1 the kernel can run with (tickets are drawn that many tiles before their chunk is needed).  The decision
+// queue / static is taken on the launch's SMALLEST range (the last XCD's), so it is the same on every XCD and on the host.
+__host__ __device__ inline F4TilePlan f4_tile_plan(int ntiles, int nblk, int xcd, int ahead) {
+    F4TilePlan q;
+    const int tpx = (ntiles + 7) >> 3;
+    q.blk = (nblk + 7 - xcd) >> 3;
+    q.t_begin = xcd * tpx < ntiles ? xcd * tpx : ntiles;
+    q.t_end = (xcd + 1) * tpx < ntiles ? (xcd + 1) * tpx : ntiles;
+    const int n = q.t_end - q.t_begin, b = q.blk > 0 ? q.blk : 1;
+    const int n_min = ntiles - 7 * tpx > 0 ? ntiles - 7 * tpx : 0, b_max = (nblk + 7) >> 3;
+    const bool queue = (nblk & 7) == 0 && nblk > 0 && n_min >= F4_TQ_MIN_SHARE * b_max && (int)((long)F4_TQ_NUM * n_min / ((long)F4_TQ_DEN * b_max)) >= ahead;
+    if (!queue) {
+        q.T1 = (n + b - 1) / b; q.pool_begin = q.pool_end = q.t_end; q.n_chunks = 0;
+        return q;
+    }
+    q.T1 = (int)((long)F4_TQ_NUM * n / ((long)F4_TQ_DEN * b));
+    if (n - q.T1 * b > F4_TQ_MAX_CHUNKS * F4_TQ_CH) q.T1 = (n - F4_TQ_MAX_CHUNKS * F4_TQ_CH + b - 1) / b;     // (huge graphs: the table bounds the pool)
+    q.pool_begin = q.t_begin + q.T1 * b; q.pool_end = q.t_end;
+    q.n_chunks = (q.pool_end - q.pool_begin + F4_TQ_CH - 1) / F4_TQ_CH;
+    return q;
+}
+
+template <int SP, int NC = 4, bool L2 = false, bool XC = false, int VPL = 1, bool TQ = false>
 struct Fused4Cfg {
     static constexpr int NW = 16, NT = 64 * NW;
     static constexpr int NCONS = NC;                 // matrix waves (wave ids 0..NC-1)
@@ -50,7 +87,10 @@ struct Fused4Cfg {
     static constexpr int WROWS = 2 * SP + (XC ? XC_K : 0);   // rows of the weight matrix in LDS: state ; agg ; (XC) constant inputs
     static constexpr int SLOT = 16 * LDX;            // floats per slot
     static constexpr int W2F = L2 ? SP * LDW + SP : 0;        // floats of the second layer: W2 [SP][LDW] + b2 [SP]
-    static constexpr size_t LDS_BYTES = sizeof(float) * ((size_t)NS * SLOT + WROWS * LDW + W2F) + sizeof(int) * 2 * NS;
+    // TQ: tickets are drawn AHEAD tiles before their chunk's first tile is needed = the gather waves' look-ahead (the node ids of job
+    // n + 2 NPROD) + one chunk + margin
+    static constexpr int AHEAD = (2 * NPROD + PPT - 1) / PPT + F4_TQ_CH + 2;
+    static constexpr size_t LDS_BYTES = sizeof(float) * ((size_t)NS * SLOT + WROWS * LDW + W2F) + sizeof(int) * (2 * NS + (TQ ? F4_TQ_TAB : 0));
 };
 
 // the activation of 4 values with ONE wave-uniform switch around them
@@ -96,14 +136,14 @@ __device__ __forceinline__ int f4_ld_acquire(const int *p) {
     return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-template <int SP, bool HAS_W, int DEPTH, int NC, bool L2, bool INIT = false, bool XC = false, int VPL = 1, bool HDR = false, bool PEERS = false>
+template <int SP, bool HAS_W, int DEPTH, int NC, bool L2, bool INIT = false, bool XC = false, int VPL = 1, bool HDR = false, bool PEERS = false, bool TQ = false>
 __global__ void __launch_bounds__(1024, 8) k_state_fused4(Fused2Args a) {
     // The gate word(s), the W1 fill and the gather waves' first CSR row are all fetched before anything is waited for:
     // three dependent round trips at the head of every launch become one.  Nothing is written to global memory before
     // the gate has been checked (after the fill's barrier).
     int open = a.gate == nullptr;
     for (int i = 0; i < a.n_gate; ++i) open |= a.gate[(size_t)i * a.gate_stride] != 0;
-    using Cfg = Fused4Cfg<SP, NC, L2, XC, VPL>;
+    using Cfg = Fused4Cfg<SP, NC, L2, XC, VPL, TQ>;
     constexpr int NT = Cfg::NT, LPR = Cfg::LPR, IPL = Cfg::IPL, LDX = Cfg::LDX, LDW = Cfg::LDW, NS = Cfg::NS;
 #ifndef GNN_F4_SPIN_MAX
 #define GNN_F4_SPIN_MAX (1 << 22)
@@ -116,6 +156,7 @@ __global__ void __launch_bounds__(1024, 8) k_state_fused4(Fused2Args a) {
     float *W2s = Ws + Cfg::WROWS * LDW;                                  // L2: [SP][LDW] second-layer kernel, then b2 [SP]
     int *fill = reinterpret_cast<int *>(W2s + Cfg::W2F);                 // [NS] gather-wave deposits so far
     int *freed = fill + NS;                                              // [NS] tiles consumed so far
+    int *tab = freed + NS;                                               // TQ: [F4_TQ_TAB] chunk c of this workgroup: 0 = not drawn yet, first tile + 1, or END
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) F4_STAMP(0);
@@ -135,7 +176,32 @@ __global__ void __launch_bounds__(1024, 8) k_state_fused4(Fused2Args a) {
     const int tpx = (ntiles + 7) >> 3;
     const int t_end = min(ntiles, (xcd + 1) * tpx);
     const int t_first = xcd * tpx + lb;
-    const int T = t_first < t_end ? (t_end - t_first + blk_per_xcd - 1) / blk_per_xcd : 0;   // tiles of this workgroup
+    const int T = t_first < t_end ? (t_end - t_first + blk_per_xcd - 1) / blk_per_xcd : 0;   // tiles of this workgroup (static form)
+    // TQ: WG-local tile L is t_first + L * blk_per_xcd below T1 (always inside the range), behind it the (L - T1) % CH-th tile of the
+    // workgroup's (L - T1) / CH-th chunk.  tile_of() is index arithmetic plus, from T1 on, one bounded acquire wait on the LDS table;
+    // L is wave-uniform in both roles.  All words below live in scalar registers.
+    const F4TilePlan tq = TQ ? f4_tile_plan(ntiles, nblk, xcd, Cfg::AHEAD) : F4TilePlan{};
+    int tq_end = F4_TQ_TAB;                        // first chunk of this workgroup known to carry the END mark
+    auto tq_entry = [&](int ci) -> int {           // the published word of chunk ci (END once the wait expired: `bad` says so)
+        if (ci >= tq_end) return F4_TQ_END;
+        int v, spin = 0;
+        while ((v = __builtin_amdgcn_readfirstlane(f4_ld_acquire(&tab[ci]))) == 0) {
+            if (spin >= SPIN_MAX) { bad = 1; v = F4_TQ_END; break; }
+            ++spin; __builtin_amdgcn_s_sleep(1);
+        }
+        if (v == F4_TQ_END) tq_end = ci;
+        return v;
+    };
+    auto tile_of = [&](int L) -> int {             // tile number, -1 (pad tile: every row absent) or F4_TQ_END
+        if constexpr (!TQ) return L < T ? t_first + L * blk_per_xcd : F4_TQ_END;
+        else {
+            if (L < tq.T1) return t_first + L * blk_per_xcd;
+            const int v = tq_entry((L - tq.T1) / F4_TQ_CH);
+            if (v == F4_TQ_END) return F4_TQ_END;
+            const int t = v - 1 + (L - tq.T1) % F4_TQ_CH;
+            return t < t_end ? t : -1;
+        }
+    };
 
     const __amdgpu_buffer_rsrc_t r_C = buf_rsrc(XC ? a.Xc : a.C), r_rows = buf_rsrc(tp.rows), r_state = buf_rsrc(a.state_in),
                                  r_rowptr = buf_rsrc(a.rowptr), r_src = buf_rsrc(a.src), r_w = buf_rsrc(HAS_W ? a.w : nullptr),
@@ -153,6 +219,11 @@ __global__ void __launch_bounds__(1024, 8) k_state_fused4(Fused2Args a) {
         const int m = (t_first + (n / Cfg::PPT) * blk_per_xcd) * 16 + (n % Cfg::PPT) * Cfg::RPWV + qr;
         return (n < njobs && m < count) ? m : -1;
     };
+    auto job_m_of = [&](int tl, int n) -> int {  // TQ: the same for a job whose tile (tile_of(n / PPT)) is tl
+        const int m = tl * 16 + (n % Cfg::PPT) * Cfg::RPWV + qr;
+        return (tl >= 0 && m < count) ? m : -1;
+    };
+    int tlA = 0, tlB = 0;                       // TQ: tiles of the jobs A and B (scalar)
     auto node_of = [&](int m) -> int {
         const int jr = buf_ld_i32(r_rows, m >= 0 ? 4u * (unsigned)m : BUF_OFF);
         return m >= 0 ? (rows ? jr : m) : -1;
@@ -162,7 +233,12 @@ __global__ void __launch_bounds__(1024, 8) k_state_fused4(Fused2Args a) {
 #pragma unroll
     for (int u = 0; u < IPL; ++u) { idsA[u] = 0; wsA[u] = 0.0f; }
     if (wave >= Cfg::NCONS) {
-        jA = node_of(job_m(p)); jB = node_of(job_m(p + Cfg::NPROD));
+        if constexpr (TQ) {                     // (both inside the static prefix: T1 >= AHEAD > 2 NPROD / PPT - the table is not read here)
+            tlA = tile_of(p / Cfg::PPT); tlB = tile_of((p + Cfg::NPROD) / Cfg::PPT);
+            jA = node_of(job_m_of(tlA, p)); jB = node_of(job_m_of(tlB, p + Cfg::NPROD));
+        } else {
+            jA = node_of(job_m(p)); jB = node_of(job_m(p + Cfg::NPROD));
+        }
         if (HDR && a.hdr) {
             // experiment: the first job's row pointers and first source ids of every lane from a per-launch-geometry
             // header (written once per graph by this kernel itself, below): ONE load instead of the dependent pair rowptr -> src
@@ -229,6 +305,7 @@ __global__ void __launch_bounds__(1024, 8) k_state_fused4(Fused2Args a) {
         if (tid < SP) W2s[SP * LDW + tid] = tid < O2 ? tp.b2[tid] : 0.0f;
     }
     if (tid < 2 * NS) fill[tid] = 0;
+    if constexpr (TQ) for (int i = tid; i < F4_TQ_TAB; i += NT) tab[i] = 0;
     __syncthreads();
     if (!open) return;                         // uniform across the launch; nothing has left the CU yet
     if (tid == 0) F4_STAMP(1);
@@ -242,17 +319,34 @@ __global__ void __launch_bounds__(1024, 8) k_state_fused4(Fused2Args a) {
         // Every load is a raw buffer load (predicated off = out of range = 0): no branches around memory operations, so
         // the waits hipcc inserts are exact counts.  The dependent chain  node id -> row pointers -> source ids -> rows
         // is cut by fetching the NEXT job's row pointers and first 16 source ids while this job's rows are in flight.
-        for (int n = p; n < njobs; n += Cfg::NPROD) {
+        for (int n = p; TQ ? tlA != F4_TQ_END : n < njobs; n += Cfg::NPROD) {
             const int t = n / Cfg::PPT;
             const int row = (n % Cfg::PPT) * Cfg::RPWV + qr;
             const int j = jA;
+            // TQ: the wave that starts part 0 of WG-local tile t draws the chunk needed AHEAD tiles later - the atomic goes out first
+            // and is read at the end of the job (loads return in issue order: no wait of its own).  Chunks are drawn in order (the
+            // previous one must be published: it was, CH tiles ago), so tickets grow with the chunk index and END marks stay behind
+            // every real chunk; after an END nothing is drawn any more.
+            bool draws = false;
+            int dci = 0, dprev = 1, ticket = 0;
+            if constexpr (TQ) {
+                const int x = t + Cfg::AHEAD - tq.T1;
+                draws = n % Cfg::PPT == 0 && x >= 0 && x % F4_TQ_CH == 0;
+                if (draws) {
+                    dci = x / F4_TQ_CH;
+                    if (dci > 0) dprev = tq_entry(dci - 1);
+                    if (dprev != F4_TQ_END && lane == 0) ticket = atomicAdd(a.tq_ctr + xcd, 1);
+                }
+            }
 #ifdef GNN_F4_PROFILE
             unsigned long long tg_ = f4_now();
 #endif
             // next job: row pointers now, node id of the job after it
             const int begB = buf_ld_i32(r_rowptr, jB >= 0 ? 4u * (unsigned)jB : BUF_OFF);
             const int endB = buf_ld_i32(r_rowptr, jB >= 0 ? 4u * (unsigned)jB + 4u : BUF_OFF);
-            const int jC = node_of(job_m(n + 2 * Cfg::NPROD));
+            int tlC = 0;
+            if constexpr (TQ) tlC = tile_of((n + 2 * Cfg::NPROD) / Cfg::PPT);
+            const int jC = node_of(TQ ? job_m_of(tlC, n + 2 * Cfg::NPROD) : job_m(n + 2 * Cfg::NPROD));
             const float scl = buf_ld_f32(r_scale, j >= 0 ? 4u * (unsigned)j : BUF_OFF);
             f32x4 own[VPL], acc[VPL];
 #pragma unroll
@@ -316,6 +410,16 @@ __global__ void __launch_bounds__(1024, 8) k_state_fused4(Fused2Args a) {
             jA = jB; begA = begB; endA = endB; jB = jC;
 #pragma unroll
             for (int u = 0; u < IPL; ++u) { idsA[u] = idsB[u]; wsA[u] = wsB[u]; }
+            if constexpr (TQ) {
+                tlA = tlB; tlB = tlC;
+                // publish the chunk BEFORE waiting for a slot: its drawer works on an earlier tile than any of its readers, so no
+                // wait ever depends on a later tile
+                if (draws) {
+                    const int tk = __builtin_amdgcn_readfirstlane(ticket);
+                    const int v = (dprev == F4_TQ_END || tk >= tq.n_chunks) ? F4_TQ_END : tq.pool_begin + tk * F4_TQ_CH + 1;
+                    if (lane == 0 && dci < F4_TQ_TAB) __hip_atomic_store(&tab[dci], v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
 
             const int s = t % NS, round = t / NS;
 #ifdef GNN_F4_PROFILE
@@ -356,7 +460,12 @@ __global__ void __launch_bounds__(1024, 8) k_state_fused4(Fused2Args a) {
 #ifdef GNN_F4_PROFILE
         const unsigned long long tr_ = f4_now();
 #endif
-        for (int t = wave; t < T; t += Cfg::NCONS) {
+        for (int t = wave; TQ || t < T; t += Cfg::NCONS) {
+            int tl = 0;                          // TQ: this tile (-1: a pad tile, whose rows are all absent)
+            if constexpr (TQ) {
+                tl = tile_of(t);
+                if (tl == F4_TQ_END) break;      // (or the wait expired: `bad` is set, the closing barrier is next)
+            }
             // accumulators start from the per-node constant: D = [state|agg].W1 + C  (col = 16*ci + r, row = 4*g + reg).
             // Raw buffer loads (predicated off = out of range = 0): branch-free, all 4*NCT in flight at once, issued
             // BEFORE the slot is ready so they land while the gather waves fill it.
@@ -365,7 +474,7 @@ __global__ void __launch_bounds__(1024, 8) k_state_fused4(Fused2Args a) {
             if (XC) {
                 // XC: the accumulators start from zero and the node's 32 constant inputs arrive as MFMA A fragments (row r of
                 // the tile, columns 4q + g: one 128-byte line per node instead of C's two) - 8 loads per lane instead of 16
-                const int m = (t_first + t * blk_per_xcd) * 16 + r;
+                const int m = TQ ? (tl >= 0 ? tl * 16 + r : count) : (t_first + t * blk_per_xcd) * 16 + r;
                 const int jr = buf_ld_i32(r_rows, m < count ? 4u * (unsigned)m : BUF_OFF);
                 const int jx = m < count ? (rows ? jr : m) : -1;
 #pragma unroll
@@ -377,7 +486,7 @@ __global__ void __launch_bounds__(1024, 8) k_state_fused4(Fused2Args a) {
                 int jrow[4];
 #pragma unroll
                 for (int reg = 0; reg < 4; ++reg) {
-                    const int m = (t_first + t * blk_per_xcd) * 16 + 4 * g + reg;
+                    const int m = TQ ? (tl >= 0 ? tl * 16 + 4 * g + reg : count) : (t_first + t * blk_per_xcd) * 16 + 4 * g + reg;
                     const int jr = buf_ld_i32(r_rows, m < count ? 4u * (unsigned)m : BUF_OFF);
                     jrow[reg] = m < count ? (rows ? jr : m) : -1;
                 }
@@ -559,30 +668,36 @@ __global__ void __launch_bounds__(1024, 8) k_state_fused4(Fused2Args a) {
     }
 }
 
-template <int SP, bool HAS_W, int DEPTH, bool L2 = false, int NC = 4, bool INIT = false, bool XC = false, int VPL = 1, bool HDR = false, bool PEERS = false>
+// workgroups of a node type with `ntiles` of the launch's `total_tiles` tiles
+inline int fused4_blocks(int ntiles, long total_tiles, int budget) {
+    if (ntiles <= 0) return 0;
+    // a workgroup wants >= 4 tiles (one per matrix wave, 16 gather jobs); never more workgroups than that allows
+    const int nb = (int)std::min<long>((ntiles + 3) / 4, std::max<long>(8, budget * (long)ntiles / std::max<long>(total_tiles, 1)));
+    return std::max(8, nb / 8 * 8);          // multiples of 8 (one per XCD), rounded DOWN: the grid stays co-resident
+}
+
+template <int SP, bool HAS_W, int DEPTH, bool L2 = false, int NC = 4, bool INIT = false, bool XC = false, int VPL = 1, bool HDR = false, bool PEERS = false, bool TQ = false>
 int launch_fused4_one(Fused2Args &fa, int n_cu, hipStream_t st) {
-    using Cfg = Fused4Cfg<SP, NC, L2, XC, VPL>;
+    using Cfg = Fused4Cfg<SP, NC, L2, XC, VPL, TQ>;
+    static_assert(2 * Cfg::LDS_BYTES <= 160 * 1024, "two workgroups per CU");
     static bool attr = false;
     if (!attr) {
-        if (hipFuncSetAttribute((const void *)k_state_fused4<SP, HAS_W, DEPTH, NC, L2, INIT, XC, VPL, HDR, PEERS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute((const void *)k_state_fused4<SP, HAS_W, DEPTH, NC, L2, INIT, XC, VPL, HDR, PEERS, TQ>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)Cfg::LDS_BYTES) != hipSuccess) return 1;
         attr = true;
     }
     // 2 workgroups (32 waves) per CU are resident at once.  (More, smaller workgroups - the dispatcher hands the next one to whichever slot
-    // frees first - levelled the +-10 % spread of workgroup run times but paid one more ramp-up each: measured, not kept; docs/rounds/.)
+    // frees first - levelled the +-10 % spread of workgroup run times but paid one more ramp-up each: measured, not kept; docs/rounds/.
+    // The tile queue levels it inside the resident workgroups instead - TQ, launch_fused4_plain: C4 exits 383 .. 473 us -> 446 .. 482 us of
+    // the instrumented launch, 22.89 -> 22.62 ms per forward.  Most of the spread was NOT idle capacity: workgroups that stay to the end slow
+    // each other down, the median exit moves from 427 to 465 us - profiles/f4_tile_queue_timeline.txt.)
     const int budget = 2 * n_cu;
     long total_tiles = 0;
     for (int t = 0; t < fa.n_types; ++t) total_tiles += (fa.tp[t].count + 15) / 16;
     fa.blk_begin[0] = 0;
     for (int t = 0; t < fa.n_types; ++t) {
         const int ntiles = (fa.tp[t].count + 15) / 16;
-        int nb = 0;
-        if (ntiles > 0) {
-            // a workgroup wants >= 4 tiles (one per matrix wave, 16 gather jobs); never more workgroups than that allows
-            nb = (int)std::min<long>((ntiles + 3) / 4, std::max<long>(8, budget * (long)ntiles / std::max<long>(total_tiles, 1)));
-            nb = std::max(8, nb / 8 * 8);          // multiples of 8 (one per XCD), rounded DOWN: the grid stays co-resident
-        }
-        fa.blk_begin[t + 1] = fa.blk_begin[t] + nb;
+        fa.blk_begin[t + 1] = fa.blk_begin[t] + fused4_blocks(ntiles, total_tiles, budget);
     }
     const int grid = fa.blk_begin[fa.n_types];
     if (grid == 0) return 0;
@@ -592,8 +707,27 @@ int launch_fused4_one(Fused2Args &fa, int n_cu, hipStream_t st) {
         GNN_SET_KERNEL_NAME("k_state_fused4<%d,%s,%d,%d,%s,%s,%s>", SP, HAS_W ? "true" : "false", DEPTH, NC, L2 ? "true" : "false", INIT ? "true" : "false", XC ? "true" : "false");
     else
         GNN_SET_KERNEL_NAME("k_state_fused4<%d,%s,%d,%d,%s,%s,%s,%d,%s>", SP, HAS_W ? "true" : "false", DEPTH, NC, L2 ? "true" : "false", INIT ? "true" : "false", XC ? "true" : "false", VPL, HDR ? "true" : "false");
-    k_state_fused4<SP, HAS_W, DEPTH, NC, L2, INIT, XC, VPL, HDR, PEERS><<<grid, Cfg::NT, Cfg::LDS_BYTES, st>>>(fa);
+    k_state_fused4<SP, HAS_W, DEPTH, NC, L2, INIT, XC, VPL, HDR, PEERS, TQ><<<grid, Cfg::NT, Cfg::LDS_BYTES, st>>>(fa);
     return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+// The plain single-type launch: with the tile queue when the caller handed in counters (gnn_loop_forward's main loop) and every
+// workgroup has enough tiles for it (f4_tile_plan), the static form otherwise.  Same kernel name either way: the queue is a launch
+// detail, not a route.
+template <int SP, bool HAS_W, bool L2, bool XC>
+int launch_fused4_plain(Fused2Args &fa, int n_cu, hipStream_t st) {
+    // Only the instantiations that hold the queue's words without spilling carry it: padded width 64, one layer, no per-arc weights, with
+    // the C or the XC constants.  The others (widths 16 / 32, per-arc weights, a second Dense) add 16 .. 32 bytes of scratch per lane with
+    // it (docs/rounds/f4_tile_queue_resources.md) and keep the static form.
+    if constexpr (SP == 64 && !HAS_W && !L2) {
+        if (fa.tq_ctr && fa.n_types == 1 && !fa.tp[0].rows) {
+            const int ntiles = (fa.tp[0].count + 15) / 16;
+            if (f4_tile_plan(ntiles, fused4_blocks(ntiles, ntiles, 2 * n_cu), 7, Fused4Cfg<SP, 4, L2, XC, 1, true>::AHEAD).n_chunks > 0)
+                return launch_fused4_one<SP, HAS_W, 4, L2, 4, false, XC, 1, false, false, true>(fa, n_cu, st);
+        }
+    }
+    fa.tq_ctr = nullptr;
+    return launch_fused4_one<SP, HAS_W, 4, L2, 4, false, XC>(fa, n_cu, st);
 }
 
 inline int launch_fused4(Fused2Args &fa, int SP, int n_cu, hipStream_t st) {
@@ -618,10 +752,10 @@ inline int launch_fused4(Fused2Args &fa, int SP, int n_cu, hipStream_t st) {
             if (fa.w) return launch_fused4_one<SPV, true, 4, false, 4, true>(fa, n_cu, st);                            \
             return fa.Xc ? launch_fused4_one<SPV, false, 4, false, 4, true, true>(fa, n_cu, st) : launch_fused4_one<SPV, false, 4, false, 4, true>(fa, n_cu, st); \
         }                                                                                                             \
-        if (fa.tp[0].W2) return fa.w ? launch_fused4_one<SPV, true, 4, true>(fa, n_cu, st) : launch_fused4_one<SPV, false, 4, true>(fa, n_cu, st); \
-        if (fa.w) return launch_fused4_one<SPV, true, 4>(fa, n_cu, st);                                                \
-        if (fa.Xc) return launch_fused4_one<SPV, false, 4, false, 4, false, true>(fa, n_cu, st);                       \
-        return launch_fused4_one<SPV, false, 4>(fa, n_cu, st);
+        if (fa.tp[0].W2) return fa.w ? launch_fused4_plain<SPV, true, true, false>(fa, n_cu, st) : launch_fused4_plain<SPV, false, true, false>(fa, n_cu, st); \
+        if (fa.w) return launch_fused4_plain<SPV, true, false, false>(fa, n_cu, st);                                   \
+        if (fa.Xc) return launch_fused4_plain<SPV, false, false, true>(fa, n_cu, st);                                  \
+        return launch_fused4_plain<SPV, false, false, false>(fa, n_cu, st);
     switch (SP) {
         F4_CASE(16)
         F4_CASE(32)

@@ -298,6 +298,17 @@ int gnn_debug_host_flag(int32_t **host_out, int32_t **dev_out);
  * by a kernel; `reset` = 1 zeroes it on `stream`, 2 raises it by hand, 0 leaves it).  Handed to gnn_debug_occupy_until as the release flag it makes a co-tenant that leaves
  * exactly when the first wait of the launch under test has expired - a device-side handshake, no clock on the host. */
 int gnn_debug_expiry_beacon(int32_t **beacon_out, int32_t reset, void *stream);
+/* The tile queue of the wave-specialised iteration kernel (GNN_F4_TILE_QUEUE=0 switches it off, read at every call).
+ * gnn_debug_f4_tile_plan: how the tiles of every XCD are dealt in a launch of `n_workgroups` over `ntiles` 16-row tiles when tickets are drawn
+ * `ahead` tiles early - out56 = [8 XCDs][7] = {t_begin, t_end, workgroups of the XCD, T1 (static tiles per workgroup), pool_begin, pool_end,
+ * n_chunks}; n_chunks == 0: the static assignment.  No GPU needed.
+ * gnn_debug_f4_tile_queue_const: which = 0 tiles per chunk, 1 `ahead` of the kernel at `padded_width` (16 / 32 / 64), 2 tiles per workgroup
+ * below which a launch stays static, 3 most chunks of a pool, 4 entries of a workgroup's chunk table.
+ * gnn_debug_f4_last_tickets: tickets drawn by all launches of the last gnn_loop_forward that ran per-iteration fused launches (synchronises
+ * the device; 0 = every launch dealt its tiles statically, -1 = the read failed). */
+void gnn_debug_f4_tile_plan(int32_t ntiles, int32_t n_workgroups, int32_t ahead, int32_t *out56);
+int32_t gnn_debug_f4_tile_queue_const(int32_t which, int32_t padded_width);
+long long gnn_debug_f4_last_tickets(void);
 
 /* ---- node-range sharded loop -------------------------------------------------------------------------
  * One process per GPU; rank r owns a contiguous node range and, per iteration, (1) runs gnn_shard_iteration on its
