@@ -142,14 +142,14 @@ int main(void) {
     hipStream_t stream; CK(hipStreamCreate(&stream));
     a.stream = stream;
     a.workspace_bytes = gnn_loop_workspace_bytes(&a);
-    if (a.workspace_bytes == 0) { fprintf(stderr, "workspace sizing failed: %s\n", gnn_last_error()); return 2; }
+    if (a.workspace_bytes == 0) { fprintf(stderr, "workspace sizing failed: %s (status %d)\n", gnn_last_error(), gnn_last_status()); return 2; }
     CK(hipMalloc(&a.workspace, a.workspace_bytes));
 
     int worst = 0;
     const int paths[4] = {0, GNN_FLAG_UNFUSED, GNN_FLAG_FUSED_GEN2, GNN_FLAG_FUSED_GEN5};
     for (int pi = 0; pi < 4; ++pi) {
         a.flags = paths[pi];
-        if (gnn_loop_forward(&a) != 0) { fprintf(stderr, "gnn_loop_forward: %s\n", gnn_last_error()); return 1; }
+        if (gnn_loop_forward(&a) != 0) { fprintf(stderr, "gnn_loop_forward: %s (status %d)\n", gnn_last_error(), gnn_last_status()); return 1; }
         CK(hipStreamSynchronize(stream));
         static float h_state[N * D], h_out[N * T];
         float h_k = -1.0f;

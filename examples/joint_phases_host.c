@@ -20,7 +20,7 @@
 #include "gnnloop.h"
 
 static int failures = 0;
-#define EXPECT(cond, what) do { if (!(cond)) { fprintf(stderr, "FAILED line %d: %s (last error: %s)\n", __LINE__, what, gnn_last_error()); ++failures; } } while (0)
+#define EXPECT(cond, what) do { if (!(cond)) { fprintf(stderr, "FAILED line %d: %s (last error: %s, status %d)\n", __LINE__, what, gnn_last_error(), gnn_last_status()); ++failures; } } while (0)
 
 /* addresses that are never dereferenced on the host: the library hands them to the device */
 #define FAKE(n) ((void *)(uintptr_t)(0x10000000u + 4096u * (n)))
@@ -120,7 +120,7 @@ int main(void) {
     /* ---- phase 1 with complete arguments: every host check passes; without a device the first HIP call ends it ------------------------ */
     px.node_out = (float *)FAKE(82);
     const int rc = gnn_train_step_ex(&ta, &px);
-    printf("phase 1 on complete arguments: rc = %d (%s)\n", rc, rc ? gnn_last_error() : "ran");
+    printf("phase 1 on complete arguments: rc = %d (%s, status %d)\n", rc, rc ? gnn_last_error() : "ran", rc ? gnn_last_status() : GNN_STATUS_OK);
     EXPECT(rc != 0 && ps.magic == 0, "a phase 1 that did not reach its synchronisation leaves phase_state alone");
     px.phase = GNN_TRAIN_PHASE_BACKWARD;      /* ... so the phase 2 that follows it is refused, not run on a stale tape */
     EXPECT(gnn_train_step_ex(&ta, &px) != 0 && strstr(gnn_last_error(), "not filled by a phase-1 call"), "phase 2 behind a failed phase 1");

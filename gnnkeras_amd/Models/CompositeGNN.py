@@ -164,8 +164,8 @@ class CompositeGNNnodeBased(GNNnodeBased):
         """(k, state, out) for one (merged) heterogeneous graph — reference CompositeGNN.py:242-272.
         `state0` / `seed` / `node_level` as in `GNNnodeBased.Loop`.  `groups` / `group_sets` (inference only): node offsets [G + 1] of G
         merged batches that run as independent loops of one launch, k is then [G] (one entry per set with `group_sets`) - as for
-        homogeneous models, on the typed one-CU-per-group kernel; a shape it does not cover raises `NativeError` ('convergence groups ..',
-        `ops.loop_groups_supported(..., type_dims=...)` != 2).  With `training=True` groups are refused here: the training-mode
+        homogeneous models, on the typed one-CU-per-group kernel; a shape it does not cover raises `NotImplementedError` (the library's
+        GNN_STATUS_NOT_COVERED; `ops.loop_groups_supported(..., type_dims=...)` != 2).  With `training=True` groups are refused here: the training-mode
         convergence groups of composite models are reached one level down, through `LoopTrainer.forward_native(groups=...)`
         (docs/serial_propagation.md)."""
         if groups is not None and training:
@@ -176,20 +176,7 @@ class CompositeGNNnodeBased(GNNnodeBased):
             from .training import LoopTrainer
             if getattr(self, '_trainer', None) is None: self._trainer = LoopTrainer(self)
             x_list = [nodes, arcs, dim_node_label, type_mask, set_mask, output_mask, composite_adjacencies, adjacency, arcnode, nodegraph]
-            # (no row in set_mask & output_mask: the in-library forward wants an output row, the building blocks skip the output network)
-            has_rows = len(self._out_index(_squeeze_last(set_mask).to(nodes.device), _squeeze_last(output_mask).to(nodes.device))) > 0
-            if has_rows and self._trainer._native_forward_applies():
-                # one library call (include/gnnloop.h, forward_only on composite arguments) instead of one aggregate plus one training-mode
-                # MLP call per node type and iteration: what a serial CompositeLGNN fit() runs on every single graph between its layers
-                try:
-                    k, state, out = self._trainer.forward_native(x_list, state0=state0, seed=seed, node_level=node_level)
-                    return torch.tensor(float(k), device=state.device), state, out
-                except nat.NativeError as e:
-                    # an expired grid barrier of the persistent forward kernel (GPU shared with long-running work) or a shape the in-library
-                    # forward does not cover: nothing has been touched - the building blocks below have no cross-workgroup waits
-                    if not any(t in str(e) for t in ('grid barrier', 'cannot be resident', 'train through the building blocks', 'empty graph')): raise
-            tp = self._trainer.forward(x_list, state0=state0, seed=seed, node_level=node_level)
-            return torch.tensor(float(tp.k), device=tp.dev), tp.state.clone(), tp.y_pred
+            return self._trainer.loop_training(x_list, set_mask, output_mask, state0=state0, seed=seed, node_level=node_level)
         nat.require_device(nodes, 'nodes'); nat.require_device(arcs, 'arcs')
         dev = nodes.device
         nodes = nodes.to(torch.float32).contiguous()

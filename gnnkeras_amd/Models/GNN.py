@@ -335,8 +335,7 @@ class _LoopModel:
             node_begin, sets = batches.groups_and_sets({b: node_begin[i + 1] - node_begin[i] for i, b in enumerate(batches)})
         try:
             return self.call(x, training=False, groups=node_begin, **({'group_sets': sets} if sets else {}))
-        except (RuntimeError, nat.NativeError) as e:
-            if 'convergence groups' not in str(e): raise
+        except NotImplementedError:      # (the library's GNN_STATUS_NOT_COVERED, as the custom op raises it: refused before the loop ran)
             return torch.cat([self.call(sequencer[b][0], training=False) for b in batches], dim=0)
 
     def _run_plan(self, plan, launch, device):
@@ -791,21 +790,7 @@ class GNNnodeBased(_LoopModel):
                                           'their results and the moving statistics are invalid')
                 self._last_k = k
                 return k, state, out
-            # (no row in set_mask & output_mask - one graph of a serial LGNN propagation can have none: the in-library step wants at least
-            # one output row, the building blocks below skip the output network and leave its moving statistics alone)
-            has_rows = len(self._out_index(_squeeze_last(set_mask).to(nodes.device), _squeeze_last(output_mask).to(nodes.device))) > 0
-            if has_rows and self._trainer._native_forward_applies():
-                # one library call (include/gnnloop.h ABI 9, forward_only) instead of ~ 40 building-block calls: what a serial LGNN fit()
-                # runs on every single graph between its layers (reference LGNN.py:325-337)
-                try:
-                    k, state, out = self._trainer.forward_native(x_list, state0=state0, seed=seed, node_level=node_level)
-                    return torch.tensor(float(k), device=state.device), state, out
-                except nat.NativeError as e:
-                    # an expired grid barrier of the persistent forward kernel (GPU shared with long-running work) or a shape the in-library
-                    # forward does not cover: nothing has been touched - the building blocks below have no cross-workgroup waits
-                    if not any(t in str(e) for t in ('grid barrier', 'cannot be resident', 'train through the building blocks', 'empty graph')): raise
-            tp = self._trainer.forward(x_list, state0=state0, seed=seed, node_level=node_level)
-            return torch.tensor(float(tp.k), device=tp.dev), tp.state.clone(), tp.y_pred
+            return self._trainer.loop_training(x_list, set_mask, output_mask, state0=state0, seed=seed, node_level=node_level)
         nat.require_device(nodes, 'nodes'); nat.require_device(arcs, 'arcs')
         dev = nodes.device
         set_mask, output_mask = _squeeze_last(set_mask).to(dev), _squeeze_last(output_mask).to(dev)

@@ -911,6 +911,26 @@ class LoopTrainer:
                                     group_out_begin=group_out_begin)
         return r['k'], r['state'], r['y_pred']
 
+    def loop_training(self, x_list, set_mask, output_mask, state0=None, seed=None, node_level=False):
+        """`Loop(..., training=True)` of both model kinds: (k as a device scalar, state, output rows).  One library call
+        (include/gnnloop.h ABI 9, forward_only) instead of ~ 40 building-block calls - what a serial LGNN / CompositeLGNN fit() runs on
+        every single graph between its layers (reference LGNN.py:325-337) - where `_native_forward_applies()` and the graph has a row in
+        `set_mask & output_mask` (one graph of a serial LGNN propagation can have none: the in-library forward wants an output row, the
+        building blocks skip the output network and leave its moving statistics alone).  A shape the library does not cover, or a
+        persistent forward kernel that was not resident (GPU shared with long-running work), has touched nothing: the building blocks,
+        which have no cross-workgroup waits, run it."""
+        from .GNN import _squeeze_last
+        dev = x_list[0].device
+        has_rows = len(self.model._out_index(_squeeze_last(set_mask).to(dev), _squeeze_last(output_mask).to(dev))) > 0
+        if has_rows and self._native_forward_applies():
+            try:
+                k, state, out = self.forward_native(x_list, state0=state0, seed=seed, node_level=node_level)
+                return torch.tensor(float(k), device=state.device), state, out
+            except (nat.NotCovered, nat.NotResident):
+                pass
+        tp = self.forward(x_list, state0=state0, seed=seed, node_level=node_level)
+        return torch.tensor(float(tp.k), device=tp.dev), tp.state.clone(), tp.y_pred
+
     def _train_step_native(self, x_list, y, sample_weight, state0, seed, apply, forward_only=False, node_level=False, groups=None,
                            group_out_begin=None, phase_forward=False):
         """One `gnn_train_step` call: training-mode forward, loss, BPTT; the tape and every scratch buffer live in one cached
@@ -1232,17 +1252,13 @@ class LoopTrainer:
         if self._native_step_applies(y):
             try:
                 return self._train_step_native(x_list, y, sample_weight, state0, seed, apply)
-            except nat.NativeError as e:
+            except nat.NotCovered:
+                pass        # a configuration the in-library step does not cover (its plan says so before anything runs) simply takes the general path
+            except nat.NotResident:
                 # the persistent forward kernel's grid barrier expired (GPU shared with other long-running work: not all of its
                 # workgroups resident within GNN_WAIT_MS).  The in-library step checks that right behind the forward loop - before the
                 # moving statistics, the gradients or the weights are touched - so the step is simply run again on the building
                 # blocks below, which have no cross-workgroup waits.
-                # a configuration the in-library step does not cover (its plan says so before anything runs) simply takes the general path
-                not_covered = any(t in str(e) for t in ('train through the building blocks', 'requires max_iteration', 'empty graph', 'homogeneous models only'))
-                if 'grid barrier' not in str(e) and 'cannot be resident' not in str(e) and not not_covered: raise
-                if not_covered:
-                    self.resolve_pending()
-                    return self._train_step_general(x_list, y, sample_weight, state0, seed, apply)
                 import warnings
                 warnings.warn('the persistent training kernels could not keep their workgroups resident (GPU shared with other '
                               'long-running work?): this step runs on the general kernels', RuntimeWarning, stacklevel=3)

@@ -28,7 +28,7 @@ FLAG_TRAIN_HIDDEN_SMALL = 1 << 8        # training steps only, opt-in: a state n
 XC_FILL, XC_VALID = 0, 1                # enum gnn_xc_mode
 FLAG_FUSED_GEN2, FLAG_FUSED_GEN4, FLAG_FUSED_GEN5, FLAG_FUSED_GEN6, FLAG_FUSED_GEN7 = 2 << 4, 4 << 4, 5 << 4, 6 << 4, 7 << 4     # pin the fused-kernel generation (tests, tuning)
 
-EXPORTS = ['gnn_last_error', 'gnn_last_kernel_name', 'gnn_abi_version', 'gnn_struct_size', 'gnn_loop_workspace_bytes', 'gnn_loop_forward', 'gnn_loop_groups_supported', 'gnn_loop_group_max_nodes', 'gnn_aggregate',
+EXPORTS = ['gnn_last_error', 'gnn_last_status', 'gnn_last_kernel_name', 'gnn_abi_version', 'gnn_struct_size', 'gnn_loop_workspace_bytes', 'gnn_loop_forward', 'gnn_loop_groups_supported', 'gnn_loop_group_max_nodes', 'gnn_aggregate',
            'gnn_loop_xc_applies', 'gnn_loop_route_name', 'gnn_train_xc_applies',
            'gnn_mlp_workspace_bytes', 'gnn_mlp_forward', 'gnn_converged', 'gnn_state_step', 'gnn_state_step_agg', 'gnn_state_ld', 'gnn_debug_occupy', 'gnn_debug_occupy_until', 'gnn_debug_expiry_beacon', 'gnn_debug_host_flag',
            'gnn_debug_f4_tile_plan', 'gnn_debug_f4_tile_queue_const', 'gnn_debug_f4_last_tickets',
@@ -180,6 +180,19 @@ class NativeError(RuntimeError):
     pass
 
 
+# enum gnn_status (include/gnnloop.h, Conventions): what kind of failure a non-zero return was - `check` turns it into the exception's type,
+# so a caller that falls back catches a class and never reads the message
+STATUS_OK, STATUS_ERROR, STATUS_NOT_COVERED, STATUS_NOT_RESIDENT = range(4)
+
+
+class NotCovered(NativeError, NotImplementedError):
+    """Well-formed arguments this entry point has no kernel form for (decided before the first launch): run the building blocks."""
+
+
+class NotResident(NativeError):
+    """A persistent kernel's workgroups were not all resident; nothing of the model has been touched: rerun on kernels that do not wait."""
+
+
 def build(verbose: bool = False) -> str:
     """Compile libgnnloop.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     res = subprocess.run(['make', '-j3', '-C', CSRC, 'all'], capture_output=True, text=True)      # the sanitizer build of the host side is tests/test_abi.py's own (`make asan`)
@@ -316,6 +329,7 @@ def lib():
             'gnn_comm_create': (C.c_int, [i32, i32, vp, C.POINTER(vp)]),
             'gnn_comm_destroy': (C.c_int, [vp]),
             'gnn_shard_loop': (C.c_int, [C.POINTER(ShardLoopArgs)]),
+            'gnn_last_status': (C.c_int, []),
         }
         for name, (res, args) in protos.items():
             fn = getattr(l, name)
@@ -336,7 +350,8 @@ def lib():
 
 def check(rc: int):
     if rc != 0:
-        raise NativeError(lib().gnn_last_error().decode())
+        kind = {STATUS_NOT_COVERED: NotCovered, STATUS_NOT_RESIDENT: NotResident}.get(lib().gnn_last_status(), NativeError)
+        raise kind(lib().gnn_last_error().decode())
 
 
 def require_device(t: torch.Tensor, name: str):

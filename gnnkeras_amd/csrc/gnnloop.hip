@@ -36,14 +36,21 @@
 namespace {
 
 thread_local char g_err[512] = "";
+thread_local int g_status = GNN_STATUS_OK;      // enum gnn_status of the failure g_err describes (gnn_last_status)
 
-int fail(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
+// Every failing call returns 1 whatever its status: inside this file a 2 from a launcher means "hand over to the next kernel form" and
+// travels through TRY(), so the public status is a query next to the message, never a return code.
+int fail_va(int status, const char *fmt, va_list ap) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
+    g_status = status;
     return 1;
 }
+#define GNN_FAIL_BODY(status) va_list ap; va_start(ap, fmt); fail_va(status, fmt, ap); va_end(ap); return 1
+int fail(const char *fmt, ...) { GNN_FAIL_BODY(GNN_STATUS_ERROR); }                    // malformed arguments, HIP failures: everything else
+int fail_as(int status, const char *fmt, ...) { GNN_FAIL_BODY(status); }
+int not_covered(const char *fmt, ...) { GNN_FAIL_BODY(GNN_STATUS_NOT_COVERED); }       // well-formed, no kernel form here: decided before the first launch
+int not_resident(const char *fmt, ...) { GNN_FAIL_BODY(GNN_STATUS_NOT_RESIDENT); }     // a persistent kernel's workgroups were not all resident
+#undef GNN_FAIL_BODY
 
 #define HIP_OK(expr)                                                                                    \
     do {                                                                                                \
@@ -513,7 +520,7 @@ int make_plan(const gnn_loop_args_t &a, void *ws, Plan &p, bool validate_ptrs) {
     p.composite = a.composite != 0;
     p.T = p.composite ? a.n_types : 1;
     if (p.T < 1 || p.T > GNN_MAX_TYPES) return fail("n_types %d out of [1,%d]", p.T, GNN_MAX_TYPES);
-    if (p.composite && a.max_iteration < 1) return fail("composite GNN requires max_iteration > 0");
+    if (p.composite && a.max_iteration < 1) return not_covered("composite GNN requires max_iteration > 0");
     p.N = a.n_nodes; p.E = a.n_arcs; p.L = a.dim_node_label; p.A = a.dim_arc_label;
     p.S = state_width(a);
     if (p.S < 1) return fail("state width is 0 (state_dim == 0 and dim_node_label == 0)");
@@ -1160,6 +1167,7 @@ int gnn_f4_wg_times(unsigned long long *out4096) {
 #endif
 
 const char *gnn_last_error(void) { return g_err; }
+int gnn_last_status(void) { return g_status; }
 const char *gnn_last_kernel_name(void) { return gnn::last_kernel_name(); }
 int gnn_abi_version(void) { return GNN_ABI_VERSION; }
 size_t gnn_struct_size(int which) {
@@ -1246,7 +1254,7 @@ int gnn_loop_forward(const gnn_loop_args_t *args) {
     // Graphs the whole-loop kernel covers: one set-up launch, the loop, the output stage.  Everything else: the general
     // set-up (one launch per constant) and one launch per iteration.
     const LoopRoute route = route_loop(a, p);
-    if (route.refused) return fail("%s", route.refused);
+    if (route.refused) return fail_as(route.refused_status, "%s", route.refused);
     switch (route.whole) {
     // Groups that fit the LDS of one CU: set-up launch, one workgroup per group, output stage.
     case WholeLoop::lds: {
@@ -1256,6 +1264,7 @@ int gnn_loop_forward(const gnn_loop_args_t *args) {
         TRY(setup_small(a, q, st));
         if (a.ev_loop_begin) HIP_OK(hipEventRecord((hipEvent_t)a.ev_loop_begin, st));
         const int rc = loop_lds(a, p, st);
+        // (an error, not NOT_COVERED: the route said this kernel covers the shape, and no caller has ever fallen back on this text)
         if (rc != 0) return rc == 2 ? fail("LDS-resident loop kernel does not cover this shape") : 1;
         if (a.ev_loop_end) HIP_OK(hipEventRecord((hipEvent_t)a.ev_loop_end, st));
         return output_stage(a, p, st);
@@ -1275,7 +1284,8 @@ int gnn_loop_forward(const gnn_loop_args_t *args) {
         LAUNCH_OK();
         if (a.ev_loop_begin) HIP_OK(hipEventRecord((hipEvent_t)a.ev_loop_begin, st));
         const int rc = loop_lds_types(a, p, st);
-        if (rc != 0) return rc == 2 ? fail("LDS-resident loop kernel does not cover these convergence groups") : 1;
+        // (the typed group ranges are device data: the one refusal behind launches - workspace and k_out are written, no result is)
+        if (rc != 0) return rc == 2 ? not_covered("LDS-resident loop kernel does not cover these convergence groups") : 1;
         if (a.ev_loop_end) HIP_OK(hipEventRecord((hipEvent_t)a.ev_loop_end, st));
         return output_stage(a, p, st);
     }
@@ -1635,7 +1645,7 @@ static int shard_iteration(const gnn_loop_args_t &a, const float *state_in_full,
     TRY(make_plan(a, a.workspace, p, false));
     if (row_base < 0 || row_base + p.N > a.adjacency.n_src) return fail("row_base out of the full buffer");
     const IterRoute it = route_iteration(a, p, knobs(a.flags));
-    if (peers && !it.fused()) return fail("peer stores need the fused iteration kernel");
+    if (peers && !it.fused()) return not_covered("peer stores need the fused iteration kernel");
     hipStream_t st = (hipStream_t)a.stream;
     const int *g;
     TRY(shard_gate(a, p, gate, n_gate, gate_stride, iteration, flag_out, &g));

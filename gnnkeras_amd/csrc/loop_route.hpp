@@ -26,6 +26,8 @@ struct LoopRoute {
     bool xc_loop;       // every iteration on the XC form of the wave-specialised kernel: C is never read
     bool xc_line;       // ... of a homogeneous graph: the constants line is filled in place / adopted (gnn_loop_args_t::xc)
     const char *refused;    // gnn_loop_forward fails with this text before its first launch (NULL: it runs); `whole` / `small_setup` then still say what the shapes alone would run
+    int refused_status;     // ... and with this enum gnn_status (refuse() below)
+    void refuse(int status, const char *text) { refused = text; refused_status = status; }
 };
 
 // the state network's LAST activation is a softmax (legal: reference MLP.py:12-78 takes any Keras activation): only the
@@ -177,7 +179,7 @@ LoopRoute route_loop(const gnn_loop_args_t &a, const Plan &p) {
     if (p.n_groups > 0 && fz == 1 && lds_covers(a, p, k) && setup_small_covers(a, p)) { r.whole = WholeLoop::lds; return r; }
     if (p.n_groups > 0 && p.composite) {
         if (fz == 1 && lds_types_covers(a, p, k)) r.whole = WholeLoop::lds_types;
-        else r.refused = "convergence groups of a composite graph need the one-CU-per-group kernel (gnn_loop_groups_supported() != 2 for these args)";
+        else r.refuse(GNN_STATUS_NOT_COVERED, "convergence groups of a composite graph need the one-CU-per-group kernel (gnn_loop_groups_supported() != 2 for these args)");
         return r;
     }
     const bool soft = state_softmax(a, p);
@@ -185,10 +187,11 @@ LoopRoute route_loop(const gnn_loop_args_t &a, const Plan &p) {
     r.small_setup = small && setup_small_covers(a, p);
     r.try_mid = !r.small_setup && fz == 1 && !soft && mid_covers(a, p, k);
     r.whole = small ? WholeLoop::small : r.try_mid ? WholeLoop::mid : WholeLoop::none;
-    if (p.has_sets) r.refused = "convergence group sets need the one-CU-per-group form (gnn_loop_groups_supported() != 2 for these args)";
+    // (sets: an error, not NOT_COVERED - the callers that rerun a refused merge batch by batch have never done so for this one)
+    if (p.has_sets) r.refuse(GNN_STATUS_ERROR, "convergence group sets need the one-CU-per-group form (gnn_loop_groups_supported() != 2 for these args)");
     else if (p.n_groups > GNN_MAX_GROUPS)
-        r.refused = "more than " GNN_ROUTE_STR(GNN_MAX_GROUPS) " convergence groups need every group to fit one CU's LDS (gnn_loop_groups_supported() != 2)";
-    else if (p.n_groups > 0 && !r.small_setup) r.refused = "convergence groups need the whole-loop kernel (gnn_loop_groups_supported() == 0 for these args)";
+        r.refuse(GNN_STATUS_NOT_COVERED, "more than " GNN_ROUTE_STR(GNN_MAX_GROUPS) " convergence groups need every group to fit one CU's LDS (gnn_loop_groups_supported() != 2)");
+    else if (p.n_groups > 0 && !r.small_setup) r.refuse(GNN_STATUS_NOT_COVERED, "convergence groups need the whole-loop kernel (gnn_loop_groups_supported() == 0 for these args)");
     if (r.refused) return r;
     // the XC form: decided from the static part of the small kernel's answer, and only where the mid-size kernel is not tried
     r.xc_loop = p.xc_ok && !small && fz == 1 && !r.try_mid && p.SP != 128 && !iter_adjacency(a, p).w &&

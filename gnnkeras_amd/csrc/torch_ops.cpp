@@ -107,7 +107,13 @@ void mlp_of(gnn_mlp_t &m, at::TensorList weights, at::IntArrayRef spec, size_t *
     *spos += 3 + 2 * (size_t)m.n_layers;
 }
 
-void check_rc(int rc) { TORCH_CHECK(rc == 0, "libgnnloop: ", gnn_last_error()); }
+// a failed library call as an exception: NotImplementedError (a RuntimeError in Python) for what the library merely does not cover
+// (gnn_last_status(), include/gnnloop.h), RuntimeError for everything else
+void check_rc(int rc) {
+    if (rc == 0) return;
+    TORCH_CHECK_NOT_IMPLEMENTED(gnn_last_status() != GNN_STATUS_NOT_COVERED, "libgnnloop: ", gnn_last_error());
+    TORCH_CHECK(false, "libgnnloop: ", gnn_last_error());
+}
 
 void *current_stream(const at::Device &dev) { return (void *)c10::hip::getCurrentHIPStream(dev.index()).stream(); }
 
@@ -234,7 +240,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> loop_forward(
     at::Tensor out = at::empty({rows_out, a.net_output.units[a.net_output.n_layers - 1]}, opts);
     a.k_out = k.data_ptr<float>(); a.state_out = state.data_ptr<float>(); a.out = out.data_ptr<float>();
     const size_t bytes = gnn_loop_workspace_bytes(&a);
-    TORCH_CHECK(bytes != 0, "libgnnloop: ", gnn_last_error());
+    check_rc(bytes == 0);
     at::Tensor ws = workspace(bytes, dev, &a.workspace);
     a.workspace_bytes = bytes;
     check_rc(gnn_loop_forward(&a));
@@ -370,7 +376,7 @@ std::tuple<at::Tensor, at::Tensor> state_step(const at::Tensor &nodes, const at:
     a.stream = current_stream(dev);
     at::Tensor out = at::empty_like(state), flag = at::empty({1}, at::TensorOptions().dtype(at::kInt).device(dev));
     const size_t bytes = gnn_loop_workspace_bytes(&a);
-    TORCH_CHECK(bytes != 0, "libgnnloop: ", gnn_last_error());
+    check_rc(bytes == 0);
     at::Tensor ws = workspace(bytes, dev, &a.workspace);
     a.workspace_bytes = bytes;
     if (given) {

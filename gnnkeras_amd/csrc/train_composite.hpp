@@ -94,9 +94,9 @@ int cplan_dims_and_path(const gnn_train_args_t &ta, void *ws, CPlan &p) {
     const gnn_loop_args_t &a = ta.loop;
     memset(&p, 0, sizeof(p));
     if (a.abi_version != GNN_ABI_VERSION) return fail("abi_version %d != %d", a.abi_version, GNN_ABI_VERSION);
-    if (a.n_nodes < 1) return fail("gnn_train_step: empty graph");
+    if (a.n_nodes < 1) return not_covered("gnn_train_step: empty graph");
     if (a.n_types < 1 || a.n_types > GNN_MAX_TYPES) return fail("n_types %d out of [1,%d]", a.n_types, GNN_MAX_TYPES);
-    if (a.max_iteration < 1) return fail("composite GNN requires max_iteration > 0");
+    if (a.max_iteration < 1) return not_covered("composite GNN requires max_iteration > 0");
     p.N = a.n_nodes; p.E = a.n_arcs; p.L = a.dim_node_label; p.A = a.dim_arc_label; p.n_types = a.n_types;
     p.S = a.state_dim > 0 ? a.state_dim : a.dim_node_label;
     p.K = a.max_iteration; p.M = a.n_out;

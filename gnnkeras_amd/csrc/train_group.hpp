@@ -45,16 +45,16 @@ int train_groups_supported(const gnn_train_args_t &ta, Make make, Covered covere
 template <class GP, class Make, class Covered, class Inputs>
 int train_group_checks(const gnn_train_args_t &ta, GP &gp, Make make, Covered covered, Inputs inputs) {
     const gnn_loop_args_t &a = ta.loop;
-    if (!ta.forward_only) return fail("gnn_train_step: convergence groups need forward_only (a grouped training step is not implemented)");
+    if (!ta.forward_only) return not_covered("gnn_train_step: convergence groups need forward_only (a grouped training step is not implemented)");
     if (ta.prev_grads_ok_host) return fail("gnn_train_step(forward_only): prev_grads_ok_host must be NULL");
     if (ta.n_groups < 0) return fail("n_groups < 0");
     TRY(make(ta, ta.tape, gp));
     const auto &p = gp.p;
-    if (!covered(ta, p)) return fail("gnn_train_step: convergence groups do not cover this shape (gnn_train_groups_supported() == %d)", GNN_TRAIN_GROUPS_UNCOVERED);
+    if (!covered(ta, p)) return not_covered("gnn_train_step: convergence groups do not cover this shape (gnn_train_groups_supported() == %d)", GNN_TRAIN_GROUPS_UNCOVERED);
     const int tab = train_group_tables(ta, p.N, p.M, true, &gp.max_nodes);
     if (tab < 0) return 1;
-    if (tab > 0) return fail("group %d has %d nodes (at most %d per convergence group: gnn_train_groups_supported())", tab - 1,
-                             ta.group_node_begin[tab] - ta.group_node_begin[tab - 1], gnn::GROUP_CAP);
+    if (tab > 0) return not_covered("group %d has %d nodes (at most %d per convergence group: gnn_train_groups_supported())", tab - 1,
+                                    ta.group_node_begin[tab] - ta.group_node_begin[tab - 1], gnn::GROUP_CAP);
     if (ta.tape_bytes < gp.bytes) return fail("tape too small: %zu < %zu bytes", ta.tape_bytes, gp.bytes);
     TRY(check_csr(a.adjacency, "adjacency", p.N, p.N));
     TRY(check_csr(a.arcnode, "arcnode", p.N, p.E));

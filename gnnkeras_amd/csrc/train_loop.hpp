@@ -61,7 +61,7 @@ int run_dropout(const DropRun &r, int q, const float *x, int ldx, float *y, int 
 int check_dropout(const gnn_dropout_spec_t &d, const gnn_mlp_t &m, const char *name) {
     if (d.n < 0 || d.n > GNN_MAX_DROPOUT) return fail("%s: %d dropout layers (0 .. %d)", name, d.n, GNN_MAX_DROPOUT);
     for (int i = 0; i < d.n; ++i) {
-        if (d.pos[i] == 0) return fail("%s: Dropout in front of the first Dense layer (position 0): such networks train through the building blocks", name);
+        if (d.pos[i] == 0) return not_covered("%s: Dropout in front of the first Dense layer (position 0): such networks train through the building blocks", name);
         if (d.pos[i] < 0 || d.pos[i] > m.n_layers || (i > 0 && d.pos[i] < d.pos[i - 1])) return fail("%s: dropout positions must ascend within [1, n_layers]", name);
         if (!(d.rate[i] > 0.0f && d.rate[i] < 1.0f)) return fail("%s: dropout rate %g outside (0, 1)", name, (double)d.rate[i]);
     }
@@ -184,8 +184,8 @@ int make_train_plan(const gnn_train_args_t &ta, void *ws, TrainPlan &p) {
     const gnn_loop_args_t &a = ta.loop;
     memset(&p, 0, sizeof(p));
     if (a.abi_version != GNN_ABI_VERSION) return fail("abi_version %d != %d", a.abi_version, GNN_ABI_VERSION);
-    if (a.composite) return fail("gnn_train_step: homogeneous models only");
-    if (a.n_nodes < 1) return fail("gnn_train_step: empty graph");
+    if (a.composite) return not_covered("gnn_train_step: homogeneous models only");
+    if (a.n_nodes < 1) return not_covered("gnn_train_step: empty graph");
     // (a.n_heavy_segments > 0: the training kernels walk the plain adjacency all the same)
     p.N = a.n_nodes; p.E = a.n_arcs; p.L = a.dim_node_label; p.A = a.dim_arc_label; p.d = a.state_dim;
     p.S = a.state_dim > 0 ? a.state_dim : a.dim_node_label;
@@ -785,7 +785,7 @@ int launch_persistent(Kern kern, const Args &args, const gnn::TileTab &tt, int n
     }
     // every workgroup waits for the others at the grid barriers: the grid must fit the device (n_wg <= CUs by the plan; this asks the
     // runtime about THIS kernel's registers / LDS)
-    if (!gnn::persistent_fits(fn, gnn::TS_NT, lds, n_wg, device_cus())) return fail("persistent training kernel: %d workgroups cannot be resident at once", n_wg);
+    if (!gnn::persistent_fits(fn, gnn::TS_NT, lds, n_wg, device_cus())) return not_resident("persistent training kernel: %d workgroups cannot be resident at once", n_wg);
     kern<<<n_wg, gnn::TS_NT, lds, st>>>(args, tt, extra...);
     LAUNCH_OK();
     return 0;
@@ -1018,7 +1018,7 @@ int read_k(const gnn_train_args_t &ta, StepPlan &p, int *k_out, hipStream_t st) 
     const int k = (int)k_f2[0];
     *ta.k_host = *k_out = k;
     if (k_f2[1] == 1.0f) return fail("tile_node_begin: an arc of `adjacency` leaves its tile");
-    if (k_f2[1] != 0.0f) return fail("a workgroup of the persistent training kernel never arrived at a grid barrier (not resident?)");
+    if (k_f2[1] != 0.0f) return not_resident("a workgroup of the persistent training kernel never arrived at a grid barrier (not resident?)");
     if (k < 0 || k > p.K) return fail("iteration count %d out of range", k);
     if (k_f2[2] != 0.0f) p.head_fast = false;
     return 0;
@@ -1573,9 +1573,10 @@ int gnn_train_step_ex(const gnn_train_args_t *args, const gnn_train_phase_args_t
     // the word on the tape: the copy must have LANDED when the caller looks at it (the caller's own view of the word is stale by then).  A call
     // that fails in front of them leaves *prev_grads_ok_host as the caller initialised it (a sentinel) and the word on the tape untouched.
     if (rc != 0 && args->prev_grads_ok_host && args->tape) {
-        const std::string msg = gnn_last_error();                 // (the synchronisation must not replace the message)
+        const std::string msg = gnn_last_error();                 // (the synchronisation must not replace the message and its status)
+        const int status = gnn_last_status();
         (void)hipStreamSynchronize((hipStream_t)args->loop.stream);
-        fail("%s", msg.c_str());
+        fail_as(status, "%s", msg.c_str());
     }
     return rc;
 }
@@ -1589,8 +1590,8 @@ static int check_phase_args(const gnn_train_args_t &ta, const gnn_train_phase_ar
     const bool used = px.phase != 0 || px.loss_scale != 0.0f || px.phase_state || px.node_out || px.d_pred_extra || px.d_out_extra || px.d_state_extra ||
                       px.d_nodes || px.d_arc_labels;
     if (!used) return 0;
-    if (p.path == TrainPath::big) return fail("gnn_train_step_ex: the row-streaming path (>= GNN_TRAIN_BIG_MIN_NODES nodes) has no phases / upstream gradients / label gradients: such steps train through the building blocks");
-    if (p.H1s > gnn::LG_MAX_H) return fail("gnn_train_step_ex: first state layer of %d units (at most %d)", p.H1s, gnn::LG_MAX_H);
+    if (p.path == TrainPath::big) return not_covered("gnn_train_step_ex: the row-streaming path (>= GNN_TRAIN_BIG_MIN_NODES nodes) has no phases / upstream gradients / label gradients: such steps train through the building blocks");
+    if (p.H1s > gnn::LG_MAX_H) return not_covered("gnn_train_step_ex: first state layer of %d units (at most %d)", p.H1s, gnn::LG_MAX_H);
     if (px.phase != 0 && !px.phase_state) return fail("gnn_train_step_ex: phase %d needs phase_state", px.phase);
     if (px.phase == GNN_TRAIN_PHASE_BACKWARD && px.phase_state->magic != PHASE_MAGIC) return fail("gnn_train_step_ex: phase_state was not filled by a phase-1 call");
     if (px.phase == GNN_TRAIN_PHASE_BACKWARD && (px.phase_state->k < 0 || px.phase_state->k > p.K)) return fail("gnn_train_step_ex: phase_state holds k = %d", px.phase_state->k);
@@ -1613,7 +1614,7 @@ static int train_step_impl(const gnn_train_args_t &ta, const gnn_train_phase_arg
     if (phase < 0 || phase > GNN_TRAIN_PHASE_BACKWARD) return fail("gnn_train_step_ex: unknown phase %d", phase);
     if ((phase != 0 || px.loss_scale != 0.0f || px.d_pred_extra || px.d_out_extra || px.d_state_extra || px.d_nodes || px.d_arc_labels || px.node_out) &&
         (ta.n_groups != 0 || a.composite || fwd_only))
-        return fail("gnn_train_step_ex: phases, upstream gradients and label gradients cover whole steps of homogeneous models only (gnn_train_phases_supported)");
+        return not_covered("gnn_train_step_ex: phases, upstream gradients and label gradients cover whole steps of homogeneous models only (gnn_train_phases_supported)");
     if (ta.n_groups != 0) return train_forward_groups(ta);         // ABI 10: independent convergence groups (train_group.hpp)
     if (a.composite) return train_step_composite(ta);             // one state network per node type (train_composite.hpp); honours forward_only
     if (fwd_only && ta.prev_grads_ok_host) return fail("gnn_train_step(forward_only): prev_grads_ok_host must be NULL");

@@ -13,6 +13,18 @@
  *     device scalar;
  *   - all arithmetic is float32 (tf.keras.backend.floatx(), reference graph_class.py:43); ids are int32;
  *   - return value: 0 = ok, non-zero = error, message via gnn_last_error() (thread-local). Never aborts.
+ *   - WHAT KIND of error: gnn_last_status() (thread-local, enum gnn_status), meaningful after a call returned non-zero, like the message.
+ *     The return value itself does not tell them apart (a failing call returns what it always returned).  A caller that falls back
+ *     decides on the status, never on the wording of the message:
+ *       GNN_STATUS_NOT_COVERED   the arguments are well-formed, but this entry point has no kernel form for them.  Decided on host data
+ *                                before the first launch: nothing was written.  The caller runs the building blocks (a training step) or
+ *                                one call per batch (convergence groups).  One refusal of gnn_loop_forward comes later: the typed one-CU-
+ *                                per-group launcher sizes its ranges at launch, behind the set-up - workspace and k_out are written then,
+ *                                no result is;
+ *       GNN_STATUS_NOT_RESIDENT  a persistent kernel could not have, or did not keep, all its workgroups resident: the occupancy check at
+ *                                launch, or an expired bounded wait seen at the step's one synchronisation.  No moving statistic, gradient
+ *                                or weight has been touched: the caller may rerun on kernels without cross-workgroup waits;
+ *       GNN_STATUS_ERROR         everything else: malformed arguments, HIP failures.
  */
 #ifndef GNNLOOP_H
 #define GNNLOOP_H
@@ -203,6 +215,8 @@ enum gnn_xc_mode { GNN_XC_FILL = 0, GNN_XC_VALID = 1 };
 #define GNN_MAX_GROUPS_RESIDENT (1 << 20) /* groups of a call that keeps every group's state in the LDS of one CU        */
 
 const char *gnn_last_error(void);
+enum gnn_status { GNN_STATUS_OK = 0, GNN_STATUS_ERROR = 1, GNN_STATUS_NOT_COVERED = 2, GNN_STATUS_NOT_RESIDENT = 3 };
+int gnn_last_status(void);   /* thread-local; meaningful after a call returned non-zero, like gnn_last_error() (Conventions above) */
 /* Name (with template arguments) of the state-transition kernel this thread launched last, e.g.
  * "k_state_fused4<64,false,4,4,false>" - what a rocprofv3 kernel trace of the same call shows; "" before any launch. */
 const char *gnn_last_kernel_name(void);

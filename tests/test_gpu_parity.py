@@ -1143,7 +1143,7 @@ def test_groups_are_refused_where_unsupported(mutag_graphs):
     model = GNNgraphBased(ns, no, 100, 5, 0.01)
     assert model._group_plan(seq, torch.device('cuda', 0)) is None
     x, begin = seq.merged_batches(0, 2)
-    with pytest.raises(RuntimeError, match='groups'):
+    with pytest.raises(NotImplementedError, match='groups'):
         model.Loop(*model.process_inputs(x), groups=begin)
     assert np.array_equal(model.predict(seq).shape, (64, 2))
 

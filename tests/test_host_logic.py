@@ -423,3 +423,54 @@ def test_graphobject_copy_field_by_field_equals_the_constructor_path(mutag_graph
     g = mutag_graphs[3].copy()
     g.nodes = np.concatenate([g.nodes, g.nodes], axis=1)         # what LGNN's propagation does: wider labels -> DIM_NODE_LABEL follows the array
     assert g.copy().DIM_NODE_LABEL[0] == g.nodes.shape[1]
+
+
+def test_fallbacks_follow_the_exception_class_not_the_message(monkeypatch):
+    """`train_step` and `Loop(training=True)` of both model kinds fall back on WHAT KIND of failure the library reported (the class `_native.check`
+    raises for `gnn_last_status`), never on the wording: the two classes below carry messages none of the library's, the plain error one that
+    used to mean "fall back"."""
+    import warnings
+    from types import SimpleNamespace
+    from gnnkeras_amd import _native as nat
+    from gnnkeras_amd.Models.training import LoopTrainer
+    assert issubclass(nat.NotCovered, NotImplementedError) and issubclass(nat.NotCovered, nat.NativeError)
+    assert issubclass(nat.NotResident, nat.NativeError)
+    ns = MLP((31,), [14], 'selu', 'zeros', 'zeros', device='cpu')
+    no = MLP((14,), [2], 'softmax', 'zeros', 'zeros', device='cpu')
+    general, tape = object(), SimpleNamespace(k=3, dev='cpu', state=torch.ones(4, 14), y_pred=torch.zeros(4, 2))
+    raised = []
+    def native(self, *args, **kw): raise raised[-1]
+    monkeypatch.setattr(LoopTrainer, '_train_step_native', native)
+    monkeypatch.setattr(LoopTrainer, '_native_step_applies', lambda self, y: True)
+    monkeypatch.setattr(LoopTrainer, '_native_forward_applies', lambda self: True)
+    monkeypatch.setattr(LoopTrainer, '_train_step_general', lambda self, *args: general)
+    monkeypatch.setattr(LoopTrainer, 'forward', lambda self, x_list, **kw: tape)
+    mask = torch.ones(4, 1, dtype=torch.bool)
+    hom = GNNnodeBased(ns, no, 0, 3, 0.01)
+    comp = CompositeGNNnodeBased([ns], no, 0, 3, 0.01)
+    loops = [lambda: hom.Loop(torch.zeros(4, 14), None, None, mask, mask, None, None, None, training=True),
+             lambda: comp.Loop(torch.zeros(4, 14), None, None, None, mask, mask, None, None, None, None, training=True)]
+    for model in (hom, comp):
+        model._trainer = LoopTrainer.__new__(LoopTrainer)
+        model._trainer.model, model._trainer.dp = model, None
+    step = lambda: hom._trainer.train_step(None, object(), None)
+
+    raised.append(nat.NotCovered('no kernel form for this'))
+    with warnings.catch_warnings():
+        warnings.simplefilter('error')                         # silently
+        assert step() is general
+        for loop in loops:
+            k, state, out = loop()
+            assert float(k) == 3.0 and torch.equal(state, tape.state) and out is tape.y_pred
+    assert getattr(hom._trainer, 'recovered_steps', 0) == 0
+
+    raised.append(nat.NotResident('the workgroups did not all fit'))
+    with pytest.warns(RuntimeWarning, match='resident'):
+        assert step() is general
+    assert hom._trainer.recovered_steps == 1
+    for loop in loops: assert float(loop()[0]) == 3.0
+
+    raised.append(nat.NativeError('malformed, although it names a grid barrier and such networks train through the building blocks'))
+    for call in [step] + loops:
+        with pytest.raises(nat.NativeError) as err: call()
+        assert err.value is raised[-1]
