@@ -15,8 +15,9 @@ import torch
 from .. import _native as nat
 from .. import ops
 from ..sparse import SparseMatrix
-from .GNN import GNNnodeBased, _LoopModel, _squeeze_last, _arc_endpoints
+from .GNN import GNNnodeBased, _LoopModel
 from .MLP import Sequential
+from .loop_operands import prepare_operands, set_ids, fold_sets, type_widths, type_mask_2d, _squeeze_last
 
 
 class CompositeGNNnodeBased(GNNnodeBased):
@@ -79,7 +80,7 @@ class CompositeGNNnodeBased(GNNnodeBased):
         """Squeeze [2] dim_node_label, [3] type_mask, [4] set_mask, [5] output_mask; [6] list of composite adjacency
         triples and [7:] triples -> `SparseMatrix` (reference CompositeGNN.py:178-191)."""
         inputs = list(inputs)
-        inputs[2:6] = [_squeeze_last(k) for k in inputs[2:6]]
+        inputs[2:6] = [_squeeze_last(inputs[2]), type_mask_2d(inputs[3]), _squeeze_last(inputs[4]), _squeeze_last(inputs[5])]
         inputs[6] = [SparseMatrix.from_triple(k) for k in inputs[6]]
         inputs[7:] = [SparseMatrix.from_triple(k) for k in inputs[7:]]
         return inputs
@@ -102,8 +103,7 @@ class CompositeGNNnodeBased(GNNnodeBased):
         nat.require_device(nodes, 'nodes'); nat.require_device(state, 'state')
         dev = nodes.device
         training = bool(training)
-        dims = [int(d) for d in (dim_node_label.reshape(-1).tolist() if isinstance(dim_node_label, torch.Tensor)
-                                 else np.asarray(dim_node_label).reshape(-1))]
+        dims = type_widths(dim_node_label)
         if len(dims) != len(self.net_state): raise ValueError(f'{len(dims)} node types but {len(self.net_state)} state networks')
         type_nodes, offsets = self._type_lists(_squeeze_last(type_mask).to(dev))
         nodes32 = nodes.to(torch.float32).contiguous()
@@ -171,58 +171,21 @@ class CompositeGNNnodeBased(GNNnodeBased):
         if groups is not None and training:
             raise NotImplementedError('convergence groups: composite (heterogeneous) models are not covered by Loop(training=True, groups=...); use LoopTrainer.forward_native(groups=...)')
         if group_sets is not None and groups is None: raise ValueError('group_sets needs groups')
-        focus = 'n' if (node_level and self._focus == 'g') else self._focus
         if training:
             from .training import LoopTrainer
             if getattr(self, '_trainer', None) is None: self._trainer = LoopTrainer(self)
             x_list = [nodes, arcs, dim_node_label, type_mask, set_mask, output_mask, composite_adjacencies, adjacency, arcnode, nodegraph]
             return self._trainer.loop_training(x_list, set_mask, output_mask, state0=state0, seed=seed, node_level=node_level)
-        nat.require_device(nodes, 'nodes'); nat.require_device(arcs, 'arcs')
-        dev = nodes.device
-        nodes = nodes.to(torch.float32).contiguous()
-        arcs = arcs.to(torch.float32).contiguous()
-        N, Lw = nodes.shape
-        dims = [int(d) for d in (dim_node_label.reshape(-1).tolist() if isinstance(dim_node_label, torch.Tensor)
-                                 else np.asarray(dim_node_label).reshape(-1))]
-        T = len(dims)
-        if T != len(self.net_state): raise ValueError(f'{T} node types but {len(self.net_state)} state networks')
-        if T > nat.GNN_MAX_TYPES: raise ValueError(f'at most {nat.GNN_MAX_TYPES} node types are supported')
-        # (T, N, 1) as the sequencers hand it over, or (T, N) after process_inputs - which for a graph of ONE node must not lose its node axis too
-        type_mask = (_squeeze_last(type_mask) if type_mask.dim() == 3 else type_mask).to(dev)
-        set_mask, output_mask = _squeeze_last(set_mask).to(dev), _squeeze_last(output_mask).to(dev)
-        out_index = self._out_index(set_mask, output_mask)
-        type_nodes, offsets = self._type_lists(type_mask)
-
-        adjacency = SparseMatrix.from_triple(adjacency)
-        adj, arcn = adjacency.device_csr(dev), SparseMatrix.from_triple(arcnode).device_csr(dev)
-        cas = [SparseMatrix.from_triple(c).device_csr(dev) for c in composite_adjacencies]
-
-        S = self.state_vect_dim if self.state_vect_dim > 0 else Lw
-        if self.state_vect_dim > 0:
-            if state0 is None:
-                gen = None
-                if seed is not None:
-                    gen = torch.Generator(device=dev); gen.manual_seed(int(seed))
-                state0 = torch.empty((N, S), device=dev, dtype=torch.float32).normal_(0.0, 0.1, generator=gen)      # tf.random.normal(stddev=0.1), one launch
-            state0 = state0.to(dev, torch.float32).contiguous()
-            if tuple(state0.shape) != (N, S): raise ValueError('state0 must be (n_nodes, state_vect_dim)')
-        else:
-            state0 = None
-        ends = _arc_endpoints(adjacency, dev) if focus == 'a' else None
-        ng = SparseMatrix.from_triple(nodegraph).device_csr(dev) if focus == 'g' else None
-        # (the first group of every set, uploaded BEFORE the launch: a pageable host-to-device copy behind it would block the host)
-        set_id = None
-        if group_sets is not None:
-            gs_ = np.asarray([int(v) for v in group_sets], dtype=np.int64)
-            set_id = torch.as_tensor(np.repeat(np.arange(len(gs_) - 1), np.diff(gs_)), device=dev)
+        op = prepare_operands(self, [nodes, arcs, dim_node_label, type_mask, set_mask, output_mask, composite_adjacencies, adjacency, arcnode,
+                                     nodegraph], state0, seed, node_level)
+        set_id = set_ids(group_sets, op.dev) if group_sets is not None else None
         # one custom op for the whole heterogeneous Loop: torch.ops.gnnkeras.loop_forward with the per-type lists
-        k, state, out = ops.loop_forward(nodes, arcs, adj, arcn, ng, self.net_state, self.net_output, state0, out_index, ends,
-                                         self.state_vect_dim, self.max_iteration, self.state_threshold, nat.FOCUS[focus],
-                                         self.native_flags, composite=(type_nodes, offsets, dims, cas), loop_events=self.loop_events,
+        k, state, out = ops.loop_forward(op.nodes, op.arcs, op.adj, op.an, op.ng, self.net_state, self.net_output, op.state0, op.out_index, op.ends,
+                                         op.d, self.max_iteration, self.state_threshold, nat.FOCUS[op.focus], self.native_flags,
+                                         composite=(op.type_nodes, op.offsets, op.dims, op.ca_csr), loop_events=self.loop_events,
                                          groups=groups, group_sets=group_sets)
         self._last_k_groups = k         # (one entry per GROUP, before the sets are folded)
-        if group_sets is not None:      # one entry per set: its groups report the same k (or -1e9 where a member's wait expired: the minimum keeps it)
-            k = torch.full((len(group_sets) - 1,), float('inf'), device=dev).scatter_reduce_(0, set_id, k, 'amin')
+        if group_sets is not None: k = fold_sets(k, set_id, len(group_sets) - 1)       # one entry per set
         self._last_k = k
         return k, state, out
 

@@ -18,6 +18,7 @@ from .. import _native as nat
 from .. import ops
 from ..sparse import SparseMatrix, XC_MIN_NODES, xc_reuse_enabled
 from .MLP import Sequential
+from .loop_operands import prepare_operands, set_ids, fold_sets, _squeeze_last
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -590,18 +591,6 @@ class _LoopModel:
         return hit[0]
 
 
-def _squeeze_last(x):
-    return x.squeeze(-1) if isinstance(x, torch.Tensor) and x.dim() > 1 and x.shape[-1] == 1 else x
-
-
-def _arc_endpoints(adjacency: SparseMatrix, device):
-    key = ('endpoints', str(device))
-    if key not in adjacency._dev:
-        idx = torch.from_numpy(adjacency.indices.astype(np.int32)).to(device)
-        adjacency._dev[key] = (idx[:, 0].contiguous(), idx[:, 1].contiguous())
-    return adjacency._dev[key]
-
-
 #######################################################################################################################
 class GNNnodeBased(_LoopModel):
     """GNN for node-focused problems (reference GNN.py:8-306)."""
@@ -774,7 +763,6 @@ class GNNnodeBased(_LoopModel):
         draw when `state_vect_dim > 0`; otherwise it is drawn on the device with `seed`. `node_level=True` makes a
         graph-focused model return its per-node outputs (what the reference obtains by calling the unbound
         `GNNnodeBased.Loop` on a graph-based model inside LGNN, LGNN.py:225)."""
-        focus = 'n' if (node_level and self._focus == 'g') else self._focus
         if training:
             if group_sets is not None: raise ValueError('group_sets are an inference-only feature')
             from .training import LoopTrainer
@@ -791,49 +779,22 @@ class GNNnodeBased(_LoopModel):
                 self._last_k = k
                 return k, state, out
             return self._trainer.loop_training(x_list, set_mask, output_mask, state0=state0, seed=seed, node_level=node_level)
-        nat.require_device(nodes, 'nodes'); nat.require_device(arcs, 'arcs')
-        dev = nodes.device
-        set_mask, output_mask = _squeeze_last(set_mask).to(dev), _squeeze_last(output_mask).to(dev)
-        out_index = self._out_index(set_mask, output_mask)
-        N = nodes.shape[0]
-        if self.state_vect_dim > 0:
-            if state0 is None:
-                gen = None
-                if seed is not None:
-                    gen = torch.Generator(device=dev); gen.manual_seed(int(seed))
-                state0 = torch.empty((N, self.state_vect_dim), device=dev, dtype=torch.float32).normal_(0.0, 0.1, generator=gen)      # tf.random.normal(stddev=0.1), one launch
-            state0 = state0.to(dev, torch.float32).contiguous()
-            if tuple(state0.shape) != (N, self.state_vect_dim): raise ValueError('state0 must be (n_nodes, state_vect_dim)')
-        else:
-            state0 = None
-        adjacency = SparseMatrix.from_triple(adjacency)
-        adj, arcn = adjacency.device_csr(dev), SparseMatrix.from_triple(arcnode).device_csr(dev)
-        ends = _arc_endpoints(adjacency, dev) if focus == 'a' else None
-        ng = SparseMatrix.from_triple(nodegraph).device_csr(dev) if focus == 'g' else None
-        # (the first group of every set, uploaded BEFORE the launch: a pageable host-to-device copy behind it would block the host
-        # until the loop has finished)
-        set_id = None
-        if group_sets is not None:
-            gs_ = np.asarray([int(v) for v in group_sets], dtype=np.int64)
-            set_id = torch.as_tensor(np.repeat(np.arange(len(gs_) - 1), np.diff(gs_)), device=dev)
+        op = prepare_operands(self, [nodes, arcs, dim_node_label, set_mask, output_mask, adjacency, arcnode, nodegraph], state0, seed, node_level)
+        set_id = set_ids(group_sets, op.dev) if group_sets is not None else None
         # a large graph keeps its constants line with the batch (sparse.py): the first call fills it, later ones read it
         xc, xc_valid = None, False
-        if groups is None and N >= XC_MIN_NODES and xc_reuse_enabled() and \
-                ops.loop_xc_applies(N, nodes.shape[1], arcs.shape[1] - 2, self.net_state, self.net_output, self.state_vect_dim, self.max_iteration,
-                                    nat.FOCUS[focus], self.native_flags, len(out_index), adj):
-            xc, xc_valid = adjacency.constants_line(nodes, arcs, SparseMatrix.from_triple(arcnode), nodes.shape[1], self.state_vect_dim > 0, dev)
+        if groups is None and op.N >= XC_MIN_NODES and xc_reuse_enabled() and \
+                ops.loop_xc_applies(op.N, op.L, op.A, self.net_state, self.net_output, op.d, self.max_iteration,
+                                    nat.FOCUS[op.focus], self.native_flags, len(op.out_index), op.adj):
+            xc, xc_valid = op.adjacency.constants_line(op.caller_nodes, op.caller_arcs, op.arcnode, op.L, op.d > 0, op.dev)
         # the whole Loop is ONE custom op: torch.ops.gnnkeras.loop_forward (csrc/torch_ops.cpp -> gnn_loop_forward)
-        k, state, out = ops.loop_forward(nodes.to(torch.float32).contiguous(), arcs.to(torch.float32).contiguous(), adj, arcn, ng,
-                                         self.net_state, self.net_output, state0, out_index, ends, self.state_vect_dim,
-                                         self.max_iteration, self.state_threshold, nat.FOCUS[focus], self.native_flags,
+        k, state, out = ops.loop_forward(op.nodes, op.arcs, op.adj, op.an, op.ng, self.net_state, self.net_output, op.state0, op.out_index,
+                                         op.ends, op.d, self.max_iteration, self.state_threshold, nat.FOCUS[op.focus], self.native_flags,
                                          loop_events=self.loop_events, groups=groups, group_sets=group_sets, xc=xc, xc_valid=xc_valid,
                                          # (ascending distinct node ids, N of them: 0 .. N - 1)
-                                         out_index_identity=focus != 'a' and len(out_index) == N and N > 0)
-        if xc is not None and not xc_valid: adjacency.constants_line_filled()
-        if group_sets is not None:
-            # one entry per set: its groups report the same k - or -1e9 where a member's wait for the others expired (any member: the
-            # minimum keeps it, so _check_k / check_last_k see it)
-            k = torch.full((len(group_sets) - 1,), float('inf'), device=dev).scatter_reduce_(0, set_id, k, 'amin')
+                                         out_index_identity=op.focus != 'a' and len(op.out_index) == op.N and op.N > 0)
+        if xc is not None and not xc_valid: op.adjacency.constants_line_filled()
+        if group_sets is not None: k = fold_sets(k, set_id, len(group_sets) - 1)       # one entry per set
         self._last_k = k
         return k, state, out
 

@@ -20,6 +20,7 @@ without ever materialising the N × in_dim concatenation or its gradient.
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -27,6 +28,7 @@ import torch
 from .. import _native as nat
 from ..sparse import SparseMatrix, CSRByDestination, XC_MIN_NODES, xc_reuse_enabled
 from .MLP import Sequential, BN_EPSILON, BN_MOMENTUM
+from .loop_operands import prepare_operands, loss_kind, dropout_in_front, state_networks, _squeeze_last
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -314,6 +316,13 @@ class LoopTrainer:
         """32-bit key of one Dropout layer call: step seed, network, call number (iteration), layer index."""
         return _mix32(self.drop_seed, ng.net_id, int(call), int(index))
 
+    def _step_drop_seed(self, seed):
+        """Seed of this step's Dropout masks (kept in `self.drop_seed`): `seed` when given (reproducible steps, tests), else a per-model step counter."""
+        m = self.model
+        m._dropout_step = getattr(m, '_dropout_step', 0) + 1
+        self.drop_seed = _mix32(0x5EED, int(seed)) if seed is not None else _mix32(id(m) & 0xFFFFFFFF, m._dropout_step)
+        return self.drop_seed
+
     def _dropped(self, ng: _NetGrads, q, x, call):
         """What the layer behind position q consumes: x through the Dropout layers sitting there (a copy), or x itself."""
         if q not in ng.drop: return x
@@ -475,118 +484,28 @@ class LoopTrainer:
         backward sweep needs: the k+1 states, the BN batch statistics per iteration, the output-network activations.
         `node_level=True` makes a graph-focused model stop at the per-node outputs (what LGNN feeds to the next layer,
         reference LGNN.py:225-246 uses `GNNnodeBased.Loop` for that)."""
-        from types import SimpleNamespace
         m = self.model
-        tp = SimpleNamespace()
-        composite = tp.composite = isinstance(m.net_state, (list, tuple))
-        inputs = m.process_inputs(x_list)
-        if composite:
-            nodes, arcs, dim_node_label, type_mask, set_mask, output_mask, _cas, adjacency, arcnode, nodegraph = inputs
-        else:
-            nodes, arcs, dim_node_label, set_mask, output_mask, adjacency, arcnode, nodegraph = inputs
-        nat.require_device(nodes, 'nodes')
-        dev = tp.dev = nodes.device
+        tp = prepare_operands(m, m.process_inputs(x_list), state0, seed, node_level)       # (the tape starts as the record of the operands)
+        tp.pooled, tp.M = tp.focus == 'g', len(tp.out_index)
+        composite, dev, N, S, adj, M = tp.composite, tp.dev, tp.N, tp.S, tp.adj, tp.M
         self.prim = p = tp.p = self.prim_cls(dev)
-        nodes = tp.nodes = nodes.to(torch.float32).contiguous(); arcs = arcs.to(torch.float32).contiguous()
-        N, L = nodes.shape
-        A = arcs.shape[1] - 2
-        d = m.state_vect_dim
-        S = d if d > 0 else L
-        tp.N, tp.L, tp.A, tp.d, tp.S = N, L, A, d, S
-        focus = tp.focus = 'n' if (node_level and m._focus == 'g') else m._focus
-        tp.pooled = m._focus == 'g' and not node_level
-        nets_s = list(m.net_state) if composite else [m.net_state]
-        for n_ in nets_s: n_.to(dev)
-        m.net_output.to(dev)
-        gs, go = [_NetGrads(n_, p) for n_ in nets_s], _NetGrads(m.net_output, p)
+        gs, go = [_NetGrads(n_, p) for n_ in state_networks(m)], _NetGrads(m.net_output, p)
         for i, g_ in enumerate(gs): g_.net_id, g_.dp_kind = i, (f'type{i}' if composite else 'nodes')      # (dp_kind: whose rows the network sees, for the data-parallel counts)
         go.net_id, go.dp_kind = 1000, 'out'
-        # Dropout masks of this step: `seed` when given (reproducible steps, tests), else a per-model step counter
-        m._dropout_step = getattr(m, '_dropout_step', 0) + 1
-        self.drop_seed = tp.drop_seed = _mix32(0x5EED, int(seed)) if seed is not None else _mix32(id(m) & 0xFFFFFFFF, m._dropout_step)
+        tp.drop_seed = self._step_drop_seed(seed)
         tp.gs, tp.go = gs, go
         self.gs, self.go = (gs if composite else gs[0]), go
-        adj = tp.adj = adjacency.device_csr(dev)
-        tp.adj_src = _by_source(adjacency, dev)
-        an = arcnode.device_csr(dev)
-        tp.arcnode = arcnode
-        tp.nodegraph = nodegraph
-        tp.cas = _cas if composite else None
-        from .GNN import _squeeze_last, _arc_endpoints
-        out_index = tp.out_index = m._out_index(_squeeze_last(set_mask).to(dev), _squeeze_last(output_mask).to(dev))
-        M = tp.M = len(out_index)
+        tp.adj_src = _by_source(tp.adjacency, dev)
 
         # node types: row lists (None = all rows for the homogeneous model)
-        if composite:
-            dims = [int(v) for v in (dim_node_label.reshape(-1).tolist() if isinstance(dim_node_label, torch.Tensor)
-                                     else np.asarray(dim_node_label).reshape(-1))]
-            type_nodes, offsets = m._type_lists(_squeeze_last(type_mask).to(dev))
-            rows = [type_nodes[int(offsets[t]):int(offsets[t + 1])].contiguous() for t in range(len(dims))]
-        else:
-            dims, rows = [L], [None]
-        tp.dims, tp.rows = dims, rows
+        rows = tp.rows = [None]
+        if composite: rows = tp.rows = [tp.type_nodes[int(tp.offsets[t]):int(tp.offsets[t + 1])].contiguous() for t in range(len(tp.dims))]
         T_types = tp.T_types = len(rows)
         counts = tp.counts = [N if r is None else len(r) for r in rows]
         rows_long = tp.rows_long = [None if r is None else r.long() for r in rows]
 
-        # ---- setup aggregates (GNN.py:254-258 / CompositeGNN.py:251-253) ----
-        arc_labels = tp.arc_labels = arcs[:, 2:]
-        agg_arcs = p.aggregate(an, arc_labels, A, p.new(N, max(A, 1)))[:, :A] if A > 0 else None
-        agg_comp = agg_nodes = None
-        if composite:
-            sum_d = sum(dims)
-            agg_comp = p.new(N, max(sum_d + A, 1))                  # [agg_nodes_0 | ... | agg_nodes_{T-1} | agg_arcs]
-            col = 0
-            for t, ca in enumerate(_cas):
-                if dims[t] > 0: p.aggregate(ca.device_csr(dev), nodes[:, :dims[t]], dims[t], agg_comp[:, col:col + dims[t]])
-                col += dims[t]
-            if A > 0: agg_comp[:, col:col + A].copy_(agg_arcs)
-            agg_comp = agg_comp[:, :sum_d + A]
-        else:
-            agg_nodes = p.aggregate(adj, nodes, L, p.new(N, L)) if d > 0 else None
-        if d > 0:
-            if state0 is None:
-                gen = None
-                if seed is not None:
-                    gen = torch.Generator(device=dev); gen.manual_seed(int(seed))
-                state0 = torch.empty((N, d), device=dev, dtype=torch.float32).normal_(0.0, 0.1, generator=gen)      # tf.random.normal(stddev=0.1), one launch
-            s_init = state0.to(dev, torch.float32)
-        else:
-            s_init = nodes
-        K_it = m.max_iteration
-        states = tp.states = p.new(K_it + 1, N, S)
-        states[0].copy_(s_init)
-        agg = tp.agg = p.new(N, S)
-
-        def state_segs(t, ty):
-            """(segments, index of the state segment, of the agg segment, of the label segment, of the agg-label segment)"""
-            r = rows[ty]
-            if composite:                                           # [labels[:, :d_t] | state | agg_state | agg_component]
-                segs = [(nodes[:, :dims[ty]], r)] if dims[ty] > 0 else []
-                i_state = len(segs)
-                segs += [(states[t], r), (agg, r)]
-                if agg_comp.shape[1] > 0: segs.append((agg_comp, r))
-                return segs, i_state, i_state + 1, (0 if dims[ty] > 0 else None), (i_state + 2 if agg_comp.shape[1] > 0 else None)
-            segs = [(states[t], None)]                              # [state | labels | agg_state | agg_labels | agg_arcs]
-            if d > 0: segs.append((nodes, None))
-            segs.append((agg, None))
-            if d > 0: segs.append((agg_nodes, None))
-            if A > 0: segs.append((agg_arcs, None))
-            return segs, 0, (2 if d > 0 else 1), (1 if d > 0 else None), (3 if d > 0 else None)
-        tp.state_segs = state_segs
-
-        const_stats = []
-        for ty in range(T_types):
-            cs = None
-            if gs[ty].bn and counts[ty] > 0:
-                cs = {}
-                segs, i_state, i_agg, _, _ = state_segs(0, ty)
-                for i, (xv, ridx) in enumerate(segs):
-                    if i in (i_state, i_agg): continue
-                    mu, va = p.new(xv.shape[1]), p.new(xv.shape[1])
-                    p.colstats(xv, ridx, counts[ty], mu, va)
-                    cs[i] = (mu, va)
-            const_stats.append(cs)
+        const_stats = self._forward_setup(tp)
+        K_it, states, agg, state_segs = m.max_iteration, tp.states, tp.agg, tp.state_segs
 
         # ---- every iteration is computed, the predicate only records where the loop stops ----
         flags = torch.zeros(K_it + 2, dtype=torch.int32, device=dev)
@@ -620,12 +539,72 @@ class LoopTrainer:
                 wts = torch.tensor([BN_MOMENTUM ** (k - 1 - t) * (1 - BN_MOMENTUM) for t in range(k)], device=dev)
                 mm.mul_(BN_MOMENTUM ** k).add_((torch.stack([stats_t[t][ty][0] for t in range(k)]) * wts[:, None]).sum(0))
                 mv.mul_(BN_MOMENTUM ** k).add_((torch.stack([stats_t[t][ty][1] for t in range(k)]) * wts[:, None]).sum(0))
-        state_k = tp.state = states[k]
+        tp.state = states[k]
+        self._forward_output(tp)
+        return tp
 
-        # ---- output network (training mode) ----
-        with_labels = tp.with_labels = (not composite) and d > 0    # composite filters use the state only (CompositeGNN.py:237-239)
+    def _forward_setup(self, tp):
+        """What `forward()` builds once in front of the iterations: the set-up aggregates, the state buffers, the segment lists of the
+        state networks (`tp.state_segs`) - and returns the BatchNormalization statistics of their constant segments, per type."""
+        p, gs, dims, rows, counts = tp.p, tp.gs, tp.dims, tp.rows, tp.counts
+        composite, nodes, N, L, A, d, S = tp.composite, tp.nodes, tp.N, tp.L, tp.A, tp.d, tp.S
+        # ---- setup aggregates (GNN.py:254-258 / CompositeGNN.py:251-253) ----
+        arc_labels = tp.arc_labels = tp.arcs[:, 2:]
+        agg_arcs = p.aggregate(tp.an, arc_labels, A, p.new(N, max(A, 1)))[:, :A] if A > 0 else None
+        agg_comp = agg_nodes = None
+        if composite:
+            sum_d = sum(dims)
+            agg_comp = p.new(N, max(sum_d + A, 1))                  # [agg_nodes_0 | ... | agg_nodes_{T-1} | agg_arcs]
+            col = 0
+            for t, ca in enumerate(tp.ca_csr):
+                if dims[t] > 0: p.aggregate(ca, nodes[:, :dims[t]], dims[t], agg_comp[:, col:col + dims[t]])
+                col += dims[t]
+            if A > 0: agg_comp[:, col:col + A].copy_(agg_arcs)
+            agg_comp = agg_comp[:, :sum_d + A]
+        else:
+            agg_nodes = p.aggregate(tp.adj, nodes, L, p.new(N, L)) if d > 0 else None
+        states = tp.states = p.new(self.model.max_iteration + 1, N, S)
+        states[0].copy_(tp.state0 if d > 0 else nodes)
+        agg = tp.agg = p.new(N, S)
+
+        def state_segs(t, ty):
+            """(segments, index of the state segment, of the agg segment, of the label segment, of the agg-label segment)"""
+            r = rows[ty]
+            if composite:                                           # [labels[:, :d_t] | state | agg_state | agg_component]
+                segs = [(nodes[:, :dims[ty]], r)] if dims[ty] > 0 else []
+                i_state = len(segs)
+                segs += [(states[t], r), (agg, r)]
+                if agg_comp.shape[1] > 0: segs.append((agg_comp, r))
+                return segs, i_state, i_state + 1, (0 if dims[ty] > 0 else None), (i_state + 2 if agg_comp.shape[1] > 0 else None)
+            segs = [(states[t], None)]                              # [state | labels | agg_state | agg_labels | agg_arcs]
+            if d > 0: segs.append((nodes, None))
+            segs.append((agg, None))
+            if d > 0: segs.append((agg_nodes, None))
+            if A > 0: segs.append((agg_arcs, None))
+            return segs, 0, (2 if d > 0 else 1), (1 if d > 0 else None), (3 if d > 0 else None)
+        tp.state_segs = state_segs
+
+        const_stats = []
+        for ty in range(len(rows)):
+            cs = None
+            if gs[ty].bn and counts[ty] > 0:
+                cs = {}
+                segs, i_state, i_agg, _, _ = state_segs(0, ty)
+                for i, (xv, ridx) in enumerate(segs):
+                    if i in (i_state, i_agg): continue
+                    mu, va = p.new(xv.shape[1]), p.new(xv.shape[1])
+                    p.colstats(xv, ridx, counts[ty], mu, va)
+                    cs[i] = (mu, va)
+            const_stats.append(cs)
+        return const_stats
+
+    def _forward_output(self, tp):
+        """The output network of `forward()` in training mode on the state the loop stopped at (`tp.state`), and the pooling."""
+        m, p, go = self.model, tp.p, tp.go
+        nodes, A, focus, out_index, M, state_k, arc_labels = tp.nodes, tp.A, tp.focus, tp.out_index, tp.M, tp.state, tp.arc_labels
+        with_labels = tp.with_labels = (not tp.composite) and tp.d > 0    # composite filters use the state only (CompositeGNN.py:237-239)
         if focus == 'a':
-            es, ed = _arc_endpoints(adjacency, dev)
+            es, ed = tp.ends
             tp.isrc, tp.idst = es[out_index.long()].contiguous(), ed[out_index.long()].contiguous()
             osegs = []
             for ends in (tp.isrc, tp.idst):
@@ -646,12 +625,11 @@ class LoopTrainer:
         else:
             tp.ohs, tp.ostats, tp.out_nodes = None, None, p.new(0, T)
         if tp.pooled:
-            ng_csr = nodegraph.device_csr(dev)
+            ng_csr = tp.ng
             if ng_csr['n_src'] != M: raise ValueError('graph focus: every node must pass the mask')
             tp.y_pred = p.aggregate(ng_csr, tp.out_nodes, T, p.new(ng_csr['n_dst'], T))
         else:
             tp.y_pred = tp.out_nodes
-        return tp
 
     def loss_and_grad(self, tp, y_pred, y, sample_weight):
         """(loss scalar tensor, d loss / d y_pred) with Keras semantics (SUM_OVER_BATCH_SIZE, sample weights)."""
@@ -660,9 +638,9 @@ class LoopTrainer:
         sw = None if sample_weight is None else sample_weight.to(tp.dev, torch.float32).contiguous()
         R, T = y_pred.shape
         dpred, loss_rows = p.new(R, T), p.zeros(max(R, 1))
-        kind = m.loss if isinstance(m.loss, str) else getattr(m.loss, '__name__', str(m.loss))
-        if kind.lower() not in nat.LOSSES: raise ValueError(f'loss {kind!r} has no device gradient')
-        p.loss_grad(nat.LOSSES[kind.lower()], y, y_pred.contiguous(), sw, dpred, loss_rows)
+        kind, name = loss_kind(m)
+        if kind is None: raise ValueError(f'loss {name!r} has no device gradient')
+        p.loss_grad(kind, y, y_pred.contiguous(), sw, dpred, loss_rows)
         if self.dp is not None:
             # SUM_OVER_BATCH_SIZE over the target rows of the merged batch: the kernel divided by this shard's row count
             R_all = self.dp.total_rows('targets', R)
@@ -879,23 +857,15 @@ class LoopTrainer:
         m = self.model
         if self.dp is not None: return False        # collectives sit between the iteration's launches: the building-block path
         if not self.use_native_step or y is None: return False
-        nets = list(m.net_state) if isinstance(m.net_state, (list, tuple)) else [m.net_state]
         if isinstance(m.net_state, (list, tuple)) and m.max_iteration < 1: return False      # what the in-library composite step refuses (make_cplan): the general path below
         # Dropout layers behind Dense layers run inside the library (ABI 8); one in FRONT of the first Dense (position 0) keeps the path below
-        for n_ in nets + [m.net_output]:
-            if any(float(r) > 0 and int(q) == 0 for r, q in zip(n_.dropout_rate or [], n_.dropout_pos or [])): return False
-        kind = m.loss if isinstance(m.loss, str) else getattr(m.loss, '__name__', str(m.loss))
-        return str(kind).lower() in nat.LOSSES
+        return not dropout_in_front(m) and loss_kind(m)[0] is not None
 
     def _native_forward_applies(self):
         """May `Loop(..., training=True)` run as ONE `gnn_train_step(forward_only)` call?  (homogeneous and composite models, no Dropout in
         front of a first Dense, no data parallelism - what the in-library steps cover, minus everything about the loss.)"""
         m = self.model
-        if self.dp is not None or not self.use_native_step or m.max_iteration < 1: return False
-        nets = list(m.net_state) if isinstance(m.net_state, (list, tuple)) else [m.net_state]
-        for n_ in nets + [m.net_output]:
-            if any(float(r) > 0 and int(q) == 0 for r, q in zip(n_.dropout_rate or [], n_.dropout_pos or [])): return False
-        return True
+        return self.dp is None and self.use_native_step and m.max_iteration >= 1 and not dropout_in_front(m)
 
     def forward_native(self, x_list, state0=None, seed=None, node_level=False, groups=None, group_out_begin=None):
         """The training-mode forward in one library call (include/gnnloop.h ABI 9, `forward_only`): (k, state, output rows) - the same
@@ -919,7 +889,6 @@ class LoopTrainer:
         building blocks skip the output network and leave its moving statistics alone).  A shape the library does not cover, or a
         persistent forward kernel that was not resident (GPU shared with long-running work), has touched nothing: the building blocks,
         which have no cross-workgroup waits, run it."""
-        from .GNN import _squeeze_last
         dev = x_list[0].device
         has_rows = len(self.model._out_index(_squeeze_last(set_mask).to(dev), _squeeze_last(output_mask).to(dev))) > 0
         if has_rows and self._native_forward_applies():
@@ -935,12 +904,10 @@ class LoopTrainer:
                            group_out_begin=None, phase_forward=False):
         """One `gnn_train_step` call: training-mode forward, loss, BPTT; the tape and every scratch buffer live in one cached
         device allocation. Same results as the general path (same kernels for the arithmetic), ~2.5x fewer launches and no
-        Python between them.  `forward_only`: the forward alone (no targets, no gradients; `Loop(..., training=True)`)."""
-        from types import SimpleNamespace
-        from .GNN import _squeeze_last, _arc_endpoints
+        Python between them.  `forward_only`: the forward alone (no targets, no gradients; `Loop(..., training=True)`);
+        `phase_forward`: phase 1 of `gnn_train_step_ex`.  The steps share one record `c` of the call: the operands, the
+        argument block, the host tables, the constants line, the tape - then one of three finishers."""
         m = self.model
-        composite = isinstance(m.net_state, (list, tuple))
-        nets_s = list(m.net_state) if composite else [m.net_state]
         if groups is not None:
             if not forward_only: raise NotImplementedError('training-mode convergence groups: the forward only (no grouped train_step)')
             if not self._native_forward_applies():
@@ -948,197 +915,24 @@ class LoopTrainer:
                                           'max_iteration < 1 or the in-library step switched off)')
             if m._focus == 'g' and not node_level:
                 raise NotImplementedError('training-mode convergence groups: a graph-focused model is covered at node level only (node_level=True)')
-        inputs = m.process_inputs(x_list)
-        if composite:       # CompositeGNN.py:275-304: one state network per node type (csrc/train_composite.hpp)
-            nodes, arcs, dim_node_label, type_mask, set_mask, output_mask, cas, adjacency, arcnode, nodegraph = inputs
-        else:
-            nodes, arcs, dim_node_label, set_mask, output_mask, adjacency, arcnode, nodegraph = inputs
-        nat.require_device(nodes, 'nodes'); nat.require_device(arcs, 'arcs')
-        dev = nodes.device
-        self.prim = p = _Prim(dev)
-        nodes = nodes.to(torch.float32).contiguous(); arcs = arcs.to(torch.float32).contiguous()
-        N, L = nodes.shape
-        d = m.state_vect_dim
-        S = d if d > 0 else L
-        focus = 'n' if (forward_only and node_level and m._focus == 'g') else m._focus
-        for n_ in nets_s: n_.to(dev)
-        m.net_output.to(dev)
+        op = prepare_operands(m, m.process_inputs(x_list), state0, seed, node_level=forward_only and node_level)
+        self.prim = p = _Prim(op.dev)
         if forward_only or phase_forward: self.resolve_pending()   # (the tape is shared with the steps: nothing of theirs may be pending on it)
-        # gnn_train_step OVERWRITES every gradient buffer: the holders of the previous step are reused as they are (eight zero-fill
-        # launches and their allocations per step otherwise; the optimizer's pointer tables stay valid too)
-        gs_all = [] if forward_only else [self._cached_grads(f'state{i}' if composite else 'state', n_, p) for i, n_ in enumerate(nets_s)]
-        if not forward_only:
-            gs, go = gs_all[0], self._cached_grads('output', m.net_output, p)
-            self.gs, self.go = (gs_all if composite else gs), go
-        out_index = m._out_index(_squeeze_last(set_mask).to(dev), _squeeze_last(output_mask).to(dev))
-        adj, an = adjacency.device_csr(dev), arcnode.device_csr(dev)
-        keep = [nodes, arcs, adj, an, out_index]
-        ta = nat.TrainArgs()
-        a = ta.loop
-        a.abi_version, a.composite = nat.GNN_ABI_VERSION, 0
-        a.n_nodes, a.n_arcs, a.dim_node_label, a.dim_arc_label = N, arcs.shape[0], L, arcs.shape[1] - 2
-        a.nodes, a.ld_nodes = nat.ptr(nodes), L
-        a.arc_labels, a.ld_arcs = C.c_void_p(arcs.data_ptr() + 8), arcs.shape[1]
-        a.adjacency, a.arcnode = nat.make_csr(adj), nat.make_csr(an)
-        a.n_types = 1
-        if composite:
-            from .GNN import _squeeze_last as _sq
-            dims = [int(v) for v in (dim_node_label.reshape(-1).tolist() if isinstance(dim_node_label, torch.Tensor)
-                                     else np.asarray(dim_node_label).reshape(-1))]
-            if len(dims) != len(nets_s): raise ValueError(f'{len(dims)} node types but {len(nets_s)} state networks')
-            type_nodes, offsets = m._type_lists(_sq(type_mask).to(dev))
-            ca_csr = [c_.device_csr(dev) for c_ in cas]
-            keep += [type_nodes, ca_csr]
-            a.composite, a.n_types = 1, len(dims)
-            a.type_nodes = nat.ptr(type_nodes)
-            for t_, dt in enumerate(dims):
-                a.type_dim_label[t_] = dt
-                a.type_offsets[t_] = int(offsets[t_])
-                a.composite_adjacency[t_] = nat.make_csr(ca_csr[t_])
-                a.net_state[t_] = nets_s[t_].native()
-            a.type_offsets[len(dims)] = int(offsets[len(dims)])
-        else:
-            a.net_state[0] = m.net_state.native()
-        a.net_output = m.net_output.native()
-        a.state_dim, a.max_iteration, a.state_threshold = d, m.max_iteration, float(m.state_threshold)
-        a.flags = _train_flags(m)
-        if d > 0:
-            if state0 is None:
-                gen = None
-                if seed is not None:
-                    gen = torch.Generator(device=dev); gen.manual_seed(int(seed))
-                state0 = torch.empty((N, d), device=dev, dtype=torch.float32).normal_(0.0, 0.1, generator=gen)      # tf.random.normal(stddev=0.1), one launch
-            state0 = state0.to(dev, torch.float32).contiguous()
-            if tuple(state0.shape) != (N, d): raise ValueError('state0 must be (n_nodes, state_vect_dim)')
-            a.state0 = nat.ptr(state0); keep.append(state0)
-        a.focus = nat.FOCUS[focus]
-        a.n_out, a.out_index = len(out_index), nat.ptr(out_index)
-        if not forward_only: ta.adjacency_by_source = nat.make_csr(_by_source(adjacency, dev))
-        if focus == 'a':
-            es, ed = _arc_endpoints(adjacency, dev)
-            a.arc_src, a.arc_dst = nat.ptr(es), nat.ptr(ed); keep += [es, ed]
-        n_rows = len(out_index)
-        if focus == 'g':
-            ng = nodegraph.device_csr(dev)
-            a.nodegraph = nat.make_csr(ng); keep.append(ng)
-            if not forward_only: ta.nodegraph_by_source = nat.make_csr(_by_source(nodegraph, dev))
-            n_rows = ng['n_dst']
-        a.stream = p.stream()
-        ta.forward_only = int(bool(forward_only))
-        if not forward_only and not phase_forward:
-            yd = y.to(dev, torch.float32).contiguous()
-            if yd.shape[0] != n_rows: raise ValueError(f'targets have {yd.shape[0]} rows, the model outputs {n_rows}')
-            sw = None if sample_weight is None else sample_weight.to(dev, torch.float32).contiguous()
-            ta.targets, ta.sample_weight = nat.ptr(yd), nat.ptr(sw)
-            kind = m.loss if isinstance(m.loss, str) else getattr(m.loss, '__name__', str(m.loss))
-            ta.loss_kind = nat.LOSSES[str(kind).lower()]
-        ta.average_st_grads = 0          # finish() divides by k AFTER adding the weight penalties, like the reference (GNN.py:295)
-        ta.bn_momentum = BN_MOMENTUM
-        # Dropout / AlphaDropout layers (reference MLP.py:60-66): their masks derive from the step's seed exactly as on the building-block path
-        m._dropout_step = getattr(m, '_dropout_step', 0) + 1
-        self.drop_seed = _mix32(0x5EED, int(seed)) if seed is not None else _mix32(id(m) & 0xFFFFFFFF, m._dropout_step)
-        ta.drop_seed = self.drop_seed
-        if forward_only:            # (the holders know the networks' Dropout layers; their buffers stay untouched)
-            gs_all = [self._cached_grads(f'state{i}' if composite else 'state', n_, p) for i, n_ in enumerate(nets_s)]
-            go = self._cached_grads('output', m.net_output, p)
-        for i, g_ in enumerate(gs_all): g_.net_id = i
-        go.net_id = 1000
-        for spec, g_ in [(ta.drop_state[i], g_) for i, g_ in enumerate(gs_all)] + [(ta.drop_output, go)]:
-            layers = [(q, r, idx) for q in sorted(g_.drop) for r, idx in g_.drop[q]]
-            if len(layers) > nat.GNN_MAX_DROPOUT: raise ValueError(f'more than {nat.GNN_MAX_DROPOUT} Dropout layers in one network')
-            spec.n, spec.alpha, spec.net_id = len(layers), int(bool(g_.alpha)), int(g_.net_id)
-            for j, (q, r, idx) in enumerate(layers): spec.pos[j], spec.rate[j], spec.index[j] = int(q), float(r), int(idx)
-        holders = [] if forward_only else ([(ta.grad_state_types[i], g_) for i, g_ in enumerate(gs_all)] if composite else [(ta.grad_state, gs)]) + [(ta.grad_output, go)]
-        for g_, ng_ in holders:
-            if ng_.bn: g_.dgamma, g_.dbeta = nat.ptr(ng_.dgamma), nat.ptr(ng_.dbeta)
-            for l in range(len(ng_.W)): g_.dkernel[l], g_.dbias[l] = ng_.dW[l].data_ptr(), ng_.db[l].data_ptr()
-        T = m.net_output.units[-1]
-        y_pred, state = p.new(n_rows, T), p.new(N, S)
-        loss = p.new(1)
-        k_host = C.c_int32(0)
-        ta.y_pred, ta.state, ta.loss, ta.k_host = nat.ptr(y_pred), nat.ptr(state), nat.ptr(loss), C.pointer(k_host)
-        k_groups = None
-        if groups is not None:
-            gb = np.ascontiguousarray(np.asarray([int(v) for v in groups] if not isinstance(groups, np.ndarray) else groups, dtype=np.int32))
-            if gb.ndim != 1 or len(gb) < 2: raise ValueError('groups: node offsets [G + 1] expected')
-            G = len(gb) - 1
-            if group_out_begin is None:
-                # the group of every output row (node focus: the row's node; arc focus: the arc's source node), from the masks
-                rows = out_index.cpu().numpy().astype(np.int64)
-                if focus == 'a': rows = arcs[:, 0].cpu().numpy().astype(np.int64)[rows]
-                gid = np.searchsorted(gb.astype(np.int64), rows, side='right') - 1
-                if len(gid) and (np.any(np.diff(gid) < 0) or gid[0] < 0 or gid[-1] >= G):
-                    raise ValueError('groups: the output rows are not ordered by group (is this a merge of the groups, in order?)')
-                ob = np.searchsorted(gid, np.arange(G + 1), side='left').astype(np.int32)
-            else:
-                ob = np.ascontiguousarray(np.asarray(group_out_begin, dtype=np.int32))
-                if ob.shape != gb.shape: raise ValueError('group_out_begin: [G + 1] offsets expected')
-            k_groups = p.new(G)
-            keep += [gb, ob, k_groups]
-            ta.group_node_begin, ta.n_groups, ta.group_out_begin, ta.k_groups = gb.ctypes.data, G, ob.ctypes.data, nat.ptr(k_groups)
-            ans = nat.lib().gnn_train_groups_supported(C.byref(ta))
-            if ans == nat.TRAIN_GROUPS_MALFORMED:
-                raise ValueError('groups / group_out_begin must span [0, n_nodes] / [0, output rows] in ascending order, no empty group')
-            if ans == nat.TRAIN_GROUPS_UNCOVERED:
-                raise NotImplementedError('training-mode convergence groups do not cover this shape (one-layer state network' + (' per type' if composite else '') +
-                                          ' of units == state width <= 64, <= ' + ('64 constant columns per type' if composite else '32 constant columns') +
-                                          ', no softmax state, no Dropout; one-layer output network <= 64 units over <= 256 columns)')
-            if ans > 0:
-                raise NotImplementedError(f'training-mode convergence groups: group {ans - 1} has {int(gb[ans] - gb[ans - 1])} nodes '
-                                          f'(at most {nat.TRAIN_GROUP_MAX_NODES} per group)')
-        tiles = adjacency.tiles(64) if (self.use_tiles and not composite and groups is None) else None      # a merged batch: graphs packed into tiles of <= 64 nodes
-        if tiles is not None and len(tiles) - 1 <= 256:
-            ta.tile_node_begin, ta.n_tiles = tiles.ctypes.data, len(tiles) - 1
-        # a large graph keeps its constants line with the batch (sparse.py), shared with the inference forward: the first call fills it
-        xc_fill = False
-        if groups is None and not composite and N >= XC_MIN_NODES and xc_reuse_enabled() and nat.lib().gnn_train_xc_applies(C.byref(ta)):
-            caller_nodes, caller_arcs = inputs[0], inputs[1]          # (the objects the caller passed: what the line's key holds)
-            line, valid = adjacency.constants_line(caller_nodes, caller_arcs, arcnode, L, d > 0, dev)
-            a.xc, a.xc_mode = nat.ptr(line), (nat.XC_VALID if valid else nat.XC_FILL)
-            xc_fill = not valid
-            keep.append(line)
-        nbytes = nat.lib().gnn_train_workspace_bytes(C.byref(ta))
-        if nbytes == 0: nat.check(1)
-        tape = getattr(self, '_tape', None)
-        if tape is None or tape.numel() < nbytes + 256 or tape.device != dev:
-            self.resolve_pending()                           # (the previous step's validity word lives in the tape that is about to go)
-            tape = self._tape = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=dev)
-        base = tape.data_ptr()
-        aligned = (base + 255) & ~255
-        ta.tape, ta.tape_bytes = C.c_void_p(aligned), tape.numel() - (aligned - base)
-        if phase_forward:
-            # phase 1 of `gnn_train_step_ex` (include/gnnloop.h): everything up to the output network and the pooling, the tape kept for
-            # `backward_phase`.  The handle carries the argument blocks (phase 2 runs on the SAME ones) and what an LGNN layer hands on.
-            if nat.lib().gnn_train_phases_supported(C.byref(ta)) != 0:
-                raise NotImplementedError('the phased in-library step does not cover this shape (gnn_train_phases_supported)')
-            ps, px = nat.TrainPhaseState(), nat.TrainPhaseArgs()
-            px.phase, px.phase_state = nat.TRAIN_PHASE_FORWARD, C.pointer(ps)
-            out_nodes = y_pred
-            if focus == 'g':
-                out_nodes = p.new(len(out_index), T)
-                px.node_out = nat.ptr(out_nodes)
-            ok_ptr, prev_ok = C.c_void_p(0), C.c_int32(1)
-            ta.grads_ok_dev = C.pointer(ok_ptr)
-            fetched = getattr(self, '_joint_word_tape', None) is tape      # the word of the last applied joint step on this tape, for free
-            self._joint_word_tape = None
-            if fetched:
-                prev_ok.value = -1
-                ta.prev_grads_ok_host = C.pointer(prev_ok)
-            nat.check(nat.lib().gnn_train_step_ex(C.byref(ta), C.byref(px)))
-            ta.prev_grads_ok_host = C.POINTER(C.c_int32)()
-            view = tape[aligned - base:aligned - base + 4].view(torch.int32)
-            E, A = int(arcs.shape[0]), int(arcs.shape[1]) - 2
-            return SimpleNamespace(ta=ta, px=px, ps=ps, keep=keep + [k_host, ok_ptr, y_pred, state, loss, out_nodes, tiles], gs=gs_all, go=go, k=int(k_host.value),
-                                   y_pred=y_pred, state=state, out_nodes=out_nodes, loss=loss, grads_ok=ok_ptr.value, grads_ok_view=view,
-                                   prev_ok=(None if not fetched or prev_ok.value < 0 else bool(prev_ok.value)), tape=tape, dev=dev, p=p,
-                                   N=N, L=L, S=S, T=T, M=len(out_index), E=E, A=A, out_index=out_index, arcnode=arcnode, n_rows=n_rows)
+        c = SimpleNamespace(op=op, p=p, ta=nat.TrainArgs(), keep=[op], backward=not forward_only)      # (`keep`: what the argument block points at)
+        if not forward_only and not phase_forward: c.keep += _bind_targets(c.ta, m, y, sample_weight, op.n_rows, op.dev)
+        self._fill_train_args(c, seed)
+        self._fill_tables(c, groups, group_out_begin)
+        self._fill_constants_line(c, grouped=groups is not None)
+        self._bind_tape(c)
+        if phase_forward: return self._finish_phase_forward(c)
+        ta, tape, k_host, gs_all, go = c.ta, c.tape, c.k_host, c.gs_all, c.go
         if forward_only:
             nat.check(nat.lib().gnn_train_step(C.byref(ta)))
-            if xc_fill: adjacency.constants_line_filled()
-            if groups is not None:
-                self._keep_groups = keep                       # (the call did not synchronise: its operands live until the next one)
-                return {'k': k_groups, 'y_pred': y_pred, 'state': state}
-            return {'k': int(k_host.value), 'y_pred': y_pred, 'state': state}
+            if c.xc_fill: op.adjacency.constants_line_filled()
+            if groups is None: return {'k': int(k_host.value), 'y_pred': c.y_pred, 'state': c.state}
+            self._keep_groups = c.keep                     # (the call did not synchronise: its operands live until the next one)
+            return {'k': c.k_groups, 'y_pred': c.y_pred, 'state': c.state}
+        if op.state0 is not None: state0 = op.state0           # (a failed step's batch is trained again from the SAME initial state)
         # the validity word of this step's gradients (first word of the tape) and - for free, at the call's one synchronisation - the one
         # the previous step left there
         ok_ptr, prev_ok = C.c_void_p(0), C.c_int32(1)
@@ -1159,12 +953,12 @@ class LoopTrainer:
                 prev_valid = bool(prev_ok.value) if (fetched_by_call and prev_ok.value >= 0) else (self._read_word(pend['view']) if fetched_by_call else prev_ok.value != 0)
                 if not prev_valid: self._recover_failed(pend)
             raise
-        if xc_fill: adjacency.constants_line_filled()
+        if c.xc_fill: op.adjacency.constants_line_filled()
         for g_ in gs_all: g_.touched = k_host.value > 0          # (a type without nodes: the library zero-fills its gradients)
-        go.touched = len(out_index) > 0
-        view = tape[aligned - base:aligned - base + 4].view(torch.int32)
-        tp = SimpleNamespace(gs=gs_all, go=go, k=int(k_host.value), y_pred=y_pred, state=state, grads_ok=ok_ptr.value, grads_ok_view=view)
-        res = {'k': tp.k, 'y_pred': y_pred, 'state': state, 'loss': loss[0]}
+        go.touched = len(op.out_index) > 0
+        view = tape[c.word_at:c.word_at + 4].view(torch.int32)
+        tp = SimpleNamespace(gs=gs_all, go=go, k=int(k_host.value), y_pred=c.y_pred, state=c.state, grads_ok=ok_ptr.value, grads_ok_view=view)
+        res = {'k': tp.k, 'y_pred': c.y_pred, 'state': c.state, 'loss': c.loss[0]}
         failed_prev = pend is not None and prev_ok.value == 0
         if failed_prev: self._uncount_gated_step()              # before THIS step's update is issued: it is update n, not n + 1
         reg = self.finish(tp, apply)
@@ -1173,6 +967,156 @@ class LoopTrainer:
         res['grads_ok'] = view                                   # device int32[1]: 1 when the gradients / the update of this step are valid
         if failed_prev: self._recover_failed(pend, uncount=False)      # the PREVIOUS step's batch, one step late
         return res
+
+    def _fill_loop_block(self, c):
+        """The loop block of the argument block: the batch, the networks, the focus - what the inference forward is handed too."""
+        m, op, a = self.model, c.op, c.ta.loop
+        a.abi_version, a.composite, a.n_types = nat.GNN_ABI_VERSION, int(op.composite), len(op.dims)
+        a.n_nodes, a.n_arcs, a.dim_node_label, a.dim_arc_label = op.N, op.arcs.shape[0], op.L, op.A
+        a.nodes, a.ld_nodes = nat.ptr(op.nodes), op.L
+        a.arc_labels, a.ld_arcs = C.c_void_p(op.arcs.data_ptr() + 8), op.arcs.shape[1]
+        a.adjacency, a.arcnode = nat.make_csr(op.adj), nat.make_csr(op.an)
+        if op.composite:       # CompositeGNN.py:275-304: one state network per node type (csrc/train_composite.hpp)
+            a.type_nodes = nat.ptr(op.type_nodes)
+            for t_, dt in enumerate(op.dims): a.type_dim_label[t_], a.composite_adjacency[t_] = dt, nat.make_csr(op.ca_csr[t_])
+            for t_, first in enumerate(op.offsets): a.type_offsets[t_] = int(first)
+        for t_, n_ in enumerate(state_networks(m)): a.net_state[t_] = n_.native()
+        a.net_output = m.net_output.native()
+        a.state_dim, a.max_iteration, a.state_threshold = op.d, m.max_iteration, float(m.state_threshold)
+        a.flags = _train_flags(m)
+        a.state0 = nat.ptr(op.state0)                              # (None at state_vect_dim 0)
+        a.focus = nat.FOCUS[op.focus]
+        a.n_out, a.out_index = len(op.out_index), nat.ptr(op.out_index)
+        if op.focus == 'a': a.arc_src, a.arc_dst = nat.ptr(op.ends[0]), nat.ptr(op.ends[1])
+        a.nodegraph = nat.make_csr(op.ng)                          # (None but for graph focus)
+        a.stream = c.p.stream()
+
+    def _fill_train_args(self, c, seed):
+        """Step 2: the argument block from the operands - loop block, by-source transposes (a backward pass alone reads them), Dropout
+        specs, gradient holders, output buffers."""
+        m, op, p, ta = self.model, c.op, c.p, c.ta
+        self._fill_loop_block(c)
+        if c.backward:
+            ta.adjacency_by_source = nat.make_csr(_by_source(op.adjacency, op.dev))
+            if op.focus == 'g': ta.nodegraph_by_source = nat.make_csr(_by_source(op.nodegraph, op.dev))
+        ta.forward_only = int(not c.backward)
+        ta.average_st_grads = 0          # finish() divides by k AFTER adding the weight penalties, like the reference (GNN.py:295)
+        ta.bn_momentum = BN_MOMENTUM
+        # Dropout / AlphaDropout layers (reference MLP.py:60-66): their masks derive from the step's seed exactly as on the building-block path
+        ta.drop_seed = self._step_drop_seed(seed)
+        # gnn_train_step OVERWRITES every gradient buffer: the holders of the previous step are reused as they are (eight zero-fill
+        # launches and their allocations per step otherwise; the optimizer's pointer tables stay valid too).  A forward-only call takes
+        # them for what they know of the networks' Dropout layers; their buffers stay untouched
+        gs_all = c.gs_all = [self._cached_grads(f'state{i}' if op.composite else 'state', n_, p) for i, n_ in enumerate(state_networks(m))]
+        go = c.go = self._cached_grads('output', m.net_output, p)
+        if c.backward: self.gs, self.go = (gs_all if op.composite else gs_all[0]), go
+        for i, g_ in enumerate(gs_all): g_.net_id = i
+        go.net_id = 1000
+        for spec, g_ in [(ta.drop_state[i], g_) for i, g_ in enumerate(gs_all)] + [(ta.drop_output, go)]:
+            layers = [(q, r, idx) for q in sorted(g_.drop) for r, idx in g_.drop[q]]
+            if len(layers) > nat.GNN_MAX_DROPOUT: raise ValueError(f'more than {nat.GNN_MAX_DROPOUT} Dropout layers in one network')
+            spec.n, spec.alpha, spec.net_id = len(layers), int(bool(g_.alpha)), int(g_.net_id)
+            for j, (q, r, idx) in enumerate(layers): spec.pos[j], spec.rate[j], spec.index[j] = int(q), float(r), int(idx)
+        holders = ([(ta.grad_state_types[i], g_) for i, g_ in enumerate(gs_all)] if op.composite else [(ta.grad_state, gs_all[0])]) + [(ta.grad_output, go)]
+        for g_, ng_ in holders if c.backward else []:
+            if ng_.bn: g_.dgamma, g_.dbeta = nat.ptr(ng_.dgamma), nat.ptr(ng_.dbeta)
+            for l in range(len(ng_.W)): g_.dkernel[l], g_.dbias[l] = ng_.dW[l].data_ptr(), ng_.db[l].data_ptr()
+        c.T = m.net_output.units[-1]
+        c.y_pred, c.state, c.loss, c.k_host = p.new(op.n_rows, c.T), p.new(op.N, op.S), p.new(1), C.c_int32(0)
+        ta.y_pred, ta.state, ta.loss, ta.k_host = nat.ptr(c.y_pred), nat.ptr(c.state), nat.ptr(c.loss), C.pointer(c.k_host)
+
+    def _fill_tables(self, c, groups, group_out_begin):
+        """Step 3: the host tables - the groups of a grouped forward, refused here where `gnn_train_groups_supported` says so before
+        anything is launched; else the tiles of a merged batch."""
+        op, p, ta = c.op, c.p, c.ta
+        c.k_groups = c.tiles = None
+        if groups is None:
+            c.tiles = op.adjacency.tiles(64) if (self.use_tiles and not op.composite) else None      # a merged batch: graphs packed into tiles of <= 64 nodes
+            if c.tiles is not None and len(c.tiles) - 1 <= 256:
+                ta.tile_node_begin, ta.n_tiles = c.tiles.ctypes.data, len(c.tiles) - 1
+            return
+        gb = np.ascontiguousarray(np.asarray([int(v) for v in groups] if not isinstance(groups, np.ndarray) else groups, dtype=np.int32))
+        if gb.ndim != 1 or len(gb) < 2: raise ValueError('groups: node offsets [G + 1] expected')
+        G = len(gb) - 1
+        if group_out_begin is None:
+            # the group of every output row (node focus: the row's node; arc focus: the arc's source node), from the masks
+            rows = op.out_index.cpu().numpy().astype(np.int64)
+            if op.focus == 'a': rows = op.arcs[:, 0].cpu().numpy().astype(np.int64)[rows]
+            gid = np.searchsorted(gb.astype(np.int64), rows, side='right') - 1
+            if len(gid) and (np.any(np.diff(gid) < 0) or gid[0] < 0 or gid[-1] >= G):
+                raise ValueError('groups: the output rows are not ordered by group (is this a merge of the groups, in order?)')
+            ob = np.searchsorted(gid, np.arange(G + 1), side='left').astype(np.int32)
+        else:
+            ob = np.ascontiguousarray(np.asarray(group_out_begin, dtype=np.int32))
+            if ob.shape != gb.shape: raise ValueError('group_out_begin: [G + 1] offsets expected')
+        c.k_groups = p.new(G)
+        c.keep += [gb, ob, c.k_groups]
+        ta.group_node_begin, ta.n_groups, ta.group_out_begin, ta.k_groups = gb.ctypes.data, G, ob.ctypes.data, nat.ptr(c.k_groups)
+        ans = nat.lib().gnn_train_groups_supported(C.byref(ta))
+        if ans == nat.TRAIN_GROUPS_MALFORMED:
+            raise ValueError('groups / group_out_begin must span [0, n_nodes] / [0, output rows] in ascending order, no empty group')
+        if ans == nat.TRAIN_GROUPS_UNCOVERED:
+            raise NotImplementedError('training-mode convergence groups do not cover this shape (one-layer state network' + (' per type' if op.composite else '') +
+                                      ' of units == state width <= 64, <= ' + ('64 constant columns per type' if op.composite else '32 constant columns') +
+                                      ', no softmax state, no Dropout; one-layer output network <= 64 units over <= 256 columns)')
+        if ans > 0:
+            raise NotImplementedError(f'training-mode convergence groups: group {ans - 1} has {int(gb[ans] - gb[ans - 1])} nodes '
+                                      f'(at most {nat.TRAIN_GROUP_MAX_NODES} per group)')
+
+    def _fill_constants_line(self, c, grouped):
+        """Step 4: a large graph keeps its constants line with the batch (sparse.py), shared with the inference forward: the first call
+        fills it (`c.xc_fill`: the finisher reports it filled once the call has been issued)."""
+        op, a = c.op, c.ta.loop
+        c.xc_fill = False
+        if not grouped and not op.composite and op.N >= XC_MIN_NODES and xc_reuse_enabled() and nat.lib().gnn_train_xc_applies(C.byref(c.ta)):
+            # (the line's key holds the objects the caller passed)
+            line, valid = op.adjacency.constants_line(op.caller_nodes, op.caller_arcs, op.arcnode, op.L, op.d > 0, op.dev)
+            a.xc, a.xc_mode = nat.ptr(line), (nat.XC_VALID if valid else nat.XC_FILL)
+            c.xc_fill = not valid
+            c.keep.append(line)
+
+    def _bind_tape(self, c):
+        """Step 5: the tape - one cached device allocation, sized by the library for this argument block, 256-byte aligned.  Its first
+        word is the step's validity word (`c.word_at`: its offset in `c.tape`)."""
+        ta, dev = c.ta, c.op.dev
+        nbytes = nat.lib().gnn_train_workspace_bytes(C.byref(ta))
+        if nbytes == 0: nat.check(1)
+        tape = getattr(self, '_tape', None)
+        if tape is None or tape.numel() < nbytes + 256 or tape.device != dev:
+            self.resolve_pending()                           # (the previous step's validity word lives in the tape that is about to go)
+            tape = self._tape = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=dev)
+        base = tape.data_ptr()
+        aligned = (base + 255) & ~255
+        ta.tape, ta.tape_bytes = C.c_void_p(aligned), tape.numel() - (aligned - base)
+        c.tape, c.word_at = tape, aligned - base
+
+    def _finish_phase_forward(self, c):
+        """Phase 1 of `gnn_train_step_ex` (include/gnnloop.h): everything up to the output network and the pooling, the tape kept for
+        `backward_phase`.  The handle carries the argument blocks (phase 2 runs on the SAME ones) and what an LGNN layer hands on."""
+        op, p, ta, tape = c.op, c.p, c.ta, c.tape
+        if nat.lib().gnn_train_phases_supported(C.byref(ta)) != 0:
+            raise NotImplementedError('the phased in-library step does not cover this shape (gnn_train_phases_supported)')
+        ps, px = nat.TrainPhaseState(), nat.TrainPhaseArgs()
+        px.phase, px.phase_state = nat.TRAIN_PHASE_FORWARD, C.pointer(ps)
+        out_nodes = c.y_pred
+        if op.focus == 'g':
+            out_nodes = p.new(len(op.out_index), c.T)
+            px.node_out = nat.ptr(out_nodes)
+        ok_ptr, prev_ok = C.c_void_p(0), C.c_int32(1)
+        ta.grads_ok_dev = C.pointer(ok_ptr)
+        fetched = getattr(self, '_joint_word_tape', None) is tape      # the word of the last applied joint step on this tape, for free
+        self._joint_word_tape = None
+        if fetched:
+            prev_ok.value = -1
+            ta.prev_grads_ok_host = C.pointer(prev_ok)
+        nat.check(nat.lib().gnn_train_step_ex(C.byref(ta), C.byref(px)))
+        ta.prev_grads_ok_host = C.POINTER(C.c_int32)()
+        view = tape[c.word_at:c.word_at + 4].view(torch.int32)
+        return SimpleNamespace(ta=ta, px=px, ps=ps, keep=c.keep + [c.k_host, ok_ptr, c.y_pred, c.state, c.loss, out_nodes, c.tiles], gs=c.gs_all, go=c.go,
+                               k=int(c.k_host.value), y_pred=c.y_pred, state=c.state, out_nodes=out_nodes, loss=c.loss, grads_ok=ok_ptr.value,
+                               grads_ok_view=view, prev_ok=(None if not fetched or prev_ok.value < 0 else bool(prev_ok.value)), tape=tape,
+                               dev=op.dev, p=p, N=op.N, L=op.L, S=op.S, T=c.T, M=len(op.out_index), E=int(op.arcs.shape[0]), A=int(op.A),
+                               out_index=op.out_index, arcnode=op.arcnode, n_rows=op.n_rows)
 
     # ---- the step in two phases (gnn_train_step_ex): what a joint LGNN step is made of (docs/joint_lgnn_step.md) ---------------------------------
     def _native_phases_apply(self, n_nodes, n_arcs, dim_node_label, dim_arc_label, n_out):
@@ -1215,13 +1159,7 @@ class LoopTrainer:
         if y is None:
             ta.loss_kind = nat.LOSS_NONE
         else:
-            yd = y.to(dev, torch.float32).contiguous()
-            if yd.shape[0] != h.n_rows: raise ValueError(f'targets have {yd.shape[0]} rows, the model outputs {h.n_rows}')
-            sw = None if sample_weight is None else sample_weight.to(dev, torch.float32).contiguous()
-            ta.targets, ta.sample_weight = nat.ptr(yd), nat.ptr(sw)
-            kind = m.loss if isinstance(m.loss, str) else getattr(m.loss, '__name__', str(m.loss))
-            ta.loss_kind = nat.LOSSES[str(kind).lower()]
-            h.keep += [yd, sw]
+            h.keep += _bind_targets(ta, m, y, sample_weight, h.n_rows, dev)
         px.loss_scale = float(loss_scale)
         for name, t, shape in (('d_pred_extra', d_pred_extra, (h.n_rows, h.T)), ('d_out_extra', d_out_extra, (h.M, h.T)),
                                ('d_state_extra', d_state_extra, (h.N, h.S))):
@@ -1303,6 +1241,17 @@ def mlp_training_call(net: Sequential, segs, M, seed=None, net_id=0, call=0):
         mm, mv = ng.moving
         mm.mul_(BN_MOMENTUM).add_(st[0] * (1 - BN_MOMENTUM)); mv.mul_(BN_MOMENTUM).add_(st[1] * (1 - BN_MOMENTUM))
     return hs.out
+
+
+def _bind_targets(ta, model, y, sample_weight, n_rows, dev):
+    """Targets, sample weights and the loss kind into an argument block: float32, contiguous, one target row per output row.  Returns
+    the tensors the block points at (the caller keeps them alive)."""
+    yd = y.to(dev, torch.float32).contiguous()
+    if yd.shape[0] != n_rows: raise ValueError(f'targets have {yd.shape[0]} rows, the model outputs {n_rows}')
+    sw = None if sample_weight is None else sample_weight.to(dev, torch.float32).contiguous()
+    ta.targets, ta.sample_weight = nat.ptr(yd), nat.ptr(sw)
+    ta.loss_kind = loss_kind(model)[0]
+    return [yd, sw]
 
 
 def _regularize(ng: _NetGrads):

@@ -27,6 +27,7 @@ import torch
 import torch.distributed as dist
 
 from .Models.GNN import History, _loss_fn, _metric_fn
+from .Models.loop_operands import dropout_in_front
 
 
 class DPContext:
@@ -119,11 +120,9 @@ class DataParallel:
         if self.exact:
             # (refused HERE, on every rank alike - not from inside a step, where a rank without rows of the network would
             #  already sit in the step's all-reduce while the others raise)
-            nets = list(model.net_state) if isinstance(model.net_state, (list, tuple)) else [model.net_state]
-            for n_ in nets + [model.net_output]:
-                if any(float(r) > 0 and int(q) == 0 for r, q in zip(n_.dropout_rate or [], n_.dropout_pos or [])):
-                    raise NotImplementedError('the exact data-parallel step does not take a Dropout layer in front of the first Dense (dropout_pos = 0): '
-                                              'use DataParallel(model, exact=False)')
+            if dropout_in_front(model):
+                raise NotImplementedError('the exact data-parallel step does not take a Dropout layer in front of the first Dense (dropout_pos = 0): '
+                                          'use DataParallel(model, exact=False)')
         self.model, self.group = model, group
         self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
         self.dp = DPContext(group)

@@ -343,6 +343,34 @@ def test_uncovered_shapes_stay_batch_by_batch(what):
     assert np.array_equal(model.predict(seq).shape, (n_out, T))
 
 
+def test_a_graph_of_one_node_trains_like_the_building_blocks():
+    """A heterogeneous graph of ONE node (its type mask is (T, 1) after `process_inputs`: the node axis must survive) through
+    `Loop(training=True)`, `forward_native` and `train_step(apply=False)`: k, state and output of the building-block `forward()`.  The
+    bound is the file's TOL: the two orchestrations differ in the order of float32 sums over < 40 input columns, five iterations."""
+    from gnnkeras_amd.Models.training import LoopTrainer
+    dims, d = (5, 3, 4), 6
+    nodes = np.zeros((1, max(dims))); nodes[0, 1] = 1.0
+    tm = np.zeros((1, len(dims)), bool); tm[0, 1] = True
+    g = CompositeGraphObject(nodes=nodes, arcs=np.array([[0, 0, 1.0, 0.0, 0.0]]), targets=np.eye(T)[:1], type_mask=tm, dim_node_label=dims, focus='n',
+                             aggregation_mode='composite_average')
+    x, y, sw = CompositeMultiGraphSequencer([g], 'n', 'composite_average', 1, shuffle=False)[0]
+    assert tuple(x[3].shape) == (len(dims), 1, 1)
+    ns, no = nets(dims, d, 'n')
+    model = CCLS['n'](ns, no, d, 5, 0.0)
+    model.compile(optimizer='adam', loss='categorical_crossentropy')
+    s0 = dev(np.full((1, d), 0.05, np.float32))
+    tp = LoopTrainer(model).forward(x, state0=s0, seed=3)
+    k, state, out = model.Loop(*model.process_inputs(x), training=True, state0=s0, seed=3)
+    k_n, state_n, out_n = LoopTrainer(model).forward_native(x, state0=s0, seed=3)
+    res = LoopTrainer(model).train_step(x, y, sw, state0=s0, seed=3, apply=False)
+    torch.cuda.synchronize()
+    assert 'grads_ok' in res                  # (the in-library step ran: the building blocks leave no validity word)
+    assert float(k) == k_n == res['k'] == tp.k >= 1
+    for got_state, got_out in ((state, out), (state_n, out_n), (res['state'], res['y_pred'])):
+        assert tuple(got_state.shape) == (1, d) and tuple(got_out.shape) == (1, T)
+        assert rel_err(got_state.cpu(), tp.state.cpu()) < TOL and rel_err(got_out.cpu(), tp.y_pred.cpu()) < TOL
+
+
 # ---- 7. determinism ----------------------------------------------------------------------------------------------------------------------------
 def test_grouped_call_twice_is_bit_identical():
     rng = np.random.default_rng(2)
