@@ -24,12 +24,12 @@ __device__ __forceinline__ float activate_grad_from_output(int act, float y) {
 __global__ void __launch_bounds__(256)
 k_act_grad(const float *__restrict__ G, int ldg, const float *__restrict__ Y, int ldy, float *__restrict__ dZ, int ldz,
            int M, int H, int act) {
-    if (act == GNN_ACT_SOFTMAX) {
-        const int m = blockIdx.x * blockDim.x + threadIdx.x;
-        if (m >= M) return;
-        float dot = 0.0f;
-        for (int h = 0; h < H; ++h) dot = fmaf(G[(size_t)m * ldg + h], Y[(size_t)m * ldy + h], dot);
-        for (int h = 0; h < H; ++h) dZ[(size_t)m * ldz + h] = Y[(size_t)m * ldy + h] * (G[(size_t)m * ldg + h] - dot);
+    if (act == GNN_ACT_SOFTMAX) {                   // one row per thread, grid-stride: the launch caps the grid (gnn_act_grad)
+        for (size_t m = (size_t)blockIdx.x * blockDim.x + threadIdx.x; m < (size_t)M; m += (size_t)gridDim.x * blockDim.x) {
+            float dot = 0.0f;
+            for (int h = 0; h < H; ++h) dot = fmaf(G[m * ldg + h], Y[m * ldy + h], dot);
+            for (int h = 0; h < H; ++h) dZ[m * ldz + h] = Y[m * ldy + h] * (G[m * ldg + h] - dot);
+        }
         return;
     }
     const size_t total = (size_t)M * H;

@@ -37,6 +37,8 @@ def _act(a, z):
     if n == 'selu': return SELU_SCALE * np.where(z > 0, z, SELU_ALPHA * (np.exp(np.minimum(z, 0)) - 1))
     if n == 'tanh': return np.tanh(z)
     if n == 'sigmoid': return 1 / (1 + np.exp(-z))
+    if n == 'elu': return np.where(z > 0, z, np.exp(np.minimum(z, 0)) - 1)
+    if n == 'softplus': return np.logaddexp(z, 0)
     if n == 'softmax':
         e = np.exp(z - z.max(1, keepdims=True)); return e / e.sum(1, keepdims=True)
     raise NotImplementedError(n)
@@ -49,6 +51,8 @@ def _act_grad(a, G, Y):
     if n == 'selu': return G * np.where(Y > 0, SELU_SCALE, Y + SELU_SCALE * SELU_ALPHA)
     if n == 'tanh': return G * (1 - Y * Y)
     if n == 'sigmoid': return G * Y * (1 - Y)
+    if n == 'elu': return G * np.where(Y > 0, 1.0, Y + 1)            # from the OUTPUT y, as the kernel forms it
+    if n == 'softplus': return G * (1 - np.exp(-Y))
     if n == 'softmax': return Y * (G - (G * Y).sum(1, keepdims=True))
     raise NotImplementedError(n)
 
@@ -165,6 +169,13 @@ class NumpyPrim:
         yt = torch.from_numpy(y.numpy().astype(np.float64))
         p = torch.from_numpy(y_pred.numpy().astype(np.float64)).requires_grad_()
         w = torch.ones(yt.shape[0], dtype=torch.float64) if sw is None else torch.from_numpy(sw.numpy().astype(np.float64))
+        if kind in (1, 3):
+            # BCE / MAE: the oracle's own formula (oracle/torch_train.py::keras_loss = sum_r w_r l_r / M) under float64 autograd; the
+            # per-row losses come out of the same call as M w_r d/dw_r
+            w.requires_grad_()
+            torch_train.keras_loss({1: 'bce', 3: 'mae'}[kind], yt, p, w).backward()
+            self._put(dpred, p.grad.numpy()); self._put(loss_rows[:yt.shape[0]], (w.grad * yt.shape[0] * w.detach()).numpy())
+            return
         name = {0: 'cce', 2: 'mse'}[kind]
         eps = 1e-7
         if name == 'cce':
