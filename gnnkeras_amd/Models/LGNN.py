@@ -29,6 +29,7 @@ from .training import LoopTrainer
 
 SERIAL_PROPAGATION = ('per_graph', 'grouped')
 JOINT_STEP = ('auto', 'library', 'blocks')
+COMPOSITE_JOINT_STEP = ('blocks', 'auto', 'library')
 
 
 def plan_runs(sizes, cap, max_nodes, max_graphs=1 << 20):
@@ -97,6 +98,9 @@ class LGNN(_LoopModel):
         # how a joint step ('parallel' / 'residual') runs: 'library' = every layer as two library calls (`gnn_train_step_ex` phases 1 and 2,
         # docs/joint_lgnn_step.md), 'blocks' = the building blocks driven from here, 'auto' = 'library' where it applies
         self.joint_step = 'auto'
+        # ... of a stack of COMPOSITE layers: 'blocks' (the default) = as `joint_step` says, which keeps such stacks on the building blocks;
+        # 'auto' / 'library' = every layer as two `gnn_train_step_composite_ex` calls where it applies / or an error
+        self.composite_joint_step = 'blocks'
         self.last_joint_route = None
         self._engine_init()
 
@@ -145,16 +149,21 @@ class LGNN(_LoopModel):
         return cls(gnns=[gnn_class.load(f'{path}{d}') for d in dirs], **config)
 
     def compile(self, *args, training_mode: str = 'parallel', average_st_grads: bool = False, serial_propagation: str = 'per_graph',
-                joint_step: str = 'auto', **kwargs):
+                joint_step: str = 'auto', composite_joint_step: str = 'blocks', **kwargs):
         """`training_mode` in 'serial' (layers trained one after another), 'parallel' (loss = mean of the layers' losses),
         'residual' (loss of the mean of the layers' outputs) — reference LGNN.py:133-152.  `serial_propagation` (additive; serial mode):
         'per_graph' - between two layers every graph runs alone through the trained layer, one library call each - or 'grouped' - the
         same arithmetic with the graphs as convergence groups of one call per run (docs/serial_propagation.md).  `joint_step` (additive;
         'parallel' / 'residual'): 'library' - every layer's forward and backward as one library call each, 'blocks' - the building blocks,
-        'auto' - 'library' where it applies; `last_joint_route` records what a step took (docs/joint_lgnn_step.md)."""
+        'auto' - 'library' where it applies; `last_joint_route` records what a step took (docs/joint_lgnn_step.md).  `composite_joint_step`
+        (additive; stacks of composite layers only): 'blocks' - everything as `joint_step` alone decides (composite stacks train through the
+        building blocks, 'library' raises), 'auto' - the library route where it applies, else the building blocks, 'library' - the library
+        route or NotImplementedError with the reason."""
         if training_mode not in ('serial', 'parallel', 'residual'): raise ValueError('unknown training_mode')
         if joint_step not in JOINT_STEP: raise ValueError(f'joint_step must be one of {JOINT_STEP}')
         self.joint_step = joint_step
+        if composite_joint_step not in COMPOSITE_JOINT_STEP: raise ValueError(f'composite_joint_step must be one of {COMPOSITE_JOINT_STEP}')
+        self.composite_joint_step = composite_joint_step
         if serial_propagation not in SERIAL_PROPAGATION: raise ValueError(f'serial_propagation must be one of {SERIAL_PROPAGATION}')
         self.serial_propagation = serial_propagation
         super().compile(*args, average_st_grads=average_st_grads, **kwargs)
@@ -240,6 +249,12 @@ class LGNN(_LoopModel):
         s0 = state0 if state0 is not None else [None] * self.LAYERS
         for g in self.gnns: g.loss = self.loss
         if self.joint_step not in JOINT_STEP: raise ValueError(f'joint_step must be one of {JOINT_STEP}')
+        if len(x) == 10 and self.composite_joint_step != 'blocks':      # a stack of composite layers that opted in
+            why = self._joint_composite_refusal(x)
+            if why is None:
+                self.last_joint_route = 'library'
+                return self._train_step_library(x, y, sample_weight, s0, seed, apply)
+            if self.composite_joint_step == 'library': raise NotImplementedError(f"composite_joint_step='library' does not apply here: {why}")
         why = None if self.joint_step == 'blocks' else self._joint_library_refusal(x)
         if self.joint_step == 'library' and why is not None:
             raise NotImplementedError(f"joint_step='library' does not apply here: {why}")
@@ -336,6 +351,29 @@ class LGNN(_LoopModel):
                 arcs.shape[1] - 2 + (T if self.get_output and arc_based else 0)
         return None
 
+    def _joint_composite_refusal(self, x):
+        """`_joint_library_refusal` for a stack of composite layers (`composite_joint_step`): None when this batch can take the library route."""
+        from .loop_operands import type_widths
+        if len(x) != 10 or not all(isinstance(g.net_state, (list, tuple)) for g in self.gnns): return 'not a stack of composite layers'
+        if self.LAYERS > 16: return 'more than 16 layers'
+        nodes, arcs = x[0], x[1]
+        if not (isinstance(nodes, torch.Tensor) and nodes.is_cuda): return 'the batch is not on the device'
+        if self.GNN_CLASS is self._gnn_classes['arc']:
+            return 'arc-focused composite layers train through the building blocks (' + \
+                ('get_output hands the outputs on through the arc labels, and there is no composite arc-label gradient' if self.get_output
+                 else 'the phased composite step is wired for node and graph focus') + ')'
+        N, E, A = int(nodes.shape[0]), int(arcs.shape[0]), int(arcs.shape[1]) - 2
+        dims, L = type_widths(x[2]), int(nodes.shape[1])
+        for tr, g in zip(self._joint_trainers(), self.gnns):
+            if not tr._native_composite_phases_apply(N, E, dims, A, 1):
+                return 'a layer is not covered by the phased in-library composite step (Dropout in front of a first Dense, a loss without a device ' \
+                       'gradient, max_iteration < 1, a first state layer above 960 units, or a batch of the row-streaming size)'
+            S = g.state_vect_dim if g.state_vect_dim > 0 else L
+            plus = (S if self.get_state else 0) + (int(g.net_output.units[-1]) if self.get_output else 0)
+            L = int(nodes.shape[1]) + plus
+            dims = [min(dt + plus, L) for dt in dims]           # (`update_graph` widens the widths it is handed, the labels it builds anew)
+        return None
+
     def resolve_joint_pending(self, failed=None):
         """Settle the last applied joint step of the library route: was its update gated off on the device (a barrier wait of a persistent
         backward launch expired)?  `failed` None: read the gate word (one synchronisation) - what `fit()` does behind its last step and
@@ -362,14 +400,15 @@ class LGNN(_LoopModel):
         import warnings
         from .. import _native as nat
         from .training import Adam, SGD
-        i_set = 3
+        composite = len(x) == 10                                    # composite lists carry type_mask at [3] (`composite_joint_step`)
+        i_set = 4 if composite else 3
         nodes_0, arcs_0, dim0, set_mask, output_mask = x[0], x[1], x[2], x[i_set], x[i_set + 1]
         trainers = self._joint_trainers()
         arc_based = self.GNN_CLASS is self._gnn_classes['arc']
         Lyr = self.LAYERS
         hs, nodes, arcs, dnl = [], nodes_0, arcs_0, dim0
         for i, tr in enumerate(trainers):
-            h = tr.forward_phase(self._layer_x(x, nodes, arcs, dnl), state0=s0[i], seed=seed)
+            h = tr.forward_phase(self._layer_x(x, nodes, arcs, dnl), state0=s0[i], seed=seed, composite_phases=composite)
             hs.append(h)
             if i < Lyr - 1: nodes, arcs, dnl = self.update_graph(nodes_0, arcs_0, dnl, set_mask, output_mask, h.state, h.out_nodes)
         # the previous applied joint step: every phase 1 above fetched its layer's word for free at its synchronisation; a layer whose tape

@@ -107,7 +107,9 @@ def prepare_operands(model, inputs, state0=None, seed=None, node_level=False):
     for n_ in state_networks(m) + [m.net_output]: n_.to(dev)
     op.dims, op.type_nodes, op.offsets, op.cas, op.ca_csr = [op.L], None, None, None, None
     if op.composite:
-        op.dims = type_widths(dim_node_label)
+        # (`nodes[:, :d_t]` of the reference stops at the last column: from the third layer of a joint CompositeLGNN step on, `update_graph`
+        # hands on widths above the column count - it widens the widths it is handed, the labels it builds anew from the first layer's)
+        op.dims = [min(dt, int(op.L)) for dt in type_widths(dim_node_label)]
         T = len(op.dims)
         if T != len(m.net_state): raise ValueError(f'{T} node types but {len(m.net_state)} state networks')
         if T > nat.GNN_MAX_TYPES: raise ValueError(f'at most {nat.GNN_MAX_TYPES} node types are supported')

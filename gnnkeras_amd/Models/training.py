@@ -901,7 +901,7 @@ class LoopTrainer:
         return torch.tensor(float(tp.k), device=tp.dev), tp.state.clone(), tp.y_pred
 
     def _train_step_native(self, x_list, y, sample_weight, state0, seed, apply, forward_only=False, node_level=False, groups=None,
-                           group_out_begin=None, phase_forward=False):
+                           group_out_begin=None, phase_forward=False, composite_phases=False):
         """One `gnn_train_step` call: training-mode forward, loss, BPTT; the tape and every scratch buffer live in one cached
         device allocation. Same results as the general path (same kernels for the arithmetic), ~2.5x fewer launches and no
         Python between them.  `forward_only`: the forward alone (no targets, no gradients; `Loop(..., training=True)`);
@@ -924,7 +924,7 @@ class LoopTrainer:
         self._fill_tables(c, groups, group_out_begin)
         self._fill_constants_line(c, grouped=groups is not None)
         self._bind_tape(c)
-        if phase_forward: return self._finish_phase_forward(c)
+        if phase_forward: return self._finish_phase_forward(c, composite_phases)
         ta, tape, k_host, gs_all, go = c.ta, c.tape, c.k_host, c.gs_all, c.go
         if forward_only:
             nat.check(nat.lib().gnn_train_step(C.byref(ta)))
@@ -1090,11 +1090,28 @@ class LoopTrainer:
         ta.tape, ta.tape_bytes = C.c_void_p(aligned), tape.numel() - (aligned - base)
         c.tape, c.word_at = tape, aligned - base
 
-    def _finish_phase_forward(self, c):
+    def _finish_phase_forward(self, c, composite_phases=False):
         """Phase 1 of `gnn_train_step_ex` (include/gnnloop.h): everything up to the output network and the pooling, the tape kept for
-        `backward_phase`.  The handle carries the argument blocks (phase 2 runs on the SAME ones) and what an LGNN layer hands on."""
+        `backward_phase`.  The handle carries the argument blocks (phase 2 runs on the SAME ones) and what an LGNN layer hands on.
+        `composite_phases`: a heterogeneous model takes `gnn_train_step_composite_ex` - its third block holds the by-source transposes of
+        the composite adjacencies and a scratch of its own, a cached allocation beside the tape."""
         op, p, ta, tape = c.op, c.p, c.ta, c.tape
-        if nat.lib().gnn_train_phases_supported(C.byref(ta)) != 0:
+        cx = None
+        if composite_phases and op.composite:
+            if nat.lib().gnn_train_composite_phases_supported(C.byref(ta)) != 0:
+                raise NotImplementedError('the phased in-library step does not cover this shape (gnn_train_composite_phases_supported)')
+            cx = nat.TrainCompositePhaseArgs()
+            by_source = [_by_source(ca, op.dev) if dt > 0 else None for ca, dt in zip(op.cas, op.dims)]
+            for t_, bs in enumerate(by_source): cx.composite_adjacency_by_source[t_] = nat.make_csr(bs)
+            nbytes = nat.lib().gnn_train_composite_phase_scratch_bytes(C.byref(ta))
+            if nbytes == 0: nat.check(1)
+            scratch = getattr(self, '_composite_scratch', None)
+            if scratch is None or scratch.numel() < nbytes + 256 or scratch.device != op.dev:
+                scratch = self._composite_scratch = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=op.dev)
+            aligned = (scratch.data_ptr() + 255) & ~255
+            cx.scratch, cx.scratch_bytes = C.c_void_p(aligned), scratch.numel() - (aligned - scratch.data_ptr())
+            c.keep += [by_source, scratch]
+        elif nat.lib().gnn_train_phases_supported(C.byref(ta)) != 0:
             raise NotImplementedError('the phased in-library step does not cover this shape (gnn_train_phases_supported)')
         ps, px = nat.TrainPhaseState(), nat.TrainPhaseArgs()
         px.phase, px.phase_state = nat.TRAIN_PHASE_FORWARD, C.pointer(ps)
@@ -1109,10 +1126,11 @@ class LoopTrainer:
         if fetched:
             prev_ok.value = -1
             ta.prev_grads_ok_host = C.pointer(prev_ok)
-        nat.check(nat.lib().gnn_train_step_ex(C.byref(ta), C.byref(px)))
+        if cx is None: nat.check(nat.lib().gnn_train_step_ex(C.byref(ta), C.byref(px)))
+        else: nat.check(nat.lib().gnn_train_step_composite_ex(C.byref(ta), C.byref(px), C.byref(cx)))
         ta.prev_grads_ok_host = C.POINTER(C.c_int32)()
         view = tape[c.word_at:c.word_at + 4].view(torch.int32)
-        return SimpleNamespace(ta=ta, px=px, ps=ps, keep=c.keep + [c.k_host, ok_ptr, c.y_pred, c.state, c.loss, out_nodes, c.tiles], gs=c.gs_all, go=c.go,
+        return SimpleNamespace(ta=ta, px=px, ps=ps, cx=cx, keep=c.keep + [c.k_host, ok_ptr, c.y_pred, c.state, c.loss, out_nodes, c.tiles], gs=c.gs_all, go=c.go,
                                k=int(c.k_host.value), y_pred=c.y_pred, state=c.state, out_nodes=out_nodes, loss=c.loss, grads_ok=ok_ptr.value,
                                grads_ok_view=view, prev_ok=(None if not fetched or prev_ok.value < 0 else bool(prev_ok.value)), tape=tape,
                                dev=op.dev, p=p, N=op.N, L=op.L, S=op.S, T=c.T, M=len(op.out_index), E=int(op.arcs.shape[0]), A=int(op.A),
@@ -1139,12 +1157,38 @@ class LoopTrainer:
         a.focus, a.n_out = nat.FOCUS[m._focus], int(n_out)
         return nat.lib().gnn_train_phases_supported(C.byref(ta)) == 0
 
-    def forward_phase(self, x_list, state0=None, seed=None):
+    def _native_composite_phases_apply(self, n_nodes, n_arcs, dims, dim_arc_label, n_out):
+        """`_native_phases_apply` for a heterogeneous model (`forward_phase(composite_phases=True)`; `dims`: the label width of every node
+        type): today's `_native_step_applies` conditions, node or graph focus, and the library's `gnn_train_composite_phases_supported`.
+        Coverage depends on the node count, the widths and the networks, not on how the nodes split into types: the query puts them all
+        into the first type."""
+        m = self.model
+        if not isinstance(m.net_state, (list, tuple)) or m.max_iteration < 1 or m._focus not in ('n', 'g'): return False
+        if len(dims) != len(m.net_state) or len(dims) > nat.GNN_MAX_TYPES: return False
+        if not self._native_step_applies(True): return False
+        ta = nat.TrainArgs()
+        a = ta.loop
+        a.abi_version, a.composite, a.n_types = nat.GNN_ABI_VERSION, 1, len(dims)
+        a.n_nodes, a.n_arcs, a.dim_node_label, a.dim_arc_label = int(n_nodes), int(n_arcs), max(int(v) for v in dims), int(dim_arc_label)
+        for t_, dt in enumerate(dims): a.type_dim_label[t_] = int(dt)
+        for t_ in range(1, len(dims) + 1): a.type_offsets[t_] = int(n_nodes)
+        a.state_dim, a.max_iteration, a.state_threshold = m.state_vect_dim, m.max_iteration, float(m.state_threshold)
+        a.flags = _train_flags(m)
+        for dst, net in [(a.net_state[t_], n_) for t_, n_ in enumerate(m.net_state)] + [(a.net_output, m.net_output)]:
+            units = [int(u) for u in net.units]
+            dst.in_dim, dst.n_layers = int(net.input_dim), len(units)
+            for i, (u, act) in enumerate(zip(units, net.activations)): dst.units[i], dst.activation[i] = u, nat.ACTIVATIONS[act]
+        a.focus, a.n_out = nat.FOCUS[m._focus], int(n_out)
+        return nat.lib().gnn_train_composite_phases_supported(C.byref(ta)) == 0
+
+    def forward_phase(self, x_list, state0=None, seed=None, *, composite_phases=False):
         """Phase 1: the training-mode forward of one batch inside the library with the tape kept - y_pred, state, k and the per-node /
         per-arc outputs before the pooling (`out_nodes`) are there when it returns (the step's one synchronisation).  Returns the handle
         `backward_phase` takes; the trainer's tape belongs to it until then.  `prev_ok`: validity of the last applied joint step on this
-        tape (None: nothing to report).  A shape the library does not cover raises NotImplementedError before anything is launched."""
-        return self._train_step_native(x_list, None, None, state0, seed, False, phase_forward=True)
+        tape (None: nothing to report).  A shape the library does not cover raises NotImplementedError before anything is launched.
+        `composite_phases` (off by default: a heterogeneous model raises): the phases of a heterogeneous model, through
+        `gnn_train_step_composite_ex`; `h.gs` is then the per-type list and `backward_phase` leaves `h.d_nodes` [N, L]."""
+        return self._train_step_native(x_list, None, None, state0, seed, False, phase_forward=True, composite_phases=composite_phases)
 
     def backward_phase(self, h, y=None, sample_weight=None, loss_scale=1.0, d_pred_extra=None, d_out_extra=None, d_state_extra=None,
                        want_label_grads=False, want_arc_label_grads=False):
@@ -1171,12 +1215,15 @@ class LoopTrainer:
         if want_label_grads:
             h.d_nodes = p.new(h.N, h.L)
             px.d_nodes, px.ld_d_nodes = nat.ptr(h.d_nodes), h.L
+        if want_arc_label_grads and h.cx is not None:
+            raise NotImplementedError('heterogeneous models have no arc-label gradient')
         if want_arc_label_grads:
             h.d_arc_labels = p.zeros(h.E, h.A)
             if h.E > 0 and h.A > 0:
                 px.d_arc_labels = nat.ptr(h.d_arc_labels)
                 px.arcnode_by_source = nat.make_csr(_by_source(h.arcnode, dev))
-        nat.check(nat.lib().gnn_train_step_ex(C.byref(ta), C.byref(px)))
+        if h.cx is None: nat.check(nat.lib().gnn_train_step_ex(C.byref(ta), C.byref(px)))
+        else: nat.check(nat.lib().gnn_train_step_composite_ex(C.byref(ta), C.byref(px), C.byref(h.cx)))
         for g_ in h.gs: g_.touched = h.k > 0
         h.go.touched = h.M > 0
         return h

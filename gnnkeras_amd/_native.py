@@ -40,6 +40,7 @@ EXPORTS = ['gnn_last_error', 'gnn_last_status', 'gnn_last_kernel_name', 'gnn_abi
            'gnn_scatter_add_rows', 'gnn_axpby', 'gnn_loss_grad', 'gnn_dropout', 'gnn_adam_step', 'gnn_adam_multi', 'gnn_sgd_step',
            'gnn_converged_gated', 'gnn_aggregate_gated', 'gnn_train_workspace_bytes', 'gnn_train_step', 'gnn_train_groups_supported', 'gnn_ragged_copy',
            'gnn_train_step_ex', 'gnn_train_phases_supported', 'gnn_gate_all',
+           'gnn_train_step_composite_ex', 'gnn_train_composite_phases_supported', 'gnn_train_composite_phase_scratch_bytes',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_destroy', 'gnn_shard_loop']
 GNN_MAX_SEGMENTS = 6
 LOSSES = {'categorical_crossentropy': 0, 'cce': 0, 'binary_crossentropy': 1, 'bce': 1, 'mse': 2,
@@ -151,6 +152,10 @@ class TrainPhaseArgs(C.Structure):      # gnn_train_phase_args_t: all-zero = gnn
     _fields_ = [('phase', C.c_int32), ('loss_scale', C.c_float), ('phase_state', C.POINTER(TrainPhaseState)), ('node_out', C.c_void_p),
                 ('d_pred_extra', C.c_void_p), ('d_out_extra', C.c_void_p), ('d_state_extra', C.c_void_p),
                 ('d_nodes', C.c_void_p), ('ld_d_nodes', C.c_int32), ('d_arc_labels', C.c_void_p), ('arcnode_by_source', CSR)]
+
+
+class TrainCompositePhaseArgs(C.Structure):      # gnn_train_composite_phase_args_t: what gnn_train_step_composite_ex takes next to TrainPhaseArgs
+    _fields_ = [('composite_adjacency_by_source', CSR * GNN_MAX_TYPES), ('scratch', C.c_void_p), ('scratch_bytes', C.c_size_t)]
 
 
 # gnn_train_groups_supported(): 0 covered, -1 shape not covered, -2 malformed group arrays, g + 1 > 0: group g has too many nodes
@@ -320,6 +325,9 @@ def lib():
             'gnn_train_step_ex': (C.c_int, [C.POINTER(TrainArgs), C.POINTER(TrainPhaseArgs)]),
             'gnn_train_phases_supported': (C.c_int, [C.POINTER(TrainArgs)]),
             'gnn_gate_all': (C.c_int, [vp, i32, vp, vp]),
+            'gnn_train_step_composite_ex': (C.c_int, [C.POINTER(TrainArgs), C.POINTER(TrainPhaseArgs), C.POINTER(TrainCompositePhaseArgs)]),
+            'gnn_train_composite_phases_supported': (C.c_int, [C.POINTER(TrainArgs)]),
+            'gnn_train_composite_phase_scratch_bytes': (sz, [C.POINTER(TrainArgs)]),
             'gnn_loop_xc_applies': (C.c_int, [C.POINTER(LoopArgs)]),
             'gnn_loop_route_name': (C.c_char_p, [C.POINTER(LoopArgs)]),
             'gnn_loop_group_max_nodes': (C.c_int, [C.POINTER(LoopArgs)]),
@@ -342,7 +350,8 @@ def lib():
                 (C.sizeof(CSR), C.sizeof(MLP), C.sizeof(LoopArgs), LoopArgs.flags.offset) or \
                 (l.gnn_struct_size(4), l.gnn_struct_size(5), l.gnn_struct_size(6), l.gnn_struct_size(7)) != \
                 (C.sizeof(TrainArgs), TrainArgs.tape.offset, C.sizeof(RaggedDesc), C.sizeof(ShardLoopArgs)) or \
-                (l.gnn_struct_size(8), l.gnn_struct_size(9)) != (C.sizeof(TrainPhaseArgs), C.sizeof(TrainPhaseState)):
+                (l.gnn_struct_size(8), l.gnn_struct_size(9), l.gnn_struct_size(10)) != \
+                (C.sizeof(TrainPhaseArgs), C.sizeof(TrainPhaseState), C.sizeof(TrainCompositePhaseArgs)):
             raise NativeError('ctypes struct layout does not match libgnnloop.so: rebuild it')
         _lib = l
     return _lib

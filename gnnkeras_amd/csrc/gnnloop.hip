@@ -1182,6 +1182,7 @@ size_t gnn_struct_size(int which) {
         case 7: return sizeof(gnn_shard_loop_args_t);
         case 8: return sizeof(gnn_train_phase_args_t);
         case 9: return sizeof(gnn_train_phase_state_t);
+        case 10: return sizeof(gnn_train_composite_phase_args_t);
         default: return 0;
     }
 }

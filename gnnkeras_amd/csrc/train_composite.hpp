@@ -8,8 +8,9 @@
 // The same arithmetic as the building blocks driven from Python (Models/training.py) with the orchestration inside the library (the general
 // kernels of train_loop.hpp with per-type row lists: k_segdense / k_dense_grad_* / k_colstats_* take a row index per segment), one host
 // synchronisation per step (to learn k).  Node, graph and arc focus (CompositeGNN.py:315-327: the output network over [state_src | state_dst
-// | arc label] of the masked arcs); LGNN label gradients keep the building-block path.  The phases the step shares with the homogeneous one
-// (argument checks, read_k, output head, loss, head backward, finish_step, ..) are train_loop.hpp's.
+// | arc label] of the masked arcs).  The phases the step shares with the homogeneous one (argument checks, read_k, output head, loss, head
+// backward, finish_step, ..) are train_loop.hpp's.  gnn_train_step_composite_ex (the end of this file) cuts the step into the two phases of
+// gnn_train_step_ex, takes upstream gradients and leaves d loss / d nodes: what a joint CompositeLGNN step is made of.
 #pragma once
 // (included by gnnloop.hip behind train_loop.hpp: shares its anonymous-namespace helpers)
 #include "train_composite_big.hpp"      // large graphs: the row-streaming kernels on per-type position ranges
@@ -516,6 +517,32 @@ gnn::ConstSegs ctype_const_segs(const gnn_loop_args_t &a, const CPlan &p, const 
     return cs;
 }
 
+// ---- label gradients (gnn_train_step_composite_ex): what the caller wants, and the scratch of its own they live in (the tape keeps its layout)
+// `lab`: the constant segments' gradient is wanted (sum of dZ per type); `g0`: state_0 = nodes - d loss / d state_0 is part of d loss / d nodes
+struct CLabelWants { bool nodes, lab, g0; };
+struct CLabelScratch {
+    float *dz;                       // small graphs: [N][SPs] sum_t dZ_t by POSITION (the persistent backward launch stores it)
+    float *g0;                       // small graphs, state_dim == 0: [N][SPs] d loss / d state_0 by position
+    float *dz_t[GNN_MAX_TYPES];      // general path: [count_t][H_t] per type, zeroed per step, accumulated by net_backward
+    size_t dz_t_bytes;               // ... all of them, contiguous from dz_t[0]
+    float *g_comp;                   // [N][W_comp] d loss / d aggregated_component by node
+    size_t bytes;
+};
+
+CLabelScratch carve_label_scratch(const gnn_train_args_t &ta, const CPlan &p, void *base) {
+    CLabelScratch sc{};
+    Carver c(base);
+    const bool small = p.path == TrainPath::small;
+    sc.dz = c.take<float>(small ? (size_t)p.N * p.SPs : 0);
+    sc.g0 = c.take<float>(small && ta.loop.state_dim == 0 ? (size_t)p.N * p.SPs : 0);
+    const size_t first = (c.off + 255) & ~(size_t)255;
+    for (int q = 0; q < p.n_types; ++q) sc.dz_t[q] = c.take<float>(small ? 0 : (size_t)std::max(p.ty[q].count, 0) * p.ty[q].m->units[0]);
+    sc.dz_t_bytes = c.off - std::min(first, c.off);
+    sc.g_comp = c.take<float>((size_t)p.N * std::max(p.W_comp, 1));
+    sc.bytes = (c.off + 255) & ~(size_t)255;
+    return sc;
+}
+
 int moving_state(const gnn_train_args_t &ta, const CPlan &p, int k, const int *gate, hipStream_t st) {
     for (int q = 0; q < p.n_types; ++q)
         if (p.ty[q].count > 0) TRY(bn_moving(*p.ty[q].m, p.ty[q].stats, k, ta.bn_momentum, gate, st));
@@ -576,8 +603,8 @@ int composite_setup(const gnn_train_args_t &ta, CPlan &p, hipStream_t st) {
 
 // ---- training-mode forward: K gated iterations; tape = states, neighbour sums, per-type statistics (large graphs: composite_big_forward) ----
 // Small graphs: one persistent launch over tiles of <= 64 consecutive positions of ONE type (`tiles`); per type the network, its statistics
-// tape and where its shares go (`yt`) - the backward launch takes the same tables
-int composite_forward_small(const gnn_train_args_t &ta, CPlan &p, gnn::TileTab &tiles, gnn::TypeTab &yt, hipStream_t st) {
+// tape and where its shares go (`yt`) - the backward launch takes the same tables (host data alone: a phase-2 call builds them again)
+int composite_tile_tables(const gnn_train_args_t &ta, const CPlan &p, gnn::TileTab &tiles, gnn::TypeTab &yt) {
     const gnn_loop_args_t &a = ta.loop;
     int b = 0;
     for (int q = 0; q < p.n_types; ++q) {
@@ -592,6 +619,12 @@ int composite_forward_small(const gnn_train_args_t &ta, CPlan &p, gnn::TileTab &
     tiles.begin[b] = p.N; tiles.n = b;
     yt.n = p.n_types; yt.wg_begin[p.n_types] = p.n_wg; yt.perm = a.type_nodes; yt.inv = p.inv;
     if (b != p.n_wg) return fail("composite tiles: %d != %d", b, p.n_wg);
+    return 0;
+}
+
+int composite_forward_small(const gnn_train_args_t &ta, CPlan &p, gnn::TileTab &tiles, gnn::TypeTab &yt, hipStream_t st) {
+    const gnn_loop_args_t &a = ta.loop;
+    TRY(composite_tile_tables(ta, p, tiles, yt));
     // the constant part of every node's first layer (its type's network over its labels and the aggregated component), in position order
     for (int q = 0; q < p.n_types; ++q) {
         const CType &y = p.ty[q];
@@ -640,11 +673,13 @@ int composite_forward_general(const gnn_train_args_t &ta, CPlan &p, hipStream_t 
 // ---- backward through the k executed iterations; p.G_state = d loss / d state_k in the caller's node order (large graphs:
 // composite_big_backward).  Small graphs: one persistent launch, then every tile's [kernel | bias] (and [d gamma | d beta]) share of ITS
 // type's gradients summed in tile order
-int composite_backward_small(const gnn_train_args_t &ta, CPlan &p, const gnn::TileTab &tiles, const gnn::TypeTab &yt, int k, hipStream_t st) {
+int composite_backward_small(const gnn_train_args_t &ta, CPlan &p, const gnn::TileTab &tiles, const gnn::TypeTab &yt, int k, const CLabelScratch &sc,
+                             const CLabelWants &w, hipStream_t st) {
     gnn::TypeConsts yc{};
     for (int q = 0; q < p.n_types; ++q) yc.cs[q] = ctype_const_segs(ta.loop, p, p.ty[q]);
     gnn::TrainSmallBwd ba{};
     ba.eps = p.ty[0].m->bn_eps; ba.dxa = p.sm_dxa;
+    ba.dz_out = w.lab ? sc.dz : nullptr; ba.g0_out = w.g0 ? sc.g0 : nullptr;      // (by POSITION, rows of SPs floats: the LAB instantiations)
     TRY(launch_train_small_bwd(ba, ta, p, k, tiles, &yt, &yc, st));
     for (int q = 0; q < p.n_types; ++q) {
         const CType &y = p.ty[q];
@@ -662,7 +697,7 @@ int composite_backward_small(const gnn_train_args_t &ta, CPlan &p, const gnn::Ti
 }
 
 // the general path: net_backward per type and iteration on the type's gathered rows, then the transposed aggregate over all nodes
-int composite_backward_general(const gnn_train_args_t &ta, CPlan &p, int k, hipStream_t st) {
+int composite_backward_general(const gnn_train_args_t &ta, CPlan &p, int k, const CLabelScratch &sc, const CLabelWants &w, hipStream_t st) {
     const gnn_loop_args_t &a = ta.loop;
     gnn::Seg segs[GNN_MAX_SEGS];
     for (int t = k - 1; t >= 0; --t) {
@@ -681,7 +716,7 @@ int composite_backward_general(const gnn_train_args_t &ta, CPlan &p, int k, hipS
             TRY(recompute_hidden(ns, segs, n, y.count, stats, y.Wf + (size_t)t * y.in_dim * ns.units[0], y.bf + (size_t)t * ns.units[0], hs, drs, drop_any, st));
             if (!drop_any) TRY(gather_rows(s_n, p.S, y.rows, y.count, p.S, hs[ns.n_layers - 1], p.S, st));      // the last layer's output: the type's rows of state t + 1
             TRY(gather_rows(p.G_state, p.S, y.rows, y.count, p.S, y.Gc, p.S, st));
-            TRY(net_backward(y.nc, segs, n, hs, y.Gc, p.S, y.count, stats, t != k - 1, y.dx, 2 * p.S, p.part, st, -1, y.off_state, &drs));
+            TRY(net_backward(y.nc, segs, n, hs, y.Gc, p.S, y.count, stats, t != k - 1, y.dx, 2 * p.S, p.part, st, -1, y.off_state, &drs, w.lab ? sc.dz_t[q] : nullptr));
             gnn::BnGradReq rq[2] = {gnn::BnGradReq{y.dx, 2 * p.S, s_t, p.S, y.rows, p.S, y.off_state},
                                     gnn::BnGradReq{y.dx + p.S, 2 * p.S, agg_t, p.S, y.rows, p.S, y.off_agg}};
             TRY(bn_input_grads(ns, y.nc, stats, rq, 2, y.count, st));
@@ -693,15 +728,106 @@ int composite_backward_general(const gnn_train_args_t &ta, CPlan &p, int k, hipS
     return 0;
 }
 
-// The step as its phases (no phase cut here: gnn_train_step_ex covers homogeneous models)
-int train_step_composite(const gnn_train_args_t &ta) {
+// ---- d loss / d nodes: one launch turns every type's sum_t dZ_t into the gradients of its constant inputs (k_label_grads_types: the own-label
+// columns straight into d_nodes, d loss / d aggregated_component into the scratch), then per type t' with labels the transposed CompositeAdjacency
+// aggregate of its component columns on top (CompositeGNN.py:251 transposed), and d loss / d state_0 where state_0 = nodes.  The composite output
+// network reads the state alone: no head label segments.
+int composite_label_grads(const gnn_train_args_t &ta, const gnn_train_phase_args_t &px, const gnn_train_composite_phase_args_t &cx, const CPlan &p,
+                          const CLabelScratch &sc, int k, const CLabelWants &w, hipStream_t st) {
+    const gnn_loop_args_t &a = ta.loop;
+    const int ldn = px.ld_d_nodes > 0 ? px.ld_d_nodes : p.L;
+    float *d_nodes = px.d_nodes;
+    const bool small = p.path == TrainPath::small;
+    if (k == 0) {                  // no iteration ran: nothing reached the constants
+        if (w.g0) return launch_copy2d(nullptr, p.G_state, p.S, d_nodes, ldn, p.N, p.L, p.L, st);
+        HIP_OK(hipMemset2DAsync(d_nodes, sizeof(float) * ldn, 0, sizeof(float) * p.L, p.N, st));
+        return 0;
+    }
+    gnn::LabelGradTypesArgs la{};
+    la.n_types = p.n_types; la.L = p.L; la.W_comp = p.W_comp;
+    la.type_nodes = a.type_nodes; la.nodes = a.nodes; la.ld_nodes = a.ld_nodes; la.agg_comp = p.agg_comp;
+    la.lab_own = d_nodes; la.ld_own = ldn; la.g_comp = sc.g_comp;
+    int H_max = 1;
+    for (int q = 0; q < p.n_types; ++q) {
+        const CType &y = p.ty[q];
+        const gnn_mlp_t &m = *y.m;
+        la.tile_begin[q + 1] = la.tile_begin[q] + cdiv(std::max(y.count, 0), gnn::LG_ROWS);
+        gnn::LabelGradType &t = la.t[q];
+        t.pos0 = a.type_offsets[q]; t.count = y.count; t.H = m.units[0];
+        t.DZ = small ? sc.dz + (size_t)t.pos0 * p.SPs : sc.dz_t[q]; t.ldz = small ? p.SPs : t.H;
+        t.W = m.kernel[0]; t.d_t = y.d_t; t.wrow_comp = y.off_comp;
+        if (m.has_bn) { t.gamma = m.bn_gamma; t.mean = y.stats_tpl; t.var = y.stats_tpl + y.in_dim; t.dgamma = y.g.dgamma; t.dbeta = y.g.dbeta; t.eps = m.bn_eps; }
+        t.inv_n = 1.0f / (float)std::max(y.count, 1);
+        if (y.count > 0) H_max = std::max(H_max, t.H);
+    }
+    const int n_tiles = la.tile_begin[p.n_types];
+    gnn::k_label_grads_types<<<std::min(n_tiles, 4096), 256, sizeof(float) * gnn::LG_ROWS * (H_max + 1), st>>>(la);
+    LAUNCH_OK();
+    int col = 0;
+    for (int q = 0; q < p.n_types; ++q) {
+        const int dt = a.type_dim_label[q];
+        if (dt > 0) TRY(launch_aggregate_add(cx.composite_adjacency_by_source[q], sc.g_comp + col, p.W_comp, dt, d_nodes, ldn, d_nodes, ldn, st));
+        col += dt;
+    }
+    if (w.g0) {                    // state_0 = nodes (CompositeGNN.py:258); the persistent launch left it by position
+        if (small) TRY(scatter_add_rows(sc.g0, p.SPs, a.type_nodes, p.N, p.S, d_nodes, ldn, st));
+        else { gnn::k_add2d<<<std::min(cdiv((long)p.N * p.S, 256), 1024), 256, 0, st>>>(d_nodes, ldn, p.G_state, p.S, p.N, p.S); LAUNCH_OK(); }
+    }
+    return 0;
+}
+
+// what gnn_train_composite_phases_supported answers from the plan: the paths with phases, first layers the label-gradient kernel can stage
+int composite_phases_covered(const CPlan &p) {
+    if (p.path == TrainPath::big)
+        return not_covered("gnn_train_step_composite_ex: the row-streaming path (>= GNN_TRAIN_BIG_MIN_NODES nodes) has no phases / upstream gradients / label gradients: such steps train through the building blocks");
+    for (int q = 0; q < p.n_types; ++q)
+        if (p.ty[q].m->units[0] > gnn::LG_MAX_H)
+            return not_covered("gnn_train_step_composite_ex: first state layer of %d units (at most %d)", p.ty[q].m->units[0], gnn::LG_MAX_H);
+    return 0;
+}
+
+// the two extra argument blocks against the plan: everything that refuses a call, before its first launch
+int check_composite_phase_args(const gnn_train_args_t &ta, const gnn_train_phase_args_t &px, const gnn_train_composite_phase_args_t *cx, const CPlan &p,
+                               const CLabelScratch &need) {
+    TRY(composite_phases_covered(p));
+    if (px.phase == 0 && ta.loss_kind == GNN_LOSS_NONE) return fail("GNN_LOSS_NONE is valid in phase %d only (a whole step needs a loss of its own)", GNN_TRAIN_PHASE_BACKWARD);
+    if (px.phase != 0 && !px.phase_state) return fail("gnn_train_step_composite_ex: phase %d needs phase_state", px.phase);
+    if (px.phase == GNN_TRAIN_PHASE_BACKWARD && px.phase_state->magic != PHASE_MAGIC) return fail("gnn_train_step_composite_ex: phase_state was not filled by a phase-1 call");
+    if (px.phase == GNN_TRAIN_PHASE_BACKWARD && (px.phase_state->k < 0 || px.phase_state->k > p.K)) return fail("gnn_train_step_composite_ex: phase_state holds k = %d", px.phase_state->k);
+    if (px.d_nodes && px.ld_d_nodes != 0 && px.ld_d_nodes < p.L) return fail("gnn_train_step_composite_ex: ld_d_nodes %d < dim_node_label %d", px.ld_d_nodes, p.L);
+    if (px.phase != 0 || px.d_nodes) {
+        if (!cx || !cx->scratch || ((uintptr_t)cx->scratch & 255) != 0) return fail("gnn_train_step_composite_ex: phases and label gradients need cx->scratch, a 256-byte aligned device buffer");
+        if (cx->scratch_bytes < need.bytes) return fail("gnn_train_step_composite_ex: scratch too small: %zu < %zu bytes", cx->scratch_bytes, need.bytes);
+    }
+    for (int q = 0; q < p.n_types && px.d_nodes; ++q) {
+        if (ta.loop.type_dim_label[q] <= 0) continue;
+        if (!cx->composite_adjacency_by_source[q].rowptr) return fail("gnn_train_step_composite_ex: d_nodes needs composite_adjacency_by_source[%d]", q);
+        TRY(check_csr(cx->composite_adjacency_by_source[q], "composite_adjacency_by_source", p.N, p.N));
+    }
+    return 0;
+}
+
+// The step as its phases.  `px` / `cx` (gnn_train_step_composite_ex; all-zero / NULL: the plain gnn_train_step): phase 1 stops behind the output
+// network, in front of the loss, with the tape kept; phase 2 goes on from there with the k phase 1 learned at its synchronisation - the launches
+// of the whole step, in its order, cut in two.
+int train_step_composite(const gnn_train_args_t &ta, const gnn_train_phase_args_t &px, const gnn_train_composite_phase_args_t *cx) {
     const gnn_loop_args_t &a = ta.loop;
     CPlan p;
     const bool fwd_only = ta.forward_only != 0;         // the training-mode forward alone: no loss, no gradients, the validity word untouched
+    const int phase = px.phase;
+    const bool ex = phase != 0 || px.loss_scale != 0.0f || px.phase_state || px.node_out || px.d_pred_extra || px.d_out_extra || px.d_state_extra || px.d_nodes;
     if (fwd_only && ta.prev_grads_ok_host) return fail("gnn_train_step(forward_only): prev_grads_ok_host must be NULL");
     TRY(make_cplan(ta, ta.tape, p));
+    CLabelScratch sc{};
+    if (ex) {
+        const CLabelScratch need = carve_label_scratch(ta, p, nullptr);
+        TRY(check_composite_phase_args(ta, px, cx, p, need));
+        if (cx && cx->scratch) sc = carve_label_scratch(ta, p, cx->scratch);
+    }
     if (!ta.tape || ta.tape_bytes < p.bytes) return fail("tape too small: %zu < %zu bytes", ta.tape_bytes, p.bytes);
-    TRY(check_step_args(ta, p, !fwd_only, !fwd_only));
+    const bool do_fwd = phase != GNN_TRAIN_PHASE_BACKWARD;        // phase 0 / 1: setup, loop, output network
+    const bool no_loss = ta.loss_kind == GNN_LOSS_NONE && phase != 0;
+    TRY(check_step_args(ta, p, !fwd_only && phase != GNN_TRAIN_PHASE_FORWARD && !no_loss, !fwd_only && phase != GNN_TRAIN_PHASE_FORWARD));
     const bool small = p.path == TrainPath::small, big = p.path == TrainPath::big;
     const gnn_mlp_t &no = a.net_output;
     hipStream_t st = (hipStream_t)a.stream;
@@ -711,40 +837,105 @@ int train_step_composite(const gnn_train_args_t &ta) {
     gnn::TypeTab yt;
     memset(&tiles, 0, sizeof(tiles)); memset(&yt, 0, sizeof(yt));
     int k = 0;
-    TRY(composite_setup(ta, p, st));
-    TRY(big ? composite_big_forward(ta, p, st) : small ? composite_forward_small(ta, p, tiles, yt, st) : composite_forward_general(ta, p, st));
-    TRY(read_k(ta, p, &k, st));
-    if (small || big) TRY(scatter_rows(state_at(p, k), p.ldS, a.type_nodes, p.N, p.S, ta.state, p.S, st));      // positions -> the caller's node order
-    else HIP_OK(hipMemcpyAsync(ta.state, state_at(p, k), sizeof(float) * p.N * p.ldS, hipMemcpyDeviceToDevice, st));
+    if (do_fwd) {
+        TRY(composite_setup(ta, p, st));
+        TRY(big ? composite_big_forward(ta, p, st) : small ? composite_forward_small(ta, p, tiles, yt, st) : composite_forward_general(ta, p, st));
+        TRY(read_k(ta, p, &k, st));
+        if (phase == GNN_TRAIN_PHASE_FORWARD) *px.phase_state = gnn_train_phase_state_t{PHASE_MAGIC, k, 1, 0};      // (phases: always the general head)
+        if (small || big) TRY(scatter_rows(state_at(p, k), p.ldS, a.type_nodes, p.N, p.S, ta.state, p.S, st));      // positions -> the caller's node order
+        else HIP_OK(hipMemcpyAsync(ta.state, state_at(p, k), sizeof(float) * p.N * p.ldS, hipMemcpyDeviceToDevice, st));
+        if (!small) TRY(moving_state(ta, p, k, nullptr, st));          // (the persistent path: moving_deferred)
+    } else {                       // phase 2: what phase 1 learned at its synchronisation; the host tables of the persistent backward launch again
+        k = px.phase_state->k;
+        if (ta.grads_ok_dev) *ta.grads_ok_dev = p.grads_ok;
+        if (small) TRY(composite_tile_tables(ta, p, tiles, yt));
+    }
     const float *state_k = ta.state;                                   // [N, S] in the caller's node order
-    if (!small) TRY(moving_state(ta, p, k, nullptr, st));              // (the persistent path: moving_deferred)
 
     // ---- output network on the converged state of the masked nodes (CompositeGNN.py:237-239, :270), training mode ----------------------------
     HeadRun h;
-    TRY(head_segments(ta, p, state_k, p.S, 0, true, h, st));
-    const bool stats_one_pass = p.M > 0 && no.has_bn && p.head_fast;
-    if (stats_one_pass) {          // every node a row, in order: one pass over the state (moments around its row 0)
-        int grid = 0;
-        TRY(rows_stats(nullptr, state_k, p.S, p.S, p.N, p.B.part_y[0], st, &grid));
-        gnn::k_stats_finish<<<p.S, 256, 0, st>>>(nullptr, p.B.part_y[0], grid, p.S, 1.0f / (float)p.N, p.stats_o, p.stats_o + no.in_dim, state_k);
-        LAUNCH_OK();
+    TRY(head_segments(ta, p, state_k, p.S, 0, do_fwd, h, st));
+    if (do_fwd) {
+        const bool stats_one_pass = p.M > 0 && no.has_bn && p.head_fast;
+        if (stats_one_pass) {      // every node a row, in order: one pass over the state (moments around its row 0)
+            int grid = 0;
+            TRY(rows_stats(nullptr, state_k, p.S, p.S, p.N, p.B.part_y[0], st, &grid));
+            gnn::k_stats_finish<<<p.S, 256, 0, st>>>(nullptr, p.B.part_y[0], grid, p.S, 1.0f / (float)p.N, p.stats_o, p.stats_o + no.in_dim, state_k);
+            LAUNCH_OK();
+        }
+        TRY(head_forward(ta, p, h, stats_one_pass, st));
+        if (px.node_out && p.M > 0) HIP_OK(hipMemcpyAsync(px.node_out, h.out_nodes, sizeof(float) * (size_t)p.M * p.T, hipMemcpyDeviceToDevice, st));
     }
-    TRY(head_forward(ta, p, h, stats_one_pass, st));
+    if (phase == GNN_TRAIN_PHASE_FORWARD) return 0;                    // THE PHASE CUT, in front of the loss: the tape is kept, phase 2 goes on from here
     if (fwd_only) return moving_deferred(ta, p, k, nullptr, st);       // the forward alone: what the persistent path keeps back for the validity word is due now
 
-    // ---- loss, then backward: output network, the k iterations on the plan's path --------------------------------------------------------------
+    // ---- loss and its gradient, upstream gradients added ------------------------------------------------------------------------------------------
     float *G_out = nullptr;
-    TRY(loss_gradient(ta, p, true, 0.0f, nullptr, &G_out, st));
+    TRY(loss_gradient(ta, p, !no_loss, px.loss_scale, px.d_pred_extra, &G_out, st));
+    if (px.d_out_extra && p.M > 0) TRY(add_into(G_out, px.d_out_extra, (size_t)p.M * p.T, st));
+    const CLabelWants want{px.d_nodes != nullptr, px.d_nodes != nullptr, px.d_nodes != nullptr && a.state_dim == 0};
+    if (want.lab && !small && k > 0 && sc.dz_t_bytes > 0) HIP_OK(hipMemsetAsync(sc.dz_t[0], 0, sc.dz_t_bytes, st));
+
+    // ---- backward: output network, the k iterations on the plan's path, label gradients ------------------------------------------------------------
     // (the thin head: its parameter gradients, d loss / d state_k written straight into the state gradient - every row is an output row)
     if (p.head_fast) TRY(head_backward(p, a, nullptr, 0, state_k, p.S, h.out_nodes, G_out, no.has_bn ? p.stats_o : nullptr, st, -1));
     else TRY(head_backward_general(ta, p, h, G_out, st));
+    if (px.d_state_extra) TRY(add_into(p.G_state, px.d_state_extra, (size_t)p.N * p.S, st));
     for (int q = 0; q < p.n_types; ++q)
         if (k == 0 || p.ty[q].count == 0) TRY(zero_grads(*p.ty[q].m, p.ty[q].g, st));
     if (big) TRY(composite_big_backward(ta, p, k, st));
-    else if (small && k > 0) TRY(composite_backward_small(ta, p, tiles, yt, k, st));
-    else if (!small) TRY(composite_backward_general(ta, p, k, st));
+    else if (small && k > 0) TRY(composite_backward_small(ta, p, tiles, yt, k, sc, want, st));
+    else if (!small) TRY(composite_backward_general(ta, p, k, sc, want, st));
+    if (want.nodes) TRY(composite_label_grads(ta, px, *cx, p, sc, k, want, st));
     for (int q = 0; q < p.n_types && ta.average_st_grads && k > 0; ++q) TRY(scale_grads(*p.ty[q].m, p.ty[q].g, 1.0f / (float)k, st));
     return finish_step(ta, p, k, st);
 }
 
+int train_step_composite(const gnn_train_args_t &ta) {
+    gnn_train_phase_args_t none;
+    memset(&none, 0, sizeof(none));
+    return train_step_composite(ta, none, nullptr);
+}
+
 }  // namespace
+
+extern "C" {
+
+int gnn_train_composite_phases_supported(const gnn_train_args_t *args) {
+    if (!args || !args->loop.composite || args->n_groups != 0 || args->forward_only) return -1;
+    CPlan p;
+    if (make_cplan(*args, nullptr, p)) return -1;
+    return composite_phases_covered(p) ? -1 : 0;
+}
+
+size_t gnn_train_composite_phase_scratch_bytes(const gnn_train_args_t *args) {
+    if (!args) { fail("args is NULL"); return 0; }
+    if (!args->loop.composite || args->n_groups != 0 || args->forward_only) {
+        not_covered("gnn_train_step_composite_ex covers whole steps of heterogeneous models only (gnn_train_composite_phases_supported)");
+        return 0;
+    }
+    CPlan p;
+    if (make_cplan(*args, nullptr, p) || composite_phases_covered(p)) return 0;
+    return carve_label_scratch(*args, p, nullptr).bytes;
+}
+
+int gnn_train_step_composite_ex(const gnn_train_args_t *args, const gnn_train_phase_args_t *px, const gnn_train_composite_phase_args_t *cx) {
+    if (!args) return fail("args is NULL");
+    gnn_train_phase_args_t x;
+    memset(&x, 0, sizeof(x));
+    if (px) x = *px;
+    const bool used = x.phase != 0 || x.loss_scale != 0.0f || x.phase_state || x.node_out || x.d_pred_extra || x.d_out_extra || x.d_state_extra || x.d_nodes ||
+                      x.d_arc_labels;
+    if (!used && !cx) return gnn_train_step(args);                 // exactly the plain call: same checks, same order, same messages
+    const gnn_train_args_t &ta = *args;
+    if (!ta.tape || ((uintptr_t)ta.tape & 255) != 0) return fail("tape must be a 256-byte aligned device buffer");
+    if (x.phase < 0 || x.phase > GNN_TRAIN_PHASE_BACKWARD) return fail("gnn_train_step_composite_ex: unknown phase %d", x.phase);
+    if (!ta.loop.composite) return not_covered("gnn_train_step_composite_ex: heterogeneous models only (homogeneous models have gnn_train_step_ex)");
+    if (ta.n_groups != 0 || ta.forward_only)
+        return not_covered("gnn_train_step_composite_ex: phases, upstream gradients and label gradients cover whole steps only (no convergence groups, no forward_only)");
+    if (x.d_arc_labels) return not_covered("gnn_train_step_composite_ex: no composite arc-label gradient (d_arc_labels): such stacks train through the building blocks");
+    return landed_on_failure(ta, train_step_composite(ta, x, cx));
+}
+
+}  // extern "C"
+

@@ -1564,21 +1564,24 @@ int gnn_gate_all(const int32_t *const *words, int32_t n, int32_t *gate, void *st
     return 0;
 }
 
+// A call that fails behind its first launches has already fetched the previous step's validity word into *prev_grads_ok_host and reset
+// the word on the tape: the copy must have LANDED when the caller looks at it (the caller's own view of the word is stale by then).  A call
+// that fails in front of them leaves *prev_grads_ok_host as the caller initialised it (a sentinel) and the word on the tape untouched.
+static int landed_on_failure(const gnn_train_args_t &ta, int rc) {
+    if (rc != 0 && ta.prev_grads_ok_host && ta.tape) {
+        const std::string msg = gnn_last_error();                 // (the synchronisation must not replace the message and its status)
+        const int status = gnn_last_status();
+        (void)hipStreamSynchronize((hipStream_t)ta.loop.stream);
+        fail_as(status, "%s", msg.c_str());
+    }
+    return rc;
+}
+
 int gnn_train_step_ex(const gnn_train_args_t *args, const gnn_train_phase_args_t *px) {
     if (!args) return fail("args is NULL");
     gnn_train_phase_args_t none;
     memset(&none, 0, sizeof(none));
-    const int rc = train_step_impl(*args, px ? *px : none);
-    // A call that fails behind its first launches has already fetched the previous step's validity word into *prev_grads_ok_host and reset
-    // the word on the tape: the copy must have LANDED when the caller looks at it (the caller's own view of the word is stale by then).  A call
-    // that fails in front of them leaves *prev_grads_ok_host as the caller initialised it (a sentinel) and the word on the tape untouched.
-    if (rc != 0 && args->prev_grads_ok_host && args->tape) {
-        const std::string msg = gnn_last_error();                 // (the synchronisation must not replace the message and its status)
-        const int status = gnn_last_status();
-        (void)hipStreamSynchronize((hipStream_t)args->loop.stream);
-        fail_as(status, "%s", msg.c_str());
-    }
-    return rc;
+    return landed_on_failure(*args, train_step_impl(*args, px ? *px : none));
 }
 
 constexpr int32_t PHASE_MAGIC = 0x50483130;

@@ -725,6 +725,29 @@ int gnn_train_phases_supported(const gnn_train_args_t *args);
  * gate of a joint step of n layers - all or nothing.  The moving statistics stay gated per layer, by the layer's own word. */
 int gnn_gate_all(const int32_t *const *words, int32_t n, int32_t *gate, void *stream);
 
+/* ---- the phased step for HETEROGENEOUS (composite) models (additive; GNN_ABI_VERSION stays 10) ---------------------------------
+ * A joint CompositeLGNN step needs of every composite layer what gnn_train_step_ex gives of a homogeneous one.  gnn_train_step_ex and
+ * gnn_train_phases_supported keep refusing composite models; these entry points carry them.  `px` means what it means there (phase 0 /
+ * 1 / 2, phase_state, node_out, loss_scale, GNN_LOSS_NONE, d_pred_extra, d_out_extra, d_state_extra, d_nodes / ld_d_nodes); an all-zero
+ * (or NULL) px with cx == NULL is exactly gnn_train_step(args).  Everything the phases and the label gradients add lives in cx->scratch:
+ * the composite tape (gnn_train_workspace_bytes) is laid out as before.
+ *   d_nodes [n_nodes, dim_node_label]: node n of type t gets d loss / d nodes[n, :d_t] - through its own network's label columns and
+ *   through CompositeAdjacency[t'] of every type t' (the aggregated component) - and zeros in the columns behind max_t' d_t' that
+ *   nothing reads; with state_dim == 0 d loss / d state_0 is added (state_0 = nodes).
+ * NOT_COVERED (gnn_last_status): homogeneous arguments (gnn_train_step_ex), n_groups != 0, forward_only, the row-streaming path, a
+ * type's first state layer above 960 units, d_arc_labels (no composite arc-label gradient), Dropout at position 0.  Every refusal is
+ * decided before the first launch and touches nothing. */
+typedef struct gnn_train_composite_phase_args {
+    gnn_csr_t composite_adjacency_by_source[GNN_MAX_TYPES]; /* CSR of CompositeAdjacency[t] itself (arcs by SOURCE); read with d_nodes, for types with type_dim_label[t] > 0 */
+    void *scratch; size_t scratch_bytes;                    /* 256-byte aligned device buffer, gnn_train_composite_phase_scratch_bytes(args) bytes; phase 1 and phase 2 get the same one */
+} gnn_train_composite_phase_args_t;
+int gnn_train_step_composite_ex(const gnn_train_args_t *args, const gnn_train_phase_args_t *px, const gnn_train_composite_phase_args_t *cx);
+/* 0 when the composite phases / upstream gradients / label gradients cover these arguments, else -1.  Reads dims and network
+ * descriptions only. */
+int gnn_train_composite_phases_supported(const gnn_train_args_t *args);
+/* bytes of cx->scratch for these arguments; 0 + message on arguments that are not covered */
+size_t gnn_train_composite_phase_scratch_bytes(const gnn_train_args_t *args);
+
 #ifdef __cplusplus
 }
 #endif
