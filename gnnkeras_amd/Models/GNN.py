@@ -404,7 +404,7 @@ class _LoopModel:
             # the loop's condition (group sets): still ONE launch, and no batch is left to the spread form
             parts = {}
             S_w = self.state_vect_dim if self.state_vect_dim > 0 else L
-            limit = ops.loop_group_max_nodes(L, A, self.net_state, self.net_output, self.state_vect_dim, self.max_iteration, focus)
+            limit = ops.loop_group_max_nodes(L, A, self.net_state, self.net_output, self.state_vect_dim, self.max_iteration, focus, flags=self.native_flags)
             for b in rest:
                 if b in fits: continue
                 cut = self._cut_batch(sequencer, b, limit)
@@ -485,7 +485,7 @@ class _LoopModel:
             return None
         if hub or len(dims) != len(self.net_state): return None
         focus = nat.FOCUS[self._focus]
-        limit = ops.loop_group_max_nodes(L, A, self.net_state, self.net_output, self.state_vect_dim, self.max_iteration, focus, dims)
+        limit = ops.loop_group_max_nodes(L, A, self.net_state, self.net_output, self.state_vect_dim, self.max_iteration, focus, dims, flags=self.native_flags)
         if limit < 1: return None
         parts = {}
         for b in range(n):

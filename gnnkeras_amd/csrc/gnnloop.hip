@@ -1084,28 +1084,38 @@ void fill_lds_args(gnn::LdsArgs &la, const gnn_loop_args_t &a, const Plan &p) {
     la.state_out = a.state_out; la.k_out = a.k_out;
 }
 
-int loop_lds(const gnn_loop_args_t &a, const Plan &p, hipStream_t st) {
+int loop_lds(const gnn_loop_args_t &a, const Plan &p, bool hidden, hipStream_t st) {
     gnn::LdsArgs la;
     memset(&la, 0, sizeof(la));
     fill_lds_args(la, a, p);
     la.tile64_begin = p.d_group_tabs + (p.n_groups + 1);
     la.Wf = p.tp[0].Wf; la.wrow_state = p.tp[0].wrow_state; la.wrow_agg = p.tp[0].wrow_agg;
     la.H = a.net_state[0].units[0]; la.act = a.net_state[0].activation[0];
-    const int rc = gnn::launch_lds(la, p.SP, p.n_groups, p.group_max_nodes, st);
+    int rc;
+    if (hidden) {                               // the second Dense: what fused_type hands the spread form
+        const gnn::FusedType ft = fused_type(a, p, 0);
+        rc = gnn::launch_lds_hidden(gnn::LdsHidArgs{la, gnn::LdsHidNet{ft.W2, ft.b2, ft.H, ft.act2}}, p.SP, p.n_groups, p.group_max_nodes, st);
+    } else rc = gnn::launch_lds(la, p.SP, p.n_groups, p.group_max_nodes, st);
     if (rc == 1) return fail("LDS-resident loop kernel: launch failed (%s)", hipGetErrorString(hipGetLastError()));
     return rc;
 }
 
 // ... of a heterogeneous model (kernel_state_lds_types.hpp)
-int loop_lds_types(const gnn_loop_args_t &a, const Plan &p, hipStream_t st) {
-    gnn::LdsTypesArgs ta;
-    memset(&ta, 0, sizeof(ta));
+int loop_lds_types(const gnn_loop_args_t &a, const Plan &p, bool hidden, hipStream_t st) {
+    gnn::LdsTypesHidArgs ha;
+    memset(&ha, 0, sizeof(ha));
+    gnn::LdsTypesArgs &ta = ha.t;
     fill_lds_args(ta.l, a, p);
     ta.n_types = p.T; ta.n_groups = p.n_groups;
     ta.type_nodes = a.type_nodes; ta.tbeg = p.tbeg;
     for (int t = 0; t < p.T; ++t)
         ta.tp[t] = gnn::LdsTypeNet{p.tp[t].Wf, p.tp[t].wrow_state, p.tp[t].wrow_agg, (int)a.net_state[t].activation[0]};
-    const int rc = gnn::launch_lds_types(ta, p.SP, p.group_max_nodes, st);
+    for (int t = 0; hidden && t < p.T; ++t) {   // the second Dense per type: what fused_type hands the per-iteration kernels
+        const gnn::FusedType ft = fused_type(a, p, t);
+        ha.hid[t] = gnn::LdsHidNet{ft.W2, ft.b2, ft.H, ft.act2};
+        ta.l.H = std::max(ta.l.H, ft.H);        // columns of C the kernel loads (a type's own H masks the rest)
+    }
+    const int rc = hidden ? gnn::launch_lds_types_hidden(ha, p.SP, p.group_max_nodes, st) : gnn::launch_lds_types(ta, p.SP, p.group_max_nodes, st);
     if (rc == 1) return fail("LDS-resident loop kernel (types): launch failed (%s)", hipGetErrorString(hipGetLastError()));
     return rc;
 }
@@ -1264,7 +1274,7 @@ int gnn_loop_forward(const gnn_loop_args_t *args) {
         q.gt.n = 0;                                 // the set-up kernel reads the device tables
         TRY(setup_small(a, q, st));
         if (a.ev_loop_begin) HIP_OK(hipEventRecord((hipEvent_t)a.ev_loop_begin, st));
-        const int rc = loop_lds(a, p, st);
+        const int rc = loop_lds(a, p, route.lds_hidden, st);
         // (an error, not NOT_COVERED: the route said this kernel covers the shape, and no caller has ever fallen back on this text)
         if (rc != 0) return rc == 2 ? fail("LDS-resident loop kernel does not cover this shape") : 1;
         if (a.ev_loop_end) HIP_OK(hipEventRecord((hipEvent_t)a.ev_loop_end, st));
@@ -1284,7 +1294,7 @@ int gnn_loop_forward(const gnn_loop_args_t *args) {
                                                         a.state_threshold, p.pred0);
         LAUNCH_OK();
         if (a.ev_loop_begin) HIP_OK(hipEventRecord((hipEvent_t)a.ev_loop_begin, st));
-        const int rc = loop_lds_types(a, p, st);
+        const int rc = loop_lds_types(a, p, route.lds_hidden, st);
         // (the typed group ranges are device data: the one refusal behind launches - workspace and k_out are written, no result is)
         if (rc != 0) return rc == 2 ? not_covered("LDS-resident loop kernel does not cover these convergence groups") : 1;
         if (a.ev_loop_end) HIP_OK(hipEventRecord((hipEvent_t)a.ev_loop_end, st));
@@ -1377,7 +1387,10 @@ int gnn_loop_group_max_nodes(const gnn_loop_args_t *args) {
     Plan p;
     if (make_plan(a, nullptr, p, false)) return 0;
     if (p.SP != 16 && p.SP != 32) return 0;
-    return p.composite ? gnn::lds_types_max_nodes(p.T, p.SP) : gnn::lds_max_nodes(p.SP);
+    // GNN_FLAG_LDS_HIDDEN on a two-layer model (not pinned away from the one-CU-per-group kernels): W2 / b2 share the budget
+    const int pin = knobs(a.flags).pin;
+    const bool hidden = (pin == 0 || pin == 7) && lds_hidden_asked(a, p, fuse_class(a, p));
+    return p.composite ? gnn::lds_types_max_nodes(p.T, p.SP, hidden) : gnn::lds_max_nodes(p.SP, hidden);
 }
 
 int gnn_aggregate(const gnn_csr_t *csr, const float *X, int32_t ldx, int32_t F, float *out, int32_t ldo, void *stream) {

@@ -25,13 +25,15 @@
 //     its own row: the constant C arrives as 16-byte loads, the predicate compares against the own-row chunks already in
 //     registers, the new rows leave as 16-byte stores: a quarter of the epilogue's instructions (it was two thirds of an iteration);
 //   * predicate, activation and iteration count as everywhere else; k_out[g] is written once at the end.
-// Used when every group fits (n_g * (4 SP + 16) <= LDS_BUDGET_BYTES), SP is 16 or 32 and the state network has one layer.
+// Used when every group fits (n_g * (4 SP + 16) <= LDS_BUDGET_BYTES), SP is 16 or 32 and the state network has one layer - or, opt-in
+// (GNN_FLAG_LDS_HIDDEN), two: the hidden-layer form (LdsHidden below) multiplies h by W2 on the result registers of the first product.
 //
 // The body of the loop is written ONCE, as __forceinline__ pieces over a compile-time row policy (below: lds_fill_wreg, lds_load_c, lds_tile,
 // lds_iter_end, lds_leaves): k_state_lds here and k_state_lds_types (kernel_state_lds_types.hpp, one state network per node type) are a
 // prologue, a walk over tiles and a result copy around them, and both launch through launch_lds_family.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "kernel_state_fused2.hpp"
 #include "kernel_state_fused4.hpp"      // activate4
 #include "buffer_ops.hpp"
@@ -107,6 +109,39 @@ __device__ __forceinline__ void lds_fill_wreg(float (&wreg)[2 * SP / 4][SP / 16]
     }
 }
 
+// ---- The hidden-layer form (GNN_FLAG_LDS_HIDDEN): state network Dense(H) - Dense(S).  The first product leaves lane (r, g) holding columns
+// 16 ct + 4 g .. + 3 of its own row - the fragment order of own[q] - so h is the B operand of a second product as it stands: no transposition,
+// no round trip of h through LDS, no barrier.  W2 [H x S] is the A operand in the k-order of lds_fill_wreg (kcol = 16 q + 4 g + e), b2 the
+// accumulators' start.  Both live in LDS, in front of the state rows (W1 alone fills the 128 registers a wave has at width 32: with W2 beside
+// it hipcc spilled), one block per state network, taken out of the group budget (lds_hidden_bytes):
+//     [SP / 4 * SP / 16 / 4 chunks][64 lanes] 16-byte chunks: value f = qe * (SP / 16) + ct of a lane is element f % 4 of its chunk f / 4
+//                       (ds_read_b128, a wave's lanes side by side: no bank conflict), value = W2[kcol(qe, g)][16 ct + r], zero at kcol >= H
+//                       or column >= S - so pad hidden columns never reach the result, whatever act1(0) is;
+//     [SP] floats       b2, zero at or past S.
+struct LdsNoHidden { static constexpr bool ON = false; };
+struct LdsHidden {
+    static constexpr bool ON = true;
+    const float *blk;               // the state network's block in LDS (lds_fill_hidden)
+    int H, act2;                    // hidden units (h is masked to zero at or past H), the LAST activation
+};
+struct LdsHidNet { const float *W2, *b2; int H, act2; };      // the second Dense of one state network: W2 [H x S] row-major, b2 [S]
+constexpr size_t lds_hidden_block_floats(int SP) { return (size_t)SP * SP + SP; }
+// LDS the hidden-layer form takes beside a group's rows (n_nets = 0: the one-layer form)
+inline size_t lds_hidden_bytes(int SP, int n_nets) { return (size_t)n_nets * lds_hidden_block_floats(SP) * sizeof(float); }
+
+// every thread of the workgroup; the caller's barrier before the first tile completes it
+template <int SP>
+__device__ __forceinline__ void lds_fill_hidden(float *blk, const LdsHidNet &hn, int S, int tid) {
+    constexpr int NCT = SP / 16, NV = SP / 4 * NCT;               // values per lane
+    for (int i = tid; i < 64 * NV; i += 64 * LDS_NW) {
+        const int ln = i & 63, f = i >> 6, r = ln & 15, g = ln >> 4;
+        const int qe = f / NCT, ct = f % NCT;
+        const int kcol = 16 * (qe / 4) + 4 * g + (qe & 3), ncol = 16 * ct + r;
+        blk[((f >> 2) * 64 + ln) * 4 + (f & 3)] = (kcol < hn.H && ncol < S) ? hn.W2[(size_t)kcol * S + ncol] : 0.0f;
+    }
+    for (int i = tid; i < SP; i += 64 * LDS_NW) blk[SP * SP + i] = i < S ? hn.b2[i] : 0.0f;
+}
+
 // the per-node constant C of one tile row, row-major: local node j (`on`: there is one), columns 16 ct + 4 g .. + 3 below `cols`
 template <int SP>
 __device__ __forceinline__ void lds_load_c(f32x4 (&c)[SP / 16], __amdgpu_buffer_rsrc_t r_C, bool on, int j, int cols, int ldC, int g) {
@@ -127,10 +162,12 @@ __device__ __forceinline__ int lds_run0(const LdsArgs &a, int lo, int hi, int la
 
 // One 16-row tile of an iteration: lane (r, g) of the wave updates LDS row 16 t + r.  c: the tile's constant C on entry (lds_load_c);
 // wreg / act: the weights and activation of the tile's rows; St: the state this iteration reads; the new rows go to Snew (DB) or to
-// the staging rows behind r_stage.  Sets `any` when a row of the tile still moves.
-template <int SP, bool HAS_W, bool DB, class Rows>
+// the staging rows behind r_stage.  Sets `any` when a row of the tile still moves.  hid (LdsHidden): the second Dense of the tile's rows -
+// `act` is then the HIDDEN activation, the width of the first product hid.H.
+template <int SP, bool HAS_W, bool DB, class Rows, class Hid = LdsNoHidden>
 __device__ __forceinline__ void lds_tile(const LdsArgs &a, const Rows &rows, int nb, int t, int r, int g, const float *St, float *Snew, const LdsRec *Rec,
-                                         __amdgpu_buffer_rsrc_t r_stage, const float (&wreg)[2 * SP / 4][SP / 16], f32x4 (&c)[SP / 16], int act, int &any) {
+                                         __amdgpu_buffer_rsrc_t r_stage, const float (&wreg)[2 * SP / 4][SP / 16], f32x4 (&c)[SP / 16], int act, int &any,
+                                         const Hid &hid = Hid{}) {
     constexpr int NQ = SP / 16;                   // 16-byte chunks of a row owned by one lane
     constexpr int NCT = SP / 16;                  // 16-column output tiles
     const int S = a.S;
@@ -204,10 +241,38 @@ __device__ __forceinline__ void lds_tile(const LdsArgs &a, const Rows &rows, int
         }
     }
     // activation + predicate against the old row chunks (still in registers); the new rows leave for the other buffer / the staging buffer
+    if constexpr (Hid::ON) {
+        // h = act1(c + c2), pad hidden columns zero; then h . W2 onto b2, h being the B operand as it stands
+        f32x4 h[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) {
+            h[ct] = c[ct] + c2[ct];
+            activate4(act, h[ct]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) h[ct][e] = 16 * ct + 4 * g + e < hid.H ? h[ct][e] : 0.0f;
+            c[ct] = *reinterpret_cast<const f32x4 *>(hid.blk + SP * SP + 16 * ct + 4 * g);
+        }
+        const f32x4 *w2 = reinterpret_cast<const f32x4 *>(hid.blk) + (16 * g + r);
+#pragma unroll
+        for (int j = 0; j < SP / 4 * NCT / 4; ++j) {
+            const f32x4 wv = w2[64 * j];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int f = 4 * j + e, qe = f / NCT, ct = f % NCT;
+                c[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[e], h[qe / 4][qe & 3], c[ct], 0, 0, 0);
+            }
+        }
+        act = hid.act2;
+        // the own row for the predicate: read again (the state of this iteration is not written before its end) instead of eight
+        // registers held across both products - what kept the single-buffered form at width 32 out of scratch
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) own[q] = on ? *reinterpret_cast<const f32x4 *>(St + row * SP + 16 * q + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
     float d2 = 0.0f, n2 = 0.0f;
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) {
-        f32x4 v = c[ct] + c2[ct];
+        f32x4 v = Hid::ON ? c[ct] : c[ct] + c2[ct];
         activate4(act, v);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -300,8 +365,19 @@ __device__ __forceinline__ bool lds_leaves(const LdsArgs &a, const int *moving_s
 // DB (round 3): the group's state fits LDS TWICE (n (8 SP + 16) <= 158 KB: 594 nodes at 32-wide rows - what the planner's balanced
 // cuts produce when there are CUs to spare): iteration it reads buffer it & 1 and writes the other one with 16-byte LDS stores.
 // No staging buffer in L2, no store drain, no copy back, ONE workgroup barrier per iteration instead of two.
-template <int SP, bool HAS_W, bool DB>
-__global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds(LdsArgs a) {
+// The kernel is written once over the hidden-layer operands `Hid`.  LdsNoHidden: one Dense layer.  LdsHidden: LdsArgs::H / act are the FIRST
+// Dense's width and activation, `hid` the second Dense, put into LDS once per workgroup (a struct of its own around the one-layer kernel's
+// arguments, which stay what they were).
+struct LdsHidArgs { LdsArgs l; LdsHidNet hid; };
+__device__ __forceinline__ const LdsArgs &lds_args(const LdsArgs &a) { return a; }
+__device__ __forceinline__ const LdsArgs &lds_args(const LdsHidArgs &a) { return a.l; }
+__device__ __forceinline__ const LdsHidNet *lds_hid_net(const LdsArgs &) { return nullptr; }
+__device__ __forceinline__ const LdsHidNet *lds_hid_net(const LdsHidArgs &a) { return &a.hid; }
+
+template <int SP, bool HAS_W, bool DB, class Hid = LdsNoHidden>
+__global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds(std::conditional_t<Hid::ON, LdsHidArgs, LdsArgs> args) {
+    const LdsArgs &a = lds_args(args);
+    const LdsHidNet *hn = lds_hid_net(args);
     constexpr int NCT = SP / 16;                  // 16-column output tiles
     constexpr int KS = 2 * SP / 4;                // MFMA k-steps over [state | agg]
     extern __shared__ __attribute__((aligned(16))) char smem_lds[];
@@ -314,10 +390,15 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds(LdsArgs a) {
     const int nb = a.node_begin[grp], ne = a.node_begin[grp + 1], n = ne - nb;
     const int S = a.S;
     const int n_tiles = (n + 15) >> 4;
-    float *St = reinterpret_cast<float *>(smem_lds);                        // [n][SP] (DB: two of them, iteration it reads the one at (it & 1) n SP)
+    float *St = reinterpret_cast<float *>(smem_lds) + (Hid::ON ? lds_hidden_block_floats(SP) : 0);   // [n][SP] (DB: two of them, iteration it reads the one at (it & 1) n SP)
     LdsRec *Rec = reinterpret_cast<LdsRec *>(St + (size_t)(DB ? 2 : 1) * n * SP);   // [n]
     float *const St_base = St;
     const LdsRowsLocal rows{n};
+    Hid hid;
+    if constexpr (Hid::ON) {                                                // W2 and b2 in front of the state rows
+        lds_fill_hidden<SP>(reinterpret_cast<float *>(smem_lds), *hn, S, tid);
+        hid = LdsHidden{reinterpret_cast<const float *>(smem_lds), hn->H, hn->act2};
+    }
 
     float wreg[KS][NCT];                                                    // the one state network's W1: loaded once
     lds_fill_wreg<SP>(wreg, a.Wf, a.wrow_state, a.wrow_agg, S, a.H, r, g);
@@ -359,7 +440,7 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds(LdsArgs a) {
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct) c[ct] = cn[ct];
             if (t + LDS_NW < n_tiles) load_c(t + LDS_NW, cn);
-            lds_tile<SP, HAS_W, DB>(a, rows, nb, t, r, g, St, Snew, Rec, r_stage, wreg, c, a.act, any);
+            lds_tile<SP, HAS_W, DB>(a, rows, nb, t, r, g, St, Snew, Rec, r_stage, wreg, c, a.act, any, hid);
         }
         const int mv_slot = lds_iter_end<SP, DB>(moving_s, any, it, St, r_stage, n, tid);
         if (DB) St = Snew;                                                     // (what the result copy below reads if the loop ends here)
@@ -374,19 +455,31 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds(LdsArgs a) {
     if (tid == 0) a.k_out[grp] = timed_out ? -1.0e9f : (float)k_done;
 }
 
-inline size_t lds_state_bytes(int n_nodes, int SP, bool db = false) { return (size_t)n_nodes * ((db ? 2 : 1) * SP * sizeof(float) + sizeof(LdsRec)); }
-inline bool lds_group_fits(int n_nodes, int SP) { return lds_state_bytes(n_nodes, SP) <= LDS_BUDGET_BYTES && n_nodes < 65536; }
-inline bool lds_group_fits_twice(int n_nodes, int SP) { return lds_state_bytes(n_nodes, SP, true) <= LDS_BUDGET_BYTES; }
+// (`hidden`: the hidden-layer form, whose W2 / b2 block comes out of the same budget)
+inline size_t lds_state_bytes(int n_nodes, int SP, bool db = false, bool hidden = false) {
+    return (size_t)n_nodes * ((db ? 2 : 1) * SP * sizeof(float) + sizeof(LdsRec)) + lds_hidden_bytes(SP, hidden ? 1 : 0);
+}
+inline bool lds_group_fits(int n_nodes, int SP, bool hidden = false) { return lds_state_bytes(n_nodes, SP, false, hidden) <= LDS_BUDGET_BYTES && n_nodes < 65536; }
+inline bool lds_group_fits_twice(int n_nodes, int SP, bool hidden = false) { return lds_state_bytes(n_nodes, SP, true, hidden) <= LDS_BUDGET_BYTES; }
 // the largest group (in nodes) that fits
-inline int lds_max_nodes(int SP) { return (int)std::min<size_t>(LDS_BUDGET_BYTES / lds_state_bytes(1, SP), 65535); }
+inline int lds_max_nodes(int SP, bool hidden = false) {
+    return (int)std::min<size_t>((LDS_BUDGET_BYTES - lds_hidden_bytes(SP, hidden ? 1 : 0)) / lds_state_bytes(1, SP), 65535);
+}
 
 // ---- One launcher for both kernels.  A kernel family F names its argument struct, the LdsArgs inside it, and its instantiations:
 //     using Args; static LdsArgs &common(Args &); static constexpr const char *name; template <int SP, bool HAS_W, bool DB> static constexpr void (*fn)(Args)
+//     static constexpr const char *tail: what gnn_last_kernel_name() shows behind the template arguments ("" / ",hidden")
 struct LdsKernel {
     using Args = LdsArgs;
     static LdsArgs &common(Args &a) { return a; }
-    static constexpr const char *name = "k_state_lds";
+    static constexpr const char *name = "k_state_lds", *tail = "";
     template <int SP, bool HAS_W, bool DB> static constexpr void (*fn)(Args) = k_state_lds<SP, HAS_W, DB>;
+};
+struct LdsHidKernel {
+    using Args = LdsHidArgs;
+    static LdsArgs &common(Args &a) { return a.l; }
+    static constexpr const char *name = "k_state_lds", *tail = ",hidden";
+    template <int SP, bool HAS_W, bool DB> static constexpr void (*fn)(Args) = k_state_lds<SP, HAS_W, DB, LdsHidden>;
 };
 
 template <class F, int SP, bool HAS_W, bool DB>
@@ -404,7 +497,7 @@ int launch_lds_one(const typename F::Args &la_in, int n_groups, size_t lds_bytes
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 1;
         if (!persistent_fits((const void *)kernel, 64 * LDS_NW, lds_bytes, n_groups, n_cu)) return 2;
     }
-    GNN_SET_KERNEL_NAME("%s<%d,%s,%s>", F::name, SP, HAS_W ? "true" : "false", DB ? "true" : "false");
+    GNN_SET_KERNEL_NAME("%s<%d,%s,%s%s>", F::name, SP, HAS_W ? "true" : "false", DB ? "true" : "false", F::tail);
     kernel<<<n_groups, 64 * LDS_NW, lds_bytes, st>>>(la);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
@@ -431,6 +524,10 @@ int launch_lds_family(typename F::Args la, int SP, bool db, int n_groups, size_t
 inline int launch_lds(const LdsArgs &la, int SP, int n_groups, int max_nodes, hipStream_t st) {
     const bool db = lds_group_fits_twice(max_nodes, SP);
     return launch_lds_family<LdsKernel>(la, SP, db, n_groups, lds_state_bytes(max_nodes, SP, db), st);
+}
+inline int launch_lds_hidden(const LdsHidArgs &ha, int SP, int n_groups, int max_nodes, hipStream_t st) {
+    const bool db = lds_group_fits_twice(max_nodes, SP, true);
+    return launch_lds_family<LdsHidKernel>(ha, SP, db, n_groups, lds_state_bytes(max_nodes, SP, db, true), st);
 }
 
 }  // namespace gnn

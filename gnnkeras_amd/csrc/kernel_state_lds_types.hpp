@@ -13,7 +13,9 @@
 //   * a wave owns a CONTIGUOUS run of tiles and holds the weights of its current tile's type in registers: they are reloaded (from L2,
 //     32 dwords per lane at width 32) only when the walk crosses into another type - at most n_types - 1 + 16 reloads per iteration over
 //     the whole workgroup, none at all in a group of one type.  (All types' blocks in LDS instead would take 8 KB per type at width 32 and
-//     one LDS read per weight register and TILE: 32 ds_read_b32 against the tile's 32 MFMAs.);
+//     one LDS read per weight register and TILE: 32 ds_read_b32 against the tile's 32 MFMAs.)  The hidden-layer form (GNN_FLAG_LDS_HIDDEN:
+//     every type Dense(H_t) - Dense(S)) does keep every type's SECOND layer in LDS - 4 KB per type at width 32, read as four ds_read_b128
+//     per tile - because W1 leaves no registers for it; W1 stays in registers as here;
 //   * the per-node constant C (setup_constants writes it per type, indexed by node), state_0 and the per-arc weights are read by original
 //     node id; the result goes back to state_out in node order;
 //   * what is this kernel's own: the prologue (rows per type, positions, Orig / Inv, records by position), the row policy LdsRowsTyped, the
@@ -91,22 +93,39 @@ struct LdsTypesArgs {
 
 // LDS of a group of n nodes in at most `rows` positions: state rows (twice: DB), records, Orig per position; Inv per node
 inline int lds_types_rows(int n_nodes, int n_types) { return n_nodes + 15 * n_types; }
-inline size_t lds_types_bytes(int n_nodes, int n_types, int SP, bool db = false) {
-    return (size_t)lds_types_rows(n_nodes, n_types) * ((db ? 2 : 1) * SP * sizeof(float) + sizeof(LdsRec) + sizeof(int)) + (size_t)n_nodes * sizeof(int);
+// (`hidden`: the hidden-layer form - a W2 / b2 block per type out of the same budget)
+inline size_t lds_types_bytes(int n_nodes, int n_types, int SP, bool db = false, bool hidden = false) {
+    return (size_t)lds_types_rows(n_nodes, n_types) * ((db ? 2 : 1) * SP * sizeof(float) + sizeof(LdsRec) + sizeof(int)) + (size_t)n_nodes * sizeof(int) +
+           lds_hidden_bytes(SP, hidden ? n_types : 0);
 }
-inline bool lds_types_group_fits(int n_nodes, int n_types, int SP) {
-    return lds_types_bytes(n_nodes, n_types, SP) <= LDS_BUDGET_BYTES && lds_types_rows(n_nodes, n_types) < 65536;
+inline bool lds_types_group_fits(int n_nodes, int n_types, int SP, bool hidden = false) {
+    return lds_types_bytes(n_nodes, n_types, SP, false, hidden) <= LDS_BUDGET_BYTES && lds_types_rows(n_nodes, n_types) < 65536;
 }
-inline bool lds_types_group_fits_twice(int n_nodes, int n_types, int SP) { return lds_types_bytes(n_nodes, n_types, SP, true) <= LDS_BUDGET_BYTES; }
+inline bool lds_types_group_fits_twice(int n_nodes, int n_types, int SP, bool hidden = false) {
+    return lds_types_bytes(n_nodes, n_types, SP, true, hidden) <= LDS_BUDGET_BYTES;
+}
 // the largest group (in nodes) that fits
-inline int lds_types_max_nodes(int n_types, int SP) {
-    const size_t per_row = SP * sizeof(float) + sizeof(LdsRec) + sizeof(int), fixed = (size_t)15 * n_types * per_row;
+inline int lds_types_max_nodes(int n_types, int SP, bool hidden = false) {
+    const size_t per_row = SP * sizeof(float) + sizeof(LdsRec) + sizeof(int);
+    const size_t fixed = (size_t)15 * n_types * per_row + lds_hidden_bytes(SP, hidden ? n_types : 0);
     if (fixed >= LDS_BUDGET_BYTES) return 0;
     return (int)((LDS_BUDGET_BYTES - fixed) / (per_row + sizeof(int)));
 }
 
-template <int SP, bool HAS_W, bool DB>
-__global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds_types(LdsTypesArgs ta) {
+// Written once over the hidden-layer operands `Hid` (kernel_state_lds.hpp).  LdsHidden: every type's state network has a hidden layer -
+// LdsTypeNet::act is the hidden activation, LdsArgs::H the widest first layer, hid[t] the second Dense of type t (a struct of its own around
+// the one-layer kernel's arguments, which stay what they were); every type's W2 / b2 block sits in LDS, and which one a wave reads changes
+// together with the first layer's registers.
+struct LdsTypesHidArgs { LdsTypesArgs t; LdsHidNet hid[GNN_MAX_TYPES]; };
+__device__ __forceinline__ const LdsTypesArgs &lds_types_args(const LdsTypesArgs &a) { return a; }
+__device__ __forceinline__ const LdsTypesArgs &lds_types_args(const LdsTypesHidArgs &a) { return a.t; }
+__device__ __forceinline__ const LdsHidNet *lds_hid_nets(const LdsTypesArgs &) { return nullptr; }
+__device__ __forceinline__ const LdsHidNet *lds_hid_nets(const LdsTypesHidArgs &a) { return a.hid; }
+
+template <int SP, bool HAS_W, bool DB, class Hid = LdsNoHidden>
+__global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds_types(std::conditional_t<Hid::ON, LdsTypesHidArgs, LdsTypesArgs> args) {
+    const LdsTypesArgs &ta = lds_types_args(args);
+    const LdsHidNet *hn = lds_hid_nets(args);
     constexpr int NCT = SP / 16;
     constexpr int KS = 2 * SP / 4;
     extern __shared__ __attribute__((aligned(16))) char smem_lds[];
@@ -116,6 +135,8 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds_types(LdsTypesArgs
     __shared__ int cnt_s[GNN_MAX_TYPES];          // rows of every type in this group
     __shared__ int tb_s[GNN_MAX_TYPES];           // ... and where they begin in type_nodes
     __shared__ LdsTypeNet net_s[GNN_MAX_TYPES];
+    LdsHidNet *hid_s = nullptr;                   // the second Dense per type: LDS of the hidden form alone
+    if constexpr (Hid::ON) { __shared__ LdsHidNet hid_nets[GNN_MAX_TYPES]; hid_s = hid_nets; }
 
     const LdsArgs &a = ta.l;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -131,6 +152,7 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds_types(LdsTypesArgs
             const int b0 = ta.tbeg[t * (ta.n_groups + 1) + grp], b1 = ta.tbeg[t * (ta.n_groups + 1) + grp + 1];
             tb_s[t] = b0; cnt_s[t] = b1 - b0;
             net_s[t] = ta.tp[t];
+            if constexpr (Hid::ON) hid_s[t] = hn[t];
         }
     if (tid == 0) { moving_s[0] = 0; moving_s[1] = 0; moving_s[2] = 0; }
     __syncthreads();
@@ -146,13 +168,16 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds_types(LdsTypesArgs
         return;
     }
     const int n_tiles = P >> 4;
-    float *St = reinterpret_cast<float *>(smem_lds);                                 // [P][SP] (DB: two of them)
+    float *const hid_blk = reinterpret_cast<float *>(smem_lds);                      // hidden form: [T] blocks of W2 / b2 (lds_fill_hidden)
+    float *St = hid_blk + (Hid::ON ? (size_t)T * lds_hidden_block_floats(SP) : 0);   // [P][SP] (DB: two of them)
     LdsRec *Rec = reinterpret_cast<LdsRec *>(St + (size_t)(DB ? 2 : 1) * P * SP);    // [P]
     int *Orig = reinterpret_cast<int *>(Rec + P);                                    // [P]: local node of a position, -1 = pad row
     int *Inv = Orig + P;                                                             // [n]: position of a local node
     float *const St_base = St;
 
     for (int i = tid; i < n; i += 64 * LDS_NW) Inv[i] = 0;      // (a node that no type lists: never a row; as a neighbour it reads position 0)
+    if constexpr (Hid::ON)
+        for (int t = 0; t < T; ++t) lds_fill_hidden<SP>(hid_blk + (size_t)t * lds_hidden_block_floats(SP), hid_s[t], S, tid);
     __syncthreads();
     for (int t = 0; t < T; ++t) {
         const int p0 = pb_s[t], c = cnt_s[t], b0 = tb_s[t], cp = (c + 15) & ~15;
@@ -198,7 +223,8 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds_types(LdsTypesArgs
     const __amdgpu_buffer_rsrc_t r_C = buf_rsrc(a.C + (size_t)nb * a.ldC), r_stage = buf_rsrc(a.stage + ((size_t)nb + (size_t)15 * T * grp) * SP);
     auto load_c = [&](int t, f32x4 (&c)[NCT]) {     // C of tile t by original node
         const int j = Orig[16 * t + r];
-        lds_load_c<SP>(c, r_C, j >= 0, j, S, a.ldC, g);
+        // (hidden form: the widest first layer of any type, LdsArgs::H - the tile masks the columns at or past its own type's H)
+        lds_load_c<SP>(c, r_C, j >= 0, j, Hid::ON ? a.H : S, a.ldC, g);
     };
 
     // a wave's tiles: a contiguous run, so that it crosses from one type into the next as rarely as possible
@@ -210,6 +236,7 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds_types(LdsTypesArgs
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) wreg[ks][ct] = 0.0f;
     int cur_ty = -1, act = 0;
+    Hid hid = {};                                 // (hidden form: set with the first tile's type, like wreg)
 
     int k_done = 0;
     for (int it = 0; run && it < a.max_iteration; ++it) {
@@ -234,9 +261,15 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds_types(LdsTypesArgs
                 const float *Wf = static_cast<const float *>(uniform_ptr(nt.Wf));
                 const int ws = __builtin_amdgcn_readfirstlane(nt.wrow_state), wa = __builtin_amdgcn_readfirstlane(nt.wrow_agg);
                 act = __builtin_amdgcn_readfirstlane(nt.act);
-                lds_fill_wreg<SP>(wreg, Wf, ws, wa, S, S, r, g);             // (the host checked units[0] == S)
+                if constexpr (Hid::ON) {                                     // W2 / b2 change hands with W1: the type's block in LDS
+                    const int H = __builtin_amdgcn_readfirstlane(hid_s[ty].H);
+                    lds_fill_wreg<SP>(wreg, Wf, ws, wa, S, H, r, g);         // (the folded block is [.. x H])
+                    hid = LdsHidden{hid_blk + (size_t)ty * lds_hidden_block_floats(SP), H, __builtin_amdgcn_readfirstlane(hid_s[ty].act2)};
+                } else {
+                    lds_fill_wreg<SP>(wreg, Wf, ws, wa, S, S, r, g);         // (the host checked units[0] == S)
+                }
             }
-            lds_tile<SP, HAS_W, DB>(a, rows, nb, t, r, g, St, Snew, Rec, r_stage, wreg, c, act, any);
+            lds_tile<SP, HAS_W, DB>(a, rows, nb, t, r, g, St, Snew, Rec, r_stage, wreg, c, act, any, hid);
         }
         const int mv_slot = lds_iter_end<SP, DB>(moving_s, any, it, St, r_stage, P, tid);
         if (DB) St = Snew;
@@ -254,14 +287,24 @@ __global__ void __launch_bounds__(64 * LDS_NW, 4) k_state_lds_types(LdsTypesArgs
 struct LdsTypesKernel {         // (launch_lds_one, kernel_state_lds.hpp)
     using Args = LdsTypesArgs;
     static LdsArgs &common(Args &a) { return a.l; }
-    static constexpr const char *name = "k_state_lds_types";
+    static constexpr const char *name = "k_state_lds_types", *tail = "";
     template <int SP, bool HAS_W, bool DB> static constexpr void (*fn)(Args) = k_state_lds_types<SP, HAS_W, DB>;
+};
+struct LdsTypesHidKernel {
+    using Args = LdsTypesHidArgs;
+    static LdsArgs &common(Args &a) { return a.t.l; }
+    static constexpr const char *name = "k_state_lds_types", *tail = ",hidden";
+    template <int SP, bool HAS_W, bool DB> static constexpr void (*fn)(Args) = k_state_lds_types<SP, HAS_W, DB, LdsHidden>;
 };
 
 // max_nodes: nodes of the largest group (every workgroup requests LDS for its bound of positions)
 inline int launch_lds_types(const LdsTypesArgs &la, int SP, int max_nodes, hipStream_t st) {
     const bool db = lds_types_group_fits_twice(max_nodes, la.n_types, SP);
     return launch_lds_family<LdsTypesKernel>(la, SP, db, la.n_groups, lds_types_bytes(max_nodes, la.n_types, SP, db), st);
+}
+inline int launch_lds_types_hidden(const LdsTypesHidArgs &ha, int SP, int max_nodes, hipStream_t st) {
+    const bool db = lds_types_group_fits_twice(max_nodes, ha.t.n_types, SP, true);
+    return launch_lds_family<LdsTypesHidKernel>(ha, SP, db, ha.t.n_groups, lds_types_bytes(max_nodes, ha.t.n_types, SP, db, true), st);
 }
 
 }  // namespace gnn

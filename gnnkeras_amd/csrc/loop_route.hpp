@@ -20,6 +20,7 @@ struct IterRoute {
 
 struct LoopRoute {
     WholeLoop whole;
+    bool lds_hidden;    // whole == lds / lds_types: the hidden-layer form (GNN_FLAG_LDS_HIDDEN, two-layer state networks)
     bool small_setup;   // whole == small: k_setup_small builds the constants in one launch (then a 2 from the launcher is an error)
     bool try_mid;       // k_state_mid is tried: first (whole == mid), or after k_state_small answered 2 at launch
     IterRoute iter;     // what runs when no whole-loop kernel does, or when its launcher answers 2 (persistent_fits, tile budget)
@@ -152,19 +153,31 @@ bool lds_common(const gnn_loop_args_t &a, const Plan &p, const Knobs &k) {
     if ((k.pin != 0 && k.pin != 7) || p.n_groups < 1 || p.n_heavy != 0 || a.max_iteration < 1 || (p.SP != 16 && p.SP != 32)) return false;
     return !(a.flags & GNN_FLAG_UNFUSED) && !(p.has_sets && p.n_groups > device_cus());      // groups that wait for each other must all be resident
 }
-// ... a homogeneous model (kernel_state_lds.hpp)
-bool lds_covers(const gnn_loop_args_t &a, const Plan &p, const Knobs &k) {
-    if (!lds_common(a, p, k) || p.composite || a.net_state[0].n_layers != 1 || a.net_state[0].activation[0] == GNN_ACT_SOFTMAX) return false;
-    return gnn::lds_group_fits(p.group_max_nodes, p.SP);
+// The hidden-layer form of both kernels, opt-in (GNN_FLAG_LDS_HIDDEN): every type's state network Dense(H) - Dense(S).  `fuse` == 2 has
+// checked H <= SP, no softmax on the hidden layer and the same depth for every type; the last activation must not be a softmax either.
+bool lds_hidden_asked(const gnn_loop_args_t &a, const Plan &p, int fuse) {
+    if (!(a.flags & GNN_FLAG_LDS_HIDDEN) || fuse != 2) return false;
+    for (int t = 0; t < p.T; ++t) {
+        const gnn_mlp_t &m = a.net_state[t];
+        if (m.n_layers != 2 || m.units[0] < 1 || (int)m.units[1] != p.S || m.activation[1] == GNN_ACT_SOFTMAX) return false;
+    }
+    return true;
+}
+// ... a homogeneous model (kernel_state_lds.hpp): one Dense layer, or two in the hidden-layer form
+bool lds_covers(const gnn_loop_args_t &a, const Plan &p, const Knobs &k, int fuse) {
+    if (!lds_common(a, p, k) || p.composite) return false;
+    if (fuse == 2 ? !lds_hidden_asked(a, p, fuse) : (a.net_state[0].n_layers != 1 || a.net_state[0].activation[0] == GNN_ACT_SOFTMAX)) return false;
+    return gnn::lds_group_fits(p.group_max_nodes, p.SP, fuse == 2);          // (the hidden form's W2 / b2 come out of the group's LDS)
 }
 // ... a heterogeneous model (kernel_state_lds_types.hpp): every type's state network one Dense layer; the largest group must fit with
 // every (group, type) range padded to 16 rows - decided from the shapes alone (type_nodes is a device array): rows <= n_g + 15 n_types.
-bool lds_types_covers(const gnn_loop_args_t &a, const Plan &p, const Knobs &k) {
+bool lds_types_covers(const gnn_loop_args_t &a, const Plan &p, const Knobs &k, int fuse) {
     if (!lds_common(a, p, k) || !p.composite || p.T < 1 || p.T > GNN_MAX_TYPES || a.n_heavy_segments > 0 || a.nodes_src) return false;
-    for (int t = 0; t < p.T; ++t)
+    if (fuse == 2 && !lds_hidden_asked(a, p, fuse)) return false;      // (two layers per type: H and the activations may differ per type)
+    for (int t = 0; fuse != 2 && t < p.T; ++t)
         if (a.net_state[t].n_layers != 1 || a.net_state[t].activation[0] == GNN_ACT_SOFTMAX || (int)a.net_state[t].units[0] != p.S) return false;
     if ((size_t)(p.N + (size_t)15 * p.T * p.n_groups) * p.SP * 4 >= ((size_t)1 << 32)) return false;      // the staging rows: 32-bit byte offsets
-    return gnn::lds_types_group_fits(p.group_max_nodes, p.T, p.SP);
+    return gnn::lds_types_group_fits(p.group_max_nodes, p.T, p.SP, fuse == 2);
 }
 
 #define GNN_ROUTE_STR_(x) #x
@@ -176,9 +189,10 @@ LoopRoute route_loop(const gnn_loop_args_t &a, const Plan &p) {
     LoopRoute r = {};
     r.iter = route_iteration(a, p, k);
     const int fz = r.iter.fuse;
-    if (p.n_groups > 0 && fz == 1 && lds_covers(a, p, k) && setup_small_covers(a, p)) { r.whole = WholeLoop::lds; return r; }
+    const bool fz12 = fz == 1 || fz == 2;       // (2: two-layer state networks - the hidden-layer form, where the caller asked for it)
+    if (p.n_groups > 0 && fz12 && lds_covers(a, p, k, fz) && setup_small_covers(a, p)) { r.whole = WholeLoop::lds; r.lds_hidden = fz == 2; return r; }
     if (p.n_groups > 0 && p.composite) {
-        if (fz == 1 && lds_types_covers(a, p, k)) r.whole = WholeLoop::lds_types;
+        if (fz12 && lds_types_covers(a, p, k, fz)) { r.whole = WholeLoop::lds_types; r.lds_hidden = fz == 2; }
         else r.refuse(GNN_STATUS_NOT_COVERED, "convergence groups of a composite graph need the one-CU-per-group kernel (gnn_loop_groups_supported() != 2 for these args)");
         return r;
     }
@@ -204,8 +218,8 @@ LoopRoute route_loop(const gnn_loop_args_t &a, const Plan &p) {
 void route_name(const LoopRoute &r, char *name, size_t n) {
     static const char *const stem[] = {"k_aggregate_vec", "k_state_fused2", "k_state_fused4", "k_state_wide", "k_state_fused4<.., L2>", "k_state_xwide_b3"};      // (IterKernel)
     if (r.refused) snprintf(name, n, "refused: %s", r.refused);
-    else if (r.whole == WholeLoop::lds) snprintf(name, n, "k_state_lds");
-    else if (r.whole == WholeLoop::lds_types) snprintf(name, n, "k_state_lds_types");
+    else if (r.whole == WholeLoop::lds) snprintf(name, n, r.lds_hidden ? "k_state_lds<.., hidden>" : "k_state_lds");
+    else if (r.whole == WholeLoop::lds_types) snprintf(name, n, r.lds_hidden ? "k_state_lds_types<.., hidden>" : "k_state_lds_types");
     else if (r.small_setup) snprintf(name, n, "k_state_small(setup_small)");
     else snprintf(name, n, "%s%s%s%s", r.whole == WholeLoop::small ? "k_state_small > " : "", r.try_mid ? "k_state_mid > " : "",
                   stem[(int)r.iter.kernel], r.xc_loop ? "+xc" : "");

@@ -296,11 +296,11 @@ int64_t loop_groups_supported(int64_t n_nodes, int64_t dim_node_label, int64_t d
 
 // Nodes of the largest group the one-CU-per-group form holds for these shapes (gnn_loop_group_max_nodes)
 int64_t loop_group_max_nodes(int64_t dim_node_label, int64_t dim_arc_label, at::IntArrayRef net_state_spec, at::IntArrayRef net_output_spec,
-                             int64_t state_dim, int64_t max_iteration, int64_t focus, at::IntArrayRef type_dim_label) {
+                             int64_t state_dim, int64_t max_iteration, int64_t focus, at::IntArrayRef type_dim_label, int64_t flags) {
     gnn_loop_args_t a{};
     fill_shape(a, 0, dim_node_label, dim_arc_label, net_state_spec, type_dim_label);
     mlp_shape_of(a.net_output, net_output_spec, "net_output");
-    a.state_dim = (int32_t)state_dim; a.max_iteration = (int32_t)max_iteration; a.focus = (int32_t)focus;
+    a.state_dim = (int32_t)state_dim; a.max_iteration = (int32_t)max_iteration; a.focus = (int32_t)focus; a.flags = (int32_t)flags;
     return gnn_loop_group_max_nodes(&a);
 }
 
@@ -453,7 +453,7 @@ TORCH_LIBRARY(gnnkeras, m) {
     m.def("loop_groups_supported(int n_nodes, int dim_node_label, int dim_arc_label, int[] net_state_spec, int[] net_output_spec, "
           "int state_dim, int max_iteration, int focus, int flags, int n_out, int[] group_node_begin, int[] group_set_begin=[], int[] type_dim_label=[]) -> int", &loop_groups_supported);
     m.def("loop_group_max_nodes(int dim_node_label, int dim_arc_label, int[] net_state_spec, int[] net_output_spec, int state_dim, int max_iteration, "
-          "int focus, int[] type_dim_label=[]) -> int", &loop_group_max_nodes);
+          "int focus, int[] type_dim_label=[], int flags=0) -> int", &loop_group_max_nodes);
     m.def("aggregate(Tensor?[] csr, int[] dims, Tensor X) -> Tensor");
     m.def("pool(Tensor?[] nodegraph, int[] dims, Tensor out_nodes) -> Tensor");
     m.def("converged(Tensor state, Tensor? state_old, float threshold) -> Tensor");

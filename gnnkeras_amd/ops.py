@@ -127,11 +127,12 @@ def loop_groups_supported(n_nodes, dim_node_label, dim_arc_label, net_state, net
                                              [int(v) for v in type_dims] if type_dims is not None else []))
 
 
-def loop_group_max_nodes(dim_node_label, dim_arc_label, net_state, net_output, state_dim, max_iteration, focus, type_dims=None):
-    """Nodes of the largest group the one-CU-per-group form holds for these shapes (include/gnnloop.h, gnn_loop_group_max_nodes)."""
+def loop_group_max_nodes(dim_node_label, dim_arc_label, net_state, net_output, state_dim, max_iteration, focus, type_dims=None, flags=0):
+    """Nodes of the largest group the one-CU-per-group form holds for these shapes (include/gnnloop.h, gnn_loop_group_max_nodes).
+    `flags`: FLAG_LDS_HIDDEN on a two-layer state network takes the second layer's weights out of the group's LDS - a smaller answer."""
     _, os_ = net_args(net_output, None, shape_only=True)
     return int(load().loop_group_max_nodes(int(dim_node_label), int(dim_arc_label), _state_specs(net_state), os_, int(state_dim),
-                                            int(max_iteration), int(focus), [int(v) for v in type_dims] if type_dims is not None else []))
+                                            int(max_iteration), int(focus), [int(v) for v in type_dims] if type_dims is not None else [], int(flags)))
 
 
 def aggregate(csr, X):

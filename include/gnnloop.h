@@ -67,7 +67,15 @@ enum gnn_flags {
      * row-streaming threshold, every tile resident, neighbour sums AND hidden rows within the tape budget).  Every other shape plans,
      * routes and computes as without the flag; gnn_last_kernel_name() then says "train_step: persistent small-graph kernels (hidden
      * layer)".  Without the flag such a network trains on the general kernels (one launch per layer and iteration). */
-    GNN_FLAG_TRAIN_HIDDEN_SMALL = 1 << 8
+    GNN_FLAG_TRAIN_HIDDEN_SMALL = 1 << 8,
+    /* The forward loop and its queries only (gnn_loop_forward, gnn_loop_groups_supported, gnn_loop_route_name; training ignores it).
+     * Opt-in: convergence groups of a model whose state network(s) are Dense(H) - Dense(state width) run the one-CU-per-group kernels
+     * in their hidden-layer form (gnn_loop_groups_supported() == 2, gnn_loop_route_name() "k_state_lds<.., hidden>" /
+     * "k_state_lds_types<.., hidden>", gnn_last_kernel_name() e.g. "k_state_lds<32,false,true,hidden>") when 1 <= H <= the padded
+     * state width (16 / 32), neither activation is softmax, every node type has two layers (H and both activations may differ per
+     * type) and every condition of the one-layer form holds; group sets included.  Every other shape - and every shape without the
+     * flag - routes, refuses and computes as before: a homogeneous model on the spread form (answer 1), a composite model refused. */
+    GNN_FLAG_LDS_HIDDEN = 1 << 9
 };
 
 /* A sparse operator A (n_src x n_dst, COO in the reference: tf.SparseTensor) stored as the CSR of its transpose:
@@ -236,7 +244,8 @@ int gnn_loop_forward(const gnn_loop_args_t *args);
 int gnn_loop_xc_applies(const gnn_loop_args_t *args);
 /* Which kernels gnn_loop_forward would run for these arguments, without launching anything (additive; reads what the two queries
  * around it read).  A thread-local string, valid until this thread's next call:
- *   "k_state_lds" / "k_state_lds_types"        convergence groups, one workgroup per group;
+ *   "k_state_lds" / "k_state_lds_types"        convergence groups, one workgroup per group ("k_state_lds<.., hidden>" /
+ *                                              "k_state_lds_types<.., hidden>": their hidden-layer form, GNN_FLAG_LDS_HIDDEN);
  *   "k_state_small(setup_small)"               the small whole-loop kernel behind its one-launch set-up;
  *   "[k_state_small > ][k_state_mid > ]<k>"    the kernels in the order they are tried: a whole-loop launcher may still decline at
  *                                              launch (residency, tile budget), <k> is the per-iteration kernel - k_state_fused2,
@@ -248,7 +257,8 @@ int gnn_loop_xc_applies(const gnn_loop_args_t *args);
  * The stems are those of gnn_last_kernel_name().  The rule itself: gnnkeras_amd/csrc/loop_route.hpp. */
 const char *gnn_loop_route_name(const gnn_loop_args_t *args);
 /* Non-zero when gnn_loop_forward accepts these args with n_groups > 0, else 0 (the caller then runs one call per batch).
- *   2: every group's state fits the LDS of one CU (nodes_g * padded width * 4 <= 156 KB, width <= 32, one-layer state network):
+ *   2: every group's state fits the LDS of one CU (nodes_g * padded width * 4 <= 156 KB, width <= 32, one-layer state network - or,
+ *      with GNN_FLAG_LDS_HIDDEN, Dense(H) - Dense(state width) with H <= the padded width and no softmax, homogeneous or composite):
  *      one workgroup per group, any number of groups up to GNN_MAX_GROUPS_RESIDENT - the more the better, 256 run at once.
  *      Composite models (composite != 0, 1 .. GNN_MAX_TYPES types) get this answer or 0: every type's state network one layer of
  *      the state's width and not softmax, padded width 16 or 32, no hub rows, no nodes_src, max_iteration >= 1, not GNN_FLAG_UNFUSED,
@@ -258,8 +268,9 @@ const char *gnn_loop_route_name(const gnn_loop_args_t *args);
  * Reads dims, flags and the host group array only. */
 int gnn_loop_groups_supported(const gnn_loop_args_t *args);
 /* The largest group, in nodes, the one-CU-per-group form (answer 2 above) holds for a call of these shapes (state width, composite,
- * n_types; the group tables of `args` are not read); 0 when the padded state width is neither 16 nor 32.  It shrinks with the number
- * of node types of a composite model: a group's rows are sorted by type and every type's range is padded to 16 rows. */
+ * n_types, and flags: the group tables of `args` are not read); 0 when the padded state width is neither 16 nor 32.  It shrinks with the
+ * number of node types of a composite model: a group's rows are sorted by type and every type's range is padded to 16 rows - and with
+ * GNN_FLAG_LDS_HIDDEN on a two-layer model, whose second layer's weights share the group's LDS (one block per node type). */
 int gnn_loop_group_max_nodes(const gnn_loop_args_t *args);
 
 /* out[j, 0:F] = sum_{e in row j} w_e * X[src_e, 0:F]   == tf.sparse.sparse_dense_matmul(A, X, adjoint_a=True)
