@@ -78,6 +78,28 @@ def relabel_graphs(graphs, state, output, get_state: bool, get_output: bool, arc
         g.DIM_NODE_LABEL = dnl
 
 
+def split_label_gradient(d_nodes, d_arc_labels, prev, get_state: bool, get_output: bool, arc_based: bool):
+    """`update_graph` backwards: the gradient w.r.t. layer i+1's labels - `d_nodes` [N, L] and, for arc focus with `get_output`,
+    `d_arc_labels` [E, A] - cut into (d_state_extra [N, S], d_out_extra [M, T]) for layer i, None where nothing flows.  `prev`: layer i's
+    tape or handle (`S`, `T`, `M`, `out_index`).  Pure slicing, gathering and zero-filling:
+      * node / graph focus: nodes_{i+1} = [state_i | out_i scattered to `out_index` | nodes_0], so the state's gradient is the first S
+        columns (with `get_state`) and the outputs' the next T, read at the rows of `out_index`;
+      * arc focus: update_graph PREPENDS the T output columns to the arcs matrix (reference LGNN.py:209: `concat([arcplus, arcs])`), so
+        the model's label view arcs[:, 2:] starts at output column 2: columns 0 and 1 sit where the arc ids used to be and are never
+        read; output column 2 + j is arc-label column j."""
+    d_state_extra = d_out_extra = None
+    col = 0
+    if get_state:
+        d_state_extra = d_nodes[:, :prev.S].contiguous(); col = prev.S
+    if get_output and not arc_based:
+        d_out_extra = d_nodes[:, col:col + prev.T].index_select(0, prev.out_index.long()).contiguous()
+    elif get_output:
+        d_out_extra = torch.zeros((prev.M, prev.T), dtype=torch.float32, device=d_nodes.device)
+        if prev.T > 2:
+            d_out_extra[:, 2:] = d_arc_labels[:, :prev.T - 2].index_select(0, prev.out_index.long())
+    return d_state_extra, d_out_extra
+
+
 class LGNN(_LoopModel):
     """Layered GNN for node-, arc- or graph-focused problems (reference LGNN.py:11-362)."""
     _gnn_classes = {"node": GNNnodeBased, "arc": GNNarcBased, "graph": GNNgraphBased}
@@ -229,102 +251,10 @@ class LGNN(_LoopModel):
         from ..sparse import SparseMatrix
         return ops.pool(SparseMatrix.from_triple(nodegraph).device_csr(out_nodes.device), out_nodes.to(torch.float32).contiguous())
 
-    # ---- joint training (parallel / residual) ----------------------------------------------------------------------------
+    # ---- joint training (parallel / residual; docs/joint_lgnn_step.md) ---------------------------------------------------
     def _layer_x(self, x, nodes, arcs, dim_node_label):
         return [nodes, arcs, dim_node_label] + list(x[3:])
 
-    def train_step(self, data, *, state0=None, seed=None, apply=True):
-        """One joint optimisation step of all layers (reference LGNN.py:252-287): 'parallel' = mean of the per-layer
-        losses, 'residual' = loss of the mean output. Gradients flow from layer i+1 into layer i through the labels
-        built by `update_graph`."""
-        if self.training_mode == 'serial':
-            raise RuntimeError("training_mode 'serial' trains layer by layer: use fit()")
-        if self.loss is None: raise RuntimeError('compile() the model with a loss before fit() / train_step()')
-        x, y, sample_weight = data
-        if y is None: raise TypeError('Target data is missing. Your model was compiled with `loss` '
-                                      'argument and so expects targets to be passed in `fit()`.')
-        x = list(x)
-        i_set = 4 if len(x) == 10 else 3                           # composite lists carry type_mask at [3]
-        nodes_0, arcs_0, dim0, set_mask, output_mask = x[0], x[1], x[2], x[i_set], x[i_set + 1]
-        s0 = state0 if state0 is not None else [None] * self.LAYERS
-        for g in self.gnns: g.loss = self.loss
-        if self.joint_step not in JOINT_STEP: raise ValueError(f'joint_step must be one of {JOINT_STEP}')
-        if len(x) == 10 and self.composite_joint_step != 'blocks':      # a stack of composite layers that opted in
-            why = self._joint_composite_refusal(x)
-            if why is None:
-                self.last_joint_route = 'library'
-                return self._train_step_library(x, y, sample_weight, s0, seed, apply)
-            if self.composite_joint_step == 'library': raise NotImplementedError(f"composite_joint_step='library' does not apply here: {why}")
-        why = None if self.joint_step == 'blocks' else self._joint_library_refusal(x)
-        if self.joint_step == 'library' and why is not None:
-            raise NotImplementedError(f"joint_step='library' does not apply here: {why}")
-        if self.joint_step != 'blocks' and why is None:
-            self.last_joint_route = 'library'
-            return self._train_step_library(x, y, sample_weight, s0, seed, apply)
-        self.last_joint_route = 'blocks'
-        self.resolve_joint_pending()
-        trainers = [LoopTrainer(g) for g in self.gnns]
-        graph_based = self.GNN_CLASS is self._gnn_classes['graph']
-        arc_based = self.GNN_CLASS is self._gnn_classes['arc']
-        tapes, outs = [], []
-        nodes, arcs, dnl = nodes_0, arcs_0, dim0
-        for i, tr in enumerate(trainers):
-            last = i == self.LAYERS - 1
-            tp = tr.forward(self._layer_x(x, nodes, arcs, dnl), state0=s0[i], seed=seed, node_level=not last)
-            tapes.append(tp)
-            if last: outs.append(tp.y_pred)
-            else:
-                outs.append(self._pool(x[-1], tp.out_nodes) if graph_based else tp.out_nodes)
-                nodes, arcs, dnl = self.update_graph(nodes_0, arcs_0, dnl, set_mask, output_mask, tp.state, tp.out_nodes)
-        # loss and its gradient w.r.t. every layer's task-level output
-        Lyr = self.LAYERS
-        if self.training_mode == 'parallel':
-            parts = [trainers[i].loss_and_grad(tapes[i], outs[i], y, sample_weight) for i in range(Lyr)]
-            loss = sum(pl[0] for pl in parts) / Lyr
-            dpreds = [pl[1] / Lyr for pl in parts]
-        else:
-            mean_out = sum(outs) / Lyr
-            loss, dmean = trainers[-1].loss_and_grad(tapes[-1], mean_out, y, sample_weight)
-            dpreds = [dmean / Lyr for _ in range(Lyr)]
-        # backward, last layer first; the label gradient of layer i+1 feeds layer i
-        d_state_extra, d_out_extra = None, None
-        for i in range(Lyr - 1, -1, -1):
-            tp, tr = tapes[i], trainers[i]
-            pooled_here = graph_based                              # every layer's task output is pooled for graph focus
-            G = tr.pool_backward(tp, dpreds[i]) if pooled_here else dpreds[i].clone()
-            if d_out_extra is not None: G = G + d_out_extra
-            arc_out = arc_based and self.get_output and i > 0        # the layer below wrote its output into the ARC labels
-            d_nodes = tr.backward(tp, G.contiguous(), d_state_extra=d_state_extra, want_label_grads=i > 0,
-                                  want_arc_label_grads=arc_out)
-            d_state_extra = d_out_extra = None
-            if i > 0:
-                prev = tapes[i - 1]
-                col = 0
-                if self.get_state:
-                    d_state_extra = d_nodes[:, :prev.S].contiguous(); col = prev.S
-                if self.get_output and not arc_based:
-                    d_out_extra = d_nodes[:, col:col + prev.T].index_select(0, prev.out_index.long()).contiguous()
-                elif arc_out:
-                    # update_graph PREPENDS the T output columns to the arcs matrix (reference LGNN.py:209: `concat([arcplus,
-                    # arcs])`), so the model's label view arcs[:, 2:] starts at output column 2: columns 0 and 1 sit where the
-                    # arc ids used to be and are never read; output column 2 + j is arc-label column j
-                    d_out_extra = torch.zeros((prev.M, prev.T), dtype=torch.float32, device=tp.dev)
-                    if prev.T > 2:
-                        d_out_extra[:, 2:] = tp.d_arc_labels[:, :prev.T - 2].index_select(0, prev.out_index.long())
-        for tp, tr in zip(tapes, trainers): tr.finish(tp, apply=False)
-        if apply:
-            gv = [pair for tp in tapes for pair in LoopTrainer.grads_and_vars(tp)]
-            self._optimizer_obj().apply_gradients(gv)
-        self._last_tapes = tapes
-        out = {'loss': loss, 'k': [tp.k for tp in tapes]}
-        yd = y.to(outs[-1].device)
-        sw = torch.ones(yd.shape[0], device=yd.device) if sample_weight is None else sample_weight.to(yd.device)
-        for mtr in self.metrics_spec:
-            n, f = _metric_fn(mtr, yd.shape[-1])
-            out[n] = (f(yd, outs[-1]) * sw).sum() / sw.sum()
-        return out
-
-    # ---- the joint step inside the library (docs/joint_lgnn_step.md) --------------------------------------------------------------------------
     def _joint_trainers(self):
         """One trainer per layer, kept across steps: its tape, gradient holders and the optimizer's pointer tables with it."""
         tr = getattr(self, '_joint_trs', None)
@@ -332,47 +262,167 @@ class LGNN(_LoopModel):
             tr = self._joint_trs = [LoopTrainer(g) for g in self.gnns]
         return tr
 
-    def _joint_library_refusal(self, x):
-        """None when this batch can take the library route, else the reason (a joint step takes one route or the other, never a mix)."""
-        from .. import _native as nat
-        if len(x) != 8 or any(isinstance(g.net_state, (list, tuple)) for g in self.gnns): return 'composite layers train through the building blocks'
-        if self.LAYERS > 16: return 'more than 16 layers'
-        nodes, arcs = x[0], x[1]
-        if not (isinstance(nodes, torch.Tensor) and nodes.is_cuda): return 'the batch is not on the device'
-        N, E, L, A = int(nodes.shape[0]), int(arcs.shape[0]), int(nodes.shape[1]), int(arcs.shape[1]) - 2
-        arc_based = self.GNN_CLASS is self._gnn_classes['arc']
-        for tr, g in zip(self._joint_trainers(), self.gnns):
-            if not tr._native_phases_apply(N, E, L, A, 1):      # (coverage depends on the dims and the networks, not on the rows of the mask)
-                return 'a layer is not covered by the phased in-library step (Dropout in front of a first Dense, a loss without a device gradient, ' \
-                       'max_iteration < 1, or a batch of the row-streaming size)'
-            S = g.state_vect_dim if g.state_vect_dim > 0 else L
-            T = int(g.net_output.units[-1])
-            L, A = nodes.shape[1] + (S if self.get_state else 0) + (T if self.get_output and not arc_based else 0), \
-                arcs.shape[1] - 2 + (T if self.get_output and arc_based else 0)
-        return None
-
-    def _joint_composite_refusal(self, x):
-        """`_joint_library_refusal` for a stack of composite layers (`composite_joint_step`): None when this batch can take the library route."""
+    def _joint_refusal(self, x, composite):
+        """None when this batch can take the library route, else the reason (a joint step takes one route or the other, never a mix).
+        `composite`: the question of `composite_joint_step` (a stack of composite layers) instead of `joint_step`'s; the two differ in the
+        per-layer coverage query and in how the label widths grow from layer to layer."""
         from .loop_operands import type_widths
-        if len(x) != 10 or not all(isinstance(g.net_state, (list, tuple)) for g in self.gnns): return 'not a stack of composite layers'
+        is_composite = [isinstance(g.net_state, (list, tuple)) for g in self.gnns]
+        if composite:
+            if len(x) != 10 or not all(is_composite): return 'not a stack of composite layers'
+        elif len(x) != 8 or any(is_composite): return 'composite layers train through the building blocks'
         if self.LAYERS > 16: return 'more than 16 layers'
         nodes, arcs = x[0], x[1]
         if not (isinstance(nodes, torch.Tensor) and nodes.is_cuda): return 'the batch is not on the device'
-        if self.GNN_CLASS is self._gnn_classes['arc']:
+        arc_based = self.GNN_CLASS is self._gnn_classes['arc']
+        if composite and arc_based:
             return 'arc-focused composite layers train through the building blocks (' + \
                 ('get_output hands the outputs on through the arc labels, and there is no composite arc-label gradient' if self.get_output
                  else 'the phased composite step is wired for node and graph focus') + ')'
-        N, E, A = int(nodes.shape[0]), int(arcs.shape[0]), int(arcs.shape[1]) - 2
-        dims, L = type_widths(x[2]), int(nodes.shape[1])
+        N, E, L0, A0 = int(nodes.shape[0]), int(arcs.shape[0]), int(nodes.shape[1]), int(arcs.shape[1]) - 2
+        L, A, dims = L0, A0, (type_widths(x[2]) if composite else None)
         for tr, g in zip(self._joint_trainers(), self.gnns):
-            if not tr._native_composite_phases_apply(N, E, dims, A, 1):
-                return 'a layer is not covered by the phased in-library composite step (Dropout in front of a first Dense, a loss without a device ' \
-                       'gradient, max_iteration < 1, a first state layer above 960 units, or a batch of the row-streaming size)'
+            # (coverage depends on the dims and the networks, not on the rows of the mask)
+            if not (tr._native_composite_phases_apply(N, E, dims, A, 1) if composite else tr._native_phases_apply(N, E, L, A, 1)):
+                if composite:
+                    return 'a layer is not covered by the phased in-library composite step (Dropout in front of a first Dense, a loss without a ' \
+                           'device gradient, max_iteration < 1, a first state layer above 960 units, or a batch of the row-streaming size)'
+                return 'a layer is not covered by the phased in-library step (Dropout in front of a first Dense, a loss without a device gradient, ' \
+                       'max_iteration < 1, or a batch of the row-streaming size)'
+            # what `update_graph` will add for the next layer
             S = g.state_vect_dim if g.state_vect_dim > 0 else L
-            plus = (S if self.get_state else 0) + (int(g.net_output.units[-1]) if self.get_output else 0)
-            L = int(nodes.shape[1]) + plus
-            dims = [min(dt + plus, L) for dt in dims]           # (`update_graph` widens the widths it is handed, the labels it builds anew)
+            T = int(g.net_output.units[-1])
+            plus = (S if self.get_state else 0) + (T if self.get_output and not arc_based else 0)
+            L, A = L0 + plus, A0 + (T if self.get_output and arc_based else 0)
+            if composite: dims = [min(dt + plus, L) for dt in dims]      # (it widens the widths it is handed, the labels it builds anew)
         return None
+
+    def _joint_route(self, x):
+        """The route of a joint step on the batch `x`: 'library' or 'blocks'.  A 10-element list (a stack of composite layers) that opted
+        in through `composite_joint_step` is asked first; then `joint_step` decides.  A forced route that does not apply raises
+        NotImplementedError with the reason."""
+        if self.joint_step not in JOINT_STEP: raise ValueError(f'joint_step must be one of {JOINT_STEP}')
+        if len(x) == 10 and self.composite_joint_step != 'blocks':
+            why = self._joint_refusal(x, composite=True)
+            if why is None: return 'library'
+            if self.composite_joint_step == 'library': raise NotImplementedError(f"composite_joint_step='library' does not apply here: {why}")
+        if self.joint_step == 'blocks': return 'blocks'
+        why = self._joint_refusal(x, composite=False)
+        if why is None: return 'library'
+        if self.joint_step == 'library': raise NotImplementedError(f"joint_step='library' does not apply here: {why}")
+        return 'blocks'
+
+    def train_step(self, data, *, state0=None, seed=None, apply=True):
+        """One joint optimisation step of all layers (reference LGNN.py:252-287): 'parallel' = mean of the per-layer
+        losses, 'residual' = loss of the mean output. Gradients flow from layer i+1 into layer i through the labels
+        built by `update_graph` (`split_label_gradient`).  One skeleton for both routes of `_joint_route`; where they differ - how a layer
+        runs forward and backward, how the update is applied - the two stand side by side under `library`:
+          'blocks'  - `LoopTrainer.forward` / `loss_and_grad` + `pool_backward` + `backward` on fresh trainers, a plain optimizer call;
+          'library' - `forward_phase` / `backward_phase` on the cached trainers (LAYERS phase-1 calls, then LAYERS phase-2 calls, the label
+                      gradients computed by the library), the update all or nothing behind one gate word (`_apply_gated`)."""
+        if self.training_mode == 'serial':
+            raise RuntimeError("training_mode 'serial' trains layer by layer: use fit()")
+        if self.loss is None: raise RuntimeError('compile() the model with a loss before fit() / train_step()')
+        x, y, sample_weight = data
+        if y is None: raise TypeError('Target data is missing. Your model was compiled with `loss` '
+                                      'argument and so expects targets to be passed in `fit()`.')
+        x = list(x)
+        composite = len(x) == 10                                   # composite lists carry type_mask at [3]
+        i_set = 4 if composite else 3
+        nodes_0, arcs_0, dnl, set_mask, output_mask = x[0], x[1], x[2], x[i_set], x[i_set + 1]
+        s0 = state0 if state0 is not None else [None] * self.LAYERS
+        for g in self.gnns: g.loss = self.loss
+        self.last_joint_route = self._joint_route(x)
+        library = self.last_joint_route == 'library'
+        if library: trainers = self._joint_trainers()
+        else:
+            self.resolve_joint_pending()
+            trainers = [LoopTrainer(g) for g in self.gnns]
+        graph_based = self.GNN_CLASS is self._gnn_classes['graph']
+        arc_based = self.GNN_CLASS is self._gnn_classes['arc']
+        Lyr, residual = self.LAYERS, self.training_mode == 'residual'
+        # forward sweep: layer i + 1 runs on the labels `update_graph` builds from layer i; `outs`: every layer's task-level output
+        tapes, outs = [], []
+        nodes, arcs = nodes_0, arcs_0
+        for i, tr in enumerate(trainers):
+            last = i == Lyr - 1
+            lx = self._layer_x(x, nodes, arcs, dnl)
+            if library:
+                tp = tr.forward_phase(lx, state0=s0[i], seed=seed, composite_phases=composite)
+                out = tp.y_pred
+            else:
+                tp = tr.forward(lx, state0=s0[i], seed=seed, node_level=not last)
+                out = tp.y_pred if last else self._pool(x[-1], tp.out_nodes) if graph_based else tp.out_nodes
+            tapes.append(tp); outs.append(out)
+            if not last: nodes, arcs, dnl = self.update_graph(nodes_0, arcs_0, dnl, set_mask, output_mask, tp.state, tp.out_nodes)
+        if library:
+            # the previous applied joint step: every phase 1 above fetched its layer's word for free at its synchronisation; a layer whose tape
+            # was reallocated in between fetched nothing, and the gate word itself is read then (before this step overwrites it)
+            fetched = [h.prev_ok for h in tapes if h.prev_ok is not None]
+            self.resolve_joint_pending(failed=(any(ok is False for ok in fetched) if len(fetched) == Lyr else None))
+        # the loss and its gradient w.r.t. every layer's task-level output ('parallel' on the library route: inside `backward_phase`)
+        loss, dpreds = None, [None] * Lyr
+        if residual:
+            loss, dmean = trainers[-1].loss_and_grad(tapes[-1], sum(outs) / Lyr, y, sample_weight)
+            dpreds = [dmean / Lyr] * Lyr if library else [dmean / Lyr for _ in range(Lyr)]      # ('blocks' keeps its one division per layer)
+        elif not library:
+            parts = [trainers[i].loss_and_grad(tapes[i], outs[i], y, sample_weight) for i in range(Lyr)]
+            loss = sum(pl[0] for pl in parts) / Lyr
+            dpreds = [pl[1] / Lyr for pl in parts]
+        # backward sweep, last layer first; the label gradient of layer i+1 feeds layer i
+        d_state_extra, d_out_extra = None, None
+        for i in range(Lyr - 1, -1, -1):
+            tp, tr = tapes[i], trainers[i]
+            arc_out = arc_based and self.get_output and i > 0        # the layer below wrote its output into the ARC labels
+            if library:
+                own = dict(y=None, sample_weight=None, d_pred_extra=dpreds[i]) if residual else \
+                    dict(y=y, sample_weight=sample_weight, loss_scale=1.0 / Lyr)
+                tr.backward_phase(tp, d_out_extra=d_out_extra, d_state_extra=d_state_extra, want_label_grads=i > 0,
+                                  want_arc_label_grads=arc_out, **own)
+                d_nodes = tp.d_nodes
+            else:
+                G = tr.pool_backward(tp, dpreds[i]) if graph_based else dpreds[i].clone()      # every layer's task output is pooled for graph focus
+                if d_out_extra is not None: G = G + d_out_extra
+                d_nodes = tr.backward(tp, G.contiguous(), d_state_extra=d_state_extra, want_label_grads=i > 0,
+                                      want_arc_label_grads=arc_out)
+            d_state_extra = d_out_extra = None
+            if i > 0:
+                # (`d_arc_labels`: there where `arc_out` asked for it; a composite layer on 'blocks' has none, and T <= 2 reads none)
+                d_state_extra, d_out_extra = split_label_gradient(d_nodes, getattr(tp, 'd_arc_labels', None), tapes[i - 1],
+                                                                  self.get_state, self.get_output, arc_based)
+        if library and not residual: loss = sum(h.loss[0] for h in tapes) / Lyr
+        for tp, tr in zip(tapes, trainers): tr.finish(tp, apply=False)
+        if apply:
+            gv = [pair for tp in tapes for pair in LoopTrainer.grads_and_vars(tp)]
+            if library: self._apply_gated(tapes, trainers, gv)
+            else: self._optimizer_obj().apply_gradients(gv)
+        self._last_tapes = tapes
+        logs = {'loss': loss, 'k': [tp.k for tp in tapes]}
+        yd = y.to(outs[-1].device)
+        sw = torch.ones(yd.shape[0], device=yd.device) if sample_weight is None else sample_weight.to(yd.device)
+        for mtr in self.metrics_spec:
+            n, f = _metric_fn(mtr, yd.shape[-1])
+            logs[n] = (f(yd, outs[-1]) * sw).sum() / sw.sum()
+        return logs
+
+    def _apply_gated(self, hs, trainers, gv):
+        """The optimizer update of a library-route step, all or nothing: one gate word over every layer's validity word (the moving
+        statistics of a layer are gated by that layer's own word).  A foreign optimizer knows nothing of the gate: the words are read."""
+        import ctypes as C
+        from .. import _native as nat
+        from .training import Adam, SGD
+        opt = self._optimizer_obj()
+        if not isinstance(opt, (Adam, SGD)):
+            if all(LoopTrainer._read_word(h.grads_ok_view) for h in hs): opt.apply_gradients(gv)
+            return
+        dev = hs[0].dev
+        gate = getattr(self, '_joint_gate', None)
+        if gate is None or gate.device != dev: gate = self._joint_gate = torch.zeros(1, dtype=torch.int32, device=dev)
+        words = (C.c_void_p * len(hs))(*[h.grads_ok for h in hs])
+        nat.check(nat.lib().gnn_gate_all(words, len(hs), nat.ptr(gate), nat.current_stream(dev)))
+        opt.apply_gradients(gv, gate=gate.data_ptr())
+        for h, tr in zip(hs, trainers): tr._joint_word_tape = h.tape      # the next phase 1 on this tape reads the word for free
+        self._joint_pending = True
 
     def resolve_joint_pending(self, failed=None):
         """Settle the last applied joint step of the library route: was its update gated off on the device (a barrier wait of a persistent
@@ -390,83 +440,6 @@ class LGNN(_LoopModel):
                           'resident): weights and optimizer slots untouched', RuntimeWarning, stacklevel=3)
             opt = self._optimizer_obj()
             if isinstance(getattr(opt, 'iterations', None), int) and opt.iterations > 0: opt.iterations -= 1
-
-    def _train_step_library(self, x, y, sample_weight, s0, seed, apply):
-        """The joint step as LAYERS phase-1 calls followed by LAYERS phase-2 calls (`LoopTrainer.forward_phase` / `backward_phase`): the same
-        arithmetic and the same column bookkeeping as the building-block route of `train_step`, the label gradients computed by the library.
-        The optimizer update is all or nothing: one gate word over every layer's validity word; the moving statistics of a layer are gated
-        by that layer's own word."""
-        import ctypes as C
-        import warnings
-        from .. import _native as nat
-        from .training import Adam, SGD
-        composite = len(x) == 10                                    # composite lists carry type_mask at [3] (`composite_joint_step`)
-        i_set = 4 if composite else 3
-        nodes_0, arcs_0, dim0, set_mask, output_mask = x[0], x[1], x[2], x[i_set], x[i_set + 1]
-        trainers = self._joint_trainers()
-        arc_based = self.GNN_CLASS is self._gnn_classes['arc']
-        Lyr = self.LAYERS
-        hs, nodes, arcs, dnl = [], nodes_0, arcs_0, dim0
-        for i, tr in enumerate(trainers):
-            h = tr.forward_phase(self._layer_x(x, nodes, arcs, dnl), state0=s0[i], seed=seed, composite_phases=composite)
-            hs.append(h)
-            if i < Lyr - 1: nodes, arcs, dnl = self.update_graph(nodes_0, arcs_0, dnl, set_mask, output_mask, h.state, h.out_nodes)
-        # the previous applied joint step: every phase 1 above fetched its layer's word for free at its synchronisation; a layer whose tape
-        # was reallocated in between fetched nothing, and the gate word itself is read then (before this step overwrites it)
-        fetched = [h.prev_ok for h in hs if h.prev_ok is not None]
-        self.resolve_joint_pending(failed=(any(ok is False for ok in fetched) if len(fetched) == Lyr else None))
-        outs = [h.y_pred for h in hs]
-        dmean = None
-        if self.training_mode == 'residual':
-            mean_out = sum(outs) / Lyr
-            loss, dmean = trainers[-1].loss_and_grad(hs[-1], mean_out, y, sample_weight)
-            dmean = dmean / Lyr
-        d_state_extra, d_out_extra = None, None
-        for i in range(Lyr - 1, -1, -1):
-            h, tr = hs[i], trainers[i]
-            arc_out = arc_based and self.get_output and i > 0        # the layer below wrote its output into the ARC labels
-            if dmean is None:
-                tr.backward_phase(h, y, sample_weight, loss_scale=1.0 / Lyr, d_out_extra=d_out_extra, d_state_extra=d_state_extra,
-                                  want_label_grads=i > 0, want_arc_label_grads=arc_out)
-            else:
-                tr.backward_phase(h, None, None, d_pred_extra=dmean, d_out_extra=d_out_extra, d_state_extra=d_state_extra,
-                                  want_label_grads=i > 0, want_arc_label_grads=arc_out)
-            d_state_extra = d_out_extra = None
-            if i > 0:                                               # (the column bookkeeping of `train_step`)
-                prev, d_nodes = hs[i - 1], h.d_nodes
-                col = 0
-                if self.get_state:
-                    d_state_extra = d_nodes[:, :prev.S].contiguous(); col = prev.S
-                if self.get_output and not arc_based:
-                    d_out_extra = d_nodes[:, col:col + prev.T].index_select(0, prev.out_index.long()).contiguous()
-                elif arc_out:
-                    d_out_extra = torch.zeros((prev.M, prev.T), dtype=torch.float32, device=h.dev)
-                    if prev.T > 2:
-                        d_out_extra[:, 2:] = h.d_arc_labels[:, :prev.T - 2].index_select(0, prev.out_index.long())
-        if dmean is None: loss = sum(h.loss[0] for h in hs) / Lyr
-        for h, tr in zip(hs, trainers): tr.finish(h, apply=False)
-        if apply:
-            gv = [pair for h in hs for pair in LoopTrainer.grads_and_vars(h)]
-            opt = self._optimizer_obj()
-            if isinstance(opt, (Adam, SGD)):
-                dev = hs[0].dev
-                gate = getattr(self, '_joint_gate', None)
-                if gate is None or gate.device != dev: gate = self._joint_gate = torch.zeros(1, dtype=torch.int32, device=dev)
-                words = (C.c_void_p * Lyr)(*[h.grads_ok for h in hs])
-                nat.check(nat.lib().gnn_gate_all(words, Lyr, nat.ptr(gate), nat.current_stream(dev)))
-                opt.apply_gradients(gv, gate=gate.data_ptr())
-                for h, tr in zip(hs, trainers): tr._joint_word_tape = h.tape      # the next phase 1 on this tape reads the word for free
-                self._joint_pending = True
-            elif all(LoopTrainer._read_word(h.grads_ok_view) for h in hs):      # a foreign optimizer knows nothing of the gate: read the words
-                opt.apply_gradients(gv)
-        self._last_tapes = hs
-        out = {'loss': loss, 'k': [h.k for h in hs]}
-        yd = y.to(outs[-1].device)
-        sw = torch.ones(yd.shape[0], device=yd.device) if sample_weight is None else sample_weight.to(yd.device)
-        for mtr in self.metrics_spec:
-            n, f = _metric_fn(mtr, yd.shape[-1])
-            out[n] = (f(yd, outs[-1]) * sw).sum() / sw.sum()
-        return out
 
     # ---- fit: serial mode trains the layers one after another (reference LGNN.py:290-362) -----------------------------------
     def _propagate(self, gnn, seq_now, seq_t0, state0s=None):

@@ -1078,17 +1078,23 @@ class LoopTrainer:
     def _bind_tape(self, c):
         """Step 5: the tape - one cached device allocation, sized by the library for this argument block, 256-byte aligned.  Its first
         word is the step's validity word (`c.word_at`: its offset in `c.tape`)."""
-        ta, dev = c.ta, c.op.dev
-        nbytes = nat.lib().gnn_train_workspace_bytes(C.byref(ta))
+        ta = c.ta
+        # (`resolve_pending`: the previous step's validity word lives in the tape that is about to go)
+        c.tape, c.word_at, ta.tape, ta.tape_bytes = self._aligned_buffer('_tape', nat.lib().gnn_train_workspace_bytes(C.byref(ta)), c.op.dev,
+                                                                         before_realloc=self.resolve_pending)
+
+    def _aligned_buffer(self, attr, nbytes, dev, before_realloc=None):
+        """A cached device allocation kept in `self.<attr>`, sized by the library (`nbytes`; 0: the library refused, its message is
+        raised), grown by a quarter when it has to grow: (the buffer, the offset of its 256-byte aligned base, that base, the bytes behind
+        it).  `before_realloc` runs before a buffer that no longer fits is replaced."""
         if nbytes == 0: nat.check(1)
-        tape = getattr(self, '_tape', None)
-        if tape is None or tape.numel() < nbytes + 256 or tape.device != dev:
-            self.resolve_pending()                           # (the previous step's validity word lives in the tape that is about to go)
-            tape = self._tape = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=dev)
-        base = tape.data_ptr()
-        aligned = (base + 255) & ~255
-        ta.tape, ta.tape_bytes = C.c_void_p(aligned), tape.numel() - (aligned - base)
-        c.tape, c.word_at = tape, aligned - base
+        buf = getattr(self, attr, None)
+        if buf is None or buf.numel() < nbytes + 256 or buf.device != dev:
+            if before_realloc is not None: before_realloc()
+            buf = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=dev)
+            setattr(self, attr, buf)
+        at = ((buf.data_ptr() + 255) & ~255) - buf.data_ptr()
+        return buf, at, C.c_void_p(buf.data_ptr() + at), buf.numel() - at
 
     def _finish_phase_forward(self, c, composite_phases=False):
         """Phase 1 of `gnn_train_step_ex` (include/gnnloop.h): everything up to the output network and the pooling, the tape kept for
@@ -1103,13 +1109,7 @@ class LoopTrainer:
             cx = nat.TrainCompositePhaseArgs()
             by_source = [_by_source(ca, op.dev) if dt > 0 else None for ca, dt in zip(op.cas, op.dims)]
             for t_, bs in enumerate(by_source): cx.composite_adjacency_by_source[t_] = nat.make_csr(bs)
-            nbytes = nat.lib().gnn_train_composite_phase_scratch_bytes(C.byref(ta))
-            if nbytes == 0: nat.check(1)
-            scratch = getattr(self, '_composite_scratch', None)
-            if scratch is None or scratch.numel() < nbytes + 256 or scratch.device != op.dev:
-                scratch = self._composite_scratch = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=op.dev)
-            aligned = (scratch.data_ptr() + 255) & ~255
-            cx.scratch, cx.scratch_bytes = C.c_void_p(aligned), scratch.numel() - (aligned - scratch.data_ptr())
+            scratch, _, cx.scratch, cx.scratch_bytes = self._aligned_buffer('_composite_scratch', nat.lib().gnn_train_composite_phase_scratch_bytes(C.byref(ta)), op.dev)
             c.keep += [by_source, scratch]
         elif nat.lib().gnn_train_phases_supported(C.byref(ta)) != 0:
             raise NotImplementedError('the phased in-library step does not cover this shape (gnn_train_phases_supported)')
@@ -1137,6 +1137,27 @@ class LoopTrainer:
                                out_index=op.out_index, arcnode=op.arcnode, n_rows=op.n_rows)
 
     # ---- the step in two phases (gnn_train_step_ex): what a joint LGNN step is made of (docs/joint_lgnn_step.md) ---------------------------------
+    def _dims_only_args(self, n_nodes, n_arcs, dim_node_label, dim_arc_label, n_out, type_dims=None):
+        """The argument block of a coverage query: dims, network descriptions, flags and focus - no buffer, nothing to launch.
+        `type_dims` (a heterogeneous model): the label width of every node type; coverage does not depend on how the nodes split into
+        types, so the query puts them all into the first type."""
+        m = self.model
+        ta = nat.TrainArgs()
+        a = ta.loop
+        a.abi_version, a.n_types = nat.GNN_ABI_VERSION, 1
+        a.n_nodes, a.n_arcs, a.dim_node_label, a.dim_arc_label = int(n_nodes), int(n_arcs), int(dim_node_label), int(dim_arc_label)
+        if type_dims is not None:
+            a.composite, a.n_types = 1, len(type_dims)
+            for t_, dt in enumerate(type_dims): a.type_dim_label[t_], a.type_offsets[t_ + 1] = int(dt), int(n_nodes)
+        a.state_dim, a.max_iteration, a.state_threshold = m.state_vect_dim, m.max_iteration, float(m.state_threshold)
+        a.flags = _train_flags(m)
+        for dst, net in [(a.net_state[t_], n_) for t_, n_ in enumerate(state_networks(m))] + [(a.net_output, m.net_output)]:
+            units = [int(u) for u in net.units]
+            dst.in_dim, dst.n_layers = int(net.input_dim), len(units)
+            for i, (u, act) in enumerate(zip(units, net.activations)): dst.units[i], dst.activation[i] = u, nat.ACTIVATIONS[act]
+        a.focus, a.n_out = nat.FOCUS[m._focus], int(n_out)
+        return ta
+
     def _native_phases_apply(self, n_nodes, n_arcs, dim_node_label, dim_arc_label, n_out):
         """May a batch of these dims run as `forward_phase` + `backward_phase`?  Today's `_native_step_applies` conditions (no data
         parallelism, no Dropout in front of a first Dense, a loss with a device gradient), a homogeneous model, and the library's own answer
@@ -1144,41 +1165,17 @@ class LoopTrainer:
         m = self.model
         if isinstance(m.net_state, (list, tuple)) or m.max_iteration < 1: return False
         if not self._native_step_applies(True): return False
-        ta = nat.TrainArgs()
-        a = ta.loop
-        a.abi_version, a.n_types = nat.GNN_ABI_VERSION, 1
-        a.n_nodes, a.n_arcs, a.dim_node_label, a.dim_arc_label = int(n_nodes), int(n_arcs), int(dim_node_label), int(dim_arc_label)
-        a.state_dim, a.max_iteration, a.state_threshold = m.state_vect_dim, m.max_iteration, float(m.state_threshold)
-        a.flags = _train_flags(m)
-        for dst, net in ((a.net_state[0], m.net_state), (a.net_output, m.net_output)):
-            units = [int(u) for u in net.units]
-            dst.in_dim, dst.n_layers = int(net.input_dim), len(units)
-            for i, (u, act) in enumerate(zip(units, net.activations)): dst.units[i], dst.activation[i] = u, nat.ACTIVATIONS[act]
-        a.focus, a.n_out = nat.FOCUS[m._focus], int(n_out)
+        ta = self._dims_only_args(n_nodes, n_arcs, dim_node_label, dim_arc_label, n_out)
         return nat.lib().gnn_train_phases_supported(C.byref(ta)) == 0
 
     def _native_composite_phases_apply(self, n_nodes, n_arcs, dims, dim_arc_label, n_out):
         """`_native_phases_apply` for a heterogeneous model (`forward_phase(composite_phases=True)`; `dims`: the label width of every node
-        type): today's `_native_step_applies` conditions, node or graph focus, and the library's `gnn_train_composite_phases_supported`.
-        Coverage depends on the node count, the widths and the networks, not on how the nodes split into types: the query puts them all
-        into the first type."""
+        type): today's `_native_step_applies` conditions, node or graph focus, and the library's `gnn_train_composite_phases_supported`."""
         m = self.model
         if not isinstance(m.net_state, (list, tuple)) or m.max_iteration < 1 or m._focus not in ('n', 'g'): return False
         if len(dims) != len(m.net_state) or len(dims) > nat.GNN_MAX_TYPES: return False
         if not self._native_step_applies(True): return False
-        ta = nat.TrainArgs()
-        a = ta.loop
-        a.abi_version, a.composite, a.n_types = nat.GNN_ABI_VERSION, 1, len(dims)
-        a.n_nodes, a.n_arcs, a.dim_node_label, a.dim_arc_label = int(n_nodes), int(n_arcs), max(int(v) for v in dims), int(dim_arc_label)
-        for t_, dt in enumerate(dims): a.type_dim_label[t_] = int(dt)
-        for t_ in range(1, len(dims) + 1): a.type_offsets[t_] = int(n_nodes)
-        a.state_dim, a.max_iteration, a.state_threshold = m.state_vect_dim, m.max_iteration, float(m.state_threshold)
-        a.flags = _train_flags(m)
-        for dst, net in [(a.net_state[t_], n_) for t_, n_ in enumerate(m.net_state)] + [(a.net_output, m.net_output)]:
-            units = [int(u) for u in net.units]
-            dst.in_dim, dst.n_layers = int(net.input_dim), len(units)
-            for i, (u, act) in enumerate(zip(units, net.activations)): dst.units[i], dst.activation[i] = u, nat.ACTIVATIONS[act]
-        a.focus, a.n_out = nat.FOCUS[m._focus], int(n_out)
+        ta = self._dims_only_args(n_nodes, n_arcs, max(int(v) for v in dims), dim_arc_label, n_out, type_dims=dims)
         return nat.lib().gnn_train_composite_phases_supported(C.byref(ta)) == 0
 
     def forward_phase(self, x_list, state0=None, seed=None, *, composite_phases=False):

@@ -790,11 +790,8 @@ int composite_phases_covered(const CPlan &p) {
 int check_composite_phase_args(const gnn_train_args_t &ta, const gnn_train_phase_args_t &px, const gnn_train_composite_phase_args_t *cx, const CPlan &p,
                                const CLabelScratch &need) {
     TRY(composite_phases_covered(p));
-    if (px.phase == 0 && ta.loss_kind == GNN_LOSS_NONE) return fail("GNN_LOSS_NONE is valid in phase %d only (a whole step needs a loss of its own)", GNN_TRAIN_PHASE_BACKWARD);
-    if (px.phase != 0 && !px.phase_state) return fail("gnn_train_step_composite_ex: phase %d needs phase_state", px.phase);
-    if (px.phase == GNN_TRAIN_PHASE_BACKWARD && px.phase_state->magic != PHASE_MAGIC) return fail("gnn_train_step_composite_ex: phase_state was not filled by a phase-1 call");
-    if (px.phase == GNN_TRAIN_PHASE_BACKWARD && (px.phase_state->k < 0 || px.phase_state->k > p.K)) return fail("gnn_train_step_composite_ex: phase_state holds k = %d", px.phase_state->k);
-    if (px.d_nodes && px.ld_d_nodes != 0 && px.ld_d_nodes < p.L) return fail("gnn_train_step_composite_ex: ld_d_nodes %d < dim_node_label %d", px.ld_d_nodes, p.L);
+    TRY(check_phase_loss_kind(ta, px));
+    TRY(check_phase_state(px, p.K, p.L, "gnn_train_step_composite_ex"));
     if (px.phase != 0 || px.d_nodes) {
         if (!cx || !cx->scratch || ((uintptr_t)cx->scratch & 255) != 0) return fail("gnn_train_step_composite_ex: phases and label gradients need cx->scratch, a 256-byte aligned device buffer");
         if (cx->scratch_bytes < need.bytes) return fail("gnn_train_step_composite_ex: scratch too small: %zu < %zu bytes", cx->scratch_bytes, need.bytes);
@@ -815,7 +812,9 @@ int train_step_composite(const gnn_train_args_t &ta, const gnn_train_phase_args_
     CPlan p;
     const bool fwd_only = ta.forward_only != 0;         // the training-mode forward alone: no loss, no gradients, the validity word untouched
     const int phase = px.phase;
-    const bool ex = phase != 0 || px.loss_scale != 0.0f || px.phase_state || px.node_out || px.d_pred_extra || px.d_out_extra || px.d_state_extra || px.d_nodes;
+    // (`d_arc_labels`, which the predicate counts and this line did not spell out, is NULL here: gnn_train_step_composite_ex refuses it in
+    // front of this call, and the plain step hands in an all-zero block)
+    const bool ex = phase_block_used(px);
     if (fwd_only && ta.prev_grads_ok_host) return fail("gnn_train_step(forward_only): prev_grads_ok_host must be NULL");
     TRY(make_cplan(ta, ta.tape, p));
     CLabelScratch sc{};
@@ -924,9 +923,7 @@ int gnn_train_step_composite_ex(const gnn_train_args_t *args, const gnn_train_ph
     gnn_train_phase_args_t x;
     memset(&x, 0, sizeof(x));
     if (px) x = *px;
-    const bool used = x.phase != 0 || x.loss_scale != 0.0f || x.phase_state || x.node_out || x.d_pred_extra || x.d_out_extra || x.d_state_extra || x.d_nodes ||
-                      x.d_arc_labels;
-    if (!used && !cx) return gnn_train_step(args);                 // exactly the plain call: same checks, same order, same messages
+    if (!phase_block_used(x) && !cx) return gnn_train_step(args);                 // exactly the plain call: same checks, same order, same messages
     const gnn_train_args_t &ta = *args;
     if (!ta.tape || ((uintptr_t)ta.tape & 255) != 0) return fail("tape must be a 256-byte aligned device buffer");
     if (x.phase < 0 || x.phase > GNN_TRAIN_PHASE_BACKWARD) return fail("gnn_train_step_composite_ex: unknown phase %d", x.phase);

@@ -1516,6 +1516,32 @@ int label_grads(const gnn_train_args_t &ta, const gnn_train_phase_args_t &px, co
     return 0;
 }
 
+// ---- the phase block (gnn_train_phase_args_t) of gnn_train_step_ex / gnn_train_step_composite_ex: what both entry points ask of it ------
+constexpr int32_t PHASE_MAGIC = 0x50483130;
+
+// Is the phase block in use - any field but the by-source CSR, which only `d_arc_labels` reads?  An all-zero block is the plain gnn_train_step.
+inline bool phase_block_used(const gnn_train_phase_args_t &px) {
+    return px.phase != 0 || px.loss_scale != 0.0f || px.phase_state || px.node_out || px.d_pred_extra || px.d_out_extra || px.d_state_extra ||
+           px.d_nodes || px.d_arc_labels;
+}
+
+// GNN_LOSS_NONE is phase 2's "no loss of its own"  (phase 1 with GNN_LOSS_NONE: the same args as the phase-2 call - the loss is not looked at)
+inline int check_phase_loss_kind(const gnn_train_args_t &ta, const gnn_train_phase_args_t &px) {
+    if (px.phase == 0 && ta.loss_kind == GNN_LOSS_NONE) return fail("GNN_LOSS_NONE is valid in phase %d only (a whole step needs a loss of its own)", GNN_TRAIN_PHASE_BACKWARD);
+    return 0;
+}
+
+// The phase state against the plan's K and the leading dimension of `d_nodes` against its L; `who`: the entry point, for the message.
+// (Two functions, not one: gnn_train_step_ex refuses GNN_LOSS_NONE in front of its coverage refusals and these checks behind them,
+// gnn_train_step_composite_ex refuses both behind them - every caller keeps its order.)
+inline int check_phase_state(const gnn_train_phase_args_t &px, int K, int L, const char *who) {
+    if (px.phase != 0 && !px.phase_state) return fail("%s: phase %d needs phase_state", who, px.phase);
+    if (px.phase == GNN_TRAIN_PHASE_BACKWARD && px.phase_state->magic != PHASE_MAGIC) return fail("%s: phase_state was not filled by a phase-1 call", who);
+    if (px.phase == GNN_TRAIN_PHASE_BACKWARD && (px.phase_state->k < 0 || px.phase_state->k > K)) return fail("%s: phase_state holds k = %d", who, px.phase_state->k);
+    if (px.d_nodes && px.ld_d_nodes != 0 && px.ld_d_nodes < L) return fail("%s: ld_d_nodes %d < dim_node_label %d", who, px.ld_d_nodes, L);
+    return 0;
+}
+
 // heterogeneous models: train_composite.hpp (behind this file in the same translation unit)
 int train_step_composite(const gnn_train_args_t &ta);
 size_t composite_train_workspace_bytes(const gnn_train_args_t &ta);
@@ -1584,21 +1610,13 @@ int gnn_train_step_ex(const gnn_train_args_t *args, const gnn_train_phase_args_t
     return landed_on_failure(*args, train_step_impl(*args, px ? *px : none));
 }
 
-constexpr int32_t PHASE_MAGIC = 0x50483130;
-
 // the second argument block of gnn_train_step_ex against the plan: everything that refuses a call, before its first launch
 static int check_phase_args(const gnn_train_args_t &ta, const gnn_train_phase_args_t &px, const TrainPlan &p) {
-    if (px.phase == 0 && ta.loss_kind == GNN_LOSS_NONE) return fail("GNN_LOSS_NONE is valid in phase %d only (a whole step needs a loss of its own)", GNN_TRAIN_PHASE_BACKWARD);
-    // (phase 1 with GNN_LOSS_NONE: the same args as the phase-2 call - the loss is not looked at)
-    const bool used = px.phase != 0 || px.loss_scale != 0.0f || px.phase_state || px.node_out || px.d_pred_extra || px.d_out_extra || px.d_state_extra ||
-                      px.d_nodes || px.d_arc_labels;
-    if (!used) return 0;
+    TRY(check_phase_loss_kind(ta, px));
+    if (!phase_block_used(px)) return 0;
     if (p.path == TrainPath::big) return not_covered("gnn_train_step_ex: the row-streaming path (>= GNN_TRAIN_BIG_MIN_NODES nodes) has no phases / upstream gradients / label gradients: such steps train through the building blocks");
     if (p.H1s > gnn::LG_MAX_H) return not_covered("gnn_train_step_ex: first state layer of %d units (at most %d)", p.H1s, gnn::LG_MAX_H);
-    if (px.phase != 0 && !px.phase_state) return fail("gnn_train_step_ex: phase %d needs phase_state", px.phase);
-    if (px.phase == GNN_TRAIN_PHASE_BACKWARD && px.phase_state->magic != PHASE_MAGIC) return fail("gnn_train_step_ex: phase_state was not filled by a phase-1 call");
-    if (px.phase == GNN_TRAIN_PHASE_BACKWARD && (px.phase_state->k < 0 || px.phase_state->k > p.K)) return fail("gnn_train_step_ex: phase_state holds k = %d", px.phase_state->k);
-    if (px.d_nodes && px.ld_d_nodes != 0 && px.ld_d_nodes < p.L) return fail("gnn_train_step_ex: ld_d_nodes %d < dim_node_label %d", px.ld_d_nodes, p.L);
+    TRY(check_phase_state(px, p.K, p.L, "gnn_train_step_ex"));
     if (px.d_arc_labels && p.A > 0 && p.E > 0) {
         if (!px.arcnode_by_source.rowptr) return fail("gnn_train_step_ex: d_arc_labels needs arcnode_by_source");
         TRY(check_csr(px.arcnode_by_source, "arcnode_by_source", p.E, p.N));
@@ -1615,8 +1633,11 @@ static int train_step_impl(const gnn_train_args_t &ta, const gnn_train_phase_arg
     const bool fwd_only = ta.forward_only != 0;                   // ABI 9: the training-mode forward alone (no loss, no gradients)
     const int phase = px.phase;
     if (phase < 0 || phase > GNN_TRAIN_PHASE_BACKWARD) return fail("gnn_train_step_ex: unknown phase %d", phase);
-    if ((phase != 0 || px.loss_scale != 0.0f || px.d_pred_extra || px.d_out_extra || px.d_state_extra || px.d_nodes || px.d_arc_labels || px.node_out) &&
-        (ta.n_groups != 0 || a.composite || fwd_only))
+    // (this refusal has never counted a bare `phase_state`: a block with nothing else set asks for nothing, and a grouped, heterogeneous or
+    // forward_only call that carries one stays the plain call - the one term of phase_block_used() left out here, explicitly)
+    gnn_train_phase_args_t asked = px;
+    asked.phase_state = nullptr;
+    if (phase_block_used(asked) && (ta.n_groups != 0 || a.composite || fwd_only))
         return not_covered("gnn_train_step_ex: phases, upstream gradients and label gradients cover whole steps of homogeneous models only (gnn_train_phases_supported)");
     if (ta.n_groups != 0) return train_forward_groups(ta);         // ABI 10: independent convergence groups (train_group.hpp)
     if (a.composite) return train_step_composite(ta);             // one state network per node type (train_composite.hpp); honours forward_only
