@@ -315,21 +315,19 @@ int launch_rowdense_wide(const gnn::SegDenseArgs &a, hipStream_t st) {
 
 int launch_segdense(gnn::SegDenseArgs &a, hipStream_t st) {
     if (a.M == 0) return 0;
-    if (a.H <= 4) {
+    if (thin_dense_applies(a)) {            // the ONE statement of the rule: the callers that finish a softmax in this launch ask the same question
         int K = 0;
         for (int s = 0; s < a.nseg; ++s) K = std::max(K, a.seg[s].wrow + a.seg[s].width);
-        if ((size_t)K * a.H * sizeof(float) <= 48 * 1024) {
-            const int grid = (int)std::max<long>(1, std::min<long>(cdiv(a.M, 16 * gnn::TD_ROWS), 256 * 8));
-            const size_t lds = ((size_t)((K * a.H + 3) & ~3) + K + 4) * sizeof(float);
-            switch (a.H) {
-                case 1: gnn::k_thin_dense<1><<<grid, 256, lds, st>>>(a, K); break;
-                case 2: gnn::k_thin_dense<2><<<grid, 256, lds, st>>>(a, K); break;
-                case 3: gnn::k_thin_dense<3><<<grid, 256, lds, st>>>(a, K); break;
-                default: gnn::k_thin_dense<4><<<grid, 256, lds, st>>>(a, K); break;
-            }
-            LAUNCH_OK();
-            return 0;
+        const int grid = (int)std::max<long>(1, std::min<long>(cdiv(a.M, 16 * gnn::TD_ROWS), 256 * 8));
+        const size_t lds = ((size_t)((K * a.H + 3) & ~3) + K + 4) * sizeof(float);
+        switch (a.H) {
+            case 1: gnn::k_thin_dense<1><<<grid, 256, lds, st>>>(a, K); break;
+            case 2: gnn::k_thin_dense<2><<<grid, 256, lds, st>>>(a, K); break;
+            case 3: gnn::k_thin_dense<3><<<grid, 256, lds, st>>>(a, K); break;
+            default: gnn::k_thin_dense<4><<<grid, 256, lds, st>>>(a, K); break;
         }
+        LAUNCH_OK();
+        return 0;
     }
     if (rowdense_applies(a)) return launch_rowdense(a, st);
     if (rowdense_wide_applies(a)) return launch_rowdense_wide(a, st);

@@ -64,22 +64,33 @@ def index(a, dev):
 def _map(fn, a):
     if isinstance(a, torch.Tensor): return fn(a)
     if isinstance(a, tuple): return tuple(_map(fn, t) for t in a)
+    if isinstance(a, list): return [_map(fn, t) for t in a]
+    if isinstance(a, dict): return {k: _map(fn, t) for k, t in a.items()}
     return a
+
+
+def device_side(method):
+    """`method`: the name of a `_Prim` method, or a pair of callables (device call, float64 reference) for what `_Prim` does not express."""
+    return method[0] if isinstance(method, tuple) else getattr(_Prim(_dev()), method)
+
+
+def reference_side(method):
+    return method[1] if isinstance(method, tuple) else getattr(NumpyPrim(None), method)
 
 
 def both(method, *args):
     """`_Prim(cuda).method(*args)` on the device tensors and `NumpyPrim(None).method` on CPU clones of the same float32 inputs (taken
     before the device call: an output's old value is an input; one clone per tensor object, so aliases stay aliases).  Returns both
-    argument lists afterwards, tensors as NumPy arrays."""
+    argument lists afterwards, tensors as NumPy arrays.  `method` may be a pair of callables (`device_side`)."""
     memo = {}
 
     def clone(t):
         if id(t) not in memo: memo[id(t)] = t.detach().cpu().clone()
         return memo[id(t)]
     ref_args = [_map(clone, a) for a in args]
-    getattr(_Prim(_dev()), method)(*args)
+    device_side(method)(*args)
     torch.cuda.synchronize()
-    getattr(NumpyPrim(None), method)(*ref_args)
+    reference_side(method)(*ref_args)
     out = lambda t: t.detach().cpu().numpy()
     return [_map(out, a) for a in args], [_map(out, a) for a in ref_args]
 
@@ -124,7 +135,7 @@ def reference(case, pre=None):
     args, outs = case.build('cpu')
     old = outputs(args, outs)
     if pre is not None: args = pre(list(args))
-    getattr(NumpyPrim(None), case.method)(*args)
+    reference_side(case.method)(*args)
     return outputs(args, outs), old
 
 
