@@ -294,9 +294,9 @@ def _mix32(*values):
 
 
 def _train_flags(model):
-    """What a training step takes of `model.native_flags`: the opt-in bit of the hidden-layer persistent kernels alone (the other bits
-    steer the inference loop and keep having no effect on a step)."""
-    return int(getattr(model, 'native_flags', 0)) & nat.FLAG_TRAIN_HIDDEN_SMALL
+    """What a training step takes of `model.native_flags`: the opt-in bits of the hidden-layer persistent kernels and of the hidden-layer
+    grouped forward (independent of each other) alone - the other bits steer the inference loop and keep having no effect on a step."""
+    return int(getattr(model, 'native_flags', 0)) & (nat.FLAG_TRAIN_HIDDEN_SMALL | nat.FLAG_TRAIN_GROUPS_HIDDEN)
 
 
 class LoopTrainer:
@@ -1058,7 +1058,8 @@ class LoopTrainer:
         if ans == nat.TRAIN_GROUPS_UNCOVERED:
             raise NotImplementedError('training-mode convergence groups do not cover this shape (one-layer state network' + (' per type' if op.composite else '') +
                                       ' of units == state width <= 64, <= ' + ('64 constant columns per type' if op.composite else '32 constant columns') +
-                                      ', no softmax state, no Dropout; one-layer output network <= 64 units over <= 256 columns)')
+                                      ', no softmax state, no Dropout; one-layer output network <= 64 units over <= 256 columns; with '
+                                      'native_flags |= FLAG_TRAIN_GROUPS_HIDDEN also Dense(H) - Dense(state width), H <= the padded width, state width <= 32)')
         if ans > 0:
             raise NotImplementedError(f'training-mode convergence groups: group {ans - 1} has {int(gb[ans] - gb[ans - 1])} nodes '
                                       f'(at most {nat.TRAIN_GROUP_MAX_NODES} per group)')

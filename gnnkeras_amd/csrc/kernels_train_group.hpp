@@ -23,6 +23,15 @@
 //
 // The body of k_train_group_fwd is written as tg_* pieces (LDS carve, prologue, tile statistics, normalisation, dense update, epilogue)
 // that k_train_group_fwd_types (kernels_train_group_types.hpp: one state network per node type) is made of as well.
+//
+// Hidden-layer form (template parameter HID; opt-in through GNN_FLAG_TRAIN_GROUPS_HIDDEN, both model kinds; the rule is
+// train_groups_hidden_net() in train_group.hpp): the state network is Dense(H) - Dense(S), 1 <= H <= the padded width, padded width 16 / 32.
+// BatchNormalization sits in front of the first Dense only, so the statistics, the normalisation and the head are the one-layer form's.  The
+// first kernel is [in_s][Hw] (Cc has Hw real columns); the first product leaves lane (c, g) holding columns 16 ct + 4 g .. + 3 of tile row
+// c - exactly the B operand of k-step (ct, e) of a second v_mfma_f32_16x16x4_f32 product - so h . W2 runs from the first product's
+// accumulators: no transposition, no trip of h through LDS, no barrier.  W2 ([S][S + 4]: rows >= Hw and columns >= Sw zero) and b2 sit in
+// LDS behind `fin`, in front of the state rows.  The one-layer instantiations (HID = false) are the kernels they were: the hidden form's
+// arguments travel in derived structs (TrainGroupFwdH, GroupTypeNetH), read under `if constexpr`.
 #pragma once
 #include "kernels_train_small.hpp"
 
@@ -34,8 +43,9 @@ constexpr int GROUP_HEAD_MAX_UNITS = 64;
 
 // ---- constants ---------------------------------------------------------------------------------------------------------------------------
 // One workgroup per group.  stats[g][t][wrow] / [in_s + wrow] (all K slots: the constants' statistics do not change between iterations)
+// Hw: the row length of the first kernel = the real columns of Cc (the state's width; the hidden width in the hidden-layer form)
 __global__ void __launch_bounds__(256)
-k_train_group_const(const int *__restrict__ gbeg, int S, int Sw, ConstSegs cs, const float *__restrict__ W, const float *__restrict__ b, const float *gamma,
+k_train_group_const(const int *__restrict__ gbeg, int S, int Hw, ConstSegs cs, const float *__restrict__ W, const float *__restrict__ b, const float *gamma,
                     const float *beta, float eps, float *__restrict__ Cc, float *__restrict__ stats, int K, int in_s) {
     __shared__ float red[8][33];
     __shared__ float mu[32], ak[32], ck[32];
@@ -85,13 +95,13 @@ k_train_group_const(const int *__restrict__ gbeg, int S, int Sw, ConstSegs cs, c
     for (int i = tid; i < ng * S; i += 256) {
         const int h = i % S, n = n0 + i / S;
         float acc = 0.0f;
-        if (h < Sw) {
+        if (h < Hw) {
             acc = b[h];
             int col = 0;
             for (int s = 0; s < cs.n; ++s)
                 for (int j = 0; j < cs.width[s]; ++j, ++col) {
                     const float x = fmaf(cs.ptr[s][(size_t)n * cs.ld[s] + j] - mu[col], ak[col], ck[col]);
-                    acc = fmaf(x, W[(size_t)wr[col] * Sw + h], acc);
+                    acc = fmaf(x, W[(size_t)wr[col] * Hw + h], acc);
                 }
         }
         Cc[(size_t)n * S + h] = acc;
@@ -126,15 +136,21 @@ struct TrainGroupFwd : TrainGroupCommon {
     const float *W, *gamma, *beta; float eps;
     int act;
 };
+// ... of the hidden-layer form (the HID instantiations): W is [in_s][Hw], Cc has Hw real columns, `act` is the hidden activation
+struct TrainGroupFwdH : TrainGroupFwd {
+    int Hw;                      // hidden width, 1 .. 16 SQ
+    const float *W2, *b2;        // second Dense: [Hw][Sw], [Sw]
+    int act2;                    // its activation (the state's)
+};
 
-template <int SQ>
+template <int SQ, bool HID = false>
 inline size_t train_group_fwd_lds(int rows) {          // rows = the largest group of the launch (<= GROUP_CAP)
     constexpr int S = 16 * SQ;
-    return sizeof(float) * (64 * (2 * S + 4) + (2 * S) * (S + 4) + 3 * 2 * S + 512 + 4 * S + (size_t)rows * (S + 4));
+    return sizeof(float) * (64 * (2 * S + 4) + (2 * S) * (S + 4) + 3 * 2 * S + 512 + 4 * S + (HID ? S * (S + 4) + S : 0) + (size_t)rows * (S + 4));
 }
 
 // the LDS of a workgroup in the order of train_group_fwd_lds: everything but the state, which follows at rest()
-template <int SQ>
+template <int SQ, bool HID = false>
 struct TrainGroupLds {
     static constexpr int S = 16 * SQ, LDX = 2 * S + 4, LDW = S + 4, LDS_ST = S + 4;
     float *Xs;                   // [64][LDX]  [own | agg] of the current tile
@@ -143,18 +159,33 @@ struct TrainGroupLds {
     float *red, *fin;            // reduction scratch [512] | tile sums [4 S]
     __device__ __forceinline__ explicit TrainGroupLds(float *smem)
         : Xs(smem), W0(Xs + 64 * LDX), st_a(W0 + 2 * S * LDW), st_c(st_a + 2 * S), piv(st_c + 2 * S), red(piv + 2 * S), fin(red + 512) {}
-    __device__ __forceinline__ float *rest() const { return fin + 4 * S; }
+    __device__ __forceinline__ float *W2s() const { return fin + 4 * S; }        // HID: [S][LDW] the current network's second kernel
+    __device__ __forceinline__ float *b2s() const { return W2s() + S * LDW; }    // HID: [S] its bias
+    __device__ __forceinline__ float *rest() const { return fin + 4 * S + (HID ? S * LDW + S : 0); }
 };
 
-// the [2 S][LDW] weight block of one network: its state rows, then its neighbour-sum rows
+// the [2 S][LDW] weight block of one network: its state rows, then its neighbour-sum rows.  Hw: the kernel's row length (the state's width
+// Sw; the hidden width in the hidden-layer form)
 template <int SQ>
-__device__ __forceinline__ void tg_load_weights(float *W0, const float *W, int off_state, int off_agg, int Sw, int tid) {
+__device__ __forceinline__ void tg_load_weights(float *W0, const float *W, int off_state, int off_agg, int Sw, int Hw, int tid) {
     constexpr int S = 16 * SQ, LDW = S + 4;
     for (int i = tid; i < 2 * S * S; i += TS_NT) {
         const int k = i / S, h = i % S;
         const int kk = k < S ? k : k - S;
-        W0[k * LDW + h] = (kk < Sw && h < Sw) ? W[(size_t)((k < S ? off_state : off_agg) + kk) * Sw + h] : 0.0f;
+        W0[k * LDW + h] = (kk < Sw && h < Hw) ? W[(size_t)((k < S ? off_state : off_agg) + kk) * Hw + h] : 0.0f;
     }
+}
+// hidden-layer form: the second kernel [Hw][Sw] as [S][LDW] rows (rows >= Hw and columns >= Sw zero) and its bias - the pitch of W0, for
+// the same conflict-free A-operand reads
+template <int SQ>
+__device__ __forceinline__ void tg_load_weights2(const TrainGroupLds<SQ, true> &L, const float *W2, const float *b2, int Sw, int Hw, int tid) {
+    constexpr int S = 16 * SQ, LDW = S + 4;
+    float *W2s = L.W2s(), *b2s = L.b2s();
+    for (int i = tid; i < S * S; i += TS_NT) {
+        const int k = i / S, h = i % S;
+        W2s[k * LDW + h] = (k < Hw && h < Sw) ? W2[(size_t)k * Sw + h] : 0.0f;
+    }
+    if (tid < S) b2s[tid] = tid < Sw ? b2[tid] : 0.0f;
 }
 
 // state_0 of the group into LDS; whether the loop runs at all
@@ -178,8 +209,8 @@ __device__ __forceinline__ bool tg_prologue(const TrainGroupCommon &a, float *St
 
 // the tile in Xs (nr rows) adds its share to the column sums S1 / S2 of thread tid < 2 S: float32 sums around the tile's first row, moved
 // to the origin and added in double (merge_tile_stats)
-template <int SQ>
-__device__ __forceinline__ void tg_tile_stats(const TrainGroupLds<SQ> &L, int nr, int tid, double &S1, double &S2) {
+template <int SQ, bool HID>
+__device__ __forceinline__ void tg_tile_stats(const TrainGroupLds<SQ, HID> &L, int nr, int tid, double &S1, double &S2) {
     constexpr int S = 16 * SQ, LDX = 2 * S + 4;
     const int col = tid & (2 * S - 1), part_i = tid / (2 * S);
     constexpr int NG = TS_NT / (2 * S), RPG = 64 / NG;
@@ -211,8 +242,8 @@ __device__ __forceinline__ void tg_tile_stats(const TrainGroupLds<SQ> &L, int nr
 
 // S1 / S2 over `rows` rows -> the normalisation st_a (x - piv) + st_c of the current network, and the iteration's statistics slot `sl`
 // [2 in_dim].  Column tid < S is weight row off_state + tid, column S + kk weight row off_agg + kk.
-template <int SQ, class Form>
-__device__ __forceinline__ void tg_set_norm(const TrainGroupLds<SQ> &L, bool bn, double S1, double S2, int rows, int Sw, int off_state, int off_agg,
+template <int SQ, class Form, bool HID>
+__device__ __forceinline__ void tg_set_norm(const TrainGroupLds<SQ, HID> &L, bool bn, double S1, double S2, int rows, int Sw, int off_state, int off_agg,
                                             const float *gamma, const float *beta, float eps, float *sl, int in_dim, int tid) {
     constexpr int S = 16 * SQ;
     if (!Form::NORM_WITHOUT_BN && !bn) return;
@@ -235,9 +266,11 @@ __device__ __forceinline__ void tg_set_norm(const TrainGroupLds<SQ> &L, bool bn,
 // The dense update of the tile in Xs: (a (x - mean) + beta) . W + Cc on v_mfma_f32_16x16x4_f32 (operand layout of k_train_small_fwd),
 // activation, predicate; this lane's row (row 16 wave + c of the tile, `oin`: it is a row) goes back into the LDS state at row lrow of the
 // group - in place: it depends on the same row of the old state only.
-template <int SQ, class Form>
-__device__ __forceinline__ void tg_dense_tile(const TrainGroupLds<SQ> &L, float *St, const float (&wreg)[Form::template WREG<SQ> ? 2 * SQ : 1][4][SQ],
-                                              const TrainGroupCommon &a, int n0, int lrow, bool oin, bool bn, int act, int wave, int c, int g, int &any) {
+// HID: `act` is the hidden activation, h = act(..) with the columns at or past Hw zeroed, then act2(h . W2 + b2) from the block at L.W2s().
+template <int SQ, class Form, bool HID>
+__device__ __forceinline__ void tg_dense_tile(const TrainGroupLds<SQ, HID> &L, float *St, const float (&wreg)[Form::template WREG<SQ> ? 2 * SQ : 1][4][SQ],
+                                              const TrainGroupCommon &a, int n0, int lrow, bool oin, bool bn, int act, int wave, int c, int g, int &any,
+                                              int Hw = 0, int act2 = 0) {
     constexpr int S = 16 * SQ, LDX = 2 * S + 4, LDW = S + 4, LDS_ST = S + 4;
     constexpr bool WREG = Form::template WREG<SQ>;
     f32x4 acc[SQ];
@@ -263,13 +296,37 @@ __device__ __forceinline__ void tg_dense_tile(const TrainGroupLds<SQ> &L, float 
         }
     }
     asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");          // (MFMA results consumed behind a branch: see kernels_train_big.hpp)
+    if constexpr (HID) {
+        // lane (c, g) holds columns 16 qq + 4 g + e of row c of ITS wave - the B operand of k-step (qq, e): h goes from the accumulators
+        // into the second product as it is.  Columns at or past Hw are zeroed (act(0) != 0 for sigmoid / softplus), whatever W2's rows hold
+        const float *W2s = L.W2s(), *b2s = L.b2s();
+        f32x4 hv[SQ];
+#pragma unroll
+        for (int ct = 0; ct < SQ; ++ct) {
+            hv[ct] = acc[ct];
+            activate4(act, hv[ct]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) hv[ct][e] = 16 * ct + 4 * g + e < Hw ? hv[ct][e] : 0.0f;
+            acc[ct] = *reinterpret_cast<const f32x4 *>(b2s + 16 * ct + 4 * g);
+        }
+#pragma unroll
+        for (int qq = 0; qq < SQ; ++qq)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float *wr = W2s + (16 * qq + 4 * g + e) * LDW + c;
+#pragma unroll
+                for (int ct = 0; ct < SQ; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[16 * ct], hv[qq][e], acc[ct], 0, 0, 0);
+            }
+        asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
+    }
+    const int act_out = HID ? act2 : act;
     float d2 = 0.0f, n2 = 0.0f;
     const float *old_lds = L.Xs + (16 * wave + c) * LDX + 4 * g;
     float *new_lds = St + lrow * LDS_ST + 4 * g;
 #pragma unroll
     for (int ct = 0; ct < SQ; ++ct) {
         f32x4 v = acc[ct];
-        activate4(act, v);
+        activate4(act_out, v);
         const f32x4 o = *reinterpret_cast<const f32x4 *>(old_lds + 16 * ct);
 #pragma unroll
         for (int e = 0; e < 4; ++e) { v[e] = (oin && 16 * ct + 4 * g + e < a.Sw) ? v[e] : 0.0f; const float d = v[e] - o[e]; d2 = fmaf(d, d, d2); n2 = fmaf(o[e], o[e], n2); }
@@ -292,16 +349,19 @@ __device__ __forceinline__ void tg_epilogue(const TrainGroupCommon &a, const flo
     if (tid == 0) a.k_groups[gi] = bad ? -1.0f : (float)k_done;
 }
 
-template <int SQ, bool HAS_W>
-__global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd(TrainGroupFwd a) {
+// HID: the state network has a hidden layer (see the header comment); HID = false is the one-layer kernel, unchanged
+template <int SQ, bool HAS_W, bool HID = false>
+__global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd(std::conditional_t<HID, TrainGroupFwdH, TrainGroupFwd> a) {
     using Csr = TileCsr<SQ, HAS_W, true>;
     using Form = TrainGroupFormRange;
     constexpr int S = 16 * SQ, LPR = S / 4, NPP = Csr::NPP, NPASS = Csr::NPASS;
     constexpr int LDX = 2 * S + 4, LDW = S + 4, LDS_ST = S + 4;
     extern __shared__ __attribute__((aligned(16))) float tg_smem[];
-    const TrainGroupLds<SQ> L(tg_smem);
+    const TrainGroupLds<SQ, HID> L(tg_smem);
     float *Xs = L.Xs, *W0 = L.W0;
     float *St = L.rest();                 // [ng][LDS_ST] the group's state
+    int Hw = a.Sw, act2 = 0;              // width of the first layer's output (= the kernel's row length); HID: the state's activation
+    if constexpr (HID) { Hw = a.Hw; act2 = a.act2; }
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, g = lane >> 4;
@@ -315,7 +375,8 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd(TrainGroupFwd a) {
     const bool single = ntiles == 1;
     const bool bn = a.gamma != nullptr;
 
-    tg_load_weights<SQ>(W0, a.W, 0, a.off_agg, a.Sw, tid);
+    tg_load_weights<SQ>(W0, a.W, 0, a.off_agg, a.Sw, Hw, tid);
+    if constexpr (HID) tg_load_weights2<SQ>(L, a.W2, a.b2, a.Sw, Hw, tid);
     if (tid < 2 * S) { L.piv[tid] = 0.0f; L.st_a[tid] = 1.0f; L.st_c[tid] = 0.0f; }
     const bool run = tg_prologue<SQ>(a, St, n0, ng, tid);
 
@@ -379,7 +440,7 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd(TrainGroupFwd a) {
                 }
                 __syncthreads();
             }
-            tg_dense_tile<SQ, Form>(L, St, wreg, a, n0, r0 + 16 * wave + c, 16 * wave + c < nr, bn, a.act, wave, c, g, any);
+            tg_dense_tile<SQ, Form>(L, St, wreg, a, n0, r0 + 16 * wave + c, 16 * wave + c < nr, bn, a.act, wave, c, g, any, Hw, act2);
         }
         k_done = it + 1;
         if (!__syncthreads_or(any)) break;        // (also: the new state is complete before the next gather)

@@ -16,6 +16,8 @@
 //                               sums of pass 1: no gather ever sees a new row of the running iteration.
 // The weight block [2 S][S + 4] of the CURRENT type is (re)loaded from L2 when the walk moves to another type with rows in the group: one block
 // fits next to a 256-row state at width 64 (138 KB), eight do not.  A group whose rows are all of one type loads it once.
+// Hidden-layer form (HID; see kernels_train_group.hpp): every type's network is Dense(H_t) - Dense(S); H_t and both activations may differ
+// between the types.  The W2 / b2 block of the current type is reloaded together with its W0 block.
 // The tile body - statistics, normalisation, dense update - and the prologue / epilogue are the tg_* pieces of kernels_train_group.hpp in
 // this kernel's form (TrainGroupFormTypes); what is written here is the walk: which rows a tile holds and which network is current.
 #pragma once
@@ -35,6 +37,13 @@ struct GroupTypeNet {
     int act, d_t, in_dim, off_state, off_agg, off_comp;
     float *stats;                          // [G][K][2 in_dim]
 };
+// ... of the hidden-layer form: W is [in_dim][Hw], `act` the hidden activation
+struct GroupTypeNetH : GroupTypeNet {
+    int Hw;                                // hidden width, 1 .. the padded width
+    const float *W2, *b2;                  // second Dense: [Hw][Sw], [Sw]
+    int act2;                              // its activation (the state's)
+};
+struct GroupTypeWidths { int Hw[GNN_MAX_TYPES]; };      // row length of every type's first kernel = the real columns of its rows of Cc
 struct TrainGroupConstTypes {
     int n_types, G, S, Sw, K, W_comp;
     const int *tbeg, *type_nodes;
@@ -44,7 +53,7 @@ struct TrainGroupConstTypes {
     GroupTypeNet net[GNN_MAX_TYPES];
 };
 
-__global__ void __launch_bounds__(256) k_train_group_const_types(TrainGroupConstTypes a) {
+__global__ void __launch_bounds__(256) k_train_group_const_types(TrainGroupConstTypes a, GroupTypeWidths hw) {
     __shared__ float red[4][65];
     __shared__ float mu[64], ak[64], ck[64];
     __shared__ int wr[64];
@@ -56,6 +65,7 @@ __global__ void __launch_bounds__(256) k_train_group_const_types(TrainGroupConst
         const GroupTypeNet &n = a.net[t];
         const int *rows = a.type_nodes + p0;
         const int Kc = n.d_t + a.W_comp;   // <= GROUP_TYPES_MAX_KC (the host checked)
+        const int Hw = hw.Hw[t];
         // this thread's constant column: the type's labels first, then the aggregated component
         const bool lab = col < n.d_t, has = col < Kc;
         const float *xp = has ? (lab ? a.nodes + col : a.agg_comp + (col - n.d_t)) : nullptr;
@@ -87,11 +97,11 @@ __global__ void __launch_bounds__(256) k_train_group_const_types(TrainGroupConst
         for (int i = tid; i < nt * a.S; i += 256) {
             const int h = i % a.S, node = rows[i / a.S];
             float acc = 0.0f;
-            if (h < a.Sw) {
+            if (h < Hw) {
                 acc = n.b[h];
                 for (int c = 0; c < Kc; ++c) {
                     const float xv = c < n.d_t ? a.nodes[(size_t)node * a.ld_nodes + c] : a.agg_comp[(size_t)node * a.W_comp + (c - n.d_t)];
-                    acc = fmaf(fmaf(xv - mu[c], ak[c], ck[c]), n.W[(size_t)wr[c] * a.Sw + h], acc);
+                    acc = fmaf(fmaf(xv - mu[c], ak[c], ck[c]), n.W[(size_t)wr[c] * Hw + h], acc);
                 }
             }
             a.Cc[(size_t)node * a.S + h] = acc;
@@ -100,24 +110,28 @@ __global__ void __launch_bounds__(256) k_train_group_const_types(TrainGroupConst
 }
 
 // ---- the loop -------------------------------------------------------------------------------------------------------------------------------
-struct TrainGroupFwdTypes : TrainGroupCommon {
+template <class Net>
+struct TrainGroupFwdTypesOf : TrainGroupCommon {
     int n_types, G;
     const int *tbeg;             // DEVICE [n_types][G + 1] positions in type_nodes
     const int *type_nodes;       // DEVICE node ids per type, ascending
-    GroupTypeNet net[GNN_MAX_TYPES];
+    Net net[GNN_MAX_TYPES];
 };
+using TrainGroupFwdTypes = TrainGroupFwdTypesOf<GroupTypeNet>;
+using TrainGroupFwdTypesH = TrainGroupFwdTypesOf<GroupTypeNetH>;       // the hidden-layer form (the HID instantiations)
 
-template <int SQ>
-inline size_t train_group_fwd_types_lds(int rows) { return train_group_fwd_lds<SQ>(rows) + 64 * sizeof(int); }
+template <int SQ, bool HID = false>
+inline size_t train_group_fwd_types_lds(int rows) { return train_group_fwd_lds<SQ, HID>(rows) + 64 * sizeof(int); }
 
-template <int SQ, bool HAS_W>
-__global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd_types(TrainGroupFwdTypes a) {
+// HID: every state network has a hidden layer (see the header comment); HID = false is the one-layer kernel, unchanged
+template <int SQ, bool HAS_W, bool HID = false>
+__global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd_types(std::conditional_t<HID, TrainGroupFwdTypesH, TrainGroupFwdTypes> a) {
     using Csr = TileCsr<SQ, HAS_W, true>;
     using Form = TrainGroupFormTypes;
     constexpr int S = 16 * SQ, LPR = S / 4, NPP = Csr::NPP, NPASS = Csr::NPASS;
     constexpr int LDX = 2 * S + 4, LDS_ST = S + 4;
     extern __shared__ __attribute__((aligned(16))) float tgt_smem[];
-    const TrainGroupLds<SQ> L(tgt_smem);  // (Xs: rows of ONE type; W0: the current type's weight rows)
+    const TrainGroupLds<SQ, HID> L(tgt_smem);  // (Xs: rows of ONE type; W0: the current type's weight rows)
     float *Xs = L.Xs;
     int *rid = reinterpret_cast<int *>(L.rest());         // [64] the tile's rows inside the group
     float *St = L.rest() + 64;            // [ng][LDS_ST] the group's state, by node
@@ -160,7 +174,9 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd_types(TrainGroupFw
         for (int ty = 0; ty < a.n_types; ++ty) {
             const int p0 = a.tbeg[ty * (a.G + 1) + gi], nt = a.tbeg[ty * (a.G + 1) + gi + 1] - p0;
             if (nt < 1) continue;         // (uniform: no row of this type in the group - its network is skipped, its statistics stay)
-            const GroupTypeNet &net = a.net[ty];
+            const auto &net = a.net[ty];
+            int Hw = a.Sw, act2 = 0;      // width of the first layer's output (= the kernel's row length); HID: the state's activation
+            if constexpr (HID) { Hw = net.Hw; act2 = net.act2; }
             const int *rows = a.type_nodes + p0;
             const int ntl = (nt + 63) / 64;
             const bool bn = net.gamma != nullptr;
@@ -168,7 +184,8 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd_types(TrainGroupFw
             // which is all one workgroup's own stores and loads need (one CU, one vector L1); it also retires the previous type's Xs / W0 reads
             __syncthreads();
             if (loaded != ty) {
-                tg_load_weights<SQ>(L.W0, net.W, net.off_state, net.off_agg, a.Sw, tid);
+                tg_load_weights<SQ>(L.W0, net.W, net.off_state, net.off_agg, a.Sw, Hw, tid);
+                if constexpr (HID) tg_load_weights2<SQ>(L, net.W2, net.b2, a.Sw, Hw, tid);
                 loaded = ty;
             }
             auto load_tile = [&](int r0, int nr) {
@@ -204,7 +221,7 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_group_fwd_types(TrainGroupFw
                     load_tile(r0, nr);
                     __syncthreads();
                 }
-                tg_dense_tile<SQ, Form>(L, St, no_wreg, a, n0, rid[16 * wave + c], 16 * wave + c < nr, bn, net.act, wave, c, g, any);
+                tg_dense_tile<SQ, Form>(L, St, no_wreg, a, n0, rid[16 * wave + c], 16 * wave + c < nr, bn, net.act, wave, c, g, any, Hw, act2);
             }
         }
         k_done = it + 1;

@@ -99,15 +99,30 @@ void fill_train_group_common(gnn::TrainGroupCommon &fa, const gnn_train_args_t &
 
 // One launcher for both forward kernels.  A kernel family F names its argument struct, its instantiations and their LDS:
 //     using Args; template <int SQ, bool HAS_W> static constexpr void (*fn)(Args); template <int SQ> static size_t lds(int rows)
+//     static constexpr int MAX_SQ: the widest instantiation the family has (the hidden-layer forms stop at padded width 32)
 struct TrainGroupKernel {
     using Args = gnn::TrainGroupFwd;
+    static constexpr int MAX_SQ = 4;
     template <int SQ, bool HAS_W> static constexpr void (*fn)(Args) = gnn::k_train_group_fwd<SQ, HAS_W>;
     template <int SQ> static size_t lds(int rows) { return gnn::train_group_fwd_lds<SQ>(rows); }
 };
 struct TrainGroupTypesKernel {
     using Args = gnn::TrainGroupFwdTypes;
+    static constexpr int MAX_SQ = 4;
     template <int SQ, bool HAS_W> static constexpr void (*fn)(Args) = gnn::k_train_group_fwd_types<SQ, HAS_W>;
     template <int SQ> static size_t lds(int rows) { return gnn::train_group_fwd_types_lds<SQ>(rows); }
+};
+struct TrainGroupKernelH {
+    using Args = gnn::TrainGroupFwdH;
+    static constexpr int MAX_SQ = 2;
+    template <int SQ, bool HAS_W> static constexpr void (*fn)(Args) = gnn::k_train_group_fwd<SQ, HAS_W, true>;
+    template <int SQ> static size_t lds(int rows) { return gnn::train_group_fwd_lds<SQ, true>(rows); }
+};
+struct TrainGroupTypesKernelH {
+    using Args = gnn::TrainGroupFwdTypesH;
+    static constexpr int MAX_SQ = 2;
+    template <int SQ, bool HAS_W> static constexpr void (*fn)(Args) = gnn::k_train_group_fwd_types<SQ, HAS_W, true>;
+    template <int SQ> static size_t lds(int rows) { return gnn::train_group_fwd_types_lds<SQ, true>(rows); }
 };
 
 template <class F, int SQ, bool HAS_W>
@@ -134,7 +149,9 @@ int launch_train_group_fwd(const typename F::Args &fa, int G, int max_nodes, hip
     switch (fa.S) {
         case 16: return has_w ? launch_train_group_fwd_one<F, 1, true>(fa, G, max_nodes, st) : launch_train_group_fwd_one<F, 1, false>(fa, G, max_nodes, st);
         case 32: return has_w ? launch_train_group_fwd_one<F, 2, true>(fa, G, max_nodes, st) : launch_train_group_fwd_one<F, 2, false>(fa, G, max_nodes, st);
-        default: return has_w ? launch_train_group_fwd_one<F, 4, true>(fa, G, max_nodes, st) : launch_train_group_fwd_one<F, 4, false>(fa, G, max_nodes, st);
+        default:
+            if constexpr (F::MAX_SQ >= 4) return has_w ? launch_train_group_fwd_one<F, 4, true>(fa, G, max_nodes, st) : launch_train_group_fwd_one<F, 4, false>(fa, G, max_nodes, st);
+            else return fail("grouped forward: no kernel of padded width %d in this form", fa.S);       // (the coverage rule refuses the width first)
     }
 }
 
@@ -204,6 +221,15 @@ struct GroupPlan {
     size_t bytes;
 };
 
+// The hidden-layer form of the grouped forward kernels (opt-in: GNN_FLAG_TRAIN_GROUPS_HIDDEN; both model kinds, every type's network on its
+// own): what hidden_dense_of_state_width() (train_loop.hpp) accepts - Dense(H) - Dense(S), 1 <= H <= the padded state width `SPs`, neither
+// activation softmax, padded width 16 or 32.  At 64 the one-layer instantiations already hold 256 VGPRs and up to 209 AGPRs, and a W2 block
+// [64][68] with its bias next to a 256-row state would take the workgroup's LDS to 157 KB of 160 KB: that width is refused.  (A state network
+// with Dropout is refused by the callers, as in the one-layer rule.)
+inline bool train_groups_hidden_net(const gnn_train_args_t &ta, const gnn_mlp_t &m, int S, int SPs) {
+    return (ta.loop.flags & GNN_FLAG_TRAIN_GROUPS_HIDDEN) != 0 && hidden_dense_of_state_width(m, S, SPs);
+}
+
 // what the grouped kernels cover (dims and network descriptions only)
 bool train_groups_covered(const gnn_train_args_t &ta, const TrainPlan &p) {
     const gnn_loop_args_t &a = ta.loop;
@@ -211,7 +237,8 @@ bool train_groups_covered(const gnn_train_args_t &ta, const TrainPlan &p) {
     if (a.composite || a.n_types > 1) return false;
     if (ta.drop_state[0].n > 0 || ta.drop_output.n > 0) return false;
     if (a.focus != GNN_FOCUS_NODE && a.focus != GNN_FOCUS_ARC) return false;
-    if (ns.n_layers != 1 || ns.units[0] != p.S || p.S > 64 || p.Kc > 32 || ns.activation[0] == GNN_ACT_SOFTMAX || p.K < 1) return false;
+    if (!train_groups_hidden_net(ta, ns, p.S, p.SPs) && (ns.n_layers != 1 || ns.units[0] != p.S || ns.activation[0] == GNN_ACT_SOFTMAX)) return false;
+    if (p.S > 64 || p.Kc > 32 || p.K < 1) return false;
     if (no.n_layers != 1 || no.units[0] > gnn::GROUP_HEAD_MAX_UNITS || no.in_dim > gnn::GROUP_HEAD_MAX_IN) return false;
     return true;
 }
@@ -258,9 +285,10 @@ int train_forward_groups(const gnn_train_args_t &ta) {
     TRY(check_mlp(ns, "net_state", true));
     TRY(check_mlp(a.net_output, "net_output", true));
     const bool bn_s = ns.has_bn != 0;
+    const bool hidden = train_groups_hidden_net(ta, ns, p.S, p.SPs);
     hipStream_t st = (hipStream_t)a.stream;
     const int G = gp.G;
-    GNN_SET_KERNEL_NAME("train_step: grouped forward kernels");
+    GNN_SET_KERNEL_NAME(hidden ? "train_step: grouped forward kernels (hidden)" : "train_step: grouped forward kernels");
 
     TRY(upload_group_tables(ta, gp.gbeg, gp.obeg, st));
     // aggregates of the constants over the merged graph (block-diagonal: a row sees its own group only)
@@ -275,15 +303,18 @@ int train_forward_groups(const gnn_train_args_t &ta) {
         cs.ptr[1] = gp.agg_nodes; cs.ld[1] = p.L;
         cs.ptr[2] = gp.agg_arcs; cs.ld[2] = p.A;
     } else { cs.ptr[0] = gp.agg_arcs; cs.ld[0] = p.A; }
-    gnn::k_train_group_const<<<G, 256, 0, st>>>(gp.gbeg, p.SPs, p.S, cs, ns.kernel[0], ns.bias[0], bn_s ? ns.bn_gamma : nullptr, ns.bn_beta, ns.bn_eps,
+    gnn::k_train_group_const<<<G, 256, 0, st>>>(gp.gbeg, p.SPs, ns.units[0], cs, ns.kernel[0], ns.bias[0], bn_s ? ns.bn_gamma : nullptr, ns.bn_beta, ns.bn_eps,
                                                 gp.cc, gp.stats_s, p.K, p.in_s);
     LAUNCH_OK();
-    gnn::TrainGroupFwd fa;
+    gnn::TrainGroupFwdH fa;             // (the one-layer kernels take its base)
     memset(&fa, 0, sizeof(fa));
     fill_train_group_common(fa, ta, p.SPs, p.S, p.K, gp.gbeg, gp.agg, gp.cc);
     fa.stats = gp.stats_s; fa.in_s = p.in_s; fa.off_agg = p.off_agg;
     fa.W = ns.kernel[0]; fa.gamma = bn_s ? ns.bn_gamma : nullptr; fa.beta = ns.bn_beta; fa.eps = ns.bn_eps; fa.act = ns.activation[0];
-    TRY(launch_train_group_fwd<TrainGroupKernel>(fa, G, gp.max_nodes, st));
+    if (hidden) {
+        fa.Hw = ns.units[0]; fa.W2 = ns.kernel[1]; fa.b2 = ns.bias[1]; fa.act2 = ns.activation[1];
+        TRY(launch_train_group_fwd<TrainGroupKernelH>(fa, G, gp.max_nodes, st));
+    } else TRY(launch_train_group_fwd<TrainGroupKernel>(static_cast<const gnn::TrainGroupFwd &>(fa), G, gp.max_nodes, st));
     if (bn_s) {
         gnn::k_bn_moving_groups<<<cdiv(p.in_s, 64), 64, 0, st>>>(gp.stats_s, p.K, p.in_s, ta.k_groups, nullptr, G, const_cast<float *>(ns.bn_mean),
                                                                 const_cast<float *>(ns.bn_var), ta.bn_momentum);
@@ -304,17 +335,19 @@ struct GroupTypesPlan {
 };
 
 // what the *_types kernels cover (dims and network descriptions only).  BatchNormalization may differ between the types: every (group, type)
-// is normalised on its own.
+// is normalised on its own.  Hidden-layer form: every type's network train_groups_hidden_net() accepts (H and the activations may differ
+// between the types); a model that mixes one-layer and two-layer networks is not covered.
 bool train_groups_types_covered(const gnn_train_args_t &ta, const CPlan &p) {
     const gnn_loop_args_t &a = ta.loop;
     const gnn_mlp_t &no = a.net_output;
     if (!a.composite || p.n_types < 1 || p.n_types > GNN_MAX_TYPES) return false;
     if (a.focus != GNN_FOCUS_NODE && a.focus != GNN_FOCUS_ARC) return false;
     if (p.S > 64 || p.K < 1 || ta.drop_output.n > 0) return false;
+    const bool hidden = train_groups_hidden_net(ta, a.net_state[0], p.S, p.SPs);
     for (int t = 0; t < p.n_types; ++t) {
         const gnn_mlp_t &ns = a.net_state[t];
         if (ta.drop_state[t].n > 0) return false;
-        if (ns.n_layers != 1 || ns.units[0] != p.S || ns.activation[0] == GNN_ACT_SOFTMAX) return false;
+        if (hidden ? !train_groups_hidden_net(ta, ns, p.S, p.SPs) : (ns.n_layers != 1 || ns.units[0] != p.S || ns.activation[0] == GNN_ACT_SOFTMAX)) return false;
         if (a.type_dim_label[t] + p.W_comp > gnn::GROUP_TYPES_MAX_KC) return false;
     }
     if (no.n_layers != 1 || no.units[0] > gnn::GROUP_HEAD_MAX_UNITS || no.in_dim > gnn::GROUP_HEAD_MAX_IN) return false;
@@ -361,7 +394,8 @@ int train_forward_groups_types(const gnn_train_args_t &ta) {
     TRY(check_mlp(a.net_output, "net_output", true));
     hipStream_t st = (hipStream_t)a.stream;
     const int G = gp.G, SPs = gp.SPs;
-    GNN_SET_KERNEL_NAME("train_step: grouped forward kernels (types)");
+    const bool hidden = train_groups_hidden_net(ta, a.net_state[0], p.S, p.SPs);      // (the rule: then every type's network is)
+    GNN_SET_KERNEL_NAME(hidden ? "train_step: grouped forward kernels (types, hidden)" : "train_step: grouped forward kernels (types)");
 
     TRY(upload_group_tables(ta, gp.gbeg, gp.obeg, st));
     // the rows of every type per group: groups are contiguous node ranges, a type's row list ascends
@@ -382,8 +416,10 @@ int train_forward_groups_types(const gnn_train_args_t &ta) {
         if (p.A > 0) TRY(launch_aggregate(nullptr, a.arcnode, a.arc_labels, a.ld_arcs, p.A, gp.agg_comp + col, p.W_comp, st));
     }
     gnn::TrainGroupConstTypes ca;
+    gnn::GroupTypeWidths hw;
     gnn::TrainGroupFwdTypes fa;
-    memset(&ca, 0, sizeof(ca)); memset(&fa, 0, sizeof(fa));
+    gnn::TrainGroupFwdTypesH fh;
+    memset(&ca, 0, sizeof(ca)); memset(&hw, 0, sizeof(hw)); memset(&fa, 0, sizeof(fa)); memset(&fh, 0, sizeof(fh));
     for (int t = 0; t < p.n_types; ++t) {
         const CType &y = p.ty[t];
         const gnn_mlp_t &ns = a.net_state[t];
@@ -391,15 +427,27 @@ int train_forward_groups_types(const gnn_train_args_t &ta) {
         n.W = ns.kernel[0]; n.b = ns.bias[0]; n.gamma = ns.has_bn ? ns.bn_gamma : nullptr; n.beta = ns.bn_beta; n.eps = ns.bn_eps;
         n.act = ns.activation[0]; n.d_t = y.d_t; n.in_dim = y.in_dim; n.off_state = y.off_state; n.off_agg = y.off_agg; n.off_comp = y.off_comp;
         n.stats = gp.stats_t[t];
+        hw.Hw[t] = ns.units[0];
         fa.net[t] = n;
+        if (hidden) {
+            gnn::GroupTypeNetH &h = fh.net[t];
+            static_cast<gnn::GroupTypeNet &>(h) = n;
+            h.Hw = ns.units[0]; h.W2 = ns.kernel[1]; h.b2 = ns.bias[1]; h.act2 = ns.activation[1];
+        }
     }
     ca.n_types = p.n_types; ca.G = G; ca.S = SPs; ca.Sw = p.S; ca.K = p.K; ca.W_comp = p.W_comp;
     ca.tbeg = gp.tbeg; ca.type_nodes = a.type_nodes; ca.nodes = a.nodes; ca.ld_nodes = a.ld_nodes; ca.agg_comp = gp.agg_comp; ca.Cc = gp.cc;
-    gnn::k_train_group_const_types<<<G, 256, 0, st>>>(ca);
+    gnn::k_train_group_const_types<<<G, 256, 0, st>>>(ca, hw);
     LAUNCH_OK();
-    fill_train_group_common(fa, ta, SPs, p.S, p.K, gp.gbeg, gp.agg, gp.cc);
-    fa.n_types = p.n_types; fa.G = G; fa.tbeg = gp.tbeg; fa.type_nodes = a.type_nodes;
-    TRY(launch_train_group_fwd<TrainGroupTypesKernel>(fa, G, gp.max_nodes, st));
+    if (hidden) {
+        fill_train_group_common(fh, ta, SPs, p.S, p.K, gp.gbeg, gp.agg, gp.cc);
+        fh.n_types = p.n_types; fh.G = G; fh.tbeg = gp.tbeg; fh.type_nodes = a.type_nodes;
+        TRY(launch_train_group_fwd<TrainGroupTypesKernelH>(fh, G, gp.max_nodes, st));
+    } else {
+        fill_train_group_common(fa, ta, SPs, p.S, p.K, gp.gbeg, gp.agg, gp.cc);
+        fa.n_types = p.n_types; fa.G = G; fa.tbeg = gp.tbeg; fa.type_nodes = a.type_nodes;
+        TRY(launch_train_group_fwd<TrainGroupTypesKernel>(fa, G, gp.max_nodes, st));
+    }
     // the moving statistics of network t: k_g steps for every group with rows of type t, group after group
     for (int t = 0; t < p.n_types; ++t) {
         const gnn_mlp_t &ns = a.net_state[t];

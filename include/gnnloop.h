@@ -75,7 +75,15 @@ enum gnn_flags {
      * state width (16 / 32), neither activation is softmax, every node type has two layers (H and both activations may differ per
      * type) and every condition of the one-layer form holds; group sets included.  Every other shape - and every shape without the
      * flag - routes, refuses and computes as before: a homogeneous model on the spread form (answer 1), a composite model refused. */
-    GNN_FLAG_LDS_HIDDEN = 1 << 9
+    GNN_FLAG_LDS_HIDDEN = 1 << 9,
+    /* Grouped training-mode forwards only (gnn_train_step(forward_only) with convergence groups, gnn_train_groups_supported; read from
+     * gnn_train_args_t::loop.flags; everything else ignores it).  Opt-in: a model whose state network(s) are Dense(H) - Dense(state
+     * width) runs the grouped forward kernels in their hidden-layer form (gnn_train_groups_supported() == 0, gnn_last_kernel_name()
+     * "train_step: grouped forward kernels (hidden)" / "... (types, hidden)") when 1 <= H <= the padded state width (16 / 32: state
+     * width <= 32), neither activation is softmax, there is no Dropout, every node type of a composite model has two layers (H and
+     * both activations may differ per type) and every other condition of the one-layer form holds.  Every other shape - and every
+     * shape without the flag - is answered, refused and computed as before.  The workspace does not depend on the flag. */
+    GNN_FLAG_TRAIN_GROUPS_HIDDEN = 1 << 10
 };
 
 /* A sparse operator A (n_src x n_dst, COO in the reference: tf.SparseTensor) stored as the CSR of its transpose:
@@ -674,7 +682,11 @@ int gnn_train_xc_applies(const gnn_train_args_t *args);
  *   GNN_TRAIN_GROUPS_UNCOVERED (-1)   the shape is not covered: anything but a homogeneous model with a one-layer state network of
  *                                     units == state width <= 64, <= 32 constant input columns, no softmax state activation, no Dropout,
  *                                     max_iteration >= 1, node / arc focus, and a one-layer output network of <= 64 units over <= 256
- *                                     input columns without Dropout (BatchNormalization or not in both)
+ *                                     input columns without Dropout (BatchNormalization or not in both); composite models: 1 .. 8 node
+ *                                     types, every type's network of that kind, <= 64 constant input columns per type.  With
+ *                                     GNN_FLAG_TRAIN_GROUPS_HIDDEN in loop.flags also: state network(s) Dense(H) - Dense(state width),
+ *                                     1 <= H <= the padded state width (16 / 32: state width <= 32), no softmax in either layer, every
+ *                                     type of a composite model two-layered (a mix of one- and two-layer networks is not covered)
  *   GNN_TRAIN_GROUPS_MALFORMED (-2)   the group arrays are missing or do not span [0, n_nodes] / [0, n_out] in ascending order
  *   g + 1 > 0                         group g (the first such) has more than GNN_TRAIN_GROUP_MAX_NODES nodes: run that graph by a plain
  *                                     forward_only call between two grouped calls (the order of the moving-statistics updates holds) */
