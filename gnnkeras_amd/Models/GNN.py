@@ -607,10 +607,12 @@ class GNNnodeBased(_LoopModel):
         self.state_vect_dim = int(state_vect_dim)
         self.max_iteration = int(max_iteration)
         self.state_threshold = state_threshold
-        self.native_flags = 0          # OR of _native.FLAG_* (tests use FLAG_UNFUSED).  The two opt-in bits the training side reads, independent
-                                       # of each other, for a state network Dense(H) - Dense(state width): FLAG_TRAIN_HIDDEN_SMALL - it trains on
+        self.native_flags = 0          # OR of _native.FLAG_* (tests use FLAG_UNFUSED).  The opt-in bits the training side reads, independent
+                                       # of each other.  For a state network Dense(H) - Dense(state width): FLAG_TRAIN_HIDDEN_SMALL - it trains on
                                        # the persistent small-graph kernels; FLAG_TRAIN_GROUPS_HIDDEN - its training-mode convergence groups
-                                       # (Loop(training=True, groups=...), serial_propagation='grouped') run the grouped kernels' hidden form
+                                       # (Loop(training=True, groups=...), serial_propagation='grouped') run the grouped kernels' hidden form.
+                                       # For a state network with Dropout / AlphaDropout behind its Dense layers: FLAG_TRAIN_DROPOUT_SMALL - it
+                                       # keeps the persistent small-graph kernels (with FLAG_TRAIN_HIDDEN_SMALL as well when it has a hidden layer)
         self.loop_events = None        # optional (begin, end) torch.cuda.Event pair recorded around the iterations
         self._engine_init()
 

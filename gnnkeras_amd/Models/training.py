@@ -294,9 +294,10 @@ def _mix32(*values):
 
 
 def _train_flags(model):
-    """What a training step takes of `model.native_flags`: the opt-in bits of the hidden-layer persistent kernels and of the hidden-layer
-    grouped forward (independent of each other) alone - the other bits steer the inference loop and keep having no effect on a step."""
-    return int(getattr(model, 'native_flags', 0)) & (nat.FLAG_TRAIN_HIDDEN_SMALL | nat.FLAG_TRAIN_GROUPS_HIDDEN)
+    """What a training step takes of `model.native_flags`: the opt-in bits of the hidden-layer persistent kernels, of their Dropout form and
+    of the hidden-layer grouped forward (independent of each other) alone - the other bits steer the inference loop and keep having no
+    effect on a step."""
+    return int(getattr(model, 'native_flags', 0)) & (nat.FLAG_TRAIN_HIDDEN_SMALL | nat.FLAG_TRAIN_GROUPS_HIDDEN | nat.FLAG_TRAIN_DROPOUT_SMALL)
 
 
 class LoopTrainer:

@@ -47,6 +47,20 @@
 // 16, the hidden row pieces) do not fit beside the one-layer kernel's (it is at 256 + 213 .. 256 registers already): the LOCAL form spilled
 // 400 .. 620 bytes per lane to scratch, so the rule refuses that width.  The one-layer instantiations (HID = false) are the kernels they
 // were: the hidden form's arguments travel in derived structs (TrainSmallFwdH / TrainSmallBwdH), read under `if constexpr`.
+//
+// Dropout form (template parameter DROP; opt-in through GNN_FLAG_TRAIN_DROPOUT_SMALL, homogeneous models, padded widths 16 / 32; the rule is
+// dropout_small_form() in train_loop.hpp): at most one Dropout / AlphaDropout layer behind each Dense of the state network.  The mask is the
+// stateless hash dropout_keep(key, GLOBAL node row, real column) of the general path (k_dropout) and the key of iteration t the arithmetic of
+// drop_key() in train_loop.hpp, so a tile regenerates every mask it needs - in the forward and in the backward launch - from a few scalars
+// (SmallDrop): no barrier, no exchange, no slot and no LDS beyond what the form has.
+//   between the two Dense layers (hidden form)   forward: h goes to the tape UN-dropped, then is dropped in registers in front of the second
+//              product (pad columns / rows zeroed AFTER it: AlphaDropout fills with a non-zero value).  backward: the hidden rows are staged
+//              twice - drop(h) where h was (P2 += drop(h)^T dZ2), h itself in the rows of Zs that dZ1 overwrites a moment later - and dH passes
+//              the mask in front of act1'(h).
+//   behind the last Dense    the new state IS the dropped-out output (LDS, states[t + 1], statistics, aggregate and predicate of the next
+//              iteration); the un-dropped activation output goes to one more tape array (`ypre`, [K][N][S]) that the backward launch reads
+//              for act'(.): dividing it back out of the state would move activation kinks under AlphaDropout and is not what the forward used.
+// The DROP = false instantiations are the kernels they were: the Dropout arguments travel in a derived struct (TrainSmallDrop<..>).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -340,12 +354,30 @@ struct TrainSmallFwdH : TrainSmallFwd {
 template <bool HID, typename A> __device__ __forceinline__ int first_layer_width(const A &a) { if constexpr (HID) return a.Hw; else return a.Sw; }
 template <bool HID, typename A> __device__ __forceinline__ int state_activation(const A &a, int act) { if constexpr (HID) return a.act2; else return act; }
 
+// ---- Dropout layers of the state network (the DROP instantiations) ------------------------------------------------------------------------------
+// slot 0: the layer between the two Dense layers of the hidden form; slot 1: the layer behind the last Dense.  thr / mul / add / fill as gnn_dropout()
+// derives them (forward: y = keep ? x mul + add : fill; backward: dx = keep ? dy mul : 0); `index` = the layer's index among the network's Dropout layers.
+struct SmallDrop {
+    unsigned seed, net_id;       // the step's seed, the network's id: with the iteration and `index` they make the key (drop_key, train_loop.hpp)
+    int on[2];
+    unsigned index[2], thr[2];
+    float mul[2], add[2], fill[2];
+    float *ypre;                 // [K][N][S] slot 1: the un-dropped output of the last Dense's activation, kept for the backward pass (pad columns zero)
+};
+template <typename Base> struct TrainSmallDrop : Base { SmallDrop dr; };
+template <bool DROP, typename Base> using train_small_args = std::conditional_t<DROP, TrainSmallDrop<Base>, Base>;
+// key of iteration t: h = 0x9E3779B9, then h = lowbias32(h ^ v) over (seed, net_id, t, index) - `base` is the state behind (seed, net_id)
+__device__ __forceinline__ unsigned small_drop_base(const SmallDrop &d) { return lowbias32(lowbias32(0x9E3779B9u ^ d.seed) ^ d.net_id); }
+__device__ __forceinline__ unsigned small_drop_key(unsigned base, int t, unsigned index) { return lowbias32(lowbias32(base ^ (unsigned)t) ^ index); }
+template <bool DROP, typename A> __device__ __forceinline__ bool small_drop_on(const A &a, int slot) { if constexpr (DROP) return a.dr.on[slot] != 0; else return false; }
+
 template <int SQ, bool HID = false>
 constexpr int train_small_fwd_floats() { return 64 * (2 * 16 * SQ + 4) + (2 * 16 * SQ) * (16 * SQ + 4) + 3 * 2 * 16 * SQ + 512 + (HID ? 16 * SQ * (16 * SQ + 4) + 16 * SQ : 0); }
 
 // HID: the state network has a hidden layer (see the header comment); HID = false is the one-layer kernel, unchanged
-template <int SQ, bool HAS_W, bool LOCAL, bool HID = false>
-__global__ void __launch_bounds__(TS_NT, 1) k_train_small_fwd(std::conditional_t<HID, TrainSmallFwdH, TrainSmallFwd> a, TileTab tt, TypeTab yt) {
+// DROP: Dropout layers behind its Dense layers (see the header comment); DROP = false are the kernels without, unchanged
+template <int SQ, bool HAS_W, bool LOCAL, bool HID = false, bool DROP = false>
+__global__ void __launch_bounds__(TS_NT, 1) k_train_small_fwd(train_small_args<DROP, std::conditional_t<HID, TrainSmallFwdH, TrainSmallFwd>> a, TileTab tt, TypeTab yt) {
     using Csr = TileCsr<SQ, HAS_W, LOCAL>;
     constexpr int S = 16 * SQ, NPP = Csr::NPP, NPASS = Csr::NPASS;
     constexpr int LDX = 2 * S + 4;        // row stride of the [own | agg] tile: == 4 (mod 32) dwords, 16-B chunks conflict-free
@@ -425,6 +457,8 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_fwd(std::conditional_t
                 for (int ct = 0; ct < SQ; ++ct) wreg[WREG ? qq : 0][e][ct] = W0[(16 * qq + 4 * g + e) * LDW + c + 16 * ct];
     }
     int k_done = 0, any_prev = 0;
+    unsigned drop_base = 0u;
+    if constexpr (DROP) drop_base = small_drop_base(a.dr);
     TS_CLOCK();
     for (int it = 0; run && it < a.K; ++it) {
         const __amdgpu_buffer_rsrc_t r_in = buf_rsrc(a.states + (size_t)it * NS), r_out = buf_rsrc(a.states + (size_t)(it + 1) * NS);
@@ -536,6 +570,19 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_fwd(std::conditional_t
                 if (oin) *reinterpret_cast<f32x4 *>(a.hid + (size_t)it * NS + (size_t)orow * S + 16 * ct + 4 * g) = hv[ct];
                 acc[ct] = *reinterpret_cast<const f32x4 *>(b2s + 16 * ct + 4 * g);
             }
+            if constexpr (DROP) {
+                if (a.dr.on[0]) {     // Dropout between the two Dense layers: in registers (the tape keeps h); pads zeroed behind it (AlphaDropout's fill)
+                    const unsigned key = small_drop_key(drop_base, it, a.dr.index[0]);
+#pragma unroll
+                    for (int ct = 0; ct < SQ; ++ct)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const int col = 16 * ct + 4 * g + e;
+                            const float x = dropout_keep(key, (unsigned)orow, (unsigned)col, a.dr.thr[0]) ? fmaf(hv[ct][e], a.dr.mul[0], a.dr.add[0]) : a.dr.fill[0];
+                            hv[ct][e] = (oin && col < Hw) ? x : 0.0f;
+                        }
+                }
+            }
 #pragma unroll
             for (int qq = 0; qq < SQ; ++qq)
 #pragma unroll
@@ -554,6 +601,17 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_fwd(std::conditional_t
             f32x4 v = acc[ct];
             activate4(act_out, v);
             const f32x4 o = *reinterpret_cast<const f32x4 *>(orow_lds + 16 * ct);
+            if constexpr (DROP) {
+                if (a.dr.on[1]) {     // Dropout behind the last Dense: the un-dropped output -> the tape, the dropped-out one IS the new state
+                    const unsigned key = small_drop_key(drop_base, it, a.dr.index[1]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = (oin && 16 * ct + 4 * g + e < a.Sw) ? v[e] : 0.0f;
+                    if (oin) *reinterpret_cast<f32x4 *>(a.dr.ypre + (size_t)it * NS + (size_t)orow * S + 16 * ct + 4 * g) = v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        v[e] = dropout_keep(key, (unsigned)orow, (unsigned)(16 * ct + 4 * g + e), a.dr.thr[1]) ? fmaf(v[e], a.dr.mul[1], a.dr.add[1]) : a.dr.fill[1];
+                }
+            }
 #pragma unroll
             for (int e = 0; e < 4; ++e) { v[e] = (oin && 16 * ct + 4 * g + e < a.Sw) ? v[e] : 0.0f; const float d = v[e] - o[e]; d2 = fmaf(d, d, d2); n2 = fmaf(o[e], o[e], n2); }
             if (LOCAL) {                  // (this wave's rows: no other wave reads them before the barrier below)
@@ -629,8 +687,9 @@ constexpr int train_small_bwd_floats(bool da) {       // `da`: the [64][S + 4] t
 
 // LAB: the instantiation that also stores sum_t dZ_t / d loss / d state_0 (label gradients); LAB = false is the kernel without them
 // HID: the state network has a hidden layer (see the header comment); HID = false is the one-layer kernel, unchanged
-template <int SQ, bool HAS_W, bool LOCAL, bool LAB = false, bool HID = false>
-__global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(std::conditional_t<HID, TrainSmallBwdH, TrainSmallBwd> a, TileTab tt, TypeTab yt, TypeConsts yc) {
+// DROP: Dropout layers behind its Dense layers (see the header comment); DROP = false are the kernels without, unchanged
+template <int SQ, bool HAS_W, bool LOCAL, bool LAB = false, bool HID = false, bool DROP = false>
+__global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(train_small_args<DROP, std::conditional_t<HID, TrainSmallBwdH, TrainSmallBwd>> a, TileTab tt, TypeTab yt, TypeConsts yc) {
     using Csr = TileCsr<SQ, HAS_W, LOCAL>;
     constexpr int S = 16 * SQ, LPR = S / 4, NPP = Csr::NPP, NPASS = Csr::NPASS;
     constexpr int LDX = 2 * S + 4;        // == 4 (mod 32)
@@ -743,6 +802,19 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(std::conditional_t
             if constexpr (HID) { if (rr < nt && t >= 0) fh[u] = *reinterpret_cast<const f32x4 *>(a.hid + (size_t)t * NS + (size_t)(n0 + rr) * S + 4 * ch); }
         }
     };
+    // DROP: the masks' key state; a layer behind the last Dense (slot 1): act'(.) takes the UN-dropped output of iteration t from the tape (`ypre`)
+    // instead of states[t + 1], and the mask of iteration t is regenerated on G in front of it
+    unsigned drop_base = 0u;
+    if constexpr (DROP) drop_base = small_drop_base(a.dr);
+    const bool drop_mid = HID && small_drop_on<DROP>(a, 0), drop_last = small_drop_on<DROP>(a, 1);
+    auto fetch_y = [&](int t, f32x4 (&fy)[DROP ? NCH : 1]) {
+#pragma unroll
+        for (int u = 0; u < (DROP ? NCH : 0); ++u) {
+            const int rr = (tid + u * TS_NT) / LPR;
+            fy[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if constexpr (DROP) { if (drop_last && rr < nt && t >= 0) fy[u] = *reinterpret_cast<const f32x4 *>(a.dr.ypre + (size_t)t * NS + (size_t)(n0 + rr) * S + 4 * ch); }
+        }
+    };
     if (a.k > 0) {
         fetch(a.k - 1, xs, xa);
         if (HID) fetch_h(a.k - 1, hp);
@@ -750,6 +822,14 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(std::conditional_t
         for (int u = 0; u < NCH; ++u) {
             const int rr = (tid + u * TS_NT) / LPR;
             y[u] = rr < nt ? *reinterpret_cast<const f32x4 *>(a.states + (size_t)a.k * NS + (size_t)(n0 + rr) * S + 4 * ch) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+        if constexpr (DROP) {
+            if (drop_last) {
+                f32x4 y0[DROP ? NCH : 1];
+                fetch_y(a.k - 1, y0);
+#pragma unroll
+                for (int u = 0; u < NCH; ++u) y[u] = y0[DROP ? u : 0];
+            }
         }
         coefficients(a.k - 1);
     }
@@ -762,6 +842,10 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(std::conditional_t
         fetch(t - 1, xs_n, xa_n);
         f32x4 hp_n[HID ? NCH : 1];
         if (HID) fetch_h(t - 1, hp_n);
+        f32x4 y_n[DROP ? NCH : 1];
+        if (DROP) fetch_y(t - 1, y_n);
+        unsigned key_mid = 0u, key_last = 0u;
+        if constexpr (DROP) { key_mid = small_drop_key(drop_base, t, a.dr.index[0]); key_last = small_drop_key(drop_base, t, a.dr.index[1]); }
         {
             f32x4 qp = {0.f, 0.f, 0.f, 0.f};
             const f32x4 r0 = *reinterpret_cast<const f32x4 *>(rs_s + 4 * ch), s0 = *reinterpret_cast<const f32x4 *>(sh_s + 4 * ch);
@@ -774,13 +858,25 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(std::conditional_t
                 for (int e = 0; e < 4; ++e) {
                     hs[e] = rr < nt ? (xs[u][e] - s0[e]) * r0[e] : 0.0f;
                     ha[e] = rr < nt ? (xa[u][e] - s1[e]) * r1[e] : 0.0f;
+                    if constexpr (DROP) { if (drop_last) gz[e] = dropout_keep(key_last, (unsigned)(n0 + rr), (unsigned)(4 * ch + e), a.dr.thr[1]) ? gz[e] * a.dr.mul[1] : 0.0f; }
                     gz[e] *= activate_grad_from_output(state_activation<HID>(a, act), y[u][e]);
                 }
                 *reinterpret_cast<f32x4 *>(Xs + rr * LDX + 4 * ch) = hs;
                 *reinterpret_cast<f32x4 *>(Xs + rr * LDX + S + 4 * ch) = ha;
                 if (HID) {      // gz = dZ2 of the SECOND layer: in place over G (dead until step D), the hidden rows beside it
                     *reinterpret_cast<f32x4 *>(Gs + rr * LDZ + 4 * ch) = gz;
-                    *reinterpret_cast<f32x4 *>(Hs + rr * LDZ + 4 * ch) = hp[HID ? u : 0];
+                    f32x4 hrow = hp[HID ? u : 0];
+                    if constexpr (DROP) {
+                        if (drop_mid) {      // Dropout between the layers: h itself -> Zs (for act1'(h); dZ1 overwrites it), drop(h) -> Hs (for P2)
+                            *reinterpret_cast<f32x4 *>(Zs + rr * LDZ + 4 * ch) = hrow;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                const float x = dropout_keep(key_mid, (unsigned)(n0 + rr), (unsigned)(4 * ch + e), a.dr.thr[0]) ? fmaf(hrow[e], a.dr.mul[0], a.dr.add[0]) : a.dr.fill[0];
+                                hrow[e] = (rr < nt && 4 * ch + e < Hw) ? x : 0.0f;
+                            }
+                        }
+                    }
+                    *reinterpret_cast<f32x4 *>(Hs + rr * LDZ + 4 * ch) = hrow;
                 } else {
                     *reinterpret_cast<f32x4 *>(Zs + rr * LDZ + 4 * ch) = gz;
                     dzsum[u] += gz;
@@ -827,7 +923,14 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(std::conditional_t
             asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
 #pragma unroll
             for (int u = 0; u < SQ; ++u) {
-                const f32x4 hv = *reinterpret_cast<const f32x4 *>(Hs + (16 * wave + c) * LDZ + 16 * u + 4 * g);
+                const f32x4 hv = *reinterpret_cast<const f32x4 *>((drop_mid ? Zs : Hs) + (16 * wave + c) * LDZ + 16 * u + 4 * g);
+                if constexpr (DROP) {
+                    if (drop_mid) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            dh[u][e] = dropout_keep(key_mid, (unsigned)orow, (unsigned)(16 * u + 4 * g + e), a.dr.thr[0]) ? dh[u][e] * a.dr.mul[0] : 0.0f;
+                    }
+                }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) dh[u][e] *= activate_grad_from_output(act, hv[e]);
                 *reinterpret_cast<f32x4 *>(Zs + (16 * wave + c) * LDZ + 16 * u + 4 * g) = dh[u];
@@ -969,6 +1072,12 @@ __global__ void __launch_bounds__(TS_NT, 1) k_train_small_bwd(std::conditional_t
         if (t > 0) coefficients(t - 1);
 #pragma unroll
         for (int u = 0; u < NCH; ++u) { y[u] = xs[u]; xs[u] = xs_n[u]; xa[u] = xa_n[u]; }       // states[t] is the output of iteration t - 1
+        if constexpr (DROP) {
+            if (drop_last) {
+#pragma unroll
+                for (int u = 0; u < NCH; ++u) y[u] = y_n[DROP ? u : 0];
+            }
+        }
         if (HID) {
 #pragma unroll
             for (int u = 0; u < NCH; ++u) hp[HID ? u : 0] = hp_n[HID ? u : 0];

@@ -10,6 +10,21 @@ inline int rows_per_chunk_for(int M, int *n_chunks) {
     *n_chunks = std::max(1, cdiv(M, rpc));
     return rpc;
 }
+// what k_dropout (and the persistent small-graph kernels' Dropout form) takes of a layer: y = keep ? x mul + add : fill, keep <=> hash >= thr
+struct DropScalars { unsigned thr; float mul, add, fill; };
+inline DropScalars drop_scalars(float rate, int alpha, bool backward) {
+    const double t = (double)rate * 4294967296.0;
+    DropScalars d{t >= 4294967295.0 ? 4294967295u : (unsigned)t, 0.0f, 0.0f, 0.0f};
+    if (alpha) {
+        const double ap = -1.6732632423543772 * 1.0507009873554805;
+        const double a = 1.0 / sqrt((1.0 - rate) * (1.0 + rate * ap * ap)), b = -a * ap * rate;
+        d.mul = (float)a;
+        if (!backward) { d.fill = (float)(a * ap + b); d.add = (float)b; }
+    } else {
+        d.mul = (float)(1.0 / (1.0 - (double)rate));
+    }
+    return d;
+}
 }  // namespace
 
 extern "C" {
@@ -172,18 +187,8 @@ int gnn_dropout(const float *x, int32_t ldx, float *y, int32_t ldy, int32_t M, i
     if (M < 0 || H < 1 || ldx < H || ldy < H || !(rate >= 0.0f && rate < 1.0f)) return fail("bad arguments (0 <= rate < 1)");
     if (M == 0) return 0;
     if (!x || !y) return fail("NULL pointer");
-    const double t = (double)rate * 4294967296.0;
-    const unsigned thr = t >= 4294967295.0 ? 4294967295u : (unsigned)t;
-    float mul, fill = 0.0f, add = 0.0f;
-    if (alpha) {
-        const double ap = -1.6732632423543772 * 1.0507009873554805;
-        const double a = 1.0 / sqrt((1.0 - rate) * (1.0 + rate * ap * ap)), b = -a * ap * rate;
-        mul = (float)a;
-        if (!backward) { fill = (float)(a * ap + b); add = (float)b; }
-    } else {
-        mul = (float)(1.0 / (1.0 - (double)rate));
-    }
-    gnn::k_dropout<<<(int)std::min<long>(cdiv((long)M * H, 256), 256 * 16), 256, 0, (hipStream_t)stream>>>(x, ldx, y, ldy, M, H, key, thr, mul, fill, add);
+    const DropScalars d = drop_scalars(rate, alpha, backward != 0);
+    gnn::k_dropout<<<(int)std::min<long>(cdiv((long)M * H, 256), 256 * 16), 256, 0, (hipStream_t)stream>>>(x, ldx, y, ldy, M, H, key, d.thr, d.mul, d.fill, d.add);
     LAUNCH_OK();
     return 0;
 }

@@ -40,11 +40,11 @@ struct DropRun {
     unsigned seed; int call;
     float *buf[GNN_MAX_LAYERS + 1];        // [q]: destination of the dropped-out copy for position q (forward)
 };
-inline bool drop_at(const DropRun *r, int q) {
-    if (!r || !r->d) return false;
-    for (int i = 0; i < r->d->n; ++i) if (r->d->pos[i] == q) return true;
+inline bool drop_at_position(const gnn_dropout_spec_t &d, int q) {
+    for (int i = 0; i < d.n; ++i) if (d.pos[i] == q) return true;
     return false;
 }
+inline bool drop_at(const DropRun *r, int q) { return r && r->d && drop_at_position(*r->d, q); }
 // every Dropout layer at position q: forward x -> y (list order; later layers in place on y), backward in place on y = x (reverse order)
 int run_dropout(const DropRun &r, int q, const float *x, int ldx, float *y, int ldy, int M, int H, bool backward, hipStream_t st) {
     const gnn_dropout_spec_t &d = *r.d;
@@ -94,6 +94,8 @@ struct StepPlan {
     float *sm_cc, *sm_part; unsigned long long *sm_bar;
     bool hid_small;              // small path, hidden-layer form (GNN_FLAG_TRAIN_HIDDEN_SMALL; homogeneous models): the state network is two Dense layers
     float *sm_hid, *sm_partW2;   // ... its hidden rows on the tape [K][N][ldS], every workgroup's share of the second layer's gradients
+    bool drop_small;             // small path, Dropout form (GNN_FLAG_TRAIN_DROPOUT_SMALL; homogeneous models): Dropout layers behind the state network's Dense layers
+    float *sm_ypre;              // ... with one behind the LAST Dense: its un-dropped input on the tape [K][N][ldS] (the state is the dropped-out copy)
     float *stats_o, *Wf_o, *bf_o, *dx_o_all, *G_state, *G_out, *dpred, *loss_rows, *loss_part;
     int *isrc, *idst;            // arc focus: the end nodes of the masked arcs
     float *part, *part_h; size_t part_floats;
@@ -129,9 +131,10 @@ constexpr int BIG_AGG_BLOCKS = 4096, BIG_FWD_BLOCKS = 1024, BIG_WGRAD_BLOCKS = 5
 inline bool train_small_enabled() { const char *e = getenv("GNN_TRAIN_SMALL"); return !(e && e[0] == '0'); }
 // both fast paths run state networks of ONE Dense layer of the state's width, not softmax
 inline bool one_dense_of_state_width(const gnn_mlp_t &m, int S) { return m.n_layers == 1 && m.units[0] == S && m.activation[0] != GNN_ACT_SOFTMAX; }
-// the persistent kernels: switched on, below the large-graph threshold, no Dropout in a state network, the padded width at most 64, every
-// tile resident at once (the workgroups meet at grid barriers), every iteration's neighbour sum within the aggregate-tape budget
-// (`taped` matrices of N x SPs floats per iteration: the neighbour sums, and the hidden rows of the hidden-layer form)
+// the persistent kernels: switched on, below the large-graph threshold, no Dropout in a state network (`drop_s`; their Dropout form asks with false:
+// homogeneous_train_path), the padded width at most 64, every tile resident at once (the workgroups meet at grid barriers), every iteration's
+// neighbour sum within the aggregate-tape budget (`taped` matrices of N x SPs floats per iteration: the neighbour sums, the hidden rows of the
+// hidden-layer form, the un-dropped output of the Dropout form)
 inline bool train_small_fits(const StepPlan &p, bool drop_s, int taped = 1) {
     return train_small_enabled() && p.N < train_big_min_nodes() && !drop_s && p.S <= 64 && p.n_wg <= device_cus() &&
            (size_t)taped * std::max(p.K, 1) * p.N * p.SPs * sizeof(float) <= agg_tape_budget();
@@ -141,6 +144,18 @@ inline bool train_small_fits(const StepPlan &p, bool drop_s, int taped = 1) {
 // Padded widths 16 and 32 only: at 64 the backward kernel's second set of accumulators does not fit the register file (it would spill to scratch).
 inline bool hidden_dense_of_state_width(const gnn_mlp_t &m, int S, int SPs) {
     return SPs <= 32 && m.n_layers == 2 && m.units[1] == S && m.units[0] >= 1 && m.units[0] <= SPs && m.activation[0] != GNN_ACT_SOFTMAX && m.activation[1] != GNN_ACT_SOFTMAX;
+}
+// the Dropout form of the persistent kernels (opt-in: GNN_FLAG_TRAIN_DROPOUT_SMALL): at most ONE Dropout / AlphaDropout layer behind each Dense
+// layer (positions 1 .. n_layers; position 0 never reaches a plan: check_dropout), padded widths 16 and 32 only - at 64 the one-layer LOCAL
+// backward kernel is at 256 + 256 registers with scratch already.  `last` (out): a layer sits behind the last Dense - its un-dropped input is taped.
+inline bool dropout_small_form(const gnn_dropout_spec_t &d, int n_layers, int SPs, bool &last) {
+    last = false;
+    if (SPs > 32 || d.n < 1 || d.n > n_layers) return false;
+    for (int i = 0; i < d.n; ++i) {
+        if (d.pos[i] < 1 || d.pos[i] > n_layers || (i > 0 && d.pos[i] <= d.pos[i - 1])) return false;
+        last |= d.pos[i] == n_layers;
+    }
+    return true;
 }
 
 size_t grad_part_floats(int K, int H, int M) { int nc; rows_per_chunk_for(std::max(M, 1), &nc); return (size_t)nc * ((size_t)K * H + H); }
@@ -169,8 +184,23 @@ void carve_net(Carver &c, NetCtx &x, const gnn_mlp_t &m, int rows, size_t &part_
 // `hidden` (out): the persistent kernels in their hidden-layer form - asked for by GNN_FLAG_TRAIN_HIDDEN_SMALL, a network
 // hidden_dense_of_state_width() accepts, and every condition of the persistent path with the hidden rows counted on the tape beside the
 // neighbour sums; with the flag set every other shape is routed exactly as without it.
-TrainPath homogeneous_train_path(const gnn_train_args_t &ta, const TrainPlan &p, bool &hidden) {
+// `dropped` (out): the persistent kernels in their Dropout form - asked for by GNN_FLAG_TRAIN_DROPOUT_SMALL, Dropout layers dropout_small_form()
+// accepts behind one Dense of the state width (or, with GNN_FLAG_TRAIN_HIDDEN_SMALL as well, behind the layers of a network
+// hidden_dense_of_state_width() accepts), and every condition of the persistent path with what the form tapes counted: the neighbour sums, the hidden
+// rows, the un-dropped input of a layer behind the last Dense.  Every other shape with Dropout is routed exactly as without the flag.
+TrainPath homogeneous_train_path(const gnn_train_args_t &ta, const TrainPlan &p, bool &hidden, bool &dropped) {
     const bool drop_s = ta.drop_state[0].n > 0;
+    const gnn_mlp_t &m = ta.loop.net_state[0];
+    hidden = dropped = false;
+    if (drop_s && (ta.loop.flags & GNN_FLAG_TRAIN_DROPOUT_SMALL) != 0 && p.K >= 1 && p.Kc <= 32) {
+        const bool hid = (ta.loop.flags & GNN_FLAG_TRAIN_HIDDEN_SMALL) != 0 && hidden_dense_of_state_width(m, p.S, p.SPs);
+        bool last = false;
+        if ((hid || one_dense_of_state_width(m, p.S)) && dropout_small_form(ta.drop_state[0], m.n_layers, p.SPs, last) &&
+            train_small_fits(p, false, 1 + (hid ? 1 : 0) + (last ? 1 : 0))) {
+            hidden = hid; dropped = true;
+            return TrainPath::small;
+        }
+    }
     hidden = (ta.loop.flags & GNN_FLAG_TRAIN_HIDDEN_SMALL) != 0 && hidden_dense_of_state_width(ta.loop.net_state[0], p.S, p.SPs) && !drop_s && p.K >= 1 &&
              p.Kc <= 32 && train_small_fits(p, drop_s, 2);
     if (hidden) return TrainPath::small;
@@ -215,7 +245,7 @@ int make_train_plan(const gnn_train_args_t &ta, void *ws, TrainPlan &p) {
     p.tiled = ta.n_tiles > 0 && ta.tile_node_begin != nullptr;
     p.n_wg = p.tiled ? ta.n_tiles : cdiv(p.N, 64);
     if (p.tiled && p.n_wg > 256) { p.tiled = false; p.n_wg = cdiv(p.N, 64); }
-    p.path = homogeneous_train_path(ta, p, p.hid_small);
+    p.path = homogeneous_train_path(ta, p, p.hid_small, p.drop_small);
     const bool big = p.path == TrainPath::big, small = p.path == TrainPath::small;
     // every node is an output row (out_index ascending and n_out == n_nodes: the identity), one thin Dense: kernels_train_big.hpp
     p.head_fast = big && no.n_layers == 1 && no.units[0] <= 4 && a.focus != GNN_FOCUS_ARC && p.M == p.N && p.S % 4 == 0 &&
@@ -282,6 +312,7 @@ int make_train_plan(const gnn_train_args_t &ta, void *ws, TrainPlan &p) {
     p.sm_bar = c.take<unsigned long long>(small ? 4 : 0);
     p.sm_hid = c.take<float>(p.hid_small ? (size_t)p.K * p.N * p.ldS : 0);
     p.sm_partW2 = c.take<float>(p.hid_small ? (size_t)p.n_wg * (p.H1s + 1) * p.S : 0);
+    p.sm_ypre = c.take<float>(p.drop_small && drop_at_position(ta.drop_state[0], ns.n_layers) ? (size_t)p.K * p.N * p.ldS : 0);
     p.ld_dz = small ? p.SPs : p.H1s;
     p.dz_sum = c.take<float>(big ? 0 : (size_t)p.N * p.ld_dz);
     p.g0 = c.take<float>(small ? (size_t)p.N * p.SPs : 0);
@@ -854,6 +885,40 @@ int launch_train_small_bwd_hid_sq(const gnn::TrainSmallBwdH &ba, const gnn::Tile
                  : launch_persistent(&gnn::k_train_small_bwd<SQ, false, false, false, true>, ba, tt, n_wg, lds, st, y, c);
 }
 
+// the Dropout form of both launches (homogeneous models; `dr`: the layers' scalars and the un-dropped tape), one-layer (Base = TrainSmallFwd /
+// TrainSmallBwd) or hidden-layer (Base = ..H): the kernel's argument block is the base block with the Dropout arguments behind it
+template <int SQ, bool HID, typename Base>
+int launch_train_small_fwd_drop_sq(const Base &fa, const gnn::SmallDrop &dr, const gnn::TileTab &tt, int n_wg, bool has_w, hipStream_t st) {
+    const size_t lds = gnn::train_small_fwd_lds<SQ, HID>();
+    static const gnn::TypeTab y{};
+    gnn::TrainSmallDrop<Base> d{};
+    static_cast<Base &>(d) = fa; d.dr = dr;
+    if (tt.n > 0) return has_w ? launch_persistent(&gnn::k_train_small_fwd<SQ, true, true, HID, true>, d, tt, n_wg, lds, st, y)
+                               : launch_persistent(&gnn::k_train_small_fwd<SQ, false, true, HID, true>, d, tt, n_wg, lds, st, y);
+    return has_w ? launch_persistent(&gnn::k_train_small_fwd<SQ, true, false, HID, true>, d, tt, n_wg, lds, st, y)
+                 : launch_persistent(&gnn::k_train_small_fwd<SQ, false, false, HID, true>, d, tt, n_wg, lds, st, y);
+}
+
+template <int SQ, bool HID, typename Base>
+int launch_train_small_bwd_drop_sq(const Base &ba, const gnn::SmallDrop &dr, const gnn::TileTab &tt, int n_wg, bool has_w, hipStream_t st) {
+    const bool local = tt.n > 0;
+    const size_t lds = gnn::train_small_bwd_lds<SQ>(local, HID);
+    static const gnn::TypeTab y{};
+    static const gnn::TypeConsts c{};
+    gnn::TrainSmallDrop<Base> d{};
+    static_cast<Base &>(d) = ba; d.dr = dr;
+    if (ba.dz_out || ba.g0_out) {
+        if (local) return has_w ? launch_persistent(&gnn::k_train_small_bwd<SQ, true, true, true, HID, true>, d, tt, n_wg, lds, st, y, c)
+                                : launch_persistent(&gnn::k_train_small_bwd<SQ, false, true, true, HID, true>, d, tt, n_wg, lds, st, y, c);
+        return has_w ? launch_persistent(&gnn::k_train_small_bwd<SQ, true, false, true, HID, true>, d, tt, n_wg, lds, st, y, c)
+                     : launch_persistent(&gnn::k_train_small_bwd<SQ, false, false, true, HID, true>, d, tt, n_wg, lds, st, y, c);
+    }
+    if (local) return has_w ? launch_persistent(&gnn::k_train_small_bwd<SQ, true, true, false, HID, true>, d, tt, n_wg, lds, st, y, c)
+                            : launch_persistent(&gnn::k_train_small_bwd<SQ, false, true, false, HID, true>, d, tt, n_wg, lds, st, y, c);
+    return has_w ? launch_persistent(&gnn::k_train_small_bwd<SQ, true, false, false, HID, true>, d, tt, n_wg, lds, st, y, c)
+                 : launch_persistent(&gnn::k_train_small_bwd<SQ, false, false, false, HID, true>, d, tt, n_wg, lds, st, y, c);
+}
+
 // the per-workgroup partials [grid][K H + H] of a first layer's P = X^T dZ | q summed into x.P / x.q, then its parameter gradients (and the
 // BatchNorm input-gradient moments m1 / m2) over M rows; `centred`: the rows arrived centred (P is P - mean q^T)
 int first_layer_grads(const NetCtx &x, const float *part, int grid, int M, const float *stats, bool accumulate, bool centred, hipStream_t st) {
@@ -952,7 +1017,9 @@ int check_step_args(const gnn_train_args_t &ta, const StepPlan &p, bool own_loss
 
 // the common fields of the persistent forward launch and the instance for the padded width (`fa`: zeroed, the caller's own fields set;
 // p.hid_small: `fa` / `ba` below ARE the hidden-layer blocks TrainSmallFwdH / TrainSmallBwdH - forward_small / backward_small make them)
-int launch_train_small_fwd(gnn::TrainSmallFwd &fa, const gnn_train_args_t &ta, const StepPlan &p, const gnn::TileTab &tiles, const gnn::TypeTab *yt, hipStream_t st) {
+// p.drop_small: `dr` carries the Dropout form's arguments (small_drop_args below)
+int launch_train_small_fwd(gnn::TrainSmallFwd &fa, const gnn_train_args_t &ta, const StepPlan &p, const gnn::TileTab &tiles, const gnn::TypeTab *yt, hipStream_t st,
+                           const gnn::SmallDrop *dr = nullptr) {
     const gnn_csr_t &ad = ta.loop.adjacency;
     fa.N = p.N; fa.S = p.SPs; fa.Sw = p.S; fa.K = p.K;
     fa.rowptr = ad.rowptr; fa.src = ad.src; fa.w = ad.w; fa.row_scale = ad.row_scale;
@@ -960,6 +1027,16 @@ int launch_train_small_fwd(gnn::TrainSmallFwd &fa, const gnn_train_args_t &ta, c
     fa.Cc = p.sm_cc; fa.thr = ta.loop.state_threshold; fa.flag0 = p.flags;
     fa.bar = p.sm_bar; fa.part = p.sm_part; fa.k_out = p.k_dev; fa.wait_ticks = gnn::wait_ticks();
     if (const char *e = getenv("GNN_DEBUG_FAIL_FWD")) { if (e[0] == '1') fa.wait_ticks = 0; }      // (test hook: every barrier wait of THIS forward launch expires at once)
+    if (p.drop_small) {      // (the rule: padded widths 16 / 32)
+        if (!dr) return fail("persistent forward launch: the Dropout form without its arguments");
+        if (p.hid_small) {
+            const auto &fh = static_cast<const gnn::TrainSmallFwdH &>(fa);
+            return p.SPs == 16 ? launch_train_small_fwd_drop_sq<1, true>(fh, *dr, tiles, p.n_wg, ad.w != nullptr, st)
+                               : launch_train_small_fwd_drop_sq<2, true>(fh, *dr, tiles, p.n_wg, ad.w != nullptr, st);
+        }
+        return p.SPs == 16 ? launch_train_small_fwd_drop_sq<1, false>(fa, *dr, tiles, p.n_wg, ad.w != nullptr, st)
+                           : launch_train_small_fwd_drop_sq<2, false>(fa, *dr, tiles, p.n_wg, ad.w != nullptr, st);
+    }
     if (p.hid_small) {
         const auto hid = p.SPs == 16 ? launch_train_small_fwd_hid_sq<1> : launch_train_small_fwd_hid_sq<2>;      // (the rule: padded widths 16 / 32)
         return hid(static_cast<const gnn::TrainSmallFwdH &>(fa), tiles, p.n_wg, ad.w != nullptr, st);
@@ -970,7 +1047,7 @@ int launch_train_small_fwd(gnn::TrainSmallFwd &fa, const gnn_train_args_t &ta, c
 
 // ... and of the persistent backward launch: the k iterations of back-propagation; every workgroup leaves its share of the kernel gradient
 int launch_train_small_bwd(gnn::TrainSmallBwd &ba, const gnn_train_args_t &ta, const StepPlan &p, int k, const gnn::TileTab &tiles, const gnn::TypeTab *yt,
-                           const gnn::TypeConsts *yc, hipStream_t st) {
+                           const gnn::TypeConsts *yc, hipStream_t st, const gnn::SmallDrop *dr = nullptr) {
     const gnn_csr_t &ad = ta.loop.adjacency, &cs_ = ta.adjacency_by_source;
     const bool unit_w = !ad.w;       // entries depend on the destination only: scale the agg-half once per row, walk unit weights
     ba.N = p.N; ba.S = p.SPs; ba.Sw = p.S; ba.k = k;
@@ -980,6 +1057,16 @@ int launch_train_small_bwd(gnn::TrainSmallBwd &ba, const gnn_train_args_t &ta, c
     ba.G0 = p.G_state; ba.bar = p.sm_bar + 2; ba.part = p.sm_part;
     ba.inv_n = 1.0f / (float)p.N; ba.err = p.k_dev; ba.wait_ticks = gnn::wait_ticks();
     if (const char *e = getenv("GNN_DEBUG_FAIL_BWD")) { if (e[0] == '1') ba.wait_ticks = 0; }      // (test hook: every barrier wait of THIS launch expires at once)
+    if (p.drop_small) {
+        if (!dr) return fail("persistent backward launch: the Dropout form without its arguments");
+        if (p.hid_small) {
+            const auto &bh = static_cast<const gnn::TrainSmallBwdH &>(ba);
+            return p.SPs == 16 ? launch_train_small_bwd_drop_sq<1, true>(bh, *dr, tiles, p.n_wg, ba.w_s != nullptr, st)
+                               : launch_train_small_bwd_drop_sq<2, true>(bh, *dr, tiles, p.n_wg, ba.w_s != nullptr, st);
+        }
+        return p.SPs == 16 ? launch_train_small_bwd_drop_sq<1, false>(ba, *dr, tiles, p.n_wg, ba.w_s != nullptr, st)
+                           : launch_train_small_bwd_drop_sq<2, false>(ba, *dr, tiles, p.n_wg, ba.w_s != nullptr, st);
+    }
     if (p.hid_small) {
         const auto hid = p.SPs == 16 ? launch_train_small_bwd_hid_sq<1> : launch_train_small_bwd_hid_sq<2>;
         return hid(static_cast<const gnn::TrainSmallBwdH &>(ba), tiles, p.n_wg, ba.w_s != nullptr, st);
@@ -1263,6 +1350,21 @@ int forward_big(const gnn_train_args_t &ta, TrainPlan &p, hipStream_t st) {
     return 0;
 }
 
+// the Dropout form's arguments (p.drop_small): the layers of drop_state[0] by slot - 0 between the two Dense layers of the hidden form, 1 behind the
+// last Dense - with the scalars gnn_dropout() derives for them; the kernels form every iteration's key from (seed, net_id, iteration, index) themselves
+gnn::SmallDrop small_drop_args(const gnn_train_args_t &ta, const TrainPlan &p) {
+    const gnn_dropout_spec_t &d = ta.drop_state[0];
+    const int n_layers = ta.loop.net_state[0].n_layers;
+    gnn::SmallDrop dr{};
+    dr.seed = ta.drop_seed; dr.net_id = (unsigned)d.net_id; dr.ypre = p.sm_ypre;
+    for (int i = 0; i < d.n; ++i) {
+        const int slot = d.pos[i] == n_layers ? 1 : 0;
+        const DropScalars sc = drop_scalars(d.rate[i], d.alpha, false);
+        dr.on[slot] = 1; dr.index[slot] = (unsigned)d.index[i]; dr.thr[slot] = sc.thr; dr.mul[slot] = sc.mul; dr.add[slot] = sc.add; dr.fill[slot] = sc.fill;
+    }
+    return dr;
+}
+
 // Small graphs (kernels_train_small.hpp): all K gated iterations in one persistent launch, one workgroup per 64-node tile
 int forward_small(const gnn_train_args_t &ta, TrainPlan &p, const gnn::TileTab &tiles, hipStream_t st) {
     const gnn_loop_args_t &a = ta.loop;
@@ -1276,7 +1378,8 @@ int forward_small(const gnn_train_args_t &ta, TrainPlan &p, const gnn::TileTab &
     fa.stats = p.stats_s; fa.in_s = p.in_s; fa.off_agg = p.off_agg;
     fa.W = ns.kernel[0]; fa.gamma = gamma; fa.beta = ns.bn_beta; fa.eps = ns.bn_eps; fa.act = ns.activation[0];
     if (p.hid_small) { fa.Hw = p.H1s; fa.W2 = ns.kernel[1]; fa.b2 = ns.bias[1]; fa.act2 = ns.activation[1]; fa.hid = p.sm_hid; }
-    return launch_train_small_fwd(fa, ta, p, tiles, nullptr, st);
+    const gnn::SmallDrop dr = p.drop_small ? small_drop_args(ta, p) : gnn::SmallDrop{};
+    return launch_train_small_fwd(fa, ta, p, tiles, nullptr, st, p.drop_small ? &dr : nullptr);
 }
 
 // the general path: one launch per layer and iteration
@@ -1353,7 +1456,8 @@ int backward_small(const gnn_train_args_t &ta, TrainPlan &p, const gnn::TileTab 
     ba.dxa = p.dx_s_all; ba.partW = p.sm_partW; ba.partBN = p.sm_partBN;
     ba.dz_out = w.lab ? p.dz_sum : nullptr; ba.g0_out = w.g0 ? p.g0 : nullptr;
     if (p.hid_small) { ba.Hw = p.H1s; ba.W2 = ns.kernel[1]; ba.act2 = ns.activation[1]; ba.hid = p.sm_hid; ba.partW2 = p.sm_partW2; }
-    TRY(launch_train_small_bwd(ba, ta, p, k, tiles, nullptr, nullptr, st));
+    const gnn::SmallDrop dr = p.drop_small ? small_drop_args(ta, p) : gnn::SmallDrop{};
+    TRY(launch_train_small_bwd(ba, ta, p, k, tiles, nullptr, nullptr, st, p.drop_small ? &dr : nullptr));
     const int n = (p.in_s + 1) * p.H1s;
     gnn::k_reduce_partials<<<cdiv(n, 64), 256, 0, st>>>(p.sm_partW, p.n_wg, n, ta.grad_state.dkernel[0], 0, 1.0f, p.in_s * p.H1s, ta.grad_state.dbias[0]);
     LAUNCH_OK();
@@ -1652,7 +1756,7 @@ static int train_step_impl(const gnn_train_args_t &ta, const gnn_train_phase_arg
     TRY(check_step_args(ta, p, !fwd_only && phase != GNN_TRAIN_PHASE_FORWARD && !no_loss, !fwd_only && phase != GNN_TRAIN_PHASE_FORWARD));
     const gnn_mlp_t &ns = a.net_state[0], &no = a.net_output;
     hipStream_t st = (hipStream_t)a.stream;
-    GNN_SET_KERNEL_NAME(big ? "train_step: row-streaming kernels (kernels_train_big.hpp)" : p.hid_small ? "train_step: persistent small-graph kernels (hidden layer)" : small ? "train_step: persistent small-graph kernels" : "train_step: general kernels");
+    GNN_SET_KERNEL_NAME(big ? "train_step: row-streaming kernels (kernels_train_big.hpp)" : p.drop_small ? (p.hid_small ? "train_step: persistent small-graph kernels (hidden layer, dropout)" : "train_step: persistent small-graph kernels (dropout)") : p.hid_small ? "train_step: persistent small-graph kernels (hidden layer)" : small ? "train_step: persistent small-graph kernels" : "train_step: general kernels");
     gnn::TileTab tiles;
     TRY(tile_table(ta, p, tiles));
     if (!fwd_only && ta.grads_ok_dev) *ta.grads_ok_dev = p.grads_ok;

@@ -83,7 +83,19 @@ enum gnn_flags {
      * width <= 32), neither activation is softmax, there is no Dropout, every node type of a composite model has two layers (H and
      * both activations may differ per type) and every other condition of the one-layer form holds.  Every other shape - and every
      * shape without the flag - is answered, refused and computed as before.  The workspace does not depend on the flag. */
-    GNN_FLAG_TRAIN_GROUPS_HIDDEN = 1 << 10
+    GNN_FLAG_TRAIN_GROUPS_HIDDEN = 1 << 10,
+    /* Training steps only (read like GNN_FLAG_TRAIN_HIDDEN_SMALL, and independent of it).  Opt-in: a homogeneous model whose state
+     * network has Dropout / AlphaDropout layers (gnn_train_args_t::drop_state[0]) keeps the persistent small-graph training kernels -
+     * their Dropout form - when the network is one Dense of the state width with a Dropout layer behind it (position 1), or, with
+     * GNN_FLAG_TRAIN_HIDDEN_SMALL set as well, a network that flag covers with a layer at position 1 (between the two Dense layers),
+     * at position 2 (behind the second) or both; at most one layer per position, padded state width 16 or 32 (state width <= 32),
+     * and every other condition of the persistent path (max_iteration >= 1, <= 32 constant input columns, below the row-streaming
+     * threshold, every tile resident, everything the form tapes within the budget: neighbour sums, hidden rows, and the un-dropped
+     * output in front of a layer behind the last Dense).  The masks are those of the general kernels and of gnn_dropout: same seed,
+     * same masks.  Every other shape - two layers at one position, position 0 (still not covered), width 64, composite models,
+     * convergence groups, a hidden network without GNN_FLAG_TRAIN_HIDDEN_SMALL - plans, routes and computes as without the flag;
+     * gnn_last_kernel_name() says "train_step: persistent small-graph kernels (dropout)" / "... (hidden layer, dropout)". */
+    GNN_FLAG_TRAIN_DROPOUT_SMALL = 1 << 11
 };
 
 /* A sparse operator A (n_src x n_dst, COO in the reference: tf.SparseTensor) stored as the CSR of its transpose:
@@ -639,8 +651,9 @@ typedef struct gnn_train_args {
      *                       from a sentinel - and the word on the tape untouched. */
     const int32_t **grads_ok_dev;
     int32_t *prev_grads_ok_host;
-    /* ABI 8: Dropout layers (all-zero: none).  A state network with Dropout runs the general kernels (one launch per layer and iteration);
-     * Dropout inside the OUTPUT network alone leaves the loop on whichever fast path applies. */
+    /* ABI 8: Dropout layers (all-zero: none).  A state network with Dropout runs the general kernels (one launch per layer and iteration) -
+     * or, for the shapes GNN_FLAG_TRAIN_DROPOUT_SMALL covers and with that flag in loop.flags, the persistent small-graph kernels in their
+     * Dropout form; Dropout inside the OUTPUT network alone leaves the loop on whichever fast path applies. */
     gnn_dropout_spec_t drop_state[GNN_MAX_TYPES];   /* [0] for homogeneous models                                   */
     gnn_dropout_spec_t drop_output;
     uint32_t drop_seed;                             /* the step's seed (every mask of the step derives from it)     */
