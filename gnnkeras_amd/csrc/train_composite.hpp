@@ -40,6 +40,13 @@ struct CPlan : StepPlan {            // (train_loop.hpp: what the two kinds' pla
     CBig B;
 };
 
+// The BatchNormalization epsilon of the persistent launches, one for all their tiles: that of the first type WITH ROWS.  A type without rows does
+// not count towards the path (composite_train_path) and may be the only one without BatchNormalization - its bn_eps is 0.
+inline float composite_small_eps(const CPlan &p) {
+    for (int q = 0; q < p.n_types; ++q) if (p.ty[q].count > 0) return p.ty[q].m->bn_eps;
+    return p.ty[0].m->bn_eps;
+}
+
 // inv[perm[i]] = i
 __global__ void __launch_bounds__(256) k_invert_perm(const int *__restrict__ perm, int n, int *__restrict__ inv) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) inv[perm[i]] = i;
@@ -79,12 +86,13 @@ TrainPath composite_train_path(const gnn_train_args_t &ta, CPlan &p, bool drop_s
     const gnn_loop_args_t &a = ta.loop;
     bool uniform = true;
     int bn_seen = -1;
+    float eps_seen = 0.0f;                             // (the launch has ONE epsilon for all its tiles: composite_small_eps)
     for (int t = 0; t < p.n_types; ++t) {
         const gnn_mlp_t &m = a.net_state[t];
         if (!one_dense_of_state_width(m, p.S)) uniform = false;
         if (a.type_offsets[t + 1] - a.type_offsets[t] <= 0) continue;
-        if (bn_seen < 0) bn_seen = m.has_bn ? 1 : 0;
-        else if (bn_seen != (m.has_bn ? 1 : 0)) uniform = false;
+        if (bn_seen < 0) { bn_seen = m.has_bn ? 1 : 0; eps_seen = m.bn_eps; }
+        else if (bn_seen != (m.has_bn ? 1 : 0) || (m.has_bn && m.bn_eps != eps_seen)) uniform = false;
     }
     if (uniform && train_small_fits(p, drop_s) && p.n_wg >= 1 && p.n_wg <= 256) return TrainPath::small;
     return !drop_s && composite_big_applies(ta, p.N, p.S, p.W_comp, &p.B.XT) ? TrainPath::big : TrainPath::general;
@@ -636,7 +644,7 @@ int composite_forward_small(const gnn_train_args_t &ta, CPlan &p, gnn::TileTab &
     }
     HIP_OK(hipMemsetAsync(p.sm_bar, 0, sizeof(unsigned long long) * 4, st));
     gnn::TrainSmallFwd fa{};
-    fa.eps = p.ty[0].m->bn_eps;
+    fa.eps = composite_small_eps(p);
     return launch_train_small_fwd(fa, ta, p, tiles, &yt, st);
 }
 
@@ -678,7 +686,7 @@ int composite_backward_small(const gnn_train_args_t &ta, CPlan &p, const gnn::Ti
     gnn::TypeConsts yc{};
     for (int q = 0; q < p.n_types; ++q) yc.cs[q] = ctype_const_segs(ta.loop, p, p.ty[q]);
     gnn::TrainSmallBwd ba{};
-    ba.eps = p.ty[0].m->bn_eps; ba.dxa = p.sm_dxa;
+    ba.eps = composite_small_eps(p); ba.dxa = p.sm_dxa;
     ba.dz_out = w.lab ? sc.dz : nullptr; ba.g0_out = w.g0 ? sc.g0 : nullptr;      // (by POSITION, rows of SPs floats: the LAB instantiations)
     TRY(launch_train_small_bwd(ba, ta, p, k, tiles, &yt, &yc, st));
     for (int q = 0; q < p.n_types; ++q) {
