@@ -294,10 +294,19 @@ def _mix32(*values):
 
 
 def _train_flags(model):
-    """What a training step takes of `model.native_flags`: the opt-in bits of the hidden-layer persistent kernels, of their Dropout form and
-    of the hidden-layer grouped forward (independent of each other) alone - the other bits steer the inference loop and keep having no
-    effect on a step."""
-    return int(getattr(model, 'native_flags', 0)) & (nat.FLAG_TRAIN_HIDDEN_SMALL | nat.FLAG_TRAIN_GROUPS_HIDDEN | nat.FLAG_TRAIN_DROPOUT_SMALL)
+    """What a training step takes of `model.native_flags`: the opt-in bits of the hidden-layer persistent kernels, of their Dropout form,
+    of the hidden-layer grouped forward and of Dropout in front of a first Dense (independent of each other) alone - the other bits steer
+    the inference loop and keep having no effect on a step."""
+    return int(getattr(model, 'native_flags', 0)) & (nat.FLAG_TRAIN_HIDDEN_SMALL | nat.FLAG_TRAIN_GROUPS_HIDDEN | nat.FLAG_TRAIN_DROPOUT_SMALL |
+                                                     nat.FLAG_TRAIN_DROPOUT_FRONT)
+
+
+def _front_dropout_stays_out(model):
+    """Does a Dropout layer in FRONT of a first Dense (position 0) keep `model` off the in-library step?  Always - such networks train on
+    the building blocks - but for a homogeneous model with `native_flags |= FLAG_TRAIN_DROPOUT_FRONT` (include/gnnloop.h: whole steps and
+    training-mode forwards; a shape the flag does not cover - two layers at position 0 - is answered "not covered" by the library)."""
+    if not dropout_in_front(model): return False
+    return isinstance(model.net_state, (list, tuple)) or not (_train_flags(model) & nat.FLAG_TRAIN_DROPOUT_FRONT)
 
 
 class LoopTrainer:
@@ -860,13 +869,15 @@ class LoopTrainer:
         if not self.use_native_step or y is None: return False
         if isinstance(m.net_state, (list, tuple)) and m.max_iteration < 1: return False      # what the in-library composite step refuses (make_cplan): the general path below
         # Dropout layers behind Dense layers run inside the library (ABI 8); one in FRONT of the first Dense (position 0) keeps the path below
-        return not dropout_in_front(m) and loss_kind(m)[0] is not None
+        # unless the model opted in (FLAG_TRAIN_DROPOUT_FRONT, homogeneous models)
+        return not _front_dropout_stays_out(m) and loss_kind(m)[0] is not None
 
     def _native_forward_applies(self):
         """May `Loop(..., training=True)` run as ONE `gnn_train_step(forward_only)` call?  (homogeneous and composite models, no Dropout in
-        front of a first Dense, no data parallelism - what the in-library steps cover, minus everything about the loss.)"""
+        front of a first Dense - but under FLAG_TRAIN_DROPOUT_FRONT, homogeneous models, not grouped -, no data parallelism - what the
+        in-library steps cover, minus everything about the loss.)"""
         m = self.model
-        return self.dp is None and self.use_native_step and m.max_iteration >= 1 and not dropout_in_front(m)
+        return self.dp is None and self.use_native_step and m.max_iteration >= 1 and not _front_dropout_stays_out(m)
 
     def forward_native(self, x_list, state0=None, seed=None, node_level=False, groups=None, group_out_begin=None):
         """The training-mode forward in one library call (include/gnnloop.h ABI 9, `forward_only`): (k, state, output rows) - the same
@@ -911,7 +922,7 @@ class LoopTrainer:
         m = self.model
         if groups is not None:
             if not forward_only: raise NotImplementedError('training-mode convergence groups: the forward only (no grouped train_step)')
-            if not self._native_forward_applies():
+            if not self._native_forward_applies() or dropout_in_front(m):
                 raise NotImplementedError('training-mode convergence groups: not covered (data parallelism, Dropout in front of a first Dense, '
                                           'max_iteration < 1 or the in-library step switched off)')
             if m._focus == 'g' and not node_level:
@@ -1165,7 +1176,7 @@ class LoopTrainer:
         parallelism, no Dropout in front of a first Dense, a loss with a device gradient), a homogeneous model, and the library's own answer
         (`gnn_train_phases_supported`: dims and network descriptions only, nothing is launched)."""
         m = self.model
-        if isinstance(m.net_state, (list, tuple)) or m.max_iteration < 1: return False
+        if isinstance(m.net_state, (list, tuple)) or m.max_iteration < 1 or dropout_in_front(m): return False      # (position 0: no phases, with or without its flag)
         if not self._native_step_applies(True): return False
         ta = self._dims_only_args(n_nodes, n_arcs, dim_node_label, dim_arc_label, n_out)
         return nat.lib().gnn_train_phases_supported(C.byref(ta)) == 0

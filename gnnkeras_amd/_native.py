@@ -29,6 +29,7 @@ XC_FILL, XC_VALID = 0, 1                # enum gnn_xc_mode
 FLAG_LDS_HIDDEN = 1 << 9                # inference convergence groups only, opt-in: two-layer state networks on the one-CU-per-group kernels' hidden-layer form (include/gnnloop.h)
 FLAG_TRAIN_GROUPS_HIDDEN = 1 << 10      # grouped training-mode forwards only, opt-in: two-layer state networks on the grouped forward kernels' hidden-layer form (include/gnnloop.h)
 FLAG_TRAIN_DROPOUT_SMALL = 1 << 11      # training steps only, opt-in: Dropout layers behind the state network's Dense layers on the persistent small-graph kernels (include/gnnloop.h)
+FLAG_TRAIN_DROPOUT_FRONT = 1 << 12      # training calls only, opt-in: one Dropout layer in FRONT of a network's first Dense (position 0) inside gnn_train_step, on the general kernels (include/gnnloop.h)
 FLAG_FUSED_GEN2, FLAG_FUSED_GEN4, FLAG_FUSED_GEN5, FLAG_FUSED_GEN6, FLAG_FUSED_GEN7 = 2 << 4, 4 << 4, 5 << 4, 6 << 4, 7 << 4     # pin the fused-kernel generation (tests, tuning)
 
 EXPORTS = ['gnn_last_error', 'gnn_last_status', 'gnn_last_kernel_name', 'gnn_abi_version', 'gnn_struct_size', 'gnn_loop_workspace_bytes', 'gnn_loop_forward', 'gnn_loop_groups_supported', 'gnn_loop_group_max_nodes', 'gnn_aggregate',

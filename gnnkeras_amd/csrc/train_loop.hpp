@@ -12,6 +12,7 @@
 #include "kernels_train_big.hpp"
 #include "kernels_train_small.hpp"
 #include "kernels_train_labels.hpp"
+#include "kernels_train_front.hpp"
 
 namespace {
 
@@ -27,7 +28,8 @@ struct NetCtx {
 
 // ---- Dropout / AlphaDropout layers of a network call (ABI 8: gnn_dropout_spec_t; reference MLP.py:60-66) -------------------------------------
 // The masks are the counter hash of gnn_dropout keyed by (step seed, network, call, layer): nothing is stored, the backward pass of a call
-// regenerates them.  Positions 1 .. n_layers (behind a Dense layer's activation); position 0 is refused by the plans.
+// regenerates them.  Positions 1 .. n_layers (behind a Dense layer's activation); position 0 (in front of the first Dense) is refused by the
+// plans - but for ONE layer per network of a homogeneous model under GNN_FLAG_TRAIN_DROPOUT_FRONT (kernels_train_front.hpp; `front_ok` below).
 inline unsigned lowbias32_host(unsigned h) { h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16; return h; }
 inline unsigned drop_key(unsigned seed, unsigned net_id, unsigned call, unsigned index) {
     unsigned h = 0x9E3779B9u;
@@ -58,10 +60,15 @@ int run_dropout(const DropRun &r, int q, const float *x, int ldx, float *y, int 
     }
     return 0;
 }
-int check_dropout(const gnn_dropout_spec_t &d, const gnn_mlp_t &m, const char *name) {
+// GNN_FLAG_TRAIN_DROPOUT_FRONT as a plan reads it: whole calls of homogeneous models (no convergence groups)
+inline bool dropout_front_asked(const gnn_train_args_t &ta) {
+    return (ta.loop.flags & GNN_FLAG_TRAIN_DROPOUT_FRONT) != 0 && !ta.loop.composite && ta.n_groups == 0;
+}
+int check_dropout(const gnn_dropout_spec_t &d, const gnn_mlp_t &m, const char *name, bool front_ok = false) {
     if (d.n < 0 || d.n > GNN_MAX_DROPOUT) return fail("%s: %d dropout layers (0 .. %d)", name, d.n, GNN_MAX_DROPOUT);
     for (int i = 0; i < d.n; ++i) {
-        if (d.pos[i] == 0) return not_covered("%s: Dropout in front of the first Dense layer (position 0): such networks train through the building blocks", name);
+        if (d.pos[i] == 0 && !front_ok) return not_covered("%s: Dropout in front of the first Dense layer (position 0): such networks train through the building blocks", name);
+        if (d.pos[i] == 0 && i > 0 && d.pos[i - 1] == 0) return not_covered("%s: two Dropout layers in front of the first Dense layer (position 0): such networks train through the building blocks", name);
         if (d.pos[i] < 0 || d.pos[i] > m.n_layers || (i > 0 && d.pos[i] < d.pos[i - 1])) return fail("%s: dropout positions must ascend within [1, n_layers]", name);
         if (!(d.rate[i] > 0.0f && d.rate[i] < 1.0f)) return fail("%s: dropout rate %g outside (0, 1)", name, (double)d.rate[i]);
     }
@@ -109,6 +116,7 @@ inline float *agg_at(const StepPlan &p, int t) { return p.agg + (p.agg_taped ? (
 struct TrainPlan : StepPlan {
     int d, in_s, in_o, H1s, H1o, kdx_s, off_agg;
     bool with_labels, tiled;
+    bool front;                           // a Dropout layer in front of a first Dense (GNN_FLAG_TRAIN_DROPOUT_FRONT): the general path, no phases
     float *agg_arcs, *agg_nodes;
     int ld_agg_arcs, ld_agg_nodes;        // A / L for arrays of their own; 32 where they are columns of the constants line (big, Kc > 0)
     float *stats_s, *stats_tpl, *Wf_s, *bf_s, *dx_s_all;
@@ -164,6 +172,11 @@ void carve_net(Carver &c, NetCtx &x, const gnn_mlp_t &m, int rows, size_t &part_
     int fan_in = m.in_dim;
     DropRun dr{drop, 0u, 0, {}};
     for (int q = 0; q <= GNN_MAX_LAYERS; ++q) x.dropbuf[q] = nullptr;
+    if (drop_at(&dr, 0)) {      // (GNN_FLAG_TRAIN_DROPOUT_FRONT) X0, the normalised and dropped-out input [rows x in_dim] - in the backward pass d loss / d X0; the column partials
+        x.dropbuf[0] = c.take<float>((size_t)std::max(rows, 1) * m.in_dim);
+        int nc; rows_per_chunk_for(std::max(rows, 1), &nc);
+        part_floats = std::max(part_floats, (size_t)nc * 2 * m.in_dim);
+    }
     for (int q = 1; q <= m.n_layers; ++q)
         if (drop_at(&dr, q)) x.dropbuf[q] = c.take<float>((size_t)std::max(rows, 1) * m.units[q - 1]);
     for (int l = 0; l < m.n_layers; ++l) {
@@ -192,6 +205,8 @@ TrainPath homogeneous_train_path(const gnn_train_args_t &ta, const TrainPlan &p,
     const bool drop_s = ta.drop_state[0].n > 0;
     const gnn_mlp_t &m = ta.loop.net_state[0];
     hidden = dropped = false;
+    // a layer in front of a first Dense (GNN_FLAG_TRAIN_DROPOUT_FRONT; either network): the general kernels, whatever else is asked for
+    if (drop_at_position(ta.drop_state[0], 0) || drop_at_position(ta.drop_output, 0)) return TrainPath::general;
     if (drop_s && (ta.loop.flags & GNN_FLAG_TRAIN_DROPOUT_SMALL) != 0 && p.K >= 1 && p.Kc <= 32) {
         const bool hid = (ta.loop.flags & GNN_FLAG_TRAIN_HIDDEN_SMALL) != 0 && hidden_dense_of_state_width(m, p.S, p.SPs);
         bool last = false;
@@ -223,8 +238,9 @@ int make_train_plan(const gnn_train_args_t &ta, void *ws, TrainPlan &p) {
     TRY(check_mlp(a.net_state[0], "net_state", ws != nullptr));
     TRY(check_mlp(a.net_output, "net_output", ws != nullptr));
     const gnn_mlp_t &ns = a.net_state[0], &no = a.net_output;
-    TRY(check_dropout(ta.drop_state[0], ns, "net_state"));
-    TRY(check_dropout(ta.drop_output, no, "net_output"));
+    TRY(check_dropout(ta.drop_state[0], ns, "net_state", dropout_front_asked(ta)));
+    TRY(check_dropout(ta.drop_output, no, "net_output", dropout_front_asked(ta)));
+    p.front = drop_at_position(ta.drop_state[0], 0) || drop_at_position(ta.drop_output, 0);
     p.with_labels = a.state_dim > 0;
     p.in_s = ns.in_dim; p.in_o = no.in_dim; p.H1s = ns.units[0]; p.H1o = no.units[0];
     const int expect_s = a.state_dim > 0 ? 2 * p.S + 2 * p.L + p.A : 2 * p.S + p.A;
@@ -362,6 +378,64 @@ int fold_with_stats(const gnn_mlp_t &m, const float *stats, float *Wf, float *bf
     return launch_fold_list(fl, st);
 }
 
+// ---- a Dropout layer in front of the first Dense (position 0, GNN_FLAG_TRAIN_DROPOUT_FRONT; kernels_train_front.hpp) -----------------------
+// the one layer at position 0 of the run's network: its key for this call and the scalars gnn_dropout() derives for it
+struct FrontLayer { unsigned key; DropScalars sc; };
+inline FrontLayer front_layer_of(const DropRun &r, bool backward) {
+    const gnn_dropout_spec_t &d = *r.d;
+    int i = 0;
+    while (i < d.n - 1 && d.pos[i] != 0) ++i;
+    return FrontLayer{drop_key(r.seed, (unsigned)d.net_id, (unsigned)r.call, (unsigned)d.index[i]), drop_scalars(d.rate[i], d.alpha, backward)};
+}
+inline gnn::FrontSegs front_segs(const gnn::Seg *segs, int nseg) {
+    gnn::FrontSegs fs{};
+    fs.n = nseg;
+    for (int s = 0; s < nseg; ++s) fs.seg[s] = segs[s];
+    return fs;
+}
+// forward: X0 = r.buf[0] [M x in_dim] from the segments, BatchNormalization on `bn_stats` (mean | var; NULL: none) applied on load
+int front_input(const gnn_mlp_t &m, const gnn::Seg *segs, int nseg, int M, const float *bn_stats, const DropRun &r, const int *gate, hipStream_t st) {
+    if (M == 0) return 0;
+    if (!r.buf[0]) return fail("front_input: no buffer for the dropped-out input");
+    const FrontLayer f = front_layer_of(r, false);
+    gnn::FrontFwdArgs a{};
+    a.gate = gate; a.in = front_segs(segs, nseg); a.M = M; a.K = m.in_dim;
+    if (m.has_bn && bn_stats) { a.gamma = m.bn_gamma; a.beta = m.bn_beta; a.mean = bn_stats; a.var = bn_stats + m.in_dim; a.eps = m.bn_eps; }
+    a.key = f.key; a.thr = f.sc.thr; a.mul = f.sc.mul; a.add = f.sc.add; a.fill = f.sc.fill;
+    a.X0 = r.buf[0];
+    gnn::k_front_input<<<std::min(cdiv(M, 4 * gnn::FRONT_ROWS), 2048), 256, 0, st>>>(a);
+    LAUNCH_OK();
+    return 0;
+}
+// backward: dX0 [M x in_dim] through the masks into the wanted columns of dx_all (see k_front_input_grad), and - BatchNormalization on
+// `stats` - d gamma, d beta and the moments m1 / m2 of the input gradient from the chunk partials in `part`
+int front_input_grad(NetCtx &x, const gnn::Seg *segs, int nseg, int M, const float *stats, const DropRun &r, const float *dX0, bool accumulate,
+                     float *dx_all, int kdx, int first_col, int second_row, float *part, hipStream_t st) {
+    const gnn_mlp_t &m = *x.m;
+    const FrontLayer f = front_layer_of(r, true);
+    const bool bn = m.has_bn && stats;
+    int n_chunks;
+    const int rpc = rows_per_chunk_for(std::max(M, 1), &n_chunks);
+    gnn::FrontBwdArgs a{};
+    a.in = front_segs(segs, nseg); a.M = M; a.K = m.in_dim; a.rows_per_chunk = rpc;
+    a.mean = bn ? stats : nullptr;
+    a.key = f.key; a.thr = f.sc.thr; a.mul = f.sc.mul;
+    a.dX0 = dX0;
+    if (dx_all && kdx > 0) {
+        a.dx = dx_all; a.ld_dx = kdx; a.col_a = first_col;
+        if (second_row < 0) { a.half = kdx; a.col_b = -1; } else { a.half = kdx / 2; a.col_b = second_row; }
+    }
+    a.part = part;
+    gnn::k_front_input_grad<<<dim3(n_chunks, cdiv(m.in_dim, 64)), 256, 0, st>>>(a);
+    LAUNCH_OK();
+    if (bn) {
+        gnn::k_front_bn_finish<<<cdiv(m.in_dim, 64), 256, 0, st>>>(part, n_chunks, m.in_dim, stats + m.in_dim, m.bn_eps, 1.0f / (float)M, x.g->dgamma, x.g->dbeta,
+                                                                 x.m1, x.m2, accumulate ? 1 : 0);
+        LAUNCH_OK();
+    }
+    return 0;
+}
+
 // layers of `m` over a virtual concatenation; first layer with (W0, b0); outputs into hs[l] (ld = units[l])
 struct PredFuse { const float *old; int ld; float thr; int *flag; float *k_out; float k_val; bool fused; };
 
@@ -372,13 +446,21 @@ struct PredFuse { const float *old; int ld; float thr; int *flag; float *k_out; 
 // `drop`: the network's Dropout layers (positions >= 1): hs[l] stay the layers' own outputs, what the next Dense consumes is drop->buf[l + 1];
 // the network's output is then drop->buf[n_layers] when a layer sits behind the last Dense (`skip_last_drop`: a backward recompute, which
 // does not need it).
+// A Dropout layer in FRONT of the first Dense (GNN_FLAG_TRAIN_DROPOUT_FRONT): the first layer then is (W0, b0) = the raw kernel / bias over
+// X0 = drop->buf[0], which front_input() makes of the segments - normalised with `bn_stats` (NULL: as they are), dropped out - in one launch.
 int forward_layers(const gnn_mlp_t &m, const gnn::Seg *segs, int nseg, int M, const float *W0, const float *b0, float *const *hs,
                    const int *gate, hipStream_t st, PredFuse *pred = nullptr, const float *bn_stats = nullptr, const float *center = nullptr,
                    const DropRun *drop = nullptr, bool skip_last_drop = false) {
     for (int l = 0; l < m.n_layers; ++l) {
         gnn::SegDenseArgs a{};
         a.gate = gate; a.M = M; a.H = m.units[l];
-        if (l == 0) {
+        if (l == 0 && drop_at(drop, 0)) {
+            if (center) return fail("forward_layers: a Dropout layer in front of the first Dense takes the raw first layer, not a centred fold");
+            TRY(front_input(m, segs, nseg, M, bn_stats, *drop, gate, st));
+            a.nseg = 1;
+            a.seg[0] = gnn::Seg{drop->buf[0], nullptr, (int)m.in_dim, (int)m.in_dim, 0};
+            a.W = W0; a.bias = b0;
+        } else if (l == 0) {
             a.nseg = nseg;
             for (int s = 0; s < nseg; ++s) a.seg[s] = segs[s];
             a.W = W0; a.bias = b0;
@@ -466,6 +548,21 @@ int net_backward(NetCtx &x, const gnn::Seg *segs, int nseg, float *const *hs, fl
         gnn::k_axpby<<<std::min(cdiv((long)M * H, 256), 1024), 256, 0, st>>>(1.0f, G, 1.0f, dz_acc, dz_acc, (size_t)M * H);
         LAUNCH_OK();
     }
+    if (drop_at(drop, 0)) {
+        // A Dropout layer in front of the first Dense (GNN_FLAG_TRAIN_DROPOUT_FRONT): Dense 0 is a plain layer over X0 = drop->buf[0], like the
+        // layers above; d loss / d X0 = dZ . W0^T then passes the masks and meets BatchNormalization - the first-layer algebra with W = I.
+        // (d loss / d X0 overwrites X0: the weight-gradient launch in front of it was X0's last reader.)
+        if (M == 0) return 0;
+        float *X0 = drop->buf[0];
+        dim3 grid(n_chunks, cdiv(K, 64), cdiv(H, 64));
+        gnn::k_dense_grad_partial<<<grid, 256, 0, st>>>(X0, K, nullptr, K, G, ldg, H, M, rpc, part, 1);
+        LAUNCH_OK();
+        const int n = K * H + H;
+        gnn::k_reduce_partials<<<cdiv(n, 64), 256, 0, st>>>(part, n_chunks, n, x.g->dkernel[0], accumulate ? 1 : 0, 1.0f, K * H, x.g->dbias[0]);
+        LAUNCH_OK();
+        TRY(dense_plain(G, ldg, H, x.Wt[0], K, K, M, X0, K, st));
+        return front_input_grad(x, segs, nseg, M, stats, *drop, X0, accumulate, dx_all, kdx, first_col, second_row, part, st);
+    }
     {
         gnn::GradSegs gs{};
         gs.n = nseg; gs.blk_begin[0] = 0;
@@ -525,13 +622,15 @@ DropRun drop_run(const gnn_dropout_spec_t *d, unsigned seed, int call, const Net
 
 // A state network's first layer in a training-mode forward on the general kernels, BatchNormalization on this iteration's statistics of
 // the state / agg segments `dyn` (slot `stats`): a thin first layer (<= 4 units: the thin-dense kernel wants folded weights) gets the
-// centred fold in (Wf, bf) and subtracts the means on load; else the normalisation is applied as the layer stages its inputs (no fold launch)
+// centred fold in (Wf, bf) and subtracts the means on load; else the normalisation is applied as the layer stages its inputs (no fold launch).
+// `front` (a Dropout layer in front of the first Dense): never a fold - the normalisation belongs to the launch that makes X0 (forward_layers)
 struct FirstLayer { const float *W0, *b0, *bn_on_load, *centre; };
-int first_layer_of(const gnn_mlp_t &ns, const int *gate, const gnn::Seg *dyn, int M, float *stats, float *Wf, float *bf, float *part, FirstLayer &f, hipStream_t st) {
+int first_layer_of(const gnn_mlp_t &ns, const int *gate, const gnn::Seg *dyn, int M, float *stats, float *Wf, float *bf, float *part, FirstLayer &f, hipStream_t st,
+                   bool front = false) {
     f = FirstLayer{ns.kernel[0], ns.bias[0], nullptr, nullptr};
     if (!ns.has_bn) return 0;
     TRY(colstats_segs(gate, dyn, 2, M, stats, stats + ns.in_dim, part, st));
-    if (ns.units[0] > 4) { f.bn_on_load = stats; return 0; }
+    if (ns.units[0] > 4 || front) { f.bn_on_load = stats; return 0; }
     TRY(fold_with_stats(ns, stats, Wf, bf, st, true));
     f = FirstLayer{Wf, bf, nullptr, stats};
     return 0;
@@ -541,7 +640,7 @@ int first_layer_of(const gnn_mlp_t &ns, const int *gate, const gnn::Seg *dyn, in
 int recompute_hidden(const gnn_mlp_t &ns, const gnn::Seg *segs, int n, int M, const float *stats, const float *Wf, const float *bf, float *const *hs,
                      const DropRun &drs, bool drop_any, hipStream_t st) {
     if (ns.n_layers == 1 && !drop_any) return 0;
-    const bool folded = ns.has_bn && ns.units[0] <= 4;
+    const bool folded = ns.has_bn && ns.units[0] <= 4 && !drop_at(&drs, 0);      // (first_layer_of)
     gnn_mlp_t head = ns; head.n_layers = drop_any ? ns.n_layers : ns.n_layers - 1;
     return forward_layers(head, segs, n, M, folded ? Wf : ns.kernel[0], folded ? bf : ns.bias[0], hs, nullptr, st, nullptr, (ns.has_bn && !folded) ? stats : nullptr,
                           folded ? stats : nullptr, &drs, true);
@@ -1180,13 +1279,14 @@ int head_forward(const gnn_train_args_t &ta, const StepPlan &p, const HeadRun &h
     const bool bn_o = no.has_bn != 0;
     if (p.M > 0) {
         const float *W0 = no.kernel[0], *b0 = no.bias[0];
+        const bool front = drop_at(&h.drop, 0);        // (a Dropout layer in front of the first Dense: the raw first layer over X0, normalised as X0 is made)
         if (bn_o) {
             if (!stats_ready) TRY(colstats_segs(nullptr, h.segs, h.nseg, p.M, p.stats_o, p.stats_o + no.in_dim, p.part, st));
-            TRY(fold_with_stats(no, p.stats_o, p.Wf_o, p.bf_o, st, true));      // (centred: the first layer subtracts the means on load)
+            if (!front) TRY(fold_with_stats(no, p.stats_o, p.Wf_o, p.bf_o, st, true));      // (centred: the first layer subtracts the means on load)
             if (p.path != TrainPath::small) TRY(moving_output(ta, p, nullptr, st));
-            W0 = p.Wf_o; b0 = p.bf_o;
+            if (!front) { W0 = p.Wf_o; b0 = p.bf_o; }
         }
-        TRY(forward_layers(no, h.segs, h.nseg, p.M, W0, b0, h.hs, nullptr, st, nullptr, nullptr, bn_o ? p.stats_o : nullptr, &h.drop));
+        TRY(forward_layers(no, h.segs, h.nseg, p.M, W0, b0, h.hs, nullptr, st, nullptr, (bn_o && front) ? p.stats_o : nullptr, (bn_o && !front) ? p.stats_o : nullptr, &h.drop));
     }
     if (p.pooled) TRY(launch_aggregate(nullptr, ta.loop.nodegraph, h.out_nodes, p.T, p.T, ta.y_pred, p.T, st));
     return 0;
@@ -1395,7 +1495,8 @@ int forward_general(const gnn_train_args_t &ta, TrainPlan &p, hipStream_t st) {
         const int n = state_segs(a, p, t, segs);
         const gnn::Seg dyn[2] = {segs[0], segs[p.with_labels ? 2 : 1]};
         FirstLayer f;
-        TRY(first_layer_of(ns, gate, dyn, p.N, p.stats_s + (size_t)t * 2 * p.in_s, p.Wf_s + (size_t)t * p.in_s * p.H1s, p.bf_s + (size_t)t * p.H1s, p.part, f, st));
+        TRY(first_layer_of(ns, gate, dyn, p.N, p.stats_s + (size_t)t * 2 * p.in_s, p.Wf_s + (size_t)t * p.in_s * p.H1s, p.bf_s + (size_t)t * p.H1s, p.part, f, st,
+                           drop_at_position(ta.drop_state[0], 0)));
         // Dropout layers (ABI 8): fresh masks every iteration (call = t); a layer behind the last Dense makes the NEW STATE the dropped-out
         // output (the tape holds it; the network's own output stays in its layer buffer for the backward recompute)
         DropRun drs = drop_run(&ta.drop_state[0], ta.drop_seed, t, p.cs);
@@ -1681,7 +1782,7 @@ int gnn_train_phases_supported(const gnn_train_args_t *args) {
     if (!args || args->loop.composite || args->n_groups != 0 || args->forward_only) return -1;
     TrainPlan p;
     if (make_train_plan(*args, nullptr, p)) return -1;
-    return (p.path == TrainPath::big || p.H1s > gnn::LG_MAX_H) ? -1 : 0;
+    return (p.path == TrainPath::big || p.H1s > gnn::LG_MAX_H || p.front) ? -1 : 0;
 }
 
 int gnn_gate_all(const int32_t *const *words, int32_t n, int32_t *gate, void *stream) {
@@ -1718,6 +1819,7 @@ int gnn_train_step_ex(const gnn_train_args_t *args, const gnn_train_phase_args_t
 static int check_phase_args(const gnn_train_args_t &ta, const gnn_train_phase_args_t &px, const TrainPlan &p) {
     TRY(check_phase_loss_kind(ta, px));
     if (!phase_block_used(px)) return 0;
+    if (p.front) return not_covered("gnn_train_step_ex: a Dropout layer in front of a first Dense (GNN_FLAG_TRAIN_DROPOUT_FRONT) has no phases / upstream gradients / label gradients: such steps train through the building blocks");
     if (p.path == TrainPath::big) return not_covered("gnn_train_step_ex: the row-streaming path (>= GNN_TRAIN_BIG_MIN_NODES nodes) has no phases / upstream gradients / label gradients: such steps train through the building blocks");
     if (p.H1s > gnn::LG_MAX_H) return not_covered("gnn_train_step_ex: first state layer of %d units (at most %d)", p.H1s, gnn::LG_MAX_H);
     TRY(check_phase_state(px, p.K, p.L, "gnn_train_step_ex"));
@@ -1756,7 +1858,7 @@ static int train_step_impl(const gnn_train_args_t &ta, const gnn_train_phase_arg
     TRY(check_step_args(ta, p, !fwd_only && phase != GNN_TRAIN_PHASE_FORWARD && !no_loss, !fwd_only && phase != GNN_TRAIN_PHASE_FORWARD));
     const gnn_mlp_t &ns = a.net_state[0], &no = a.net_output;
     hipStream_t st = (hipStream_t)a.stream;
-    GNN_SET_KERNEL_NAME(big ? "train_step: row-streaming kernels (kernels_train_big.hpp)" : p.drop_small ? (p.hid_small ? "train_step: persistent small-graph kernels (hidden layer, dropout)" : "train_step: persistent small-graph kernels (dropout)") : p.hid_small ? "train_step: persistent small-graph kernels (hidden layer)" : small ? "train_step: persistent small-graph kernels" : "train_step: general kernels");
+    GNN_SET_KERNEL_NAME(big ? "train_step: row-streaming kernels (kernels_train_big.hpp)" : p.drop_small ? (p.hid_small ? "train_step: persistent small-graph kernels (hidden layer, dropout)" : "train_step: persistent small-graph kernels (dropout)") : p.hid_small ? "train_step: persistent small-graph kernels (hidden layer)" : small ? "train_step: persistent small-graph kernels" : p.front ? "train_step: general kernels (dropout in front)" : "train_step: general kernels");
     gnn::TileTab tiles;
     TRY(tile_table(ta, p, tiles));
     if (!fwd_only && ta.grads_ok_dev) *ta.grads_ok_dev = p.grads_ok;

@@ -95,7 +95,21 @@ enum gnn_flags {
      * same masks.  Every other shape - two layers at one position, position 0 (still not covered), width 64, composite models,
      * convergence groups, a hidden network without GNN_FLAG_TRAIN_HIDDEN_SMALL - plans, routes and computes as without the flag;
      * gnn_last_kernel_name() says "train_step: persistent small-graph kernels (dropout)" / "... (hidden layer, dropout)". */
-    GNN_FLAG_TRAIN_DROPOUT_SMALL = 1 << 11
+    GNN_FLAG_TRAIN_DROPOUT_SMALL = 1 << 11,
+    /* Training calls only (read like GNN_FLAG_TRAIN_HIDDEN_SMALL: gnn_train_step / gnn_train_step_ex, forward_only included, and the
+     * functions that plan for them; independent of the other training flags).  Opt-in: a homogeneous model whose state network and / or
+     * output network carries ONE Dropout / AlphaDropout layer in FRONT of its first Dense (gnn_dropout_spec_t::pos == 0; reference
+     * MLP.py:58-71 with dropout_pos = 0: BatchNormalization -> Dropout -> Dense 0) runs its step and its training-mode forward inside
+     * the library, on the general kernels (one launch per layer and iteration - never the persistent or row-streaming kernels, whatever
+     * other flags are set): one launch per network call writes the normalised, dropped-out input X0 [rows x in_dim] into the workspace
+     * (gnn_train_workspace_bytes() counts it), Dense 0 runs plain on it, and the backward sweep takes d loss / d X0 through the masks to
+     * d gamma, d beta and d loss / d [state | aggregate].  Further layers at positions 1 .. n_layers keep working.  The masks are those
+     * the building blocks draw with gnn_dropout on the materialised input: key of (drop_seed, net_id, call, index), row of the call,
+     * input column.  gnn_last_kernel_name() says "train_step: general kernels (dropout in front)".  Still not covered (status
+     * GNN_STATUS_NOT_COVERED, as without the flag): two layers at position 0 of one network, composite models, convergence groups
+     * (n_groups > 0), a gnn_train_step_ex phase block (gnn_train_phases_supported() answers -1).  A model without a layer at position
+     * 0 - and every model without the flag - plans, routes and computes as before. */
+    GNN_FLAG_TRAIN_DROPOUT_FRONT = 1 << 12
 };
 
 /* A sparse operator A (n_src x n_dst, COO in the reference: tf.SparseTensor) stored as the CSR of its transpose:
@@ -590,13 +604,13 @@ int gnn_ragged_copy(const gnn_ragged_desc_t *desc, int32_t n_desc, const int32_t
  * keep mask of a call is the counter hash of gnn_dropout with key = mix32(drop_seed, net_id, call, index[i]) - call = the iteration for a
  * state network, 0 for the output network; mix32(v..): h = 0x9E3779B9; for v: h = lowbias32(h ^ v) - so a host that knows the step's seed
  * can reproduce every mask (oracle/torch_train.py does).  Position 0 (Dropout in front of the first Dense, behind BatchNormalization) is
- * not taken by gnn_train_step: such networks train through the building blocks. */
+ * not taken by gnn_train_step - such networks train through the building blocks - unless GNN_FLAG_TRAIN_DROPOUT_FRONT is set. */
 #define GNN_MAX_DROPOUT 8
 typedef struct gnn_dropout_spec {
     int32_t n;                                 /* dropout layers with rate > 0 (0: none)                            */
     int32_t alpha;                             /* != 0: AlphaDropout                                                */
     int32_t net_id;                            /* enters the key: 0.. for state networks (the node type), 1000 for the output network */
-    int32_t pos[GNN_MAX_DROPOUT];              /* ascending, 1 .. n_layers                                          */
+    int32_t pos[GNN_MAX_DROPOUT];              /* ascending, 1 .. n_layers (0: GNN_FLAG_TRAIN_DROPOUT_FRONT)         */
     int32_t index[GNN_MAX_DROPOUT];            /* the layer's index among the network's dropout layers (enters the key) */
     float rate[GNN_MAX_DROPOUT];               /* 0 < rate < 1                                                      */
 } gnn_dropout_spec_t;
@@ -653,7 +667,9 @@ typedef struct gnn_train_args {
     int32_t *prev_grads_ok_host;
     /* ABI 8: Dropout layers (all-zero: none).  A state network with Dropout runs the general kernels (one launch per layer and iteration) -
      * or, for the shapes GNN_FLAG_TRAIN_DROPOUT_SMALL covers and with that flag in loop.flags, the persistent small-graph kernels in their
-     * Dropout form; Dropout inside the OUTPUT network alone leaves the loop on whichever fast path applies. */
+     * Dropout form; Dropout inside the OUTPUT network alone leaves the loop on whichever fast path applies.  A layer in FRONT of a first
+     * Dense (pos == 0) is "not covered" unless GNN_FLAG_TRAIN_DROPOUT_FRONT is in loop.flags (homogeneous models, one such layer per
+     * network): the call then runs the general kernels. */
     gnn_dropout_spec_t drop_state[GNN_MAX_TYPES];   /* [0] for homogeneous models                                   */
     gnn_dropout_spec_t drop_output;
     uint32_t drop_seed;                             /* the step's seed (every mask of the step derives from it)     */
